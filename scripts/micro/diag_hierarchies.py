@@ -1,5 +1,6 @@
-import sys, zlib
-sys.path[:0]=['/root/repo','/root/repo/tests']
+import os, sys, zlib
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0]=[ROOT, os.path.join(ROOT, 'tests')]
 import numpy as np
 import oracle_lib as ol
 import sai2_primitives_perso_amd as pkg

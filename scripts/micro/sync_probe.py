@@ -1,5 +1,6 @@
 import sys, time, os
-sys.path[:0]=['/root/repo']
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0]=[ROOT]
 import numpy as np, torch
 import sai2_primitives_perso_amd as pkg
 B=65536

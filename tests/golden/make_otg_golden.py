@@ -1,7 +1,7 @@
 """Generates the OTG fixtures (run in the build container after `make -C oracle ref`):
 
   otg_ruckig_calc.npz   outputs of the reference's OWN ruckig core (oracle/_ref/libruckig_ref.so,
-                        compiled from /root/reference/ruckig) for random acceleration-limited
+                        compiled from the reference's ruckig/) for random acceleration-limited
                         inputs drawn like ruckig/test/test-target.cpp:21-23,1247-1283: result code,
                         duration and the state sampled along the trajectory;
   otg_wrappers.npz      the OTG_joints / OTG_6dof_cartesian wrappers (numpy restatement otg_np.py on

@@ -1,6 +1,6 @@
 """Robot descriptions of the reference's examples other than the Panda, as NUMBERS (test fixtures) and a small URDF
-writer of ours — the GPU box has no /root/reference. tests/test_urdf.py checks, where the reference tree is present,
-that these load into the same model as the reference's own files:
+writer of ours. tests/test_urdf.py checks that these load into the same model as the reference's own files (kept
+under tests/golden/urdf/):
   sliding_base : examples/06-partial_joint_task/panda_arm_sliding_base.urdf — the Panda (the library's own constants)
                  on a prismatic joint along y (effort 150, travel -1..1) under a 4 kg base link
   planar_4r    : examples/11-planar_robot_controller/rrrrbot.urdf — four 0.5 m links, 1 kg each, joints about z

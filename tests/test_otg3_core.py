@@ -1,8 +1,8 @@
 """The product's JERK-LIMITED trajectory planner (csrc/sai2b_otg3_core.hpp: ruckig's third-order position interface
 restated for the device) compiled for the HOST (tests/cpp/otg_core_test.cpp, test-only) and compared BIT FOR BIT with
 the reference's own ruckig (oracle/_ref/libruckig_ref.so = ruckig/src/ruckig/*.cpp of the reference compiled in
-place): one-shot calculations on inputs drawn like ruckig's own randomised tests (ruckig/test/test-target.cpp:
-1247-1283: positions N(0, 4), velocities / accelerations N(0, 0.8) with some zeros, limits U(0.08, 16)), ruckig's
+place; its answers are recorded in tests/golden/ruckig_recorded.npz by tests/golden/ruckig_record.py): one-shot
+calculations on inputs drawn like ruckig's own randomised tests (ruckig/test/test-target.cpp:1247-1283: positions N(0, 4), velocities / accelerations N(0, 0.8) with some zeros, limits U(0.08, 16)), ruckig's
 known answers (ruckig/test/test-target-known.cpp), and stepped Ruckig::update sequences with re-targeting through the
 OTG_joints wrapper. No GPU. The device build of the same code is held to a tolerance (tests/test_gpu_otg3.py): its cbrt /
 acos / cos / sin are another library's."""
@@ -18,10 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 
-import make_otg_golden as mog  # noqa: E402
-import otg_np  # noqa: E402
+import ruckig_record as rec  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not otg_np.ref_available(), reason="oracle/_ref/libruckig_ref.so not built")
 dp = C.POINTER(C.c_double)
 
 
@@ -36,99 +34,36 @@ def core(tmp_path_factory):
     return L
 
 
-def calc3(fn, row, jm):
-    n, sync, cp, cv, ca, tp, tv, vm, am, frac = row
-    keep = [np.ascontiguousarray(a[:n]) for a in (cp, cv, ca, tp, tv, vm, am, jm)]
-    d = C.c_double()
-    fn.restype = C.c_int
-    args = [a.ctypes.data_as(dp) for a in keep]
-    z = np.zeros(1).ctypes.data_as(dp)
-    r = fn(n, sync, *args, C.byref(d), 0, z, z, z, z)
-    T = d.value
-    times = np.ascontiguousarray(np.concatenate([frac * T, [T, T + 0.01]]))
-    op, ov, oa = (np.zeros((len(times), n)) for _ in range(3))
-    if r == 0:
-        r = fn(n, sync, *args, C.byref(d), len(times), times.ctypes.data_as(dp), op.ctypes.data_as(dp), ov.ctypes.data_as(dp), oa.ctypes.data_as(dp))
-    return r, T, op, ov, oa
-
-
 def test_third_order_planner_is_bit_equal_to_reference_ruckig_on_random_inputs(core):
-    ref = otg_np.load_ref()
-    rng = np.random.default_rng(5)
-    n_cases = int(os.environ.get("SAI2B_OTG3_CASES", "6000"))
-    seen = {}
-    for row in mog.random_calc_inputs(n_cases, seed=11):
-        if row[1] != otg_np.SYNC_PHASE:  # the wrappers always ask for Synchronization::Phase (OTG_joints.cpp:23)
-            continue
-        n = row[0]
-        jm = np.concatenate([rng.uniform(0.5, 40, n), np.zeros(mog.MAXD - n)])
-        a = calc3(ref.rref_calculate_and_sample_jerk, row, jm)
-        b = calc3(core.otg3_test_calculate_and_sample, row, jm)
-        assert a[0] == b[0] and a[1] == b[1], (n, a[:2], b[:2])
-        assert all(np.array_equal(x, y) for x, y in zip(a[2:], b[2:]))
-        seen[a[0]] = seen.get(a[0], 0) + 1
-    assert seen.get(0, 0) > n_cases // 3
+    codes = rec.assert_matches("otg3_random", rec.otg3_random(core.otg3_test_calculate_and_sample))
+    assert codes.count(0) > 6000 // 3
 
 
 def test_third_order_planner_on_ruckigs_known_answers(core):
     """inputs of ruckig/test/test-target-known.cpp (the cases with max_jerk set) through both"""
-    ref = otg_np.load_ref()
-    frac = np.linspace(0.05, 0.95, mog.N_SAMPLES - 2)
-    pad = lambda x: np.concatenate([np.asarray(x, dtype=float), np.zeros(mog.MAXD - len(x))])
-    known = [  # (cp, cv, ca, tp, tv, vmax, amax, jmax)
-        ([0.0, -2.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, -3.0, 2.0], [0.0, 0.3, 0.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0]),
-        ([0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0]),
-        ([0.0, 0.0, 0.5], [0.0, -2.2, -0.5], [0.0, 2.5, -0.5], [5.0, -2.0, -3.5], [0.0, -0.5, -2.0], [3.0, 1.0, 3.0], [3.0, 2.0, 1.0], [4.0, 3.0, 2.0]),
-        ([0.2, 0.0, -0.3], [0.0, 0.2, 0.0], [0.0, 0.0, 0.1], [1.2, -0.2, 0.4], [0.0, 0.0, 0.2], [1.0, 0.5, 0.8], [2.0, 1.5, 1.0], [10.0, 8.0, 6.0]),
-    ]
-    for cp, cv, ca, tp, tv, vm, am, jm in known:
-        row = (len(cp), otg_np.SYNC_PHASE, pad(cp), pad(cv), pad(ca), pad(tp), pad(tv), pad(vm), pad(am), frac)
-        a = calc3(ref.rref_calculate_and_sample_jerk, row, pad(jm))
-        b = calc3(core.otg3_test_calculate_and_sample, row, pad(jm))
-        assert a[0] == 0 and a[0] == b[0] and a[1] == b[1]
-        assert all(np.array_equal(x, y) for x, y in zip(a[2:], b[2:]))
+    assert rec.assert_matches("otg3_known", rec.otg3_known(core.otg3_test_calculate_and_sample)) == [0] * len(rec.OTG3_KNOWN)
 
 
 def test_stepped_updates_with_retargeting_follow_reference_ruckig(core):
     """OTG_joints driving Ruckig::update (OTG_joints.cpp:118-150): the product's wrapper + third-order planner against
     the reference's Ruckig object stepped the same way (update, pass_to_input), new goals while moving"""
-    ref = otg_np.load_ref()
-    ref.rref_set_jerk.argtypes = [C.c_void_p, dp]
-    rng = np.random.default_rng(77)
-    P = lambda a: np.ascontiguousarray(a, dtype=float).ctypes.data_as(dp)
-    for trial in range(12):
-        n = int(rng.integers(1, 8))
-        x0 = rng.normal(0, 1, n)
-        vm, am, jm = rng.uniform(0.5, 3, n), rng.uniform(1, 8, n), rng.uniform(2, 30, n)
-        h = core.otg3_test_joints_create(n, P(x0), C.c_double(0.001))
-        core.otg3_joints_set_limits(C.c_void_p(h), P(vm), P(am), P(jm))
-        r = ref.rref_create(n, 0.001)
-        ref.rref_set_synchronization(r, otg_np.SYNC_PHASE)
-        ref.rref_set_limits(r, P(vm), P(am))
-        ref.rref_set_jerk(r, P(jm))
-        ref.rref_set_current(r, P(x0), P(np.zeros(n)), P(np.zeros(n)))
-        goal = x0.copy()
-        ref.rref_set_target(r, P(goal), P(np.zeros(n)))
-        finished = False
-        for tick in range(900):
-            if tick % 250 == 20:  # a new goal, also while still moving
-                goal = x0 + rng.normal(0, 0.6, n)
-                core.otg3_joints_set_goal(C.c_void_p(h), P(goal), P(np.zeros(n)))
-                ref.rref_set_target(r, P(goal), P(np.zeros(n)))
-                finished = False
-            core.otg3_joints_update(C.c_void_p(h))
-            p, v, a = (np.zeros(n) for _ in range(3))
-            gr, res = C.c_int(), C.c_int()
-            core.otg3_test_joints_get(C.c_void_p(h), P(p), P(v), P(a), C.byref(gr), C.byref(res))
-            if not finished:
-                rr = ref.rref_update(r)
-                rp, rv, ra = (np.zeros(n) for _ in range(3))
-                t, dur, nc = C.c_double(), C.c_double(), C.c_int()
-                ref.rref_get_output(r, P(rp), P(rv), P(ra), C.byref(t), C.byref(dur), C.byref(nc))
-                assert rr == res.value, (trial, tick, rr, res.value)
-                assert np.array_equal(p, rp) and np.array_equal(v, rv) and np.array_equal(a, ra), (trial, tick)
-                if rr == 0:
-                    ref.rref_pass_to_input(C.c_void_p(r))
-                else:
-                    finished = True  # the wrapper stops calling update() once the goal is reached
-        ref.rref_destroy(r)
+
+    def product():
+        for n, x0, vm, am, jm, goals in rec.otg3_stepped_trials():
+            P = rec._P
+            h = C.c_void_p(core.otg3_test_joints_create(n, P(x0), C.c_double(0.001)))
+            core.otg3_joints_set_limits(h, P(vm), P(am), P(jm))
+            finished = False
+            for tick in range(900):
+                if tick in goals:
+                    core.otg3_joints_set_goal(h, P(goals[tick]), P(np.zeros(n)))
+                    finished = False
+                core.otg3_joints_update(h)
+                p, v, a = (np.zeros(n) for _ in range(3))
+                gr, res = C.c_int(), C.c_int()
+                core.otg3_test_joints_get(h, P(p), P(v), P(a), C.byref(gr), C.byref(res))
+                if not finished:  # the reference's object is stepped until its goal is reached
+                    yield res.value, rec.digest(res.value, p, v, a)
+                    finished = res.value != 0  # the wrapper stops calling update() once the goal is reached
+
+    rec.assert_matches("otg3_stepped", product())

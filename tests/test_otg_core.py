@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_otg_golden as mog  # noqa: E402
 import otg_np  # noqa: E402
 import otg_scenarios  # noqa: E402
+import ruckig_record as rec  # noqa: E402
 from test_otg_oracle import _Lagged, _OracleCartesian, _OracleJoints  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden")
@@ -50,16 +51,9 @@ def test_core_planner_matches_reference_ruckig_fixture(core):
     assert n == 300
 
 
-@pytest.mark.skipif(not otg_np.ref_available(), reason="oracle/_ref/libruckig_ref.so not built")
 def test_core_planner_matches_reference_ruckig_live(core):
-    ref = otg_np.load_ref()
-    for row in mog.random_calc_inputs(4000, seed=321):
-        if row[1] != otg_np.SYNC_PHASE:
-            continue
-        a = mog.calc_with(ref.rref_calculate_and_sample, row)
-        b = mog.calc_with(core.otg_test_calculate_and_sample, row)
-        assert a[0] == b[0] and a[1] == b[1]
-        assert all(np.array_equal(x, y) for x, y in zip(a[2:], b[2:]))
+    """more random inputs against the answers the reference's ruckig gave them (tests/golden/ruckig_record.py)"""
+    rec.assert_matches("core_calc", rec.core_calc(core.otg_test_calculate_and_sample))
 
 
 @pytest.mark.parametrize("name", list(otg_scenarios.scenarios().keys()))

@@ -2,7 +2,7 @@
 
 Pinned against the reference's own code: the vendored ruckig core compiles here
 (oracle/_ref/libruckig_ref.so, `make -C oracle ref`); its outputs are committed in
-tests/golden/otg_ruckig_calc.npz and compared live when the library is present. The sai2 wrappers
+tests/golden/otg_ruckig_calc.npz and tests/golden/ruckig_recorded.npz (tests/golden/ruckig_record.py). The sai2 wrappers
 are compared with their numpy restatement running on that same ruckig core
 (tests/golden/otg_wrappers.npz) and, inside the whole controller, tests/golden/c3_otg_ticks.npz.
 """
@@ -20,6 +20,7 @@ import make_otg_golden as mog  # noqa: E402
 import oracle_lib as ol  # noqa: E402
 import otg_np  # noqa: E402
 import otg_scenarios  # noqa: E402
+import ruckig_record as rec  # noqa: E402
 
 import sai2_primitives_perso_amd as pkg  # noqa: E402
 
@@ -89,47 +90,12 @@ def test_oracle_matches_reference_ruckig_fixture():
     assert n_phase > 100
 
 
-@pytest.mark.skipif(not otg_np.ref_available(), reason="oracle/_ref/libruckig_ref.so not built")
 def test_oracle_matches_reference_ruckig_live():
-    """more random inputs, and Ruckig::update stepped with re-targeting, against the live library"""
-    ref = otg_np.load_ref()
+    """more random inputs, and Ruckig::update stepped with re-targeting, against the answers the reference's ruckig
+    gave them (tests/golden/ruckig_record.py)"""
     L = _L()
-    for row in mog.random_calc_inputs(3000, seed=99):
-        a = mog.calc_with(ref.rref_calculate_and_sample, row)
-        b = mog.calc_with(L.otg_test_calculate_and_sample, row)
-        assert a[0] == b[0] and a[1] == b[1]
-        assert all(np.array_equal(x, y) for x, y in zip(a[2:], b[2:]))
-    rng = np.random.default_rng(5)
-    for n in (1, 3, 6, 7):
-        hr, ho = ref.rref_create(n, 0.004), L.otg_test_create(n, C.c_double(0.004))
-        hr, ho = C.c_void_p(hr), C.c_void_p(ho)
-        for lib, h, pre in ((ref, hr, "rref_"), (L, ho, "otg_test_")):
-            getattr(lib, pre + "set_synchronization")(h, otg_np.SYNC_PHASE)
-        vm, am = rng.uniform(0.5, 2, n), rng.uniform(1, 6, n)
-        cur = [rng.normal(0, 1, n), np.zeros(n), np.zeros(n)]
-        for lib, h, pre in ((ref, hr, "rref_"), (L, ho, "otg_test_")):
-            getattr(lib, pre + "set_limits")(h, _p(vm), _p(am))
-            getattr(lib, pre + "set_current")(h, *[_p(x) for x in cur])
-        for k in range(700):
-            if k % 170 == 0:
-                tp, tv = rng.normal(0, 1, n), (rng.normal(0, 0.2, n) if k == 340 else np.zeros(n))
-                for lib, h, pre in ((ref, hr, "rref_"), (L, ho, "otg_test_")):
-                    getattr(lib, pre + "set_target")(h, _p(tp), _p(tv))
-            outs = []
-            for lib, h, pre in ((ref, hr, "rref_"), (L, ho, "otg_test_")):
-                fn = getattr(lib, pre + "update")
-                fn.restype = C.c_int
-                r = fn(h)
-                p, v, a = np.zeros(n), np.zeros(n), np.zeros(n)
-                t, d, nc = C.c_double(), C.c_double(), C.c_int()
-                getattr(lib, pre + "get_output")(h, _p(p), _p(v), _p(a), C.byref(t), C.byref(d), C.byref(nc))
-                getattr(lib, pre + "pass_to_input")(h)
-                outs.append((r, t.value, d.value, nc.value, p, v, a))
-            a, b = outs
-            assert a[:4] == b[:4], (n, k, a[:4], b[:4])
-            assert all(np.array_equal(x, y) for x, y in zip(a[4:], b[4:])), (n, k)
-        ref.rref_destroy(hr)
-        L.otg_test_destroy(ho)
+    rec.assert_matches("oracle_calc", rec.oracle_calc(L.otg_test_calculate_and_sample))
+    rec.assert_matches("oracle_stepped", rec.oracle_stepped(L, "otg_test_", lambda n, dt: L.otg_test_create(n, C.c_double(dt))))
 
 
 class _OracleJoints:

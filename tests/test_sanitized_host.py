@@ -3,7 +3,7 @@
 sanitised objects never enter libsai2b.so).
 
   * csrc/sai2b_urdf.cpp (hand-rolled XML / number parsing of files a user supplies) over the reference's three URDFs
-    (where the reference tree is present), our own robots and malformed variants of each;
+    (kept under tests/golden/urdf/), our own robots and malformed variants of each;
   * tests/cpp/otg_core_test.cpp (the product's OTG planner compiled for the host) over random planner inputs;
   * oracle/*.c (the checker itself) over a golden case of every kind and the OTG oracle's fixtures, in a child
     interpreter with the sanitizer runtime preloaded."""
@@ -21,9 +21,7 @@ CSRC = os.path.join(ROOT, "sai2-primitives-perso_amd", "csrc")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 
-REFERENCE_URDFS = ["/root/reference/examples/15-haptic_control_impedance_type/panda_arm.urdf",
-                   "/root/reference/examples/06-partial_joint_task/panda_arm_sliding_base.urdf",
-                   "/root/reference/examples/11-planar_robot_controller/rrrrbot.urdf"]
+REFERENCE_URDFS = [os.path.join(HERE, "golden", "urdf", f) for f in ("panda_arm.urdf", "panda_arm_sliding_base.urdf", "rrrrbot.urdf")]
 
 
 def _variants(text):
@@ -76,8 +74,7 @@ def test_urdf_loader_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     exe = _build(tmp, "urdf_san", [os.path.join(HERE, "cpp", "urdf_sanitize_driver.cpp"), os.path.join(CSRC, "sai2b_urdf.cpp")])
     good = {"sliding_base": robots.sliding_base_urdf(), "planar_4r": robots.planar_4r_urdf(), "six_r": robots.six_r_urdf()}
     for p in REFERENCE_URDFS:
-        if os.path.exists(p):
-            good["ref_" + os.path.basename(p)] = open(p).read()
+        good["ref_" + os.path.basename(p)] = open(p).read()
     files, n_bad = [], 0
     for name, text in good.items():
         path = os.path.join(tmp, name + ".urdf")
