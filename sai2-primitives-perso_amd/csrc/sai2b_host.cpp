@@ -53,7 +53,7 @@ struct sai2b_ctx {
 	int fb_parity = 0;			// counter set of the last SVD-free launch
 	// How many robots the SVD-free kernel for general hierarchies keeps is a property of the workload (a 6-DOF task
 	// behind a partial JointTask is inside a blending region most of the time): every 8th such tick its count of
-	// declined robots comes back to the host (pinned word, never waited for); above 40 % of the batch the next 64
+	// declined robots comes back to the host (pinned word, consumed 8 ticks later: cert_tick); above 40 % of the batch the next 64
 	// ticks run the generic kernel alone, then the SVD-free kernel is tried again. Results are the same either way.
 	int* fb_seen = nullptr;		// pinned host words: [0] declined, [1] through the in-lane singular branch
 	// many robots inside a blending region of a 4- to 6-row MotionForceTask: the 6-row SVD-free kernel with the singular branch in
@@ -61,7 +61,11 @@ struct sai2b_ctx {
 	bool sing_mode = false, no_sing6 = false, force_sing6 = false;
 	hipEvent_t fb_seen_ev = nullptr;
 	bool fb_seen_pending = false;
-	int cert_probe = 0, cert_backoff = 0;
+	// The route of a tick is a function of the tick index: the counts recorded at tick k (counted in ticks that want the
+	// SVD-free kernel) are consumed at tick k + 8, waiting for the read-back if it has not arrived (it has, at that
+	// distance, unless the caller never fetches a result); the next probe is recorded there.
+	long long cert_tick = 0, fb_seen_tick = 0;
+	int cert_backoff = 0;
 	int fb_last_seen = -1;		// length of the work list when the host last looked (-1: never)
 	bool last_tick_generic_only = false;
 	// sai2b_update_task_models() is deferred: the reference's loop is update -> goal setters -> computeControlTorques,
@@ -82,13 +86,13 @@ struct sai2b_ctx {
 	unsigned goals_dirty = ~0u;
 	// Every generator idle (goal reached, goals untouched since): an update is a no-op for every robot, and stays one until the
 	// host touches a goal or a generator's configuration — the generator kernels are not launched at all then. Known from the
-	// count of non-idle robots otg_kernel leaves behind (read back asynchronously every 8th tick, never waited for) of a tick
+	// count of non-idle robots otg_kernel leaves behind (read back every 8th tick, consumed 8 ticks later: otg_tick) of a tick
 	// launched with the goals as they still are (goals_epoch). SAI2B_NO_OTG_IDLE_SKIP=1 switches it off.
 	bool otg_all_idle = false, no_otg_idle_skip = false, otg_seen_pending = false;
 	unsigned long long goals_epoch = 0, otg_obs_epoch = 0;
 	int* otg_busy_seen = nullptr;  // pinned host word
 	hipEvent_t otg_seen_ev = nullptr;
-	unsigned otg_probe = 0;
+	long long otg_tick = 0, otg_seen_tick = 0;	// as cert_tick / fb_seen_tick: recorded at tick k, consumed at tick k + 8
 	bool goals_exposed = false;
 	sai2b_robot_model model;
 	sai2b_task_config cfg[SAI2B_MAX_TASKS];
@@ -1170,7 +1174,9 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		}
 	}
 	if (do_torque && any_otg(ctx)) {  // the generators advance once per torque computation, before the law
-		if (ctx->otg_seen_pending && hipEventQuery(ctx->otg_seen_ev) == hipSuccess) {
+		ctx->otg_tick++;
+		if (ctx->otg_seen_pending && ctx->otg_tick - ctx->otg_seen_tick >= 8) {
+			if (hipEventQuery(ctx->otg_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->otg_seen_ev));
 			ctx->otg_seen_pending = false;
 			if (*ctx->otg_busy_seen == 0 && ctx->otg_obs_epoch == ctx->goals_epoch) ctx->otg_all_idle = true;
 		}
@@ -1181,10 +1187,11 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 			const int clean_mask = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & ((1u << SAI2B_MAX_TASKS) - 1u));
 			ctx->goals_dirty = 0;
 			if (sai2b_launch_otg(ctx->d_params, ctx->B, ctx->otg_counts, ctx->otg_list, ctx->otg_parity, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
-			if (!gated && !ctx->goals_exposed && !ctx->otg_seen_pending && (ctx->otg_probe++ & 7) == 0) {
+			if (!gated && !ctx->goals_exposed && !ctx->otg_seen_pending) {
 				HIP_TRY(ctx, hipMemcpyAsync(ctx->otg_busy_seen, ctx->otg_counts + 2 * SAI2B_MAX_TASKS + ctx->otg_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 				HIP_TRY(ctx, hipEventRecord(ctx->otg_seen_ev, ctx->stream));
 				ctx->otg_seen_pending = true;
+				ctx->otg_seen_tick = ctx->otg_tick;
 				ctx->otg_obs_epoch = ctx->goals_epoch;
 			}
 			ctx->otg_parity ^= 1;
@@ -1194,8 +1201,8 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	int fast_now = fast, cert_bits = ctx->no_inlane_singular ? 2 : 0;
 	const bool fast_wanted = fast != 0 && !ctx->introspection && do_torque && commit_sh;
 	if (fast_wanted) {
-		// Which first kernel, by what the last look at the counters said (every 8th tick they come back through two pinned
-		// words, never waited for): the hierarchy's own SVD-free kernel; while more than 20 480 robots leave it for the work list
+		// Which first kernel, by what the last look at the counters said (those of tick k - 8, through two pinned words,
+		// see cert_tick): the hierarchy's own SVD-free kernel; while more than 20 480 robots leave it for the work list
 		// and the hierarchy has a 4- to 6-row MotionForceTask, the 6-row kernel with the singular branch in the lane (until
 		// fewer than 15 360 either take that branch or leave); and the generic kernel alone for 64 ticks whenever a kernel for
 		// general hierarchies keeps less than 60 % of the batch. The numbers are the measured break-even on the Panda
@@ -1203,7 +1210,9 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		// 22 382 declined: 238 against 195): the in-lane 6-row branch costs every wavefront ~100 us whatever the batch, a pass
 		// over the work list ~60 us per round of 4 096 robots (16 lanes each) or ~450 us per 65 536 in its throughput form.
 		const int alt = sing6_kind(ctx);
-		if (ctx->fb_seen_pending && hipEventQuery(ctx->fb_seen_ev) == hipSuccess) {
+		ctx->cert_tick++;
+		if (ctx->fb_seen_pending && ctx->cert_tick - ctx->fb_seen_tick >= 8) {
+			if (hipEventQuery(ctx->fb_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->fb_seen_ev));
 			ctx->fb_seen_pending = false;
 			const long long d = ctx->fb_seen[0], took = ctx->fb_seen[1];
 			ctx->fb_last_seen = (int)d;
@@ -1232,11 +1241,12 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	if (sai2b_launch_tick(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast_now, ctx->baked_model ? 1 : 0, commit_sh, (with_comp ? 1 : 0) | cert_bits, do_torque, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !fast_launch || long_list), ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
-	if (fast_launch && !ctx->fb_seen_pending && (ctx->cert_probe++ & 7) == 0) {
+	if (fast_launch && !ctx->fb_seen_pending) {
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen, ctx->fb_counts + ctx->fb_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen + 1, ctx->fb_counts + 2 + ctx->fb_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->fb_seen_ev, ctx->stream));
 		ctx->fb_seen_pending = true;
+		ctx->fb_seen_tick = ctx->cert_tick;
 	}
 	if (do_torque) ctx->q_is_pose = true;  // computeTorques caches the tasks' current pose
 	return SAI2B_OK;

@@ -114,7 +114,8 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 	const DevParams& P = *Pp;
 	const int B = P.B;
 	const int b = blockIdx.x * 64 + threadIdx.x;
-	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0;
+	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
+	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
 	if (b >= B) return;
 	RobotCtx rc;
 	UNROLL for (int i = 0; i < N; i++) {

@@ -22,15 +22,22 @@ def _err(a, ref):
     return np.abs(a - ref).max(axis=0) / np.maximum(np.abs(ref).max(axis=0), 1.0)
 
 
-def _setup(robot, B, otg, introspection, seed=0):
+def _setup(robot, B, otg, introspection, seed=0, q=None, mft6_alone=False):
+    """q: the poses [n][B] (default: drawn from the middle 60 % of every joint range); mft6_alone: the 6R with a full
+    MotionForceTask and nothing behind it, instead of its position task + JointTask"""
     m, links = pkg.model_from_urdf(robots.TEXT[robot](), is_file=False)
     n = m.dof
     rng = np.random.default_rng(100 + seed)
     lo, hi = np.array(list(m.q_lower)[:n]), np.array(list(m.q_upper)[:n])
     mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
-    q = mid[:, None] + 0.6 * half[:, None] * rng.uniform(-1, 1, (n, B))
+    q_drawn = mid[:, None] + 0.6 * half[:, None] * rng.uniform(-1, 1, (n, B))
+    q = q_drawn if q is None else np.ascontiguousarray(q)
     dq = rng.normal(0, 0.2, (n, B))
-    if robot == "sliding_base":
+    if robot == "six_r" and mft6_alone:
+        link, fpos, frot = pkg.resolve_link_frame(links, "link6", (0.05, 0.0, 0.02))
+        mk = lambda mod, cfg_j, cfg_m: [cfg_m("motion_force_task", link, fpos, frot, internal_otg=otg, robot_dof=n)]
+        kinds = ["mft"]
+    elif robot == "sliding_base":
         link, fpos, frot = pkg.resolve_link_frame(links, "end-effector", (0.0, 0.0, 0.07))
         sel = np.zeros((2, n))
         sel[0, 0] = sel[1, 7] = 1
