@@ -381,43 +381,56 @@ DI void sigma_pair(const DevTask& t, int blk, int dim, const real* axis, const r
 	mm_nt<3, 3, 3>(T, Pb, sp);
 }
 
+// Where a task's per-robot input rows come from: row k of `law_goals`, `goals`, `sensed` and `state`. HbmRows
+// reads the batched arrays; the fast kernel's StagedRows (sai2b_fast.hpp) reads an LDS image of most of them.
+struct HbmRows {
+	const DevTask& t;
+	int B, b;
+	DI real law_goal(int k) const { return ld(t.law_goals, k, B, b); }
+	DI real goal(int k) const { return ld(t.goals, k, B, b); }
+	DI real sensed(int k) const { return ld(t.sensed, k, B, b); }
+	DI real state(int k) const { return ld(t.state, k, B, b); }
+};
+
 // Per-robot inputs of the MotionForceTask law: goals, sensed wrench, integrator state. Loaded in one
 // burst (mft_load) so a caller can issue the loads long before the law consumes them.
 struct MftIn {
 	real g_pos[3], g_rot[9], g_v[3], g_w[3], g_a[3], g_al[3], g_f[3], g_m[3], s_f[3], s_m[3];
 	real integ[12];	 // pos 3, ori 3, force 3, moment 3
 };
-DI void mft_load(const DevTask& t, int B, int b, MftIn& in) {
-	const real* G = t.law_goals;  // goal, or the internal OTG's next state (MotionForceTask.cpp:386-407)
+template <class Rows>
+DI void mft_load(const DevTask& t, const Rows& r, MftIn& in) {
+	// law_goal: goal, or the internal OTG's next state (MotionForceTask.cpp:386-407)
 	UNROLL for (int k = 0; k < 3; k++) {
-		in.g_pos[k] = ld(G, k, B, b);
-		in.g_v[k] = ld(G, 12 + k, B, b);
-		in.g_w[k] = ld(G, 15 + k, B, b);
-		in.g_a[k] = ld(G, 18 + k, B, b);
-		in.g_al[k] = ld(G, 21 + k, B, b);
+		in.g_pos[k] = r.law_goal(k);
+		in.g_v[k] = r.law_goal(12 + k);
+		in.g_w[k] = r.law_goal(15 + k);
+		in.g_a[k] = r.law_goal(18 + k);
+		in.g_al[k] = r.law_goal(21 + k);
 		in.g_f[k] = in.g_m[k] = in.s_f[k] = in.s_m[k] = 0;
 	}
-	UNROLL for (int k = 0; k < 9; k++) in.g_rot[k] = ld(G, 3 + k, B, b);
-	UNROLL for (int k = 0; k < 6; k++) in.integ[k] = ld(t.state, k, B, b);
+	UNROLL for (int k = 0; k < 9; k++) in.g_rot[k] = r.law_goal(3 + k);
+	UNROLL for (int k = 0; k < 6; k++) in.integ[k] = r.state(k);
 	UNROLL for (int k = 6; k < 12; k++) in.integ[k] = 0;
 	if ((t.fdim | t.mdim) != 0) {  // batch-uniform
 		UNROLL for (int k = 0; k < 3; k++) {
-			in.g_f[k] = ld(t.goals, 24 + k, B, b);
-			in.g_m[k] = ld(t.goals, 27 + k, B, b);
+			in.g_f[k] = r.goal(24 + k);
+			in.g_m[k] = r.goal(27 + k);
 		}
 		if (t.cl_force || t.cl_moment) {
 			UNROLL for (int k = 0; k < 3; k++) {
-				in.s_f[k] = ld(t.sensed, k, B, b);
-				in.s_m[k] = ld(t.sensed, 3 + k, B, b);
+				in.s_f[k] = r.sensed(k);
+				in.s_m[k] = r.sensed(3 + k);
 			}
 		}
 	}
 	// read whenever they are written back (mft_store_integrators), also with no force / moment space
 	// parametrised (sigma = 0: they do not move, and keep their values for when a space comes back)
 	if (t.cl_force || t.cl_moment) {
-		UNROLL for (int k = 6; k < 12; k++) in.integ[k] = ld(t.state, k, B, b);
+		UNROLL for (int k = 6; k < 12; k++) in.integ[k] = r.state(k);
 	}
 }
+DI void mft_load(const DevTask& t, int B, int b, MftIn& in) { mft_load(t, HbmRows{t, B, b}, in); }
 
 // integrators advance on every torque computation, even with ki = 0 (MotionForceTask.cpp:411-413,446);
 // the force/moment ones only in closed-loop mode (:329-331,359-361)

@@ -70,12 +70,12 @@ DI bool certify_nonsingular(const real* J, real s_abs_tol, real s_max) {
 struct JtEarly {
 	real f[N], ddq[N], integ[N];
 };
-DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, int B, int b, JtEarly& e) {
-	const real* G = t1.law_goals;
+template <class Rows>
+DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEarly& e) {
 	UNROLL for (int i = 0; i < N; i++) {  // JointTask.cpp:299-345, S = I
-		const real qd = ld(G, i, B, b), dqd = ld(G, N + i, B, b);
-		e.ddq[i] = ld(G, 2 * N + i, B, b);
-		const real integ = fma(rc.q[i] - qd, t1.dt, ld(t1.state, i, B, b));
+		const real qd = r.law_goal(i), dqd = r.law_goal(N + i);
+		e.ddq[i] = r.law_goal(2 * N + i);
+		const real integ = fma(rc.q[i] - qd, t1.dt, r.state(i));
 		e.integ[i] = integ;
 		if (t1.use_vsat) {
 			const real kvi = gain_pinv(t1.kv[i]);
@@ -91,6 +91,79 @@ DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, int B, int b, JtEar
 // Scheduling fence between phases (and a marker in the ISA for per-phase inspection): the kernel is
 // one huge basic block, and without fences the scheduler interleaves phases and inflates the live set.
 #define SAI2B_PHASE() do { __builtin_amdgcn_sched_barrier(0); asm volatile("; SAI2B_PHASE_MARK"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
+// ---- Input staging of tick_fast_kernel (used by FAST = 2; FAST = 1 keeps its loads in registers). Every per-robot
+// row the fast tick reads besides q goes global -> LDS by DMA (global_load_lds) at kernel entry, while the model
+// phase runs from q alone, and is read back from LDS after one barrier. The LDS image is [row][64] doubles, one column per lane of the (single-wavefront) workgroup:
+//   dq (N) | JointTask law_goals (3N) and state (N), FAST == 2 only | MotionForceTask law_goals (24) and state (6)
+//   | one pad row when the count is odd | the MotionForceTask istate row IS_NTYPES (64 ints)
+// The force-space rows (MotionForceTask goals 24-29, sensed, state 6-11) are not staged: they stay plain loads
+// after the barrier (StagedRows), which keeps the image within 40 KiB (4 workgroups per CU).
+template <int FAST>
+struct StageLayout {
+	static constexpr int DQ = 0, JG = N, JS = JG + (FAST == 2 ? 3 * N : 0), MG = JS + (FAST == 2 ? N : 0);
+	static constexpr int MS = MG + 24, ROWS = MS + 6;
+	static constexpr int PAIRS = (ROWS + 1) / 2;  // a 16-byte glds moves two rows (lanes 0-31: row 2i, 32-63: 2i+1)
+	static constexpr int IROW = 2 * PAIRS;		 // the istate row, 256 bytes
+	static constexpr int DOUBLES = IROW * 64 + 32;
+};
+
+// first element of image row k in the batched arrays (the pad row repeats the last one)
+template <int FAST>
+DI const real* stage_row(const DevParams& P, int k) {
+	using S = StageLayout<FAST>;
+	const int B = P.B;
+	if (k >= S::ROWS) k = S::ROWS - 1;
+	if (k < S::JG) return P.dq + (size_t)(k - S::DQ) * B;
+	if (k < S::JS) return P.task[1].law_goals + (size_t)(k - S::JG) * B;
+	if (k < S::MG) return P.task[1].state + (size_t)(k - S::JS) * B;
+	if (k < S::MS) return P.task[0].law_goals + (size_t)(k - S::MG) * B;
+	return P.task[0].state + (size_t)(k - S::MS) * B;
+}
+
+DI void glds(const void* src, real* lds, int bytes) {
+	typedef __attribute__((address_space(1))) void gvoid;
+	typedef __attribute__((address_space(3))) void lvoid;
+	if (bytes == 16)
+		__builtin_amdgcn_global_load_lds((gvoid*)src, (lvoid*)lds, 16, 0, 0);
+	else
+		__builtin_amdgcn_global_load_lds((gvoid*)src, (lvoid*)lds, 4, 0, 0);
+}
+
+// Issue the DMA of the whole image for the 64 robots from b0 on; all 64 lanes take part, also those past B (the
+// source columns of lanes past B are clamped into the batch, and the columns they fill are never read).
+template <int FAST>
+DI void stage_issue(const DevParams& P, real* img, int b0) {
+	using S = StageLayout<FAST>;
+	const int B = P.B, lane = threadIdx.x;
+	if ((B & 1) == 0) {	 // every row starts 16-byte aligned: lane l moves robots col, col + 1 of row 2i + l / 32
+		const int col = min(b0 + 2 * (lane & 31), B - 2);
+		const bool hi = lane >= 32;
+		UNROLL for (int i = 0; i < S::PAIRS; i++)
+			glds((hi ? stage_row<FAST>(P, 2 * i + 1) : stage_row<FAST>(P, 2 * i)) + col, img + 2 * i * 64, 16);
+	} else {  // odd batch: 4-byte DMA, two per row; lane l moves dword l % 2 of robot col
+		UNROLL for (int h = 0; h < 2; h++) {
+			const int col = min(b0 + 32 * h + (lane >> 1), B - 1);
+			UNROLL for (int k = 0; k < S::ROWS; k++)
+				glds((const int*)(stage_row<FAST>(P, k) + col) + (lane & 1), img + k * 64 + 32 * h, 4);
+		}
+	}
+	glds(P.task[0].istate + (size_t)IS_NTYPES * B + min(b0 + lane, B - 1), img + S::IROW * 64, 4);
+}
+
+// The rows of one task as the fast kernel reads them after the barrier: staged rows from the image (this lane's
+// column), force-space rows from HBM.
+struct StagedRows {
+	const DevTask& t;
+	int B, b;
+	const real* lg;	 // image row of law_goals row 0, at this lane's column
+	const real* st;	 // same for state
+	int st_rows;	 // state rows in the image
+	DI real law_goal(int k) const { return lg[k * 64]; }
+	DI real goal(int k) const { return ld(t.goals, k, B, b); }
+	DI real sensed(int k) const { return ld(t.sensed, k, B, b); }
+	DI real state(int k) const { return k < st_rows ? st[k * 64] : ld(t.state, k, B, b); }
+};
 
 // The Cholesky part of the fast tick. J and M are the Jacobian and mass matrix at rc.q, Fu/Ff the task
 // forces of the MotionForceTask law, jt the JointTask law; HAS_JT selects the 2-level form. Ordered to

@@ -98,25 +98,12 @@ __global__ __launch_bounds__(64) void tick_kernel(const DevParams* __restrict__ 
 }
 
 #if SAI2B_N == 7  // the SVD-free kernels are for 7-joint robots (6-DOF task + a one-dimensional nullspace)
-// FAST = 1: hierarchy [full MFT]; FAST = 2: [full MFT, full JT] — the SVD-free path of
-// sai2b_fast.hpp. A robot takes it only when it is certified non-singular (and is not leaving a
-// singular region); otherwise its lane touches no state and appends the robot to the work list of
-// the generic kernel launched right behind (one atomic per wavefront that has such robots).
-// fb_counts: two counters alternating between ticks (`parity`): this launch fills [parity] and clears
-// [1 - parity] for the next one (the generic pass that read it finished before this kernel started).
-// BAKED selects where the robot constants come from: false = the ctx's parameter block (any robot),
-// true = the compile-time Panda literals of sai2b_baked_panda.h (chosen by the host only when the ctx
-// model is bit-equal to them): no scalar loads from the parameter block for the model phase.
-template <int FAST, bool BAKED>
-__global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restrict__ Pp, int with_comp,
-														  int* __restrict__ fb_counts, int* __restrict__ fb_list,
-														  int parity) {
-	const DevParams& P = *Pp;
+// [full MFT] (FAST = 1) with its inputs loaded into registers up front, as before the staged path: at C2's 4 096
+// robots (one wavefront per 16 SIMDs, nothing to contend for HBM) the staged form measured 13 % slower.
+template <bool BAKED>
+DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb_counts, int* __restrict__ fb_list, int parity,
+						 int b) {
 	const int B = P.B;
-	const int b = blockIdx.x * 64 + threadIdx.x;
-	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
-	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
-	if (b >= B) return;
 	RobotCtx rc;
 	UNROLL for (int i = 0; i < N; i++) {
 		rc.q[i] = ld(P.q, i, B, b);
@@ -124,11 +111,9 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 	}
 	const DevTask& t0 = P.task[0];
 	const bool clean = ldi(t0.istate, IS_NTYPES, B, b) == 0;
-	// Phase order keeps the live set small (only 256 of the 512 registers are VGPRs the VALU can
-	// address; the rest are AGPRs the compiler uses as spill space) and gives every load a phase of
-	// arithmetic to hide behind: JT law inputs -> FK/Jacobian -> MFT law -> CRBA -> certificate.
+	// Phase order keeps the live set small and gives every load a phase of arithmetic to hide behind:
+	// FK/Jacobian -> MFT law -> CRBA -> certificate.
 	JtEarly jt;
-	if (FAST == 2) fast_jt_early(P.task[1], rc, B, b, jt);
 	MftIn in0;
 	mft_load(t0, B, b, in0);
 	SAI2B_PHASE();
@@ -175,6 +160,118 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 			return;
 		}
 	}
+	mft_store_integrators(t0, B, b, in0);
+	SAI2B_PHASE();
+	real tau[N];
+	fast_tick<false>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
+	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
+}
+
+// FAST = 1: hierarchy [full MFT]; FAST = 2: [full MFT, full JT] — the SVD-free path of
+// sai2b_fast.hpp. A robot takes it only when it is certified non-singular (and is not leaving a
+// singular region); otherwise its lane touches no state and appends the robot to the work list of
+// the generic kernel launched right behind (one atomic per wavefront that has such robots).
+// fb_counts: two counters alternating between ticks (`parity`): this launch fills [parity] and clears
+// [1 - parity] for the next one (the generic pass that read it finished before this kernel started).
+// BAKED selects where the robot constants come from: false = the ctx's parameter block (any robot),
+// true = the compile-time Panda literals of sai2b_baked_panda.h (chosen by the host only when the ctx
+// model is bit-equal to them): no scalar loads from the parameter block for the model phase.
+template <int FAST, bool BAKED>
+__global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restrict__ Pp, int with_comp,
+														  int* __restrict__ fb_counts, int* __restrict__ fb_list,
+														  int parity) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
+	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
+	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
+	if constexpr (FAST == 1) {
+		if (b < B) tick_fast1_loads<BAKED>(P, with_comp, fb_counts, fb_list, parity, b);
+		return;
+	}
+	// Inputs: q in registers (FK needs it and nothing else), every other row by DMA into the LDS image (StageLayout,
+	// sai2b_fast.hpp). q is waited for before the DMA is issued, and the window up to the barrier issues no other
+	// global load and touches no scratch, so the DMA lands behind the kinematics and the barrier retires it.
+	using S = StageLayout<FAST>;
+	__shared__ real img[S::DOUBLES];
+	RobotCtx rc;
+	UNROLL for (int i = 0; i < N; i++) {
+		rc.q[i] = ld(P.q, i, B, min(b, B - 1));
+		asm volatile("" : "+v"(rc.q[i]));  // the wait for q goes here, ahead of the DMA
+	}
+	SAI2B_PHASE();
+	stage_issue<FAST>(P, img, b0);
+	SAI2B_PHASE();
+	if (b >= B) return;
+	const DevTask& t0 = P.task[0];
+	// Window: FK -> frame pose -> Jacobian -> certificate, from q alone. Phase order by register count: the law
+	// comes before CRBA (M is not live across it), and FK runs a second time for CRBA and gravity after the law
+	// rather than keeping the frames or M live across it; the same code on the same q gives the same frames.
+	real J[6 * N], x[3], R[9];
+	{
+		Frames F;
+		if constexpr (BAKED)
+			fk(PandaBaked{}, rc.q, F);
+		else
+			fk(P.model, rc.q, F);
+		frame_pose(t0, F, x, R);
+		if constexpr (BAKED)
+			jacobian(PandaBaked{}, t0, F, x, J);
+		else
+			jacobian(P.model, t0, F, x, J);
+	}
+	SAI2B_PHASE();
+	const bool ok = certify_nonsingular(J, t0.s_abs_tol, t0.s_max);
+	SAI2B_PHASE();
+	__syncthreads();  // one wavefront per workgroup: vmcnt(0) + barrier, the DMA-written image is readable from here
+	const real* col = img + threadIdx.x;
+	UNROLL for (int i = 0; i < N; i++) {
+		rc.dq[i] = col[(S::DQ + i) * 64];
+		rc.q[i] = ld(P.q, i, B, b);  // again (an L2 hit): not live across the window
+	}
+	const bool clean = ((const int*)(img + S::IROW * 64))[threadIdx.x] == 0;
+	MftIn in0;
+	mft_load(t0, StagedRows{t0, B, b, col + S::MG * 64, col + S::MS * 64, 6}, in0);
+	SAI2B_PHASE();
+	real Fu[6], Ff[6];
+	mft_law(t0, rc, J, x, R, in0, Fu, Ff);	// MotionForceTask.cpp:278-503 (integrators not yet stored)
+	SAI2B_PHASE();
+	real M[N * N], g[N];
+	{
+		Frames F;
+		if constexpr (BAKED)
+			fk(PandaBaked{}, rc.q, F);
+		else
+			fk(P.model, rc.q, F);
+		if constexpr (BAKED)
+			mass_matrix(PandaBaked{}, F, M);
+		else
+			mass_matrix(P.model, F, M);
+		if (P.gravity_comp) {
+			if constexpr (BAKED)
+				gravity_vector(PandaBaked{}, F, g);
+			else
+				gravity_vector(P.model, F, g);
+		}
+		else {
+			UNROLL for (int i = 0; i < N; i++) g[i] = 0;
+		}
+	}
+	SAI2B_PHASE();
+	const bool mine = ok && clean;
+	const unsigned long long declined = __ballot(!mine);
+	if (declined) {
+		int base = 0;
+		if (threadIdx.x == 0) base = atomicAdd(&fb_counts[parity], __popcll(declined));  // lane 0 is always in range
+		base = __shfl(base, 0);
+		if (!mine) {
+			((gint*)fb_list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
+			return;
+		}
+	}
+	// the JointTask law, from its staged rows (late: its results would be live across the model phase)
+	JtEarly jt;
+	if constexpr (FAST == 2) fast_jt_early(P.task[1], rc, StagedRows{P.task[1], B, b, col + S::JG * 64, col + S::JS * 64, N}, jt);
 	// committed to the fast path: integrators can go out now
 	mft_store_integrators(t0, B, b, in0);
 	if (FAST == 2) {
