@@ -1993,6 +1993,13 @@ int oracle_get_mft_integrators(oracle_ctx* c, int task, double* out) {
 	}
 	return 0;
 }
+int oracle_get_jt_integrators(oracle_ctx* c, int task, double* out) {
+	if (task < 0 || task >= c->T || !c->jt[task]) return fail("not a JointTask");
+	const int k0 = c->cfg[task].task_dof;
+	for (int b = 0; b < c->B; b++)
+		for (int i = 0; i < k0; i++) out[i * c->B + b] = c->jt[task][b].integ[i];
+	return 0;
+}
 int oracle_get_jt_desired(oracle_ctx* c, int task, double* q, double* dq, double* ddq) {
 	if (task < 0 || task >= c->T || !c->jt[task]) return fail("not a JointTask");
 	const int k0 = c->cfg[task].task_dof;

@@ -24,7 +24,8 @@ def lib(dof=DOF):
     if dof in _libs:
         return _libs[dof]
     path = ORACLE_LIB if dof == DOF else os.path.join(ORACLE_DIR, f"libsai2_oracle_n{dof}.so")
-    srcs = [os.path.join(ORACLE_DIR, f) for f in ("sai2_oracle.c", "otg_oracle.c", "otg_oracle.h", "sai2_oracle.h")]
+    srcs = [os.path.join(ORACLE_DIR, f) for f in ("sai2_oracle.c", "otg_oracle.c", "otg_oracle.h", "sai2_oracle.h",
+                                                  "../include/sai2b.h", "../include/sai2b_detfk.h", "../include/sai2b_detmath.h")]
     if dof == DOF and os.environ.get("SAI2B_ORACLE_LIB"):  # another build of the 7-joint oracle (tests/test_sanitized_host.py)
         path = os.environ["SAI2B_ORACLE_LIB"]
     elif not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(f) for f in srcs):
@@ -69,6 +70,7 @@ def lib(dof=DOF):
     L.oracle_get_mft_task_forces.argtypes = [vp, i, vp, vp]
     L.oracle_get_jt_inertia.argtypes = [vp, i, vp, vp]
     L.oracle_get_mft_integrators.argtypes = [vp, i, vp]
+    L.oracle_get_jt_integrators.argtypes = [vp, i, vp]
     L.oracle_get_jt_desired.argtypes = [vp, i, vp, vp, vp]
     L.oracle_get_mft_desired.argtypes = [vp, i] + [vp] * 6
     L.oracle_get_otg_status.argtypes = [vp, i, vp, vp]
@@ -323,6 +325,11 @@ class Oracle:
     def get_mft_integrators(self, task):
         out = np.empty((12, self.B))
         assert self.L.oracle_get_mft_integrators(self.h, task, _ptr(out)) == 0
+        return out
+
+    def get_jt_integrators(self, task):
+        out = np.empty((self._k0(task), self.B))
+        assert self.L.oracle_get_jt_integrators(self.h, task, _ptr(out)) == 0
         return out
 
     def reset_integrators(self, task, which=0):
