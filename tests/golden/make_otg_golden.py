@@ -31,12 +31,12 @@ MAXD = 7
 N_SAMPLES = 8
 
 
-def random_calc_inputs(n_cases, seed=7):
-    """(n, sync, cp, cv, ca, tp, tv, vmax, amax, sample fractions), padded to MAXD"""
+def random_calc_inputs(n_cases, seed=7, nmax=7, maxd=MAXD):
+    """(n, sync, cp, cv, ca, tp, tv, vmax, amax, sample fractions), 1 <= n <= nmax, padded to maxd"""
     rng = np.random.default_rng(seed)
     rows = []
     for it in range(n_cases):
-        n = int(rng.integers(1, 8))
+        n = int(rng.integers(1, nmax + 1))
         sync = otg_np.SYNC_PHASE if it % 2 == 0 else otg_np.SYNC_TIME
         cp, tp = rng.normal(0, 4, n), rng.normal(0, 4, n)
         cv = np.where(rng.random(n) < 0.9, rng.normal(0, 0.8, n), 0.0)
@@ -52,7 +52,7 @@ def random_calc_inputs(n_cases, seed=7):
         if it % 13 == 0:  # already at the target
             tp, cv, tv = cp.copy(), cv * 0, tv * 0
         frac = np.sort(rng.uniform(0, 1, N_SAMPLES - 2))
-        pad = lambda x: np.concatenate([x, np.zeros(MAXD - n)])
+        pad = lambda x: np.concatenate([x, np.zeros(maxd - n)])
         rows.append((n, sync, pad(cp), pad(cv), pad(ca), pad(tp), pad(tv), pad(vm), pad(am), frac))
     return rows
 
@@ -75,7 +75,7 @@ def calc_with(fn, row):
     if r == 0:
         r = fn(n, sync, *args, C.byref(d), N_SAMPLES, times.ctypes.data_as(dp), op.ctypes.data_as(dp),
                ov.ctypes.data_as(dp), oa.ctypes.data_as(dp))
-    padk = lambda x: np.concatenate([x, np.zeros((N_SAMPLES, MAXD - n))], axis=1)
+    padk = lambda x: np.concatenate([x, np.zeros((N_SAMPLES, len(cp) - n))], axis=1)
     return r, T, times, padk(op), padk(ov), padk(oa)
 
 

@@ -5,7 +5,8 @@ Every comparison those tests make is an OBSERVATION: the result code, duration a
 or the output of one stepped Ruckig::update. Each observation is stored as a 16-byte BLAKE2b digest of its float64
 bytes (ruckig_recorded.npz), which keeps the comparison bit for bit in a fixture of a few hundred kB. The input draws
 live here once, shared by the recording (`python tests/golden/ruckig_record.py` after `make -C oracle ref`) and the
-tests, so both see the same inputs.
+tests, so both see the same inputs. `python tests/golden/ruckig_record.py --append` records only the sequences the
+fixture does not hold yet.
 """
 import ctypes as C
 import hashlib
@@ -82,6 +83,16 @@ def otg3_random(fn, n_cases=6000):
         yield out[0], digest(*out)
 
 
+def otg3_random8(fn, n_cases=8000):
+    """otg3_random for the 8-DoF generators of the 8-joint build (SAI2B_OTG_MAXD = 8): the rows with n = 8"""
+    rng = np.random.default_rng(55)
+    for row in mog.random_calc_inputs(n_cases, seed=811, nmax=8, maxd=8):
+        if row[1] != otg_np.SYNC_PHASE or row[0] != 8:
+            continue
+        out = calc3(fn, row, rng.uniform(0.5, 40, 8))
+        yield out[0], digest(*out)
+
+
 OTG3_KNOWN = [  # (cp, cv, ca, tp, tv, vmax, amax, jmax): inputs of ruckig/test/test-target-known.cpp with max_jerk set
     ([0.0, -2.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, -3.0, 2.0], [0.0, 0.3, 0.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0]),
     ([0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0], [1.0, 1.0, 1.0]),
@@ -149,6 +160,15 @@ def core_calc(fn):
         yield out[0], digest(*out)
 
 
+def core_calc8(fn):
+    """core_calc for the 8-DoF generators of the 8-joint build: the rows with n = 8"""
+    for row in mog.random_calc_inputs(16000, seed=3218, nmax=8, maxd=8):
+        if row[1] != otg_np.SYNC_PHASE or row[0] != 8:
+            continue
+        out = mog.calc_with(fn, row)
+        yield out[0], digest(*out)
+
+
 def oracle_calc(fn):
     """acceleration-limited one-shot calculations, every row"""
     for row in mog.random_calc_inputs(3000, seed=99):
@@ -187,18 +207,36 @@ def _digests(seq):
 
 
 def main():
+    """record every sequence; with --append only the ones the fixture lacks, added as new members of the archive (the
+    recorded ones stay as they are, byte for byte)"""
     if not otg_np.ref_available():
         raise SystemExit("oracle/_ref/libruckig_ref.so missing: run `make -C oracle ref` first")
     ref = otg_np.load_ref()
-    out = {
-        "otg3_random": _digests(otg3_random(ref.rref_calculate_and_sample_jerk)),
-        "otg3_known": _digests(otg3_known(ref.rref_calculate_and_sample_jerk)),
-        "otg3_stepped": _digests(otg3_stepped_ref(ref)),
-        "core_calc": _digests(core_calc(ref.rref_calculate_and_sample)),
-        "oracle_calc": _digests(oracle_calc(ref.rref_calculate_and_sample)),
-        "oracle_stepped": _digests(oracle_stepped(ref, "rref_", ref.rref_create)),
+    seqs = {
+        "otg3_random": lambda: otg3_random(ref.rref_calculate_and_sample_jerk),
+        "otg3_known": lambda: otg3_known(ref.rref_calculate_and_sample_jerk),
+        "otg3_stepped": lambda: otg3_stepped_ref(ref),
+        "core_calc": lambda: core_calc(ref.rref_calculate_and_sample),
+        "oracle_calc": lambda: oracle_calc(ref.rref_calculate_and_sample),
+        "oracle_stepped": lambda: oracle_stepped(ref, "rref_", ref.rref_create),
+        "otg3_random8": lambda: otg3_random8(ref.rref_calculate_and_sample_jerk),
+        "core_calc8": lambda: core_calc8(ref.rref_calculate_and_sample),
     }
-    np.savez_compressed(FIXTURE, **out)
+    if "--append" in sys.argv[1:]:
+        import io
+        import zipfile
+
+        with np.load(FIXTURE) as z:
+            have = set(z.files)
+        out = {k: _digests(f()) for k, f in seqs.items() if k not in have}
+        with zipfile.ZipFile(FIXTURE, "a", compression=zipfile.ZIP_DEFLATED) as zf:
+            for k, v in out.items():
+                buf = io.BytesIO()
+                np.lib.format.write_array(buf, v, allow_pickle=False)
+                zf.writestr(k + ".npy", buf.getvalue())
+    else:
+        out = {k: _digests(f()) for k, f in seqs.items()}
+        np.savez_compressed(FIXTURE, **out)
     print({k: v.shape for k, v in out.items()})
 
 

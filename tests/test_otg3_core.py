@@ -23,10 +23,9 @@ import ruckig_record as rec  # noqa: E402
 dp = C.POINTER(C.c_double)
 
 
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
+def _build(tmp_path_factory, defines=()):
     out = str(tmp_path_factory.mktemp("otg3core") / "libotg_core_test.so")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", *defines,
                     "-I", os.path.join(ROOT, "sai2-primitives-perso_amd", "csrc"), os.path.join(HERE, "cpp", "otg_core_test.cpp"), "-o", out],
                    check=True)
     L = C.CDLL(out)
@@ -34,9 +33,26 @@ def core(tmp_path_factory):
     return L
 
 
+@pytest.fixture(scope="module")
+def core(tmp_path_factory):
+    return _build(tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def core8(tmp_path_factory):
+    """the generators as the 8-joint build of the library compiles them (sai2b_otg.hip: SAI2B_OTG_MAXD = 8)"""
+    return _build(tmp_path_factory, ["-DSAI2B_OTG_MAXD=8"])
+
+
 def test_third_order_planner_is_bit_equal_to_reference_ruckig_on_random_inputs(core):
     codes = rec.assert_matches("otg3_random", rec.otg3_random(core.otg3_test_calculate_and_sample))
     assert codes.count(0) > 6000 // 3
+
+
+def test_third_order_planner_with_eight_dofs_is_bit_equal_to_reference_ruckig(core8):
+    """8-DoF rows (n = 8, every lane of a device group active) on the 8-DoF build"""
+    codes = rec.assert_matches("otg3_random8", rec.otg3_random8(core8.otg3_test_calculate_and_sample))
+    assert codes.count(0) > len(codes) // 3
 
 
 def test_third_order_planner_on_ruckigs_known_answers(core):

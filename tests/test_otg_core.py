@@ -23,16 +23,26 @@ from test_otg_oracle import _Lagged, _OracleCartesian, _OracleJoints  # noqa: E4
 GOLDEN = os.path.join(HERE, "golden")
 
 
-@pytest.fixture(scope="module")
-def core(tmp_path_factory):
+def _build(tmp_path_factory, defines=()):
     out = str(tmp_path_factory.mktemp("otgcore") / "libotg_core_test.so")
     subprocess.run(
-        ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
+        ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", *defines,
          "-I", os.path.join(ROOT, "sai2-primitives-perso_amd", "csrc"),
          os.path.join(HERE, "cpp", "otg_core_test.cpp"), "-o", out],
         check=True,
     )
     return C.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def core(tmp_path_factory):
+    return _build(tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def core8(tmp_path_factory):
+    """the generators as the 8-joint build of the library compiles them (sai2b_otg.hip: SAI2B_OTG_MAXD = 8)"""
+    return _build(tmp_path_factory, ["-DSAI2B_OTG_MAXD=8"])
 
 
 def test_core_planner_matches_reference_ruckig_fixture(core):
@@ -54,6 +64,17 @@ def test_core_planner_matches_reference_ruckig_fixture(core):
 def test_core_planner_matches_reference_ruckig_live(core):
     """more random inputs against the answers the reference's ruckig gave them (tests/golden/ruckig_record.py)"""
     rec.assert_matches("core_calc", rec.core_calc(core.otg_test_calculate_and_sample))
+
+
+def test_core_planner_with_eight_dofs_matches_reference_ruckig(core8):
+    """8-DoF rows (n = 8, every lane of a device group active) against the reference's ruckig, on the 8-DoF build"""
+    codes = rec.assert_matches("core_calc8", rec.core_calc8(core8.otg_test_calculate_and_sample))
+    assert codes.count(0) > len(codes) // 2
+
+
+def test_eight_dof_build_keeps_the_seven_dof_answers(core8):
+    """the same code with one more slot per vector: the n <= 7 rows are unchanged"""
+    rec.assert_matches("core_calc", rec.core_calc(core8.otg_test_calculate_and_sample))
 
 
 @pytest.mark.parametrize("name", list(otg_scenarios.scenarios().keys()))
