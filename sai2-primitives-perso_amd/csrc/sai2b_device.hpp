@@ -1043,11 +1043,20 @@ DI void mft_task(const DevParams& P, const DevTask& t, const RobotCtx& rc, int B
 				} else {
 					UNROLL for (int i = 0; i < N * N; i++) LjMod[i] = Lj[i];
 				}
+				// Lambda_s from the rows U_s^T Jp themselves: column j of Q is Jp^T u_j, of norm s_j, so H = Q^T M^-1 Q has
+				// its singular block at the scale s_s^2 of what it holds. Projecting the whole Jp M^-1 Jp^T on Ps instead
+				// carries rounding of its s_0^2-sized entries into that block: a relative error eps (s_0 / s_s)^2 in Lambda_s
 				real LsMod[36];
-				if (bie)
-					pinv_proj<6>(AB, Ps, LsMod);
-				else
-					pinv_proj<6>(A, Ps, LsMod);
+				{
+					real Y[N * 6], H[36], S6[36], Hi[36];
+					mm<N, N, 6>(bie ? rc.MinvB : rc.Minv, Q, Y);
+					mm_tn<6, N, 6>(Q, Y, H);
+					UNROLL for (int i = 0; i < 6; i++) UNROLL for (int j = 0; j < 6; j++)
+						S6[i * 6 + j] = (i == j && pos[j] >= split && pos[j] < rank) ? 1.0 : 0.0;
+					pinv_proj<6>(H, S6, Hi);  // the inverse of the singular block, embedded
+					mm<6, 6, 6>(W, Hi, H);
+					mm_nt<6, 6, 6>(H, W, LsMod);  // W Hi W^T = U_s Lambda_s U_s^T
+				}
 				// joint strategy (:327-351)
 				real ut[N], y7[N], tau_j[N];
 				if (c1 > c2 || t.enforce_t1) {

@@ -662,8 +662,20 @@ SAI2B_TASK_FN void mft_task_g(const DevParams& P, const DevTask& t, const Rob& r
 				} else {
 					UNROLL for (int j = 0; j < N; j++) ljMod[j] = lj[j];
 				}
+				// Lambda_s from the rows U_s^T Jp themselves: column j of x6 is Jp^T u_j, of norm s_j, so H = X^T M^-1 X has
+				// its singular block at the scale s_s^2 of what it holds. Projecting the whole Jp M^-1 Jp^T on U_s U_s^T instead
+				// carries rounding of its s_0^2-sized entries into that block: a relative error eps (s_0 / s_s)^2 in Lambda_s
 				real lsMod[6];
-				pinv_proj_rows<G, 6>(bie ? AB : A, ps, lsMod);
+				{
+					real y[6], xT[N], h[6], sel[6], hinv[6], t6[6];
+					mm_rr<G, N, 6>(bie ? rb.minvB : rb.minv, x6, y);  // Y = M^-1 X, row r in lane r
+					transpose_lds<G, N, 6>(rb.pad, x6, xT);
+					mm_rr<G, N, 6>(xT, y, h);  // H = X^T Y, row i in lane i < 6
+					UNROLL for (int j = 0; j < 6; j++) sel[j] = (pos[j] >= split && pos[j] < rank) ? kd(r, j) : 0.0;
+					pinv_proj_rows<G, 6>(h, sel, hinv);	 // the inverse of the singular block, embedded
+					mm_rr<G, 6, 6>(w6, hinv, t6);
+					mm_rt<G, 6, 6>(t6, w6, lsMod);	// U Hinv U^T = U_s Lambda_s U_s^T
+				}
 				// joint strategy (:327-351)
 				real tau_j;
 				if (c1 > c2 || t.enforce_t1) {

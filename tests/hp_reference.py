@@ -1,0 +1,493 @@
+"""One control tick of a task hierarchy in mpmath at 40 significant digits (test infrastructure): the ground truth the
+singular branch of every kernel route, and the CPU oracle, are held to (tests/test_hp_reference.py,
+tests/test_gpu_hp_singular.py through the fixture tests/golden/hp_singular.npz).
+
+mpmath and numpy only, nothing of the product's or the oracle's code. The robot is read from its URDF text the way
+tests/urdf_np.py reads it (joint origin, then a rotation about / translation along the joint's <axis>; fixed joints'
+bodies move with the link they hang on), every float64 of the file taken as the exact number it is, every sine and
+cosine evaluated at the working precision. The tasks are plain dicts of the numbers a task config carries (gains,
+thresholds, the perturbation step, the partial projection): tests/golden/make_hp_golden.py reads them from the
+product's own defaults.
+
+The SingularityHandler (SingularityHandler.cpp:75-368, read as tests/golden/make_golden.py reads it): thin SVD of
+J N_prec with every right singular vector oriented "largest-magnitude component positive", the split at the first
+ratio s_i / s_0 below s_max, alpha = clip((rho - s_min) / (s_max - s_min)), s_abs_tol; Lambda_ns, Lambda_s and
+Lambda_joint for full dynamic decoupling, BIE and impedance; the type-1 / type-2 classification by FK perturbation with
+the singular-vector-sign setting; the history ring and its counters, q_prior, the type-2 joint-limit directions; the
+effort clamp of tau_s and tau = tau_ns + alpha tau_s + (1 - alpha) tau_joint.
+
+HOOKS plants errors for tests/test_hp_reference.py (each must be caught by the checker): alpha_rel, flip_vs_type2,
+no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior."""
+import copy
+import re
+import xml.etree.ElementTree as ET
+
+import mpmath
+import numpy as np
+from mpmath import mp, mpf
+
+mp.dps = 40
+EPS = 2.0 ** -52
+HOOKS = {}
+FULL, BIE, IMPEDANCE = 0, 1, 2
+
+
+def _nums(text, n, default):
+    if text is None:
+        return [float(x) for x in default]
+    out = [float(re.match(r"[-+]?(\d+\.?\d*([eE][-+]?\d+)?|\.\d+([eE][-+]?\d+)?)", tok).group(0)) for tok in text.split()]
+    assert len(out) == n, text
+    return out
+
+
+def M_(a):
+    """float / nested list / numpy array -> object array of exact mpf"""
+    a = np.asarray(a)
+    if a.dtype != object:
+        a = a.astype(float)
+    return np.vectorize(lambda v: mpf(v) if not isinstance(v, mpf) else v, otypes=[object])(a)
+
+
+def zeros(*shape):
+    return np.full(shape, mpf(0), dtype=object)
+
+
+def eye(n):
+    out = zeros(n, n)
+    for i in range(n):
+        out[i, i] = mpf(1)
+    return out
+
+
+def inv(a):
+    return np.array(mp.inverse(mp.matrix(a.tolist())).tolist(), dtype=object)
+
+
+def svd(a):
+    """thin SVD a = U diag(s) V^T, s descending"""
+    U, S, Vt = mp.svd_r(mp.matrix(a.tolist()), full_matrices=False)
+    return np.array(U.tolist(), dtype=object), np.array([S[i] for i in range(S.rows)], dtype=object), np.array(Vt.tolist(), dtype=object).T
+
+
+def sym_pinv(a):
+    """pseudo-inverse of a symmetric matrix, singular values below n eps s_0 dropped (the oracle's cut-off)"""
+    U, s, V = svd(a)
+    n = a.shape[0]
+    d = [1 / x if x > n * EPS * s[0] and x > 0 else mpf(0) for x in s]
+    return V @ np.diag(np.array(d, dtype=object)) @ U.T
+
+
+def norm_inf(v):
+    return max(abs(x) for x in np.ravel(v))
+
+
+def norm_fro(a):
+    return mp.sqrt(sum(x * x for x in np.ravel(a)))
+
+
+def _rpy(r):
+    cr, sr, cp, sp, cy, sy = mp.cos(r[0]), mp.sin(r[0]), mp.cos(r[1]), mp.sin(r[1]), mp.cos(r[2]), mp.sin(r[2])
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr], [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]], dtype=object)
+
+
+def _skew(a):
+    z = mpf(0)
+    return np.array([[z, -a[2], a[1]], [a[2], z, -a[0]], [-a[1], a[0], z]], dtype=object)
+
+
+def _cross(a, b):
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]], dtype=object)
+
+
+class Model:
+    """a serial chain from URDF text; every number of the file as a float64, made exact mpf where it is used"""
+
+    def __init__(self, text):
+        root = ET.fromstring(text)
+        self.links = {}
+        for l in root.findall("link"):
+            inn = l.find("inertial")
+            if inn is None:
+                self.links[l.get("name")] = None
+                continue
+            o, I = inn.find("origin"), inn.find("inertia")
+            g = lambda k: float(I.get(k, "0")) if I is not None else 0.0
+            self.links[l.get("name")] = dict(
+                m=float(inn.find("mass").get("value")), com=_nums(o.get("xyz") if o is not None else None, 3, [0, 0, 0]),
+                rpy=_nums(o.get("rpy") if o is not None else None, 3, [0, 0, 0]),
+                I=[[g("ixx"), g("ixy"), g("ixz")], [g("ixy"), g("iyy"), g("iyz")], [g("ixz"), g("iyz"), g("izz")]])
+        self.joints, children = [], set()
+        for j in root.findall("joint"):
+            o, ax, lim = j.find("origin"), j.find("axis"), j.find("limit")
+            self.joints.append(dict(type=j.get("type"), parent=j.find("parent").get("link"), child=j.find("child").get("link"),
+                                    xyz=_nums(o.get("xyz") if o is not None else None, 3, [0, 0, 0]),
+                                    rpy=_nums(o.get("rpy") if o is not None else None, 3, [0, 0, 0]),
+                                    axis=_nums(ax.get("xyz") if ax is not None else None, 3, [1, 0, 0]),
+                                    lower=float(lim.get("lower", "0")) if lim is not None else 0.0,
+                                    upper=float(lim.get("upper", "0")) if lim is not None else 0.0,
+                                    effort=float(lim.get("effort", "0")) if lim is not None else 0.0))
+            children.add(self.joints[-1]["child"])
+        (self.root,) = [n for n in self.links if n not in children]
+        self.order, cur = [], [self.root]  # joints parent before child
+        while cur:
+            nxt = []
+            for j in self.joints:
+                if j["parent"] in cur:
+                    self.order.append(j)
+                    nxt.append(j["child"])
+            cur = nxt
+        self.moving = [j for j in self.order if j["type"] != "fixed"]
+        self.dof = len(self.moving)
+        self.lower = np.array([j["lower"] for j in self.moving])
+        self.upper = np.array([j["upper"] for j in self.moving])
+        self.effort = np.array([j["effort"] for j in self.moving])
+
+    def poses(self, q):
+        """{link: (R, p, index of the last moving joint at or before it, -1 for none)}, per moving joint (axis, origin, type)"""
+        out = {self.root: (eye(3), zeros(3), -1)}
+        jinfo = [None] * self.dof
+        for j in self.order:
+            Rp, pp, mv = out[j["parent"]]
+            R, p = Rp @ _rpy([mpf(x) for x in j["rpy"]]), pp + Rp @ M_(j["xyz"])
+            if j["type"] != "fixed":
+                k = self.moving.index(j)
+                a = M_(j["axis"])
+                a = a / mp.sqrt(a @ a)
+                aw = R @ a
+                if j["type"] == "prismatic":
+                    p = p + aw * q[k]
+                else:
+                    K = _skew(a)
+                    R = R @ (eye(3) + mp.sin(q[k]) * K + (1 - mp.cos(q[k])) * (K @ K))
+                jinfo[k] = (aw, p, j["type"])
+                mv = k
+            out[j["child"]] = (R, p, mv)
+        return out, jinfo
+
+    def jacobian(self, pos, jinfo, link, point):
+        R, p, mv = pos[link]
+        x = p + R @ point
+        J = zeros(6, self.dof)
+        for k in range(mv + 1):
+            aw, o, typ = jinfo[k]
+            if typ == "prismatic":
+                J[:3, k] = aw
+            else:
+                J[:3, k] = _cross(aw, x - o)
+                J[3:, k] = aw
+        return J, x, R
+
+    def dynamics(self, q, gravity=(0, 0, -9.81)):
+        """pose tables, mass matrix M = sum_k m_k Jv^T Jv + Jw^T I_k Jw, gravity vector"""
+        pos, jinfo = self.poses(q)
+        n = self.dof
+        M, g = zeros(n, n), zeros(n)
+        gr = M_(gravity)
+        for name, body in self.links.items():
+            if body is None or pos[name][2] < 0:
+                continue
+            J, _, R = self.jacobian(pos, jinfo, name, M_(body["com"]))
+            Ro = R @ _rpy([mpf(x) for x in body["rpy"]])
+            Iw = Ro @ M_(body["I"]) @ Ro.T
+            m = mpf(body["m"])
+            M += m * (J[:3].T @ J[:3]) + J[3:].T @ Iw @ J[3:]
+            g -= m * (J[:3].T @ gr)
+        return pos, jinfo, M, g
+
+    def frame(self, pos, jinfo, task):
+        J, x, R = self.jacobian(pos, jinfo, task["link"], M_(task["point"]))
+        return J, x, R @ M_(task["frot"])
+
+
+def orientation_error(Rd, Rc):
+    e = zeros(3)
+    for i in range(3):
+        e = e - _cross(Rc[:, i], Rd[:, i]) / 2
+    return e
+
+
+def opspace(J, Minv):
+    L = inv(J @ Minv @ J.T)
+    Jbar = Minv @ J.T @ L
+    return L, Jbar, eye(Minv.shape[0]) - Jbar @ J
+
+
+def bie_minv(M, thr):
+    MB = M.copy()
+    for i in range(M.shape[0]):
+        if MB[i, i] < thr:
+            MB[i, i] = mpf(thr)
+    return inv(MB)
+
+
+def new_state(model, tasks):
+    """per MotionForceTask: the SingularityHandler's state after construction"""
+    return [dict(types=[], hist=[], c1=0, c2=0, q_prior=(M_(model.lower) + M_(model.upper)) / 2, t2dir=[1] * model.dof)
+            if t["kind"] == "mft" else None for t in tasks]
+
+
+def _mft_update(model, t, st, q, M, Minv, MiB, Jw, N_prec, pose0, pert, types_override, out):
+    n = model.dof
+    J = M_(t["P"]) @ Jw
+    Jp = J @ N_prec
+    out["Jp"] = Jp
+    if pert is not None:
+        Jp = Jp + pert["Jp"]
+    U, s, V = svd(Jp)
+    for j in range(V.shape[1]):
+        k = max(range(n), key=lambda i: abs(V[i, j]))
+        if V[k, j] < 0:
+            V[:, j], U[:, j] = -V[:, j], -U[:, j]
+    rank = min(t["rank"], len(s))
+    smin, smax = mpf(t["s_min"]), mpf(t["s_max"])
+    if s[0] < t["s_abs_tol"]:
+        alpha, split = mpf(0), 0
+    else:
+        alpha, split = mpf(1), rank
+        for i in range(1, rank):
+            rho = s[i] / s[0]
+            if rho < smax:
+                a = (rho - smin) / (smax - smin)
+                if "alpha_rel" in HOOKS:
+                    a = a * (1 + mpf(HOOKS["alpha_rel"]))
+                alpha, split = min(max(a, mpf(0)), mpf(1)), i
+                break
+    ns, sc = split, rank - split
+    m = dict(J=J, Jp=Jp, alpha=alpha, ns=ns, sc=sc, have_post=False, sv=s)
+    if ns:
+        m["U_ns"] = U[:, :ns]
+        m["J_ns"] = m["U_ns"].T @ Jp
+        m["L_ns"], _, m["N_ns"] = opspace(m["J_ns"], Minv)
+    if sc:
+        m["U_s"], m["V_s"] = U[:, split:rank], V[:, split:rank]
+        m["J_s"] = m["U_s"].T @ Jp
+        A = m["J_s"] @ Minv @ m["J_s"].T
+        m["L_s"] = sym_pinv(A) if ns == 0 or "pinv_ls" in HOOKS else inv(A)
+    if ns == 0:
+        Nt = N_prec
+    elif sc == 0 or not t["enforce_handling"]:
+        Nt = m["N_ns"]
+    else:
+        m["J_post"] = m["V_s"].T @ m["N_ns"] @ N_prec
+        m["L_joint"], _, Np = opspace(m["J_post"], Minv)
+        Nt = Np @ m["N_ns"]
+        m["have_post"] = True
+    dec = t["decoupling"]
+    for key, Jk, on in (("ns", "J_ns", ns), ("s", "J_s", sc), ("joint", "J_post", m["have_post"])):
+        if not on:
+            continue
+        if dec == IMPEDANCE:
+            m["Lm_" + key] = eye(m[Jk].shape[0])
+        elif dec == BIE:
+            m["Lm_" + key] = inv(m[Jk] @ MiB @ m[Jk].T)
+        else:
+            m["Lm_" + key] = m["L_" + key]
+    m["N_total"] = Nt @ N_prec
+    # classification (SingularityHandler.cpp:230-295)
+    if (len(st["types"]) == 0 or st["c2"] > st["c1"]) and "stale_q_prior" not in HOOKS:
+        st["q_prior"] = q.copy()
+    out["d1"] = []
+    if sc == 0:
+        st.update(types=[], hist=[], c1=0, c2=0)
+    else:
+        x0, R0 = pose0
+        types = []
+        for i in range(sc):
+            if types_override is not None:
+                types.append(types_override[i])
+                continue
+            moved, dmin = [], []
+            for step in (t["perturb"], -t["perturb"]):
+                qp = q + mpf(step) * m["V_s"][:, i]
+                pos, jinfo = model.poses(qp)
+                _, x1, R1 = model.frame(pos, jinfo, t)
+                d = np.concatenate([x1 - x0, orientation_error(R1, R0)])
+                dm = abs(d @ m["U_s"][:, i])
+                moved.append(dm > t["type1_tol"])
+                dmin.append(dm)
+            out["d1"] += dmin
+            sgn = t["sv_sign"]
+            t1 = {0: moved[0], 1: moved[1], 2: moved[0] or moved[1], 3: moved[0] and moved[1]}[sgn]
+            types.append(1 if t1 else 2)
+        st["types"] = types
+        st["hist"].append(1 if 1 in types else 2)
+        st["c1" if 1 in types else "c2"] += 1
+        if len(st["hist"]) > t["buffer"]:
+            st["c1" if st["hist"].pop(0) == 1 else "c2"] -= 1
+    out.update(s0=s[0], ratios=[x / s[0] for x in s], alpha=alpha, sc=sc, types=list(st["types"]), c1=st["c1"], c2=st["c2"])
+    return m
+
+
+def _mft_torques(model, t, st, m, q, dq, x, R, goal, out):
+    n = model.dof
+    if t["rank"] == 0:
+        return zeros(n)
+    P = M_(t["P"])
+    sp, so = P[:3, :3], P[3:, 3:]  # no force / moment space: sigma_position and sigma_orientation are the projections
+    J = m["J"]
+    v, w = J[:3] @ dq, J[3:] @ dq
+    gpos, grot = M_(goal["pos"]), M_(np.asarray(goal["rot"]).reshape(3, 3))
+    f_pos = sp @ (M_(goal["a"]) - M_(t["kp_pos"]) * (x - gpos) - M_(t["kv_pos"]) * (v - M_(goal["v"])))
+    step = so @ orientation_error(grot, R)
+    f_ori = so @ (M_(goal["alpha"]) - M_(t["kp_ori"]) * step - M_(t["kv_ori"]) * (w - M_(goal["w"])))
+    Fu = np.concatenate([f_pos, f_ori])
+    ns, sc = m["ns"], m["sc"]
+    if len(st["types"]) == 0:
+        return m["J_ns"].T @ (m["Lm_ns"] @ (m["U_ns"].T @ Fu)) if ns else zeros(n)
+    if t["decoupling"] == IMPEDANCE:
+        return m["J_ns"].T @ (m["U_ns"].T @ Fu) if ns else zeros(n)
+    if ns == 0:
+        return zeros(n)
+    tau_ns = m["J_ns"].T @ (m["Lm_ns"] @ (m["U_ns"].T @ Fu))
+    if not t["enforce_handling"]:
+        return tau_ns
+    V_s, J_post, Lj = m["V_s"], m["J_post"], m["Lm_joint"]
+    if st["c1"] > st["c2"] or t["enforce_type_1"]:
+        ut = -mpf(t["kp1"]) * (q - st["q_prior"]) - mpf(t["kv1"]) * dq
+        tau_j = J_post.T @ (Lj @ (V_s.T @ ut))
+        out["branch"] = 1
+    else:
+        lo, hi = model.lower, model.upper
+        for i in range(n):
+            if V_s[i, 0] != 0:
+                if abs(q[i] - mpf(hi[i])) < t["t2_angle"]:
+                    st["t2dir"][i] = -1
+                elif abs(q[i] - mpf(lo[i])) < t["t2_angle"]:
+                    st["t2dir"][i] = 1
+        nF = mp.sqrt(Fu @ Fu)
+        fTd = (Fu / nF if nF > 0 else Fu) @ m["U_s"][:, 0]
+        ut = np.array([st["t2dir"][i] * abs(fTd) * mpf(t["t2_ratio"]) * mpf(model.effort[i]) for i in range(n)], dtype=object)
+        Vt = -V_s if "flip_vs_type2" in HOOKS else V_s
+        kv2 = t["kv1"] if "kv1_for_kv2" in HOOKS else t["kv2"]
+        tau_j = J_post.T @ (Vt.T @ ut) + J_post.T @ (Lj @ (V_s.T @ (-mpf(kv2) * dq)))
+        out["branch"] = 2
+    tau_s = m["J_s"].T @ (m["Lm_s"] @ (m["U_s"].T @ Fu))
+    eff = M_(model.effort)
+    out["clamped"] = int(sum(abs(tau_s[i]) > eff[i] for i in range(n)))
+    if "no_clamp" not in HOOKS:
+        tau_s = np.array([min(max(tau_s[i], -eff[i]), eff[i]) for i in range(n)], dtype=object)
+    a = m["alpha"]
+    return tau_ns + a * tau_s + (1 - a) * tau_j
+
+
+def _jt_update(t, M, Minv, MiB, N_prec, out):
+    n = M.shape[0]
+    S = M_(t["S"])
+    Jp = S @ N_prec
+    U, s, _ = svd(Jp)
+    out["range_ratio"] = [x / s[0] for x in s[1:]]
+    k = len(s)
+    for i in range(len(s) - 1, 0, -1):  # the range basis of sai2-model, tolerance 1e-3 on s_i / s_0
+        if s[i] / s[0] < 1e-3:
+            k -= 1
+        else:
+            break
+    if s[0] < 1e-3:
+        return dict(k=0, N_total=eye(n) @ N_prec, Jp=Jp)
+    Rb = eye(S.shape[0]) if k == S.shape[0] else U[:, :k]
+    Jr = Rb.T @ Jp
+    Mp, _, N = opspace(Jr, Minv)
+    dec = t["decoupling"]
+    Mpm = Mp if dec == FULL else (inv(Jr @ MiB @ Jr.T) if dec == BIE else eye(k))
+    return dict(k=k, Rb=Rb, Jp=Jp, Mp=Mp, Mpm=Mpm, S=S, N_total=N @ N_prec)
+
+
+def _jt_torques(t, m, q, dq, Minv, tau_prec, goal):
+    n = len(q)
+    if m["k"] == 0:
+        return zeros(n)
+    S, Rb, Jp = m["S"], m["Rb"], m["Jp"]
+    f = -M_(t["kp"]) * (S @ q - M_(goal["q"])) - M_(t["kv"]) * (S @ dq - M_(goal["dq"]))
+    xx = m["Mp"] @ (Rb.T @ M_(goal["ddq"])) + m["Mpm"] @ (Rb.T @ f)
+    tau = Jp.T @ (Rb @ xx)
+    return tau - Jp.T @ (Rb @ (m["Mp"] @ (Rb.T @ (S @ (Minv @ tau_prec)))))
+
+
+def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=None):
+    """one tick of the hierarchy: update_task_models() then compute_control_torques() with the compensation terms.
+    state (new_state) is advanced. pert: additive perturbations of the model quantities {M, Jp[t], x[t], R[t], dq}.
+    types_override[t]: the types of the classification (the perturbed re-evaluations keep the unperturbed decisions).
+    kin: the FK quantities of an earlier call at the same q. Returns (tau, info per task, kin)."""
+    q, dq = M_(q), M_(dq)
+    if kin is None:
+        pos, jinfo, M, g = model.dynamics(q)
+        frames = [model.frame(pos, jinfo, t) if t["kind"] == "mft" else None for t in tasks]
+        kin = dict(M=M, g=g, frames=frames)
+    M = kin["M"]
+    frames = list(kin["frames"])
+    if pert is not None:
+        M = M + pert["M"]
+        dq = dq + pert["dq"]
+        frames = [None if f is None else (f[0], f[1] + pert["x"][t], f[2] + pert["R"][t]) for t, f in enumerate(frames)]
+    Minv = inv(M)
+    MiB = {}
+    n = model.dof
+    N_prec = eye(n)
+    info, mods = [], []
+    for ti, t in enumerate(tasks):
+        out = {}
+        thr = t["bie"]
+        if thr not in MiB:
+            MiB[thr] = bie_minv(M, thr)
+        if t["kind"] == "mft":
+            Jw, x, R = frames[ti]
+            p = None if pert is None else dict(Jp=pert["Jp"][ti])
+            unpert = kin["frames"][ti]
+            m = _mft_update(model, t, state[ti], q, M, Minv, MiB[thr], Jw, N_prec, (unpert[1], unpert[2]), p,
+                            None if types_override is None else types_override[ti], out)
+        else:
+            m = _jt_update(t, M, Minv, MiB[thr], N_prec, out)
+        N_prec = m["N_total"]
+        mods.append(m)
+        info.append(out)
+    tau = zeros(n)
+    for ti, t in enumerate(tasks):
+        if t["kind"] == "mft":
+            Jw, x, R = frames[ti]
+            tt = _mft_torques(model, t, state[ti], mods[ti], q, dq, x, R, goals[ti], info[ti])
+        else:
+            tt = _jt_torques(t, mods[ti], q, dq, Minv, tau, goals[ti])
+        tau = tau + tt
+    return tau, info, kin
+
+
+def _sym_dir(rng, n):
+    A = rng.standard_normal((n, n))
+    return A + A.T
+
+
+def perturbation(rng, kin, tasks, dq, Jps):
+    """one seeded random direction: every model quantity moved normwise by eps times its own norm"""
+
+    def scaled(d, ref):
+        d = M_(d)
+        return d * (mpf(EPS) * norm_fro(ref) / norm_fro(d))
+
+    n = kin["M"].shape[0]
+    p = dict(M=scaled(_sym_dir(rng, n), kin["M"]), dq=scaled(rng.standard_normal(n), M_(dq)) if np.any(dq) else zeros(n),
+             Jp=[], x=[], R=[])
+    for t, f in enumerate(kin["frames"]):
+        if f is None:
+            p["Jp"].append(None), p["x"].append(None), p["R"].append(None)
+            continue
+        p["Jp"].append(scaled(rng.standard_normal((6, n)), Jps[t]))
+        p["x"].append(scaled(rng.standard_normal(3), f[1]))
+        p["R"].append(scaled(rng.standard_normal((3, 3)), f[2]))
+    return p
+
+
+def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, dirs=16):
+    """max over `dirs` seeded directions of ||dtau||_inf / (eps max(||tau||_inf, 1)): the error one ulp of noise in M,
+    J N_prec, x / R and dq causes, the classification held at the unperturbed decisions"""
+    rng = np.random.default_rng(seed)
+    Jps = [i.get("Jp") for i in info]
+    types = [None if i is None or "types" not in i else i["types"] for i in info]
+    worst = mpf(0)
+    for _ in range(dirs):
+        st = copy.deepcopy(state_before)
+        p = perturbation(rng, kin, tasks, dq, Jps)
+        tp, _, _ = tick(model, tasks, st, q, dq, goals, pert=p, types_override=types, kin=kin)
+        worst = max(worst, norm_inf(tp - tau))
+    return float(worst / (mpf(EPS) * max(norm_inf(tau), mpf(1))))
+
