@@ -50,9 +50,14 @@ def truth_tasks(cell):
     c = CELLS[cell]
     _, links = product_model(c["robot"])
     cfgs = product_configs(cell, pkg.joint_task_config, pkg.motion_force_task_config, links)
+    return config_tasks(cfgs, hierarchy(c["hier"], cfgs[0].robot_dof))
+
+
+def config_tasks(cfgs, specs):
+    """task configs and their hierarchy specs -> the tasks as hp_reference takes them"""
     n = cfgs[0].robot_dof
     out = []
-    for cfg, spec in zip(cfgs, hierarchy(c["hier"], n)):
+    for cfg, spec in zip(cfgs, specs):
         common = dict(decoupling=int(cfg.dynamic_decoupling_type), bie=float(cfg.bie_threshold))
         if spec[0] == "jt":
             k0 = cfg.task_dof

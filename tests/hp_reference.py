@@ -16,8 +16,14 @@ Lambda_joint for full dynamic decoupling, BIE and impedance; the type-1 / type-2
 the singular-vector-sign setting; the history ring and its counters, q_prior, the type-2 joint-limit directions; the
 effort clamp of tau_s and tau = tau_ns + alpha tau_s + (1 - alpha) tau_joint.
 
-HOOKS plants errors for tests/test_hp_reference.py (each must be caught by the checker): alpha_rel, flip_vs_type2,
-no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior."""
+The rigid-body dynamics of the simulation harness (csrc/sai2b_sim.hip), derived without a Newton-Euler recursion:
+bias() sums b = C(q, dq) dq + g(q) over the bodies from their velocity-product accelerations, found by differentiating
+the body poses along q + t dq; bias_lagrange() is the Lagrangian form from derivatives of M; sim_step() restates the
+integrator (the torque held over the period, `substeps` semi-implicit Euler steps).
+
+HOOKS plants errors for tests/test_hp_reference.py and tests/test_hp_dynamics.py (each must be caught by the checker):
+alpha_rel, flip_vs_type2, no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior; pris_coriolis_half, no_gyroscopic,
+explicit_euler."""
 import copy
 import re
 import xml.etree.ElementTree as ET
@@ -103,7 +109,14 @@ def _cross(a, b):
 class Model:
     """a serial chain from URDF text; every number of the file as a float64, made exact mpf where it is used"""
 
-    def __init__(self, text):
+    def __init__(self, text, base=None):
+        """base: (position, rotation) of the root link in the world (Sai2Model::setTRobotBase), float64 numbers; the
+        rotation is taken as the orthogonal matrix nearest to it (U V^T of its SVD, at the working precision): a rigid
+        motion, as the product's own (it keeps the base as roll-pitch-yaw angles)"""
+        if base is not None:
+            U, _, V = svd(M_(base[1]))
+            base = (M_(base[0]), U @ V.T)
+        self.base = base
         root = ET.fromstring(text)
         self.links = {}
         for l in root.findall("link"):
@@ -145,7 +158,7 @@ class Model:
 
     def poses(self, q):
         """{link: (R, p, index of the last moving joint at or before it, -1 for none)}, per moving joint (axis, origin, type)"""
-        out = {self.root: (eye(3), zeros(3), -1)}
+        out = {self.root: (eye(3), zeros(3), -1) if self.base is None else (self.base[1], self.base[0], -1)}
         jinfo = [None] * self.dof
         for j in self.order:
             Rp, pp, mv = out[j["parent"]]
@@ -404,8 +417,9 @@ def _jt_torques(t, m, q, dq, Minv, tau_prec, goal):
     return tau - Jp.T @ (Rb @ (m["Mp"] @ (Rb.T @ (S @ (Minv @ tau_prec)))))
 
 
-def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=None):
-    """one tick of the hierarchy: update_task_models() then compute_control_torques() with the compensation terms.
+def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=None, gravity_comp=False):
+    """one tick of the hierarchy: update_task_models() then compute_control_torques() with the compensation terms,
+    g(q) added when gravity_comp (RobotController.cpp:70-72).
     state (new_state) is advanced. pert: additive perturbations of the model quantities {M, Jp[t], x[t], R[t], dq}.
     types_override[t]: the types of the classification (the perturbed re-evaluations keep the unperturbed decisions).
     kin: the FK quantities of an earlier call at the same q. Returns (tau, info per task, kin)."""
@@ -449,6 +463,8 @@ def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=
         else:
             tt = _jt_torques(t, mods[ti], q, dq, Minv, tau, goals[ti])
         tau = tau + tt
+    if gravity_comp:
+        tau = tau + kin["g"]
     return tau, info, kin
 
 
@@ -477,7 +493,7 @@ def perturbation(rng, kin, tasks, dq, Jps):
     return p
 
 
-def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, dirs=16):
+def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, dirs=16, gravity_comp=False):
     """max over `dirs` seeded directions of ||dtau||_inf / (eps max(||tau||_inf, 1)): the error one ulp of noise in M,
     J N_prec, x / R and dq causes, the classification held at the unperturbed decisions"""
     rng = np.random.default_rng(seed)
@@ -487,7 +503,135 @@ def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, di
     for _ in range(dirs):
         st = copy.deepcopy(state_before)
         p = perturbation(rng, kin, tasks, dq, Jps)
-        tp, _, _ = tick(model, tasks, st, q, dq, goals, pert=p, types_override=types, kin=kin)
+        tp, _, _ = tick(model, tasks, st, q, dq, goals, pert=p, types_override=types, kin=kin, gravity_comp=gravity_comp)
         worst = max(worst, norm_inf(tp - tau))
     return float(worst / (mpf(EPS) * max(norm_inf(tau), mpf(1))))
 
+
+
+# ---- rigid-body dynamics: the simulation harness (csrc/sai2b_sim.hip) ----
+
+GRAVITY = (0, 0, -9.81)
+
+
+def _stencil(f, dps, second=False):
+    """df/dt at t = 0 (and d^2f/dt^2 when second; f returns a flat object array): five-point central differences,
+    evaluated at the extra precision that puts their truncation (h^4) and their cancellation both far below 10^-dps"""
+    with mp.workdps(dps * 2 + 20):
+        h = mpf(10) ** -(dps // 4 + 4)
+        fm2, fm1, fp1, fp2 = f(-2 * h), f(-h), f(h), f(2 * h)
+        d1 = (fm2 - 8 * fm1 + 8 * fp1 - fp2) / (12 * h)
+        d2 = (-fm2 + 16 * fm1 - 30 * f(mpf(0)) + 16 * fp1 - fp2) / (12 * h * h) if second else None
+    rnd = lambda d: np.array([+x for x in d], dtype=object)  # rounded to the working precision
+    return (rnd(d1), rnd(d2)) if second else rnd(d1)
+
+
+def _bodies(model, q):
+    """per body hanging on a moving joint: (mass, COM Jacobian 6 x n, world inertia about the COM)"""
+    pos, jinfo = model.poses(q)
+    out = []
+    for name, body in model.links.items():
+        if body is None or pos[name][2] < 0:
+            continue
+        J, _, R = model.jacobian(pos, jinfo, name, M_(body["com"]))
+        Ro = R @ _rpy([mpf(x) for x in body["rpy"]])
+        out.append((name, mpf(body["m"]), J, Ro @ M_(body["I"]) @ Ro.T))
+    return out
+
+
+def _body_motion(model, q, v):
+    """f(t) along q + t v: every body's COM position and angular velocity (with velocity v) stacked, flat"""
+
+    def f(t):
+        qt = q + t * v
+        pos, jinfo = model.poses(qt)
+        parts = []
+        for name, body in model.links.items():
+            if body is None or pos[name][2] < 0:
+                continue
+            R, p, mv = pos[name]
+            w = zeros(3)
+            for k in range(mv + 1):
+                if jinfo[k][2] != "prismatic":
+                    w = w + jinfo[k][0] * v[k]
+            parts += list(p + R @ M_(body["com"])) + list(w)
+        return np.array(parts, dtype=object)
+
+    return f
+
+
+def bias_terms(model, q, dq, gravity=None):
+    """b = sum_k Jv_k^T m_k a_k + Jw_k^T (I_k al_k + w_k x I_k w_k) - m_k Jv_k^T gravity, with a_k, al_k the COM and
+    angular accelerations of body k at qdd = 0 (derivatives of the body poses along q + t dq). Returns (b, beta):
+    beta[i] = the sum of the absolute values of the products b[i] is summed from (the forward-error scale)"""
+    q, dq = M_(q), M_(dq)
+    n = model.dof
+    dps = mp.dps
+    bodies = _bodies(model, q)
+    d1, d2 = _stencil(_body_motion(model, q, dq), dps, second=True)
+    acc, alpha = d2.reshape(-1, 6)[:, :3], d1.reshape(-1, 6)[:, 3:]
+    if "pris_coriolis_half" in HOOKS:  # the part of a_k bilinear in revolute and prismatic velocities, halved
+        pris = np.array([j["type"] == "prismatic" for j in model.moving])
+        vr, vp = dq.copy(), dq.copy()
+        vr[pris], vp[~pris] = mpf(0), mpf(0)
+        ar = _stencil(_body_motion(model, q, vr), dps, second=True)[1].reshape(-1, 6)[:, :3]
+        ap = _stencil(_body_motion(model, q, vp), dps, second=True)[1].reshape(-1, 6)[:, :3]
+        acc = ar + ap + (acc - ar - ap) / 2
+    b, beta = zeros(n), zeros(n)
+    gr = M_(GRAVITY if gravity is None else gravity) if gravity is not False else zeros(3)
+    for k, (_, m, J, Iw) in enumerate(bodies):
+        Jv, Jw = J[:3], J[3:]
+        w = Jw @ dq
+        Ia = Iw @ alpha[k]
+        gyro = _cross(w, Iw @ w) if "no_gyroscopic" not in HOOKS else zeros(3)
+        for vec, Jx in ((m * acc[k], Jv), (Ia, Jw), (gyro, Jw), (-m * gr, Jv)):
+            b += Jx.T @ vec
+            beta += np.abs(Jx).T @ np.abs(vec)
+    return b, beta
+
+
+def bias(model, q, dq, gravity=None):
+    """b = C(q, dq) dq + g(q); gravity None: the model's (0, 0, -9.81), False: none"""
+    return bias_terms(model, q, dq, gravity)[0]
+
+
+def bias_lagrange(model, q, dq, gravity=None):
+    """the Lagrangian form b_i = sum_jk dM_ij/dq_k dq_k dq_j - 1/2 dq^T dM/dq_i dq + g_i, derivatives of M"""
+    q, dq = M_(q), M_(dq)
+    n = model.dof
+    dps = mp.dps
+    Mf = lambda v: (lambda t: model.dynamics(q + t * v)[2].ravel())
+    Mdot = _stencil(Mf(dq), dps).reshape(n, n)
+    b = Mdot @ dq
+    for i in range(n):
+        e = zeros(n)
+        e[i] = mpf(1)
+        b[i] -= dq @ _stencil(Mf(e), dps).reshape(n, n) @ dq / 2
+    if gravity is not False:
+        b = b + model.dynamics(q, GRAVITY if gravity is None else gravity)[3]
+    return b
+
+
+def solve(M, r):
+    return np.array(list(mp.lu_solve(mp.matrix(M.tolist()), mp.matrix(list(r)))), dtype=object)
+
+
+def sim_step(model, q, dq, tau, dt, substeps, gravity, info=None):
+    """one control period of csrc/sai2b_sim.hip: tau held, `substeps` semi-implicit Euler steps of h = dt / substeps,
+    dq += h M^-1 (tau - b), q += h dq (b with g when gravity). Returns (q, dq). info: a list, per step appended
+    cond_2(M), ||M^-1||_2, ||M^-1 (tau - b)||_inf and ||beta||_inf of the bias"""
+    q, dq, tau = M_(q), M_(dq), M_(tau)
+    h = mpf(dt) / substeps
+    for _ in range(substeps):
+        M = model.dynamics(q)[2]
+        b, beta = bias_terms(model, q, dq, None if gravity else False)
+        x = solve(M, tau - b)
+        if info is not None:
+            with mp.workdps(20):
+                ev = mp.eigsy(mp.matrix(M.tolist()), eigvals_only=True)
+                lo, hi = min(ev), max(ev)
+                info.append(dict(cond=float(hi / lo), minv=float(1 / lo), x=float(norm_inf(x)), beta=float(norm_inf(beta))))
+        dq_old = dq
+        dq = dq + h * x
+        q = q + h * (dq_old if "explicit_euler" in HOOKS else dq)
+    return q, dq

@@ -6,7 +6,14 @@ under tests/golden/urdf/):
   planar_4r    : examples/11-planar_robot_controller/rrrrbot.urdf — four 0.5 m links, 1 kg each, joints about z
   six_r        : a 6R arm of PUMA-like geometry (wrist links heavier than a PUMA's: a closed loop on 1e-5 kg m^2 inertias amplifies rounding by the period) (the robot of examples/01-joint_control; its URDF lives in sai2-model's
                  resources, outside the reference tree: geometry and inertias here are ours), joint axes about z, y, y,
-                 x, y, x of the link frames — every non-z axis goes through the loader's axis folding"""
+                 x, y, x of the link frames — every non-z axis goes through the loader's axis folding
+Robots with prismatic joints inside the chain (ours, numbers and all): what the hardest terms of the prismatic branches
+are multiplied by is never zero on them (tests/test_hp_dynamics.py, tests/test_gpu_hp_dynamics.py)
+  rprp_4       : R P R P; a slide behind a revolute joint, a prismatic last joint with nothing outboard of it, every
+                 axis folded or tilted by an rpy offset so that none is parallel to gravity or to another
+  stanford_6   : R R P R R R (Stanford-arm layout): the boom slides along a folded x axis behind an rpy offset, a
+                 three-joint wrist outboard of it
+  slider_7     : R R R P R R R: seven joints that are not the Panda (the non-baked N=7 kernels), a slide mid-chain"""
 import sai2_primitives_perso_amd as pkg
 
 PANDA_LINKS = [dict(m=3, c=(0, 0, -0.07), i=(0.3, 0.3, 0.3)), dict(m=3, c=(0, -0.1, 0), i=(0.3, 0.3, 0.3)),
@@ -72,4 +79,54 @@ def six_r_urdf():
     return "\n".join(out)
 
 
-TEXT = {"sliding_base": sliding_base_urdf, "planar_4r": planar_4r_urdf, "six_r": six_r_urdf}
+def _chain(name, base, links, joints):
+    """base: (m, c, i); links: [(m, c, i)] one per joint; joints: [(type, xyz, rpy, axis, lower, upper, effort)]"""
+    out = [f'<robot name="{name}">', _link("base", *base)]
+    for k, r in enumerate(links):
+        out.append(_link(f"link{k + 1}", *r))
+    for k, (typ, xyz, rpy, axis, lo, hi, eff) in enumerate(joints):
+        out.append(_joint(f"j{k + 1}", typ, "base" if k == 0 else f"link{k}", f"link{k + 1}", xyz, rpy, axis, lo, hi, eff))
+    out.append("</robot>")
+    return "\n".join(out)
+
+
+def rprp_4_urdf():
+    links = [(4.0, (0.05, 0.0, 0.1), (0.08, 0.07, 0.05)), (2.5, (0.0, 0.04, 0.05), (0.04, 0.03, 0.035)),
+             (1.8, (0.06, 0.0, 0.02), (0.025, 0.03, 0.02)), (1.2, (0.03, 0.01, 0.0), (0.012, 0.015, 0.01))]
+    joints = [("revolute", (0, 0, 0.3), (0, 0.3, 0), (1, 0, 0), -2.5, 2.5, 120.0),
+              ("prismatic", (0.1, 0, 0.2), (0.2, 0, 0.1), (0, 1, 0), -0.3, 0.3, 200.0),
+              ("revolute", (0, 0.15, 0.1), (0, 0.4, 0.2), (0, 0, 1), -2.5, 2.5, 80.0),
+              ("prismatic", (0.2, 0, 0), (0.3, 0, 0), (1, 0, 0), -0.2, 0.2, 150.0)]
+    return _chain("rprp_4", (6.0, (0, 0, 0.1), (0.1, 0.1, 0.1)), links, joints)
+
+
+def stanford_6_urdf():
+    links = [(9.0, (0, 0, 0.1), (0.2, 0.2, 0.1)), (6.0, (0, 0.05, 0.08), (0.12, 0.1, 0.06)),
+             (3.0, (0.2, 0, 0), (0.02, 0.09, 0.09)), (1.4, (0.02, 0, 0), (0.012, 0.009, 0.01)),
+             (1.0, (0, 0.01, 0.02), (0.008, 0.007, 0.006)), (0.7, (0.03, 0, 0), (0.005, 0.006, 0.006))]
+    joints = [("revolute", (0, 0, 0.4), (0, 0, 0), (0, 0, 1), -2.8, 2.8, 150.0),
+              ("revolute", (0, 0.12, 0.25), (0, 0, 0), (0, 1, 0), -1.6, 1.6, 150.0),
+              ("prismatic", (0.15, 0.05, 0.1), (0, 0.2, 0.1), (1, 0, 0), -0.15, 0.35, 250.0),
+              ("revolute", (0.45, 0, 0), (0, 0, 0), (1, 0, 0), -2.6, 2.6, 30.0),
+              ("revolute", (0.08, 0, 0), (0.1, 0, 0), (0, 1, 0), -1.7, 1.7, 25.0),
+              ("revolute", (0.07, 0, 0), (0, 0, 0), (1, 0, 0), -3.0, 3.0, 20.0)]
+    return _chain("stanford_6", (12.0, (0, 0, 0.15), (0.4, 0.4, 0.2)), links, joints)
+
+
+def slider_7_urdf():
+    links = [(6.0, (0, 0, 0.1), (0.12, 0.12, 0.06)), (5.0, (0, 0.06, 0.1), (0.1, 0.08, 0.05)),
+             (3.5, (0.02, 0, 0.12), (0.06, 0.06, 0.03)), (2.5, (0, 0.05, 0.04), (0.03, 0.025, 0.03)),
+             (1.6, (0.03, 0, 0.05), (0.015, 0.012, 0.01)), (1.1, (0, 0.02, 0.03), (0.009, 0.008, 0.007)),
+             (0.8, (0.02, 0, 0.02), (0.006, 0.006, 0.005))]
+    joints = [("revolute", (0, 0, 0.33), (0, 0, 0), (0, 0, 1), -2.8, 2.8, 87.0),
+              ("revolute", (0, 0, 0.12), (0, 0, 0), (0, 1, 0), -1.7, 1.7, 87.0),
+              ("revolute", (0, 0, 0.3), (0, 0, 0.1), (0, 0, 1), -2.8, 2.8, 87.0),
+              ("prismatic", (0.05, 0, 0.1), (0.3, 0, 0), (0, 1, 0), -0.2, 0.2, 200.0),
+              ("revolute", (0, 0, 0.25), (0, 0, 0), (1, 0, 0), -2.6, 2.6, 12.0),
+              ("revolute", (0, 0, 0.12), (0, 0, 0), (0, 1, 0), -1.8, 1.8, 12.0),
+              ("revolute", (0.06, 0, 0.05), (0, -0.2, 0), (0, 0, 1), -2.8, 2.8, 12.0)]
+    return _chain("slider_7", (8.0, (0, 0, 0.1), (0.2, 0.2, 0.1)), links, joints)
+
+
+TEXT = {"sliding_base": sliding_base_urdf, "planar_4r": planar_4r_urdf, "six_r": six_r_urdf, "rprp_4": rprp_4_urdf,
+        "stanford_6": stanford_6_urdf, "slider_7": slider_7_urdf}

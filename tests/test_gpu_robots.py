@@ -2,8 +2,9 @@
 base with the hierarchy of examples/06-partial_joint_task/06-partial_joint_task.cpp:107-125 ([partial JointTask on
 the slider and the last joint, MotionForceTask, full JointTask]) and the planar 4R with the planar MotionForceTask
 of examples/11-planar_robot_controller/11-planar_robot_controller.cpp:108-125 (+ JointTask), against the CPU oracle
-built for that robot size. The models themselves are pinned against an independent numpy reading of the URDFs in
-tests/test_urdf.py."""
+built for that robot size; the same for the 6R arm and the robots with prismatic joints inside the chain (rprp_4,
+stanford_6, slider_7: the hierarchies of their tick cells in tests/golden/hp_dynamics.npz). The models themselves are
+pinned against an independent numpy reading of the URDFs in tests/test_urdf.py."""
 import os
 
 import numpy as np
@@ -52,6 +53,24 @@ def _setup(robot, B, otg, introspection, seed=0, q=None, mft6_alone=False):
         mk = lambda mod, cfg_j, cfg_m: [cfg_m("motion_force_task", link, fpos, frot, partial, internal_otg=otg, robot_dof=n),
                                         cfg_j("joint_task", None, internal_otg=otg, robot_dof=n)]
         kinds = ["mft", "jt"]
+    elif robot in ("rprp_4", "stanford_6"):
+        # the hierarchy of their tick cells in tests/golden/hp_dynamics.npz: a position task and the joint task behind it
+        link, fpos, frot = pkg.resolve_link_frame(links, f"link{n}", (0.05, 0.0, 0.02))
+        partial = (np.eye(3), np.zeros((0, 3)))
+        mk = lambda mod, cfg_j, cfg_m: [cfg_m("motion_force_task", link, fpos, frot, partial, internal_otg=otg, robot_dof=n),
+                                        cfg_j("joint_task", None, internal_otg=otg, robot_dof=n)]
+        kinds = ["mft", "jt"]
+    elif robot == "slider_7":
+        # C4's three levels on a 7-joint robot that is not the Panda: position MotionForceTask, JointTask on the first
+        # and last joints, full JointTask
+        link, fpos, frot = pkg.resolve_link_frame(links, "link7", (0.0, 0.0, 0.1))
+        sel = np.zeros((2, n))
+        sel[0, 0] = sel[1, n - 1] = 1
+        partial = (np.eye(3), np.zeros((0, 3)))
+        mk = lambda mod, cfg_j, cfg_m: [cfg_m("motion_force_task", link, fpos, frot, partial, internal_otg=otg, robot_dof=n),
+                                        cfg_j("partial_joint_task", sel, internal_otg=otg, robot_dof=n),
+                                        cfg_j("joint_task", None, internal_otg=otg, robot_dof=n)]
+        kinds = ["mft", "jt", "jt"]
     else:
         link, fpos, frot = pkg.resolve_link_frame(links, "link4", (0.5, 0.0, 0.0))
         partial = (np.array([[1.0, 0, 0], [0, 1.0, 0]]), np.array([[0, 0, 1.0]]))
