@@ -121,6 +121,43 @@ public:
 	const Batch& dq() const { return _dq; }
 	// Sai2Model::updateModel(): the model update is fused into the tick kernel; this pushes the state
 	inline void updateModel();
+	// What each robot of the batch carries (sai2b.h "per-robot payloads"): one rigid body on moving link `link`, per robot
+	// mass [B], com [3][B] in the link's frame (empty: zeros), inertia [6][B] about the body's COM in link axes, ixx iyy izz
+	// ixy ixz iyz (empty: a point mass). Where the reference gives each robot its own Sai2Model, the batch shares one and
+	// differs in these rows. target: SAI2B_PAYLOAD_CONTROLLER / _PLANT / _BOTH. Kept for controllers and tasks built later.
+	inline void setLinkPayload(int link, const Batch& mass, const Batch& com = Batch(), const Batch& inertia = Batch(),
+							   int target = SAI2B_PAYLOAD_BOTH);
+	// the same by URDF link NAME and a pose of the payload's frame in it (rot_in_link row-major 3 x 3, nullptr = identity): a
+	// body behind fixed joints (e.g. "end-effector") resolves to its moving link, COM and inertia re-expressed in it
+	void setLinkPayload(const std::string& link_name, const double pos_in_link[3], const double* rot_in_link, const Batch& mass,
+						const Batch& com = Batch(), const Batch& inertia = Batch(), int target = SAI2B_PAYLOAD_BOTH) {
+		double fp[3], R[9];
+		const double zero[3] = {0, 0, 0};
+		const int link = resolveLink(link_name, pos_in_link ? pos_in_link : zero, rot_in_link, fp, R);
+		const size_t B = (size_t)_batch;
+		if ((!com.empty() && com.size() != 3 * B) || (!inertia.empty() && inertia.size() != 6 * B))
+			throw std::invalid_argument("setLinkPayload: com must be [3][B] and inertia [6][B]");
+		Batch c(3 * B), I;
+		for (size_t b = 0; b < B; b++)
+			for (int i = 0; i < 3; i++) {
+				double v = fp[i];
+				for (int j = 0; j < 3 && !com.empty(); j++) v += R[3 * i + j] * com[j * B + b];
+				c[i * B + b] = v;
+			}
+		if (!inertia.empty()) {
+			I.resize(6 * B);
+			const int ia[6] = {0, 1, 2, 0, 0, 1}, ib[6] = {0, 1, 2, 1, 2, 2}, at[9] = {0, 3, 4, 3, 1, 5, 4, 5, 2};
+			for (size_t b = 0; b < B; b++)
+				for (int e = 0; e < 6; e++) {  // (R I R^T)[ia][ib]
+					double v = 0;
+					for (int k = 0; k < 3; k++)
+						for (int l = 0; l < 3; l++) v += R[3 * ia[e] + k] * inertia[at[3 * k + l] * B + b] * R[3 * ib[e] + l];
+					I[e * B + b] = v;
+				}
+		}
+		setLinkPayload(link, mass, c, I, target);
+	}
+	inline void clearLinkPayload(int target = SAI2B_PAYLOAD_BOTH);
 
 private:
 	friend class RobotController;
@@ -132,6 +169,20 @@ private:
 	void resizeState() {
 		_q.assign((size_t)_model.dof * _batch, 0.0);
 		_dq.assign((size_t)_model.dof * _batch, 0.0);
+	}
+	struct LinkPayload {
+		bool set = false;
+		int link = 0;
+		Batch mass, com, inertia;
+	};
+	LinkPayload _payload[2];  // controller, plant
+	void applyPayloads(sai2b_ctx* c, int target) const {
+		for (int s = 0; s < 2; s++) {
+			const LinkPayload& p = _payload[s];
+			if (!(target & (1 << s)) || !p.set) continue;
+			detail::check(c, sai2b_set_link_payload(c, 1 << s, p.link, p.mass.data(), p.com.empty() ? nullptr : p.com.data(),
+													p.inertia.empty() ? nullptr : p.inertia.data(), 0));
+		}
 	}
 	std::vector<sai2b_ctx*> _standalone;  // contexts of tasks driven on their own (TemplateTask-level calls)
 	int _batch, _device;
@@ -884,6 +935,7 @@ public:
 		}
 		_tasks = tasks;
 		robot->_controller = this;
+		robot->applyPayloads(_ctx, SAI2B_PAYLOAD_BOTH);
 		detail::check(_ctx, sai2b_set_state(_ctx, robot->q().data(), robot->dq().data(), 0));
 		detail::check(_ctx, sai2b_reinitialize(_ctx));	// tasks are constructed at the model's current state
 		for (size_t i = 0; i < _tasks.size(); i++) {
@@ -953,6 +1005,23 @@ inline void BatchedRobotModel::updateModel() {
 	if (_controller) detail::check(_controller->ctx(), sai2b_set_state(_controller->ctx(), _q.data(), _dq.data(), 0));
 	for (sai2b_ctx* c : _standalone) detail::check(c, sai2b_set_state(c, _q.data(), _dq.data(), 0));
 }
+inline void BatchedRobotModel::setLinkPayload(int link, const Batch& mass, const Batch& com, const Batch& inertia, int target) {
+	const size_t B = (size_t)_batch;
+	if (target < 1 || target > 3) throw std::invalid_argument("setLinkPayload: bad target");
+	if (link < 0 || link >= _model.dof) throw std::invalid_argument("setLinkPayload: link must be in [0, dof)");
+	if (mass.size() != B || (!com.empty() && com.size() != 3 * B) || (!inertia.empty() && inertia.size() != 6 * B))
+		throw std::invalid_argument("setLinkPayload: mass must be [B], com [3][B], inertia [6][B]");
+	for (int s = 0; s < 2; s++)
+		if (target & (1 << s)) _payload[s].set = true, _payload[s].link = link, _payload[s].mass = mass, _payload[s].com = com, _payload[s].inertia = inertia;
+	if (_controller) applyPayloads(_controller->ctx(), target);
+	for (sai2b_ctx* c : _standalone) applyPayloads(c, target);
+}
+inline void BatchedRobotModel::clearLinkPayload(int target) {
+	for (int s = 0; s < 2; s++)
+		if (target & (1 << s)) _payload[s] = LinkPayload();
+	if (_controller) detail::check(_controller->ctx(), sai2b_clear_link_payload(_controller->ctx(), target));
+	for (sai2b_ctx* c : _standalone) detail::check(c, sai2b_clear_link_payload(c, target));
+}
 inline sai2b_ctx* TemplateTask::ctx() const {
 	if (_owner) return _owner->ctx();
 	if (!_own_ctx) {
@@ -963,6 +1032,7 @@ inline sai2b_ctx* TemplateTask::ctx() const {
 			throw std::invalid_argument(msg);
 		}
 		_robot->_standalone.push_back(_own_ctx);
+		_robot->applyPayloads(_own_ctx, SAI2B_PAYLOAD_BOTH);
 		// goals := the pose the task was constructed at, then follow the robot
 		detail::check(_own_ctx, sai2b_set_state(_own_ctx, _q_construction.data(), nullptr, 0));
 		detail::check(_own_ctx, sai2b_reinitialize(_own_ctx));
@@ -1069,6 +1139,20 @@ public:
 			for (int i = 0; i < 6; i++) s[i] = slice(*v[i], i == 1 ? 9 : 3, sh);
 			detail::check(sh.ctx, sai2b_set_mft_goals(sh.ctx, task, ptr(s[0]), ptr(s[1]), ptr(s[2]), ptr(s[3]), ptr(s[4]), ptr(s[5]), 0));
 		});
+	}
+	// BatchedRobotModel::setLinkPayload for the whole sharded batch: mass [B_total], com [3][B_total] (empty: zeros), inertia
+	// [6][B_total] (empty: point masses); each shard gets the rows of its robots
+	void setLinkPayload(const int link, const Batch& mass, const Batch& com = {}, const Batch& inertia = {}, const int target = SAI2B_PAYLOAD_BOTH) {
+		rows(mass, 1, "payload mass");
+		if (!com.empty()) rows(com, 3, "payload com");
+		if (!inertia.empty()) rows(inertia, 6, "payload inertia");
+		forAll([&](Shard& sh) {
+			const Batch m = slice(mass, 1, sh), c = slice(com, 3, sh), i = slice(inertia, 6, sh);
+			detail::check(sh.ctx, sai2b_set_link_payload(sh.ctx, target, link, ptr(m), ptr(c), ptr(i), 0));
+		});
+	}
+	void clearLinkPayload(const int target = SAI2B_PAYLOAD_BOTH) {
+		forAll([target](Shard& sh) { detail::check(sh.ctx, sai2b_clear_link_payload(sh.ctx, target)); });
 	}
 	// a run-time setter of the reference applied to every shard (gains, decoupling, force space, OTG switches ...)
 	void updateTaskConfig(const int task, const sai2b_task_config& cfg) {

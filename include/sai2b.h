@@ -364,7 +364,13 @@ enum sai2b_buffer {
 	 * sai2b_task_update_model(ctx, next, sai2b_device_buffer(ctx, SAI2B_BUF_TASK_N_TOTAL, task), 1) — instead of through
 	 * sai2b_task_get_nullspaces() and the host. NULL before the task's first task-level call. */
 	SAI2B_BUF_TASK_N = 6,		/* the task's nullspace N (getTaskNullspace) */
-	SAI2B_BUF_TASK_N_TOTAL = 7	/* N * N_prec (getTaskAndPreviousNullspace) */
+	SAI2B_BUF_TASK_N_TOTAL = 7,	/* N * N_prec (getTaskAndPreviousNullspace) */
+	/* per-robot payload rows (sai2b_set_link_payload), [10][B] = mass, com 3, inertia 6 (ixx iyy izz ixy ixz iyz): the
+	 * controller's set and the plant's. NULL until a payload has been set for that target (and after it is cleared). A
+	 * device-resident producer may rewrite the rows between ticks, ordered with sai2b_stream(); the next tick / sim step
+	 * reads them. Such rows are not inspected. */
+	SAI2B_BUF_PAYLOAD = 8,
+	SAI2B_BUF_PLANT_PAYLOAD = 9
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -392,6 +398,30 @@ int sai2b_get_mft_singularity_state(sai2b_ctx* ctx, int task, int* n_singular, i
  * MotionForceTask::getUnitMassForce and the observers of POPCBilateralTeleoperation.cpp:81-92,172-182
  * read (MotionForceTask.cpp:478-487) */
 int sai2b_get_mft_task_forces(sai2b_ctx* ctx, int task, double* F_unit, double* F_force);
+/* ------------------------------------------------------------------ per-robot payloads
+ * One extra rigid body per robot, fixed to moving link `link` (0-based, as sai2b_task_config.link), different for every
+ * robot of the batch: what a robot holds, or a tool whose mass is randomised per environment. Everything else of the model
+ * (sai2b_robot_model) stays shared by the batch. Two independent sets per context:
+ *   SAI2B_PAYLOAD_CONTROLLER  what M, g, Lambda, the nullspaces and the torques are computed with (every tick kernel, the
+ *                             task-level calls, the M of sai2b_get_model),
+ *   SAI2B_PAYLOAD_PLANT       what sai2b_sim_step integrates and sai2b_get_bias reports;
+ * setting both (SAI2B_PAYLOAD_BOTH) is the common case, setting them apart models a controller that is wrong about its load.
+ * mass [B] (kg), com [3][B] (metres, in the link's frame; NULL: zeros), inertia [6][B] (about the body's own COM, link axes,
+ * ixx iyy izz ixy ixz iyz as sai2b_robot_model.inertia; NULL: a point mass). Zero mass and inertia: nothing attached to that
+ * robot. Host arrays are validated (SAI2B_INVALID_ARGUMENT: link outside [0, dof), negative or non-finite mass, non-finite com
+ * or inertia, negative ixx / iyy / izz); DEVICE arrays (on_device != 0) are copied as they are and NOT inspected. The call is
+ * ordered on the ctx stream like the goal setters and takes effect at the next tick / sim step. Kinematics, Jacobians, the
+ * singularity handling and the trajectory generators never see a payload; sai2b_reinitialize keeps it (model, not task
+ * state). A context that never sets one, or has cleared it, launches the kernels it would without this feature. */
+enum sai2b_payload_target { SAI2B_PAYLOAD_CONTROLLER = 1, SAI2B_PAYLOAD_PLANT = 2, SAI2B_PAYLOAD_BOTH = 3 };
+int sai2b_set_link_payload(sai2b_ctx* ctx, int target, int link, const double* mass, const double* com,
+						   const double* inertia, int on_device);
+/* back to the kernels and results of a context without a payload (the rows are kept for a later set, the buffer ids give NULL) */
+int sai2b_clear_link_payload(sai2b_ctx* ctx, int target);
+/* the rows of ONE target (SAI2B_PAYLOAD_CONTROLLER or SAI2B_PAYLOAD_PLANT) to host arrays, any may be NULL; *link = -1 and
+ * zeros when that target has no payload */
+int sai2b_get_link_payload(sai2b_ctx* ctx, int target, int* link, double* mass, double* com, double* inertia);
+
 /* ------------------------------------------------------------------ simulation harness
  * What the reference's examples obtain from the external sai2-simulation (examples/05-...cpp:215-236:
  * setJointTorques / integrate / getJointPositions, getJointVelocities): one control period of

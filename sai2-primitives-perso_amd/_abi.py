@@ -23,6 +23,9 @@ SV_SIGN_V_MAX_POSITIVE, SV_SIGN_V_MAX_NEGATIVE, SV_SIGN_EITHER, SV_SIGN_BOTH = 0
 OK, INVALID_ARGUMENT, RUNTIME_ERROR, UNSUPPORTED = 0, 1, 2, 3
 # enum sai2b_buffer
 BUF_Q, BUF_DQ, BUF_TAU, BUF_GOALS, BUF_SENSED, BUF_STATE, BUF_TASK_N, BUF_TASK_N_TOTAL = 0, 1, 2, 3, 4, 5, 6, 7
+BUF_PAYLOAD, BUF_PLANT_PAYLOAD = 8, 9  # [10][B] per-robot payload rows of the controller / the plant (sai2b_set_link_payload)
+PAYLOAD_CONTROLLER, PAYLOAD_PLANT, PAYLOAD_BOTH = 1, 2, 3  # enum sai2b_payload_target
+PAYLOAD_TARGETS = {"controller": PAYLOAD_CONTROLLER, "plant": PAYLOAD_PLANT, "both": PAYLOAD_BOTH}
 
 _d = C.c_double
 _i = C.c_int
@@ -235,6 +238,9 @@ EXPORTS = [
     "sai2b_device_count",
     "sai2b_get_fallback_count",
     "sai2b_counters",
+    "sai2b_set_link_payload",
+    "sai2b_clear_link_payload",
+    "sai2b_get_link_payload",
 ]
 
 _lib = None
@@ -325,5 +331,8 @@ def load_library():
     lib.sai2b_profile_tick.argtypes = [vp, _i, P(_d), P(_d)]
     lib.sai2b_get_fallback_count.argtypes = [vp, P(_i)]
     lib.sai2b_counters.argtypes = [vp, P(C.c_longlong), P(C.c_longlong)]
+    lib.sai2b_set_link_payload.argtypes = [vp, _i, _i, vp, vp, vp, _i]
+    lib.sai2b_clear_link_payload.argtypes = [vp, _i]
+    lib.sai2b_get_link_payload.argtypes = [vp, _i, P(_i), vp, vp, vp]
     _lib = lib
     return lib

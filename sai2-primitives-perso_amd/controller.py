@@ -224,6 +224,37 @@ class Controller:
         ins = [self._in(o, k0) for o in (q, dq, ddq)]
         self._rc(self.lib.sai2b_set_jt_goals(self.h, task, *[p for p, _ in ins], self._dev(q, dq, ddq)))
 
+    # -- per-robot payloads (sai2b.h "per-robot payloads")
+    @staticmethod
+    def _payload_target(target):
+        try:
+            return _abi.PAYLOAD_TARGETS[target] if isinstance(target, str) else int(target)
+        except KeyError:
+            raise ValueError("target must be 'controller', 'plant' or 'both'") from None
+
+    def set_link_payload(self, link, mass, com=None, inertia=None, target="both"):
+        """one rigid body per robot on moving link `link`: mass [B], com [3][B] in the link frame (None: zeros), inertia
+        [6][B] about the body's COM (ixx iyy izz ixy ixz iyz; None: point mass); numpy arrays or torch CUDA tensors.
+        target: 'controller' (what M, g and the torques are computed with), 'plant' (what sim_step integrates) or 'both'"""
+        if mass is not None and not hasattr(mass, "data_ptr"):
+            mass = np.ascontiguousarray(mass, dtype=np.float64).reshape(1, -1)
+        elif mass is not None and mass.dim() == 1:
+            mass = mass.view(1, -1)
+        ins = [self._in(o, r) for o, r in zip((mass, com, inertia), (1, 3, 6))]
+        self._rc(self.lib.sai2b_set_link_payload(self.h, self._payload_target(target), int(link), *[p for p, _ in ins],
+                                                 self._dev(mass, com, inertia)))
+
+    def clear_link_payload(self, target="both"):
+        self._rc(self.lib.sai2b_clear_link_payload(self.h, self._payload_target(target)))
+
+    def get_link_payload(self, target="controller"):
+        """-> (link, mass [B], com [3][B], inertia [6][B]) of one target; link -1 and zeros when it has no payload"""
+        link = C.c_int()
+        m, c, i = np.empty(self.B), np.empty((3, self.B)), np.empty((6, self.B))
+        self._rc(self.lib.sai2b_get_link_payload(self.h, self._payload_target(target), C.byref(link),
+                                                 *[C.c_void_p(x.ctypes.data) for x in (m, c, i)]))
+        return link.value, m, c, i
+
     # -- the path
     def reinitialize(self):
         self._rc(self.lib.sai2b_reinitialize(self.h))
@@ -451,6 +482,7 @@ class BatchedRobotModel:
         self._dq = np.zeros((self.model.dof, self.batch))
         self._controller = None
         self._standalone = []  # tasks driven on their own (TemplateTask-level calls): each has its 1-task context
+        self._payloads = {}  # 'controller' / 'plant' -> (link, mass, com, inertia): applied to contexts created later too
 
     def dof(self):
         return int(self.model.dof)
@@ -493,6 +525,49 @@ class BatchedRobotModel:
         for own in self._standalone:
             own._ctrl.set_state(self._q, self._dq)
 
+    def setLinkPayload(self, link, mass, com=None, inertia=None, target="both"):
+        """What each robot of the batch carries: one rigid body on `link` (0-based moving link, or a URDF link name when the
+        model came from a URDF file), per robot mass [B], com [3][B] in that link's frame, inertia [6][B] about the body's
+        COM. Where the reference gives each robot its own Sai2Model, the batch shares one model and differs in these rows
+        (Controller.set_link_payload). Kept for controllers and tasks created on this model later."""
+        if isinstance(link, str):
+            if self.links is None:
+                raise ValueError("setLinkPayload: a link name needs a model read from a URDF file")
+            idx, pos, R = resolve_link_frame(self.links, link)
+            if not (np.allclose(pos, 0) and np.allclose(R, np.eye(3))):  # a fixed-joint child: re-express in the moving link
+                if hasattr(mass, "data_ptr"):
+                    raise ValueError("setLinkPayload: a payload on a fixed-joint link takes host arrays")
+                B = self.batch
+                c = np.zeros((3, B)) if com is None else np.asarray(com, dtype=np.float64)
+                com = pos[:, None] + R @ c
+                if inertia is not None:
+                    i6 = np.asarray(inertia, dtype=np.float64)
+                    I = np.stack([i6[[0, 3, 4]], i6[[3, 1, 5]], i6[[4, 5, 2]]])  # [3][3][B]
+                    I = np.einsum("ij,jkb,lk->ilb", R, I, R)
+                    inertia = np.stack([I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]])
+            link = idx
+        if target not in _abi.PAYLOAD_TARGETS:
+            raise ValueError("target must be 'controller', 'plant' or 'both'")
+        for name in (("controller", "plant") if target == "both" else (target,)):
+            self._payloads[name] = (int(link), mass, com, inertia)
+        for c in self._contexts():
+            c.set_link_payload(int(link), mass, com, inertia, target)
+
+    def clearLinkPayload(self, target="both"):
+        if target not in _abi.PAYLOAD_TARGETS:
+            raise ValueError("target must be 'controller', 'plant' or 'both'")
+        for name in (("controller", "plant") if target == "both" else (target,)):
+            self._payloads.pop(name, None)
+        for c in self._contexts():
+            c.clear_link_payload(target)
+
+    def _contexts(self):
+        return ([self._controller._ctrl] if self._controller is not None else []) + [own._ctrl for own in self._standalone]
+
+    def _apply_payloads(self, ctrl):
+        for name, (link, mass, com, inertia) in self._payloads.items():
+            ctrl.set_link_payload(link, mass, com, inertia, name)
+
 
 class _StandaloneOwner:
     """What a task that is not attached to a RobotController runs on: a context holding that one task
@@ -500,6 +575,7 @@ class _StandaloneOwner:
 
     def __init__(self, robot, cfg, q_construction):
         self._ctrl = Controller(robot.model, [cfg], robot.batch, robot.device)
+        robot._apply_payloads(self._ctrl)
         # the reference constructs a task at the model's state of that moment (goals := current pose)
         self._ctrl.set_state(q_construction, np.zeros_like(q_construction))
         self._ctrl.reinitialize()
@@ -1281,6 +1357,7 @@ class RobotController:
         self._robot = robot
         self._tasks = list(tasks)
         self._ctrl = Controller(robot.model, [t._cfg for t in tasks], robot.batch, robot.device, introspection)
+        robot._apply_payloads(self._ctrl)
         robot._controller = self
         self._ctrl.set_state(robot.q(), robot.dq())
         self._ctrl.reinitialize()  # tasks are constructed at the model's current state

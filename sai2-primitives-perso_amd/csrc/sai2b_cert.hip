@@ -14,7 +14,9 @@ namespace sai2b {
 // (The robot constants are read from the parameter block: compiling the stock Panda in, as tick_fast_kernel does,
 // measured 9 % SLOWER here — 53.2 vs 49.0 us on the same box — the literals cost registers this kernel does not have.)
 // fb_counts[2 + parity]: how many robots went through the in-lane singular branch (cleared and filled like the work list's count)
-template <int MCAP, bool S6 = false>
+// PL = Payload: the form for contexts with per-robot payloads (sai2b_set_link_payload), an instantiation of its own so that the
+// others stay the code they are
+template <int MCAP, bool S6 = false, class PL = NoPayload>
 __global__ __launch_bounds__(64) void tick_cert_kernel(const DevParams* __restrict__ Pp, int with_comp, int* __restrict__ fb_counts,
 													  int* __restrict__ fb_list, int parity) {
 	__shared__ real pend_lds[(cert::LDS_SLOTS + (MCAP <= 3 ? cert::POSE_SLOTS : 0)) * 64];
@@ -29,7 +31,9 @@ __global__ __launch_bounds__(64) void tick_cert_kernel(const DevParams* __restri
 	// instead of through cert::singular_part (SAI2B_NO_INLANE_SINGULAR=1, the A/B switch)
 	cert::SingPend sp;
 	sp.task = -1, sp.commit = 1, sp.store_t2 = 1, sp.took = 0;
-	const bool mine = cert::tick<MCAP, cert::DM, DevModel, false, S6>(P, P.model, B, b, (with_comp & 1) != 0, pend, tau, nullptr, (with_comp & 2) ? nullptr : &sp);
+	PL pl;
+	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
+	const bool mine = cert::tick<MCAP, cert::DM, DevModel, false, S6, PL>(P, P.model, B, b, (with_comp & 1) != 0, pend, tau, nullptr, (with_comp & 2) ? nullptr : &sp, pl);
 	{
 		const unsigned long long took = __ballot(sp.took != 0);
 		if (took && threadIdx.x == 0) atomicAdd(&fb_counts[2 + parity], __popcll(took));  // lane 0 is always in range
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(64) void tick_cert_kernel(const DevParams* __restri
 // carry singularity history go — nothing stored — to a work list for the generic task_kernel (sai2b_kernels.hip).
 // tk_counts: two counters alternating between launches (`parity`), as behind tick_fast_kernel: this launch fills
 // [parity] and clears [1 - parity] for the next one.
-template <int MCAP>
+template <int MCAP, class PL = NoPayload>
 __global__ __launch_bounds__(64) void task_cert_kernel(const DevParams* __restrict__ Pp, int task, const double* __restrict__ Nprec_in,
 													  const double* __restrict__ tau_prec, double* __restrict__ tau_out, double* __restrict__ N_out,
 													  double* __restrict__ Ntot_out, int call_bits, int* __restrict__ tk_counts,
@@ -79,7 +83,9 @@ __global__ __launch_bounds__(64) void task_cert_kernel(const DevParams* __restri
 	real tau[N];
 	cert::SingPend sp;
 	sp.task = -1, sp.commit = (call_bits >> 1) & 1, sp.store_t2 = do_torque, sp.took = 0;
-	const bool mine = cert::tick<MCAP, cert::DM, DevModel, true>(P, P.model, B, b, tau_prec != nullptr, pend, tau, &io, (call_bits & 4) ? nullptr : &sp);
+	PL pl;
+	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
+	const bool mine = cert::tick<MCAP, cert::DM, DevModel, true, false, PL>(P, P.model, B, b, tau_prec != nullptr, pend, tau, &io, (call_bits & 4) ? nullptr : &sp, pl);
 	const unsigned long long declined = __ballot(!mine);
 	if (declined) {
 		int base = 0;
@@ -102,7 +108,7 @@ __global__ __launch_bounds__(64) void task_cert_kernel(const DevParams* __restri
 // The range pass ahead of the trajectory generators (cert::range_tick): OTG_ACTIVE of the gated JointTasks for the
 // robots whose levels are all certified; the others go to a work list for the generic kernel's range pass, with
 // the same two alternating counters protocol as above.
-template <int MCAP>
+template <int MCAP, class PL = NoPayload>
 __global__ __launch_bounds__(64) void range_cert_kernel(const DevParams* __restrict__ Pp, int* __restrict__ rg_counts, int* __restrict__ rg_list,
 													   int parity, int inlane) {
 	const DevParams& P = *Pp;
@@ -110,7 +116,9 @@ __global__ __launch_bounds__(64) void range_cert_kernel(const DevParams* __restr
 	const int b = blockIdx.x * 64 + threadIdx.x;
 	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)rg_counts)[1 - parity] = 0;
 	if (b >= B) return;
-	const bool mine = cert::range_tick<MCAP>(P, P.model, B, b, inlane != 0);
+	PL pl;
+	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
+	const bool mine = cert::range_tick<MCAP, DevModel, PL>(P, P.model, B, b, inlane != 0, pl);
 	const unsigned long long declined = __ballot(!mine);
 	if (declined) {
 		int base = 0;
@@ -141,6 +149,14 @@ extern "C" int sai2b_debug_read_cstamps(unsigned long long* out, int cap) {
 extern "C" int sai2b_launch_range_cert(const sai2b::DevParams* d_params, int B, int max_rows, int* rg_counts, int* rg_list, int parity, int inlane,
 									   hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);
+	using sai2b::Payload;
+	if (inlane & 2) {  // bit 1: the context has per-robot payloads
+		if (max_rows <= 3)
+			hipLaunchKernelGGL((sai2b::range_cert_kernel<3, Payload>), grid, block, 0, stream, d_params, rg_counts, rg_list, parity, inlane & 1);
+		else
+			hipLaunchKernelGGL((sai2b::range_cert_kernel<6, Payload>), grid, block, 0, stream, d_params, rg_counts, rg_list, parity, 0);
+		return (int)hipGetLastError();
+	}
 	if (max_rows <= 3)
 		hipLaunchKernelGGL(sai2b::range_cert_kernel<3>, grid, block, 0, stream, d_params, rg_counts, rg_list, parity, inlane);
 	else
@@ -152,6 +168,17 @@ extern "C" int sai2b_launch_task_cert(const sai2b::DevParams* d_params, int B, i
 									  const double* tau_prec, double* tau_out, double* N_out, double* Ntot_out, int do_torque, int* tk_counts,
 									  int* tk_list, int parity, hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);
+	using sai2b::Payload;
+	if (do_torque & 8) {  // bit 3 of the call bits: the context has per-robot payloads
+		do_torque &= 7;
+		if (max_rows <= 3)
+			hipLaunchKernelGGL((sai2b::task_cert_kernel<3, Payload>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
+							   do_torque, tk_counts, tk_list, parity);
+		else
+			hipLaunchKernelGGL((sai2b::task_cert_kernel<6, Payload>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
+							   do_torque, tk_counts, tk_list, parity);
+		return (int)hipGetLastError();
+	}
 	if (max_rows <= 3)
 		hipLaunchKernelGGL(sai2b::task_cert_kernel<3>, grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
 						   do_torque, tk_counts, tk_list, parity);
@@ -164,7 +191,18 @@ extern "C" int sai2b_launch_task_cert(const sai2b::DevParams* d_params, int B, i
 extern "C" int sai2b_launch_tick_cert(const sai2b::DevParams* d_params, int B, int max_rows, int with_comp, int* fb_counts, int* fb_list,
 									  int parity, hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);
-	// with_comp bit 2: the 6-row instantiation with the singular branch in the lane (cert::tick<.., S6>)
+	// with_comp bit 2: the 6-row instantiation with the singular branch in the lane (cert::tick<.., S6>); bit 3: the payload forms
+	using sai2b::Payload;
+	if (with_comp & 8) {
+		with_comp &= 7;
+		if (max_rows <= 3)
+			hipLaunchKernelGGL((sai2b::tick_cert_kernel<3, false, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		else if (with_comp & 4)
+			hipLaunchKernelGGL((sai2b::tick_cert_kernel<6, true, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		else
+			hipLaunchKernelGGL((sai2b::tick_cert_kernel<6, false, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		return (int)hipGetLastError();
+	}
 	if (max_rows <= 3)
 		hipLaunchKernelGGL((sai2b::tick_cert_kernel<3>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
 	else if (with_comp & 4)

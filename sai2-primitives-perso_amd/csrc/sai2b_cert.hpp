@@ -1306,9 +1306,10 @@ DI int q0_slot(int k) { return k < N ? k : (k < TASK_FREE ? k + 12 : LDS_SLOTS +
 // S6: the instantiation whose 4- to 6-row MotionForceTasks have the singular branch too (singular_streamed). A kernel of its
 // own, chosen by the host while many robots are inside a blending region (sai2b_host.cpp: launch_tick): the branch's
 // registers cost the REGULAR path of the 6-row kernel 45 -> 75 us, inlined, and more as a call.
-template <int MCAP, int DCAP, class MD, bool TASK = false, bool S6 = false>
+// pl: the robot's payload (Payload), added to M and g, or NoPayload
+template <int MCAP, int DCAP, class MD, bool TASK = false, bool S6 = false, class PL = NoPayload>
 DI bool tick(const DevParams& P, const MD& md, int B, int b, bool with_comp, real* pend, real* tau, const TaskArgs* io = nullptr,
-			 SingPend* sp = nullptr) {
+			 SingPend* sp = nullptr, const PL& pl = PL{}) {
 	CSTAMP(0);
 	Fact f;
 	bool ok = true;
@@ -1322,11 +1323,11 @@ DI bool tick(const DevParams& P, const MD& md, int B, int b, bool with_comp, rea
 		fk(md, q, F);
 		CSTAMP(2);
 		real M[N * N];
-		mass_matrix(md, F, M);
+		mass_matrix(md, F, M, pl);
 		CSTAMP(3);
 		if (P.gravity_comp) {
 			real g[N];
-			gravity_vector(md, F, g);
+			gravity_vector(md, F, g, pl);
 			UNROLL for (int i = 0; i < N; i++) pend[i * 64] = g[i];
 		} else {
 			UNROLL for (int i = 0; i < N; i++) pend[i * 64] = 0.0;
@@ -1629,8 +1630,8 @@ DI void flush_task(const DevParams& P, int task, int B, int b, const real* pend)
 // rows are left. Returns false when some level could not be certified: the caller hands the robot to the range pass
 // of the generic kernel, which decides (and overwrites) with the reference's own rule.
 // inlane: robots inside a blending region of a 2- or 3-row MotionForceTask stay (singular_range), as in tick()
-template <int MCAP, class MD>
-DI bool range_tick(const DevParams& P, const MD& md, int B, int b, bool inlane = false) {
+template <int MCAP, class MD, class PL = NoPayload>
+DI bool range_tick(const DevParams& P, const MD& md, int B, int b, bool inlane = false, const PL& pl = PL{}) {
 	Fact f;
 	f.lb = nullptr;
 	real q[N];
@@ -1639,7 +1640,7 @@ DI bool range_tick(const DevParams& P, const MD& md, int B, int b, bool inlane =
 		Frames F;
 		fk(md, q, F);
 		real M[N * N];
-		mass_matrix(md, F, M);
+		mass_matrix(md, F, M, pl);
 		SAI2B_PHASE();
 		chol<N>(M, f.L, f.dL);
 	}

@@ -271,10 +271,73 @@ DI void jacobian(const MD& md, const DevTask& t, const Frames& F, const real* x,
 		}
 	}
 }
+// Per-robot payload: one rigid body fixed to link `link` (batch-uniform), its mass, COM (link frame) and inertia about its
+// COM (link axes, xx yy zz xy xz yz) per robot: rows mass, com 3, inertia 6 of a [10][B] buffer (sai2b_set_link_payload).
+// NoPayload: the functions below compile to what they are without the feature. Payload with link < 0 adds nothing.
+struct NoPayload {
+	static constexpr bool on = false;
+};
+struct Payload {
+	static constexpr bool on = true;
+	int link;
+	real m, c[3], I[6];
+};
+DI real ld(const real* p, int row, int B, int b);
+// rows == NULL (wave-uniform): nothing attached
+DI void payload_load(const real* rows, int link, int B, int b, Payload& pl) {
+	pl.link = rows ? link : -1;
+	pl.m = 0;
+	UNROLL for (int k = 0; k < 3; k++) pl.c[k] = 0;
+	UNROLL for (int k = 0; k < 6; k++) pl.I[k] = 0;
+	if (rows) {
+		pl.m = ld(rows, 0, B, b);
+		UNROLL for (int k = 0; k < 3; k++) pl.c[k] = ld(rows, 1 + k, B, b);
+		UNROLL for (int k = 0; k < 6; k++) pl.I[k] = ld(rows, 4 + k, B, b);
+	}
+}
+// the payload's (m, m c, I_O) about the world origin, link frame (R, p): R I_p R^T + m (|c|^2 1 - c c^T), c = p + R c_p
+DI void payload_composite(const Payload& pl, const real* R, const real* p, real& mt, real* h, real* IO) {
+	real c[3];
+	UNROLL for (int a = 0; a < 3; a++) c[a] = fma(R[3 * a], pl.c[0], fma(R[3 * a + 1], pl.c[1], fma(R[3 * a + 2], pl.c[2], p[a])));
+	const real* li = pl.I;
+	real Il[9] = {li[0], li[3], li[4], li[3], li[1], li[5], li[4], li[5], li[2]}, T[9];
+	mm<3, 3, 3>(R, Il, T);
+	const real c2 = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+	const int ia[6] = {0, 1, 2, 0, 0, 1}, ib[6] = {0, 1, 2, 1, 2, 2};
+	UNROLL for (int e = 0; e < 6; e++) {
+		real s = 0;
+		UNROLL for (int l = 0; l < 3; l++) s = fma(T[3 * ia[e] + l], R[3 * ib[e] + l], s);
+		IO[e] += s + pl.m * ((ia[e] == ib[e] ? c2 : 0.0) - c[ia[e]] * c[ib[e]]);
+	}
+	mt += pl.m;
+	UNROLL for (int a = 0; a < 3; a++) h[a] = fma(pl.m, c[a], h[a]);
+}
+
+// The same terms from the frames of the whole chain, computed ONCE ahead of the composite-body loops, which then add them at
+// the payload's link by selects: straight-line code (a branch per link would cut the loops into basic blocks and take the
+// phase fences of the SVD-free kernels with it). The link's frame is selected without dynamic register indexing.
+struct PayloadTerms {
+	real m, h[3], IO[6];
+};
+DI void payload_terms(const Payload& pl, const Frames& F, PayloadTerms& t) {
+	real R[9], p[3];
+	UNROLL for (int k = 0; k < 9; k++) R[k] = F.R[N - 1][k];
+	UNROLL for (int k = 0; k < 3; k++) p[k] = F.p[N - 1][k];
+	UNROLL for (int i = 0; i < N - 1; i++)
+		if (pl.link == i) {
+			UNROLL for (int k = 0; k < 9; k++) R[k] = F.R[i][k];
+			UNROLL for (int k = 0; k < 3; k++) p[k] = F.p[i][k];
+		}
+	t.m = 0;
+	UNROLL for (int k = 0; k < 3; k++) t.h[k] = 0;
+	UNROLL for (int k = 0; k < 6; k++) t.IO[k] = 0;
+	payload_composite(pl, R, p, t.m, t.h, t.IO);
+}
+
 // Joint-space inertia matrix by the composite-rigid-body algorithm with spatial inertias expressed
 // about the world origin (what Sai2Model::updateModel() obtains from RBDL's CRBA).
-template <class MD>
-DI void mass_matrix(const MD& md, const Frames& F, real* M) {
+template <class MD, class PL = NoPayload>
+DI void mass_matrix(const MD& md, const Frames& F, real* M, const PL& pl = PL{}) {
 	real z[N][3], v[N][3];	// joint twists about the world origin: (z_i, p_i x z_i) revolute, (0, z_i) prismatic
 	UNROLL for (int i = 0; i < N; i++) {
 		const real ax[3] = {F.R[i][2], F.R[i][5], F.R[i][8]};
@@ -287,6 +350,8 @@ DI void mass_matrix(const MD& md, const Frames& F, real* M) {
 		}
 	}
 	real mt = 0, h[3] = {0, 0, 0}, IO[6] = {0, 0, 0, 0, 0, 0};	// xx yy zz xy xz yz
+	[[maybe_unused]] PayloadTerms pt;
+	if constexpr (PL::on) payload_terms(pl, F, pt);
 	UNROLL for (int k = N - 1; k >= 0; k--) {
 		const real* R = F.R[k];
 		real c[3];
@@ -305,6 +370,12 @@ DI void mass_matrix(const MD& md, const Frames& F, real* M) {
 		}
 		mt += m;
 		UNROLL for (int a = 0; a < 3; a++) h[a] = fma(m, c[a], h[a]);
+		if constexpr (PL::on) {
+			const bool here = pl.link == k;
+			mt += here ? pt.m : 0.0;
+			UNROLL for (int a = 0; a < 3; a++) h[a] += here ? pt.h[a] : 0.0;
+			UNROLL for (int e = 0; e < 6; e++) IO[e] += here ? pt.IO[e] : 0.0;
+		}
 		// wrench of the composite body under unit acceleration of joint k
 		real n[3], f[3], hv[3], hz[3];
 		cross3(h, v[k], hv);
@@ -321,9 +392,11 @@ DI void mass_matrix(const MD& md, const Frames& F, real* M) {
 	}
 }
 // Sai2Model::jointGravityVector (RobotController.cpp:71): g_i = -sum_k m_k (z_i x (c_k - p_i)) . gravity
-template <class MD>
-DI void gravity_vector(const MD& md, const Frames& F, real* g) {
+template <class MD, class PL = NoPayload>
+DI void gravity_vector(const MD& md, const Frames& F, real* g, const PL& pl = PL{}) {
 	real mt = 0, h[3] = {0, 0, 0};
+	[[maybe_unused]] PayloadTerms pt;
+	if constexpr (PL::on) payload_terms(pl, F, pt);
 	UNROLL for (int k = N - 1; k >= 0; k--) {
 		const real* R = F.R[k];
 		real c[3];
@@ -331,6 +404,11 @@ DI void gravity_vector(const MD& md, const Frames& F, real* g) {
 			c[a] = fma(R[3 * a], md.com[k][0], fma(R[3 * a + 1], md.com[k][1], fma(R[3 * a + 2], md.com[k][2], F.p[k][a])));
 		mt += md.mass[k];
 		UNROLL for (int a = 0; a < 3; a++) h[a] = fma(md.mass[k], c[a], h[a]);
+		if constexpr (PL::on) {
+			const bool here = pl.link == k;
+			mt += here ? pt.m : 0.0;
+			UNROLL for (int a = 0; a < 3; a++) h[a] += here ? pt.h[a] : 0.0;
+		}
 		real d[3] = {h[0] - mt * F.p[k][0], h[1] - mt * F.p[k][1], h[2] - mt * F.p[k][2]};
 		real zk[3] = {R[2], R[5], R[8]}, x[3];
 		cross3(zk, d, x);

@@ -99,25 +99,30 @@ DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEa
 //   | one pad row when the count is odd | the MotionForceTask istate row IS_NTYPES (64 ints)
 // The force-space rows (MotionForceTask goals 24-29, sensed, state 6-11) are not staged: they stay plain loads
 // after the barrier (StagedRows), which keeps the image within 40 KiB (4 workgroups per CU).
-template <int FAST>
+// PAY: the ten rows of the robot's payload (sai2b_set_link_payload) behind the others, the payload form of the kernel only:
+// 39 168 bytes for FAST = 2, still 4 workgroups per CU
+template <int FAST, bool PAY = false>
 struct StageLayout {
 	static constexpr int DQ = 0, JG = N, JS = JG + (FAST == 2 ? 3 * N : 0), MG = JS + (FAST == 2 ? N : 0);
-	static constexpr int MS = MG + 24, ROWS = MS + 6;
+	static constexpr int MS = MG + 24, PLD = MS + 6, ROWS = PLD + (PAY ? PAYLOAD_ROWS : 0);
 	static constexpr int PAIRS = (ROWS + 1) / 2;  // a 16-byte glds moves two rows (lanes 0-31: row 2i, 32-63: 2i+1)
 	static constexpr int IROW = 2 * PAIRS;		 // the istate row, 256 bytes
 	static constexpr int DOUBLES = IROW * 64 + 32;
 };
 
 // first element of image row k in the batched arrays (the pad row repeats the last one)
-template <int FAST>
+template <int FAST, bool PAY = false>
 DI const real* stage_row(const DevParams& P, int k) {
-	using S = StageLayout<FAST>;
+	using S = StageLayout<FAST, PAY>;
 	const int B = P.B;
 	if (k >= S::ROWS) k = S::ROWS - 1;
 	if (k < S::JG) return P.dq + (size_t)(k - S::DQ) * B;
 	if (k < S::JS) return P.task[1].law_goals + (size_t)(k - S::JG) * B;
 	if (k < S::MG) return P.task[1].state + (size_t)(k - S::JS) * B;
 	if (k < S::MS) return P.task[0].law_goals + (size_t)(k - S::MG) * B;
+	if constexpr (PAY) {
+		if (k >= S::PLD) return P.payload + (size_t)(k - S::PLD) * B;
+	}
 	return P.task[0].state + (size_t)(k - S::MS) * B;
 }
 
@@ -132,20 +137,20 @@ DI void glds(const void* src, real* lds, int bytes) {
 
 // Issue the DMA of the whole image for the 64 robots from b0 on; all 64 lanes take part, also those past B (the
 // source columns of lanes past B are clamped into the batch, and the columns they fill are never read).
-template <int FAST>
+template <int FAST, bool PAY = false>
 DI void stage_issue(const DevParams& P, real* img, int b0) {
-	using S = StageLayout<FAST>;
+	using S = StageLayout<FAST, PAY>;
 	const int B = P.B, lane = threadIdx.x;
 	if ((B & 1) == 0) {	 // every row starts 16-byte aligned: lane l moves robots col, col + 1 of row 2i + l / 32
 		const int col = min(b0 + 2 * (lane & 31), B - 2);
 		const bool hi = lane >= 32;
 		UNROLL for (int i = 0; i < S::PAIRS; i++)
-			glds((hi ? stage_row<FAST>(P, 2 * i + 1) : stage_row<FAST>(P, 2 * i)) + col, img + 2 * i * 64, 16);
+			glds((hi ? stage_row<FAST, PAY>(P, 2 * i + 1) : stage_row<FAST, PAY>(P, 2 * i)) + col, img + 2 * i * 64, 16);
 	} else {  // odd batch: 4-byte DMA, two per row; lane l moves dword l % 2 of robot col
 		UNROLL for (int h = 0; h < 2; h++) {
 			const int col = min(b0 + 32 * h + (lane >> 1), B - 1);
 			UNROLL for (int k = 0; k < S::ROWS; k++)
-				glds((const int*)(stage_row<FAST>(P, k) + col) + (lane & 1), img + k * 64 + 32 * h, 4);
+				glds((const int*)(stage_row<FAST, PAY>(P, k) + col) + (lane & 1), img + k * 64 + 32 * h, 4);
 		}
 	}
 	glds(P.task[0].istate + (size_t)IS_NTYPES * B + min(b0 + lane, B - 1), img + S::IROW * 64, 4);

@@ -104,8 +104,11 @@ DI void frame_pose_g(const DevTask& t, const real* FR, const real* Fp, real* x, 
 
 // ------------------------------------------------------------------ joint-space inertia (CRBA) and gravity
 // Mrow: row r of M; g: this lane's component of the gravity vector (only when want_g)
+// prow: the per-robot payload rows ([10][B], robot b; sai2b_set_link_payload) or NULL, a wave-uniform branch: the lane of link
+// `plink` adds the body to its composite before the suffix sums
 template <int G>
-DI void crba_g(const DevModel& md, int r, const real* R, const real* p, real* Mrow, bool want_g, real* g) {
+DI void crba_g(const DevModel& md, int r, const real* R, const real* p, real* Mrow, bool want_g, real* g, const real* prow = nullptr,
+			   int plink = -1, int B = 0, int b = 0) {
 	const bool act = r < N;
 	const int rr = act ? r : 0;
 	real c[3], comp[10];  // composite: mass, first moment (3), inertia about the world origin xx yy zz xy xz yz
@@ -126,6 +129,17 @@ DI void crba_g(const DevModel& md, int r, const real* R, const real* p, real* Mr
 		}
 		comp[0] = m;
 		UNROLL for (int a = 0; a < 3; a++) comp[1 + a] = m * c[a];
+	}
+	if (prow) {
+		const bool mine = act && r == plink;
+		Payload pl;
+		pl.link = plink;
+		pl.m = mine ? ld(prow, 0, B, b) : 0.0;
+		UNROLL for (int k = 0; k < 3; k++) pl.c[k] = mine ? ld(prow, 1 + k, B, b) : 0.0;
+		UNROLL for (int k = 0; k < 6; k++) pl.I[k] = mine ? ld(prow, 4 + k, B, b) : 0.0;
+		real add[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		payload_composite(pl, R, p, add[0], add + 1, add + 4);
+		UNROLL for (int i = 0; i < 10; i++) comp[i] += sel0(mine, add[i]);
 	}
 	// composite rigid bodies: suffix sums over the lanes (link k and everything outboard of it)
 	UNROLL for (int i = 0; i < 10; i++) comp[i] += shift_down<G, 1>(comp[i], 0.0);
@@ -905,7 +919,7 @@ DI void tick_robot(const DevParams& P, int b, real* pad, int commit_sh, int with
 		fk_scan<G>(P.model, rb.r, rb.q, rb.FR, rb.Fp);
 		GMARK(14, "model_fk_done");
 		real Mrow[N];
-		crba_g<G>(P.model, rb.r, rb.FR, rb.Fp, Mrow, P.gravity_comp != 0, &g);
+		crba_g<G>(P.model, rb.r, rb.FR, rb.Fp, Mrow, P.gravity_comp != 0, &g, P.payload, P.payload_link, B, b);
 		GMARK(15, "model_crba_done");
 		UNROLL for (int j = 0; j < N; j++) rb.minv[j] = Mrow[j];
 		spd_inverse_rows<G, N>(rb.minv);
@@ -973,7 +987,7 @@ DI void task_robot(const DevParams& P, int task, int b, real* pad, const real* N
 		fk_scan<G>(P.model, rb.r, rb.q, rb.FR, rb.Fp);
 		GMARK(14, "model_fk_done");
 		real Mrow[N];
-		crba_g<G>(P.model, rb.r, rb.FR, rb.Fp, Mrow, false, &g);
+		crba_g<G>(P.model, rb.r, rb.FR, rb.Fp, Mrow, false, &g, P.payload, P.payload_link, B, b);
 		GMARK(15, "model_crba_done");
 		UNROLL for (int j = 0; j < N; j++) rb.minv[j] = Mrow[j];
 		spd_inverse_rows<G, N>(rb.minv);

@@ -105,6 +105,9 @@ struct sai2b_ctx {
 	hipEvent_t ev_in = nullptr, ev_out = nullptr;
 	double *q = nullptr, *dq = nullptr, *tau = nullptr;
 	double* status_buf = nullptr;  // [68][B] scratch of sai2b_get_mft_status
+	// per-robot payloads (sai2b_set_link_payload): [0] the controller's rows, [1] the plant's, [10][B] each, created on first use;
+	// h_params.payload / plant_payload point at them while that set is in force
+	double* payload_rows[2] = {nullptr, nullptr};
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
@@ -1162,7 +1165,7 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		// for the robots it can certify and only the others take the generic kernel's range pass
 		const int ck = (ctx->introspection || ctx->cert_backoff > 0) ? 0 : cert_kind(ctx);
 		if (ck) {
-			if (sai2b_launch_range_cert(ctx->d_params, ctx->B, ck - 3, ctx->rg_counts, ctx->rg_list, ctx->rg_parity, ctx->no_inlane_singular ? 0 : 1, ctx->stream) ||
+			if (sai2b_launch_range_cert(ctx->d_params, ctx->B, ck - 3, ctx->rg_counts, ctx->rg_list, ctx->rg_parity, (ctx->no_inlane_singular ? 0 : 1) | (ctx->h_params.payload ? 2 : 0), ctx->stream) ||
 				sai2b_launch_tick_group(ctx->d_params, ctx->B, 16, 1, 0, with_comp, 0, ctx->rg_counts + ctx->rg_parity, ctx->rg_list, ctx->stream))
 				return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
 			ctx->rg_parity ^= 1;
@@ -1238,7 +1241,7 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	if (fast_launch) ctx->fb_parity ^= 1;
 	// a long work list (thousands of robots) is throughput, not latency: two robots per DPP row, as for a whole batch
 	const bool long_list = fast_launch && ctx->fb_last_seen > 4096;	 // (16 lanes: 4 robots x 1024 wavefronts in one round)
-	if (sai2b_launch_tick(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast_now, ctx->baked_model ? 1 : 0, commit_sh, (with_comp ? 1 : 0) | cert_bits, do_torque, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !fast_launch || long_list), ctx->stream))
+	if (sai2b_launch_tick(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast_now, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), commit_sh, (with_comp ? 1 : 0) | cert_bits, do_torque, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !fast_launch || long_list), ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
 	if (fast_launch && !ctx->fb_seen_pending) {
@@ -1377,7 +1380,7 @@ static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const do
 		}
 		ctx->tk_parity ^= 1;
 		if (sai2b_launch_task_cert(ctx->d_params, ctx->B, task, rows, Np, tp, tau_out, N_out, Ntot_out,
-								   (do_torque ? 1 : 0) | (commit_sh ? 2 : 0) | (ctx->no_inlane_singular ? 4 : 0), ctx->tk_count, ctx->tk_list,
+								   (do_torque ? 1 : 0) | (commit_sh ? 2 : 0) | (ctx->no_inlane_singular ? 4 : 0) | (ctx->h_params.payload ? 8 : 0), ctx->tk_count, ctx->tk_list,
 								   ctx->tk_parity, ctx->stream) ||
 			launch_task_generic(ctx, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, ctx->tk_count + ctx->tk_parity, ctx->tk_list))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task launch failed");
@@ -1530,6 +1533,8 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_STATE: return task_ok ? ctx->h_params.task[task].state : nullptr;
 		case SAI2B_BUF_TASK_N: return task_ok ? ctx->tio[task].N : nullptr;
 		case SAI2B_BUF_TASK_N_TOTAL: return task_ok ? ctx->tio[task].Ntot : nullptr;
+		case SAI2B_BUF_PAYLOAD: return (void*)ctx->h_params.payload;
+		case SAI2B_BUF_PLANT_PAYLOAD: return (void*)ctx->h_params.plant_payload;
 	}
 	return nullptr;
 }
@@ -1620,6 +1625,87 @@ static int fetch_rows(sai2b_ctx* ctx, const double* src, size_t row0, size_t row
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }
+// ---- per-robot payloads ----
+static int payload_target_check(sai2b_ctx* ctx, int target, const char* fn) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
+	if (target < 1 || target > 3) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": target must be SAI2B_PAYLOAD_CONTROLLER, _PLANT or _BOTH");
+	return SAI2B_OK;
+}
+// a set changed: nothing computed from the old one may be reused
+static void payload_changed(sai2b_ctx* ctx) {
+	ctx->params_dirty = true;
+	ctx->models_fresh = false;
+	for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
+}
+extern "C" int sai2b_set_link_payload(sai2b_ctx* ctx, int target, int link, const double* mass, const double* com, const double* inertia,
+									  int on_device) {
+	int rc = payload_target_check(ctx, target, "sai2b_set_link_payload");
+	if (rc) return rc;
+	if (link < 0 || link >= N) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: link must be in [0, dof)");
+	if (!mass) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: mass is required");
+	const size_t B = ctx->B;
+	if (!on_device) {
+		for (size_t b = 0; b < B; b++)
+			if (!std::isfinite(mass[b]) || mass[b] < 0) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: mass must be finite and >= 0");
+		for (size_t i = 0; com && i < 3 * B; i++)
+			if (!std::isfinite(com[i])) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: com must be finite");
+		for (size_t i = 0; inertia && i < 6 * B; i++) {
+			if (!std::isfinite(inertia[i])) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: inertia must be finite");
+			if (i < 3 * B && inertia[i] < 0) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_link_payload: ixx, iyy, izz must be >= 0");
+		}
+	}
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	DevParams& hp = ctx->h_params;
+	for (int s = 0; s < 2; s++) {
+		if (!(target & (1 << s))) continue;
+		double*& rows = ctx->payload_rows[s];
+		if (!rows && (rc = dev_alloc(ctx, &rows, (size_t)sai2b::PAYLOAD_ROWS * B))) return rc;
+		if ((rc = copy_rows(ctx, rows, mass, 1, on_device))) return rc;
+		if (com) {
+			if ((rc = copy_rows(ctx, rows + B, com, 3, on_device))) return rc;
+		} else
+			HIP_TRY(ctx, hipMemsetAsync(rows + B, 0, 3 * B * sizeof(double), ctx->stream));
+		if (inertia) {
+			if ((rc = copy_rows(ctx, rows + 4 * B, inertia, 6, on_device))) return rc;
+		} else
+			HIP_TRY(ctx, hipMemsetAsync(rows + 4 * B, 0, 6 * B * sizeof(double), ctx->stream));
+	}
+	// both sets are written: only now does either become the one in force (a failed copy above leaves the context as it was)
+	if (target & SAI2B_PAYLOAD_CONTROLLER) hp.payload = ctx->payload_rows[0], hp.payload_link = link;
+	if (target & SAI2B_PAYLOAD_PLANT) hp.plant_payload = ctx->payload_rows[1], hp.plant_payload_link = link;
+	payload_changed(ctx);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_link_payload(sai2b_ctx* ctx, int target) {
+	int rc = payload_target_check(ctx, target, "sai2b_clear_link_payload");
+	if (rc) return rc;
+	if ((rc = flush_update(ctx))) return rc;
+	if (target & SAI2B_PAYLOAD_CONTROLLER) ctx->h_params.payload = nullptr, ctx->h_params.payload_link = 0;
+	if (target & SAI2B_PAYLOAD_PLANT) ctx->h_params.plant_payload = nullptr, ctx->h_params.plant_payload_link = 0;
+	payload_changed(ctx);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_link_payload(sai2b_ctx* ctx, int target, int* link, double* mass, double* com, double* inertia) {
+	int rc = payload_target_check(ctx, target, "sai2b_get_link_payload");
+	if (rc) return rc;
+	if (target == SAI2B_PAYLOAD_BOTH) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_link_payload: one target at a time");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const bool plant = target == SAI2B_PAYLOAD_PLANT;
+	const double* rows = plant ? ctx->h_params.plant_payload : ctx->h_params.payload;
+	const size_t B = ctx->B;
+	if (link) *link = rows ? (plant ? ctx->h_params.plant_payload_link : ctx->h_params.payload_link) : -1;
+	if (!rows) {
+		if (mass) std::fill(mass, mass + B, 0.0);
+		if (com) std::fill(com, com + 3 * B, 0.0);
+		if (inertia) std::fill(inertia, inertia + 6 * B, 0.0);
+		return SAI2B_OK;
+	}
+	if ((rc = fetch_rows(ctx, rows, 0, 1, mass))) return rc;
+	if ((rc = fetch_rows(ctx, rows, 1, 3, com))) return rc;
+	return fetch_rows(ctx, rows, 4, 6, inertia);
+}
+
 // ---- simulation harness ----
 extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, double dt, int substeps, int with_gravity) {
 	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
@@ -1839,9 +1925,9 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 			HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
 			for (int s = 0; s < steps; s++) {
 				if (two) ctx->fb_parity ^= 1;
-				if (sai2b_launch_tick_part(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast, ctx->baked_model ? 1 : 0, 0, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !two), ctx->stream))
+				if (sai2b_launch_tick_part(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), 0, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !two), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
-				if (phase == 1 && sai2b_launch_tick_part(ctx->d_params, ctx->B, 0, fast, ctx->baked_model ? 1 : 0, 1, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, false), ctx->stream))
+				if (phase == 1 && sai2b_launch_tick_part(ctx->d_params, ctx->B, 0, fast, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), 1, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, false), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 			}
 			HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));

@@ -38,11 +38,18 @@ __global__ __launch_bounds__(64) void tick_kernel(const DevParams* __restrict__ 
 	}
 	real g[N];
 	{
+		// never the hot route: one kernel for contexts with and without payloads, a wave-uniform branch around the payload's
+		// work (without rows the calls are the ones this kernel always made)
+		Payload pl;
+		payload_load(P.payload, P.payload_link, B, b, pl);
 		// Sai2Model::updateModel(): kinematics, M (CRBA), M^-1 (examples/05-using_robot_controller.cpp:143-145)
 		Frames F;
 		fk(P.model, rc.q, F);
 		real M[N * N];
-		mass_matrix(P.model, F, M);
+		if (P.payload)
+			mass_matrix(P.model, F, M, pl);
+		else
+			mass_matrix(P.model, F, M);
 		spd_inverse<N>(M, rc.Minv);
 		if (DEBUG && P.dbg_M) {
 			UNROLL for (int i = 0; i < N * N; i++) st(P.dbg_M, i, B, b, M[i]);
@@ -62,7 +69,9 @@ __global__ __launch_bounds__(64) void tick_kernel(const DevParams* __restrict__ 
 		} else {
 			UNROLL for (int i = 0; i < N * N; i++) rc.MinvB[i] = rc.Minv[i];
 		}
-		if (P.gravity_comp)
+		if (P.gravity_comp && P.payload)
+			gravity_vector(P.model, F, g, pl);
+		else if (P.gravity_comp)
 			gravity_vector(P.model, F, g);
 		else {
 			UNROLL for (int i = 0; i < N; i++) g[i] = 0;
@@ -100,7 +109,25 @@ __global__ __launch_bounds__(64) void tick_kernel(const DevParams* __restrict__ 
 #if SAI2B_N == 7  // the SVD-free kernels are for 7-joint robots (6-DOF task + a one-dimensional nullspace)
 // [full MFT] (FAST = 1) with its inputs loaded into registers up front, as before the staged path: at C2's 4 096
 // robots (one wavefront per 16 SIMDs, nothing to contend for HBM) the staged form measured 13 % slower.
-template <bool BAKED>
+// M and g of the headline kernels' model phase. PL = NoPayload: the code this was before payloads existed.
+template <bool BAKED, class PL>
+DI void fast_model(const DevParams& P, const Frames& F, const PL& pl, real* M, real* g) {
+	if constexpr (BAKED)
+		mass_matrix(PandaBaked{}, F, M, pl);
+	else
+		mass_matrix(P.model, F, M, pl);
+	if (P.gravity_comp) {
+		if constexpr (BAKED)
+			gravity_vector(PandaBaked{}, F, g, pl);
+		else
+			gravity_vector(P.model, F, g, pl);
+	}
+	else {
+		UNROLL for (int i = 0; i < N; i++) g[i] = 0;
+	}
+}
+
+template <bool BAKED, class PL>
 DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb_counts, int* __restrict__ fb_list, int parity,
 						 int b) {
 	const int B = P.B;
@@ -133,18 +160,24 @@ DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb
 		SAI2B_PHASE();
 		mft_law(t0, rc, J, x, R, in0, Fu, Ff);	// MotionForceTask.cpp:278-503 (integrators not yet stored)
 		SAI2B_PHASE();
-		if constexpr (BAKED)
-			mass_matrix(PandaBaked{}, F, M);
-		else
-			mass_matrix(P.model, F, M);
-		if (P.gravity_comp) {
+		if constexpr (PL::on) {	 // (the ten rows are loaded here, not with the other inputs: nothing of them is live across the law)
+			PL pl;
+			payload_load(P.payload, P.payload_link, B, b, pl);
+			fast_model<BAKED>(P, F, pl, M, g);
+		} else {	// spelled out as it was before payloads: the register allocation of this form follows the text
 			if constexpr (BAKED)
-				gravity_vector(PandaBaked{}, F, g);
+				mass_matrix(PandaBaked{}, F, M);
 			else
-				gravity_vector(P.model, F, g);
-		}
-		else {
-			UNROLL for (int i = 0; i < N; i++) g[i] = 0;
+				mass_matrix(P.model, F, M);
+			if (P.gravity_comp) {
+				if constexpr (BAKED)
+					gravity_vector(PandaBaked{}, F, g);
+				else
+					gravity_vector(P.model, F, g);
+			}
+			else {
+				UNROLL for (int i = 0; i < N; i++) g[i] = 0;
+			}
 		}
 	}
 	SAI2B_PHASE();
@@ -176,31 +209,26 @@ DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb
 // BAKED selects where the robot constants come from: false = the ctx's parameter block (any robot),
 // true = the compile-time Panda literals of sai2b_baked_panda.h (chosen by the host only when the ctx
 // model is bit-equal to them): no scalar loads from the parameter block for the model phase.
-template <int FAST, bool BAKED>
-__global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restrict__ Pp, int with_comp,
-														  int* __restrict__ fb_counts, int* __restrict__ fb_list,
-														  int parity) {
+// PL = Payload: the form for contexts with per-robot payloads (tick_fast_payload_kernel below); its ten rows join the staged
+// image (StageLayout<FAST, true>), so nothing of them is live, and no global load is issued, before the model phase reads
+// them from LDS. img: the kernel's LDS image.
+template <int FAST, bool BAKED, class PL>
+DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __restrict__ fb_counts, int* __restrict__ fb_list,
+					   int parity, real* img) {
 	const DevParams& P = *Pp;
 	const int B = P.B;
 	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
-	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
-	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
-	if constexpr (FAST == 1) {
-		if (b < B) tick_fast1_loads<BAKED>(P, with_comp, fb_counts, fb_list, parity, b);
-		return;
-	}
 	// Inputs: q in registers (FK needs it and nothing else), every other row by DMA into the LDS image (StageLayout,
 	// sai2b_fast.hpp). q is waited for before the DMA is issued, and the window up to the barrier issues no other
 	// global load and touches no scratch, so the DMA lands behind the kinematics and the barrier retires it.
-	using S = StageLayout<FAST>;
-	__shared__ real img[S::DOUBLES];
+	using S = StageLayout<FAST, PL::on>;
 	RobotCtx rc;
 	UNROLL for (int i = 0; i < N; i++) {
 		rc.q[i] = ld(P.q, i, B, min(b, B - 1));
 		asm volatile("" : "+v"(rc.q[i]));  // the wait for q goes here, ahead of the DMA
 	}
 	SAI2B_PHASE();
-	stage_issue<FAST>(P, img, b0);
+	stage_issue<FAST, PL::on>(P, img, b0);
 	SAI2B_PHASE();
 	if (b >= B) return;
 	const DevTask& t0 = P.task[0];
@@ -238,24 +266,19 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 	SAI2B_PHASE();
 	real M[N * N], g[N];
 	{
+		PL pl;
+		if constexpr (PL::on) {
+			pl.link = P.payload_link;
+			pl.m = col[S::PLD * 64];
+			UNROLL for (int k = 0; k < 3; k++) pl.c[k] = col[(S::PLD + 1 + k) * 64];
+			UNROLL for (int k = 0; k < 6; k++) pl.I[k] = col[(S::PLD + 4 + k) * 64];
+		}
 		Frames F;
 		if constexpr (BAKED)
 			fk(PandaBaked{}, rc.q, F);
 		else
 			fk(P.model, rc.q, F);
-		if constexpr (BAKED)
-			mass_matrix(PandaBaked{}, F, M);
-		else
-			mass_matrix(P.model, F, M);
-		if (P.gravity_comp) {
-			if constexpr (BAKED)
-				gravity_vector(PandaBaked{}, F, g);
-			else
-				gravity_vector(P.model, F, g);
-		}
-		else {
-			UNROLL for (int i = 0; i < N; i++) g[i] = 0;
-		}
+		fast_model<BAKED>(P, F, pl, M, g);
 	}
 	SAI2B_PHASE();
 	const bool mine = ok && clean;
@@ -281,6 +304,40 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 	real tau[N];
 	fast_tick<FAST == 2>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
 	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
+}
+
+template <int FAST, bool BAKED>
+__global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restrict__ Pp, int with_comp,
+														  int* __restrict__ fb_counts, int* __restrict__ fb_list,
+														  int parity) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
+	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
+	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
+	if constexpr (FAST == 1) {
+		if (b < B) tick_fast1_loads<BAKED, NoPayload>(P, with_comp, fb_counts, fb_list, parity, b);
+		return;
+	}
+	__shared__ real img[StageLayout<FAST>::DOUBLES];
+	tick_fast_body<FAST, BAKED, NoPayload>(Pp, with_comp, fb_counts, fb_list, parity, img);
+}
+// the same tick with each robot's payload added to its M and g (selected by the host: sai2b_set_link_payload)
+template <int FAST, bool BAKED>
+__global__ __launch_bounds__(64) void tick_fast_payload_kernel(const DevParams* __restrict__ Pp, int with_comp,
+																  int* __restrict__ fb_counts, int* __restrict__ fb_list,
+																  int parity) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
+	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
+	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
+	if constexpr (FAST == 1) {
+		if (b < B) tick_fast1_loads<BAKED, Payload>(P, with_comp, fb_counts, fb_list, parity, b);
+		return;
+	}
+	__shared__ real img[StageLayout<FAST, true>::DOUBLES];
+	tick_fast_body<FAST, BAKED, Payload>(Pp, with_comp, fb_counts, fb_list, parity, img);
 }
 
 #endif	// SAI2B_N == 7
@@ -319,7 +376,12 @@ __global__ __launch_bounds__(64) void task_kernel(const DevParams* __restrict__ 
 		Frames F;
 		fk(P.model, rc.q, F);
 		real M[N * N];
-		mass_matrix(P.model, F, M);
+		if (P.payload) {  // wave-uniform
+			Payload pl;
+			payload_load(P.payload, P.payload_link, B, b, pl);
+			mass_matrix(P.model, F, M, pl);
+		} else
+			mass_matrix(P.model, F, M);
 		spd_inverse<N>(M, rc.Minv);
 		if (tk.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES) {
 			UNROLL for (int i = 0; i < N; i++) M[i * N + i] = fmax(M[i * N + i], tk.bie_threshold);
@@ -393,11 +455,23 @@ __global__ __launch_bounds__(64) void reinit_kernel(const DevParams* __restrict_
 
 static void launch_fast(int fast, int baked, dim3 grid, dim3 block, hipStream_t stream, const sai2b::DevParams* d_params,
 						int with_comp, int* fb_counts, int* fb_list, int parity) {
-	if (fast >= 3) {  // general hierarchies (sai2b_cert.hip); fast - 3 = most rows of a partial task
-		sai2b_launch_tick_cert(d_params, (int)grid.x * 64, fast - 3, with_comp, fb_counts, fb_list, parity, stream);
+	if (fast >= 3) {  // general hierarchies (sai2b_cert.hip); fast - 3 = most rows of a partial task; bit 3: the payload form
+		sai2b_launch_tick_cert(d_params, (int)grid.x * 64, fast - 3, with_comp | ((baked & 2) ? 8 : 0), fb_counts, fb_list, parity, stream);
 		return;
 	}
 #if SAI2B_N == 7
+	if (baked & 2) {  // the context has per-robot payloads
+		baked &= 1;
+		if (fast == 2 && baked)
+			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<2, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		else if (fast == 2)
+			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<2, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		else if (baked)
+			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<1, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		else
+			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<1, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+		return;
+	}
 	if (fast == 2 && baked)
 		hipLaunchKernelGGL((sai2b::tick_fast_kernel<2, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
 	else if (fast == 2)
@@ -410,6 +484,8 @@ static void launch_fast(int fast, int baked, dim3 grid, dim3 block, hipStream_t 
 }
 
 // with_comp: bit 0 = JointTask compensation, bit 1 (tick_cert_kernel only) = no in-lane singular handling
+// baked: bit 0 = the compile-time Panda, bit 1 = the context has per-robot payloads (the SVD-free kernels' payload forms;
+// the generic kernels find the rows in the parameter block)
 extern "C" int sai2b_launch_tick(const sai2b::DevParams* d_params, int B, int debug, int fast, int baked, int commit_sh,
 								 int with_comp_bits, int do_torque, int* fb_counts, int* fb_list, int parity, int group, hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);

@@ -134,6 +134,8 @@ constexpr int POPC_WINDOW = 250, POPC_MAX_COUNTER = 50;	 // POPCExplicitForceCon
 // istate rows
 constexpr int IS_NTYPES = 7, IS_COUNT = 8, IS_SIZE = 9, IS_C1 = 10, IS_C2 = 11;
 
+constexpr int PAYLOAD_ROWS = 10;  // rows of a payload buffer: mass, com 3, inertia 6
+
 struct DevParams {
 	int B;
 	int n_tasks;
@@ -146,6 +148,12 @@ struct DevParams {
 	double bie_thr;
 	DevModel model;
 	DevTask task[SAI2B_MAX_TASKS];
+	// per-robot payloads (sai2b_set_link_payload), behind everything else so that no other field moves: [10][B] rows mass,
+	// com 3, inertia 6 of the body on link *_link, or NULL. payload: what the tick kernels build M and g with;
+	// plant_payload: what sim_kernel integrates
+	const double* payload;
+	const double* plant_payload;
+	int payload_link, plant_payload_link;
 };
 
 }  // namespace sai2b

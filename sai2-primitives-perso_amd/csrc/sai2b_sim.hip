@@ -19,9 +19,11 @@ namespace sai2b {
 // b(q, dq) = C dq (+ g): Newton-Euler with zero joint accelerations. World-frame angular velocity w,
 // angular acceleration al, linear acceleration a of each joint-frame origin; forces F and moments Nn
 // about the link COMs; backward accumulation to the joint axes.
+// pl: the plant's payload, a second body on link pl.link (none: link < 0)
 template <class MD>
-DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gravity, real* b) {
+DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gravity, real* b, const Payload& pl) {
 	real F[N][3], Nn[N][3], rc[N][3];
+	real Fp[3] = {0, 0, 0}, Np[3] = {0, 0, 0}, rp[3] = {0, 0, 0};  // the payload's force, moment about its COM, COM from the link origin
 	real w[3] = {0, 0, 0}, al[3] = {0, 0, 0}, a[3] = {0, 0, 0}, o[3] = {0, 0, 0};
 	if (with_gravity) {
 		UNROLL for (int k = 0; k < 3; k++) a[k] = -md.gravity[k];
@@ -69,6 +71,26 @@ DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gr
 			F[i][k] = md.mass[i] * ac[k];
 			Nn[i][k] = Ial[k] + t1[k];
 		}
+		if (pl.link == i) {
+			UNROLL for (int k = 0; k < 3; k++) rp[k] = fma(R[3 * k], pl.c[0], fma(R[3 * k + 1], pl.c[1], R[3 * k + 2] * pl.c[2]));
+			cross3(al, rp, t1);
+			cross3(w, rp, t2);
+			cross3(w, t2, t3);
+			const real* pi = pl.I;
+			real Ip[9] = {pi[0], pi[3], pi[4], pi[3], pi[1], pi[5], pi[4], pi[5], pi[2]};
+			mv_t<3, 3>(R, al, u);
+			mv<3, 3>(Ip, u, Iu);
+			mv<3, 3>(R, Iu, Ial);
+			mv_t<3, 3>(R, w, u);
+			mv<3, 3>(Ip, u, Iu);
+			mv<3, 3>(R, Iu, Iw);
+			real t4[3];
+			cross3(w, Iw, t4);
+			UNROLL for (int k = 0; k < 3; k++) {
+				Fp[k] = pl.m * (a[k] + t1[k] + t3[k]);
+				Np[k] = Ial[k] + t4[k];
+			}
+		}
 	}
 	real f[3] = {0, 0, 0}, n[3] = {0, 0, 0};
 	UNROLL for (int i = N - 1; i >= 0; i--) {
@@ -82,6 +104,13 @@ DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gr
 		UNROLL for (int k = 0; k < 3; k++) {
 			n[k] += Nn[i][k] + t1[k];
 			f[k] += F[i][k];
+		}
+		if (pl.link == i) {
+			cross3(rp, Fp, t1);
+			UNROLL for (int k = 0; k < 3; k++) {
+				n[k] += Np[k] + t1[k];
+				f[k] += Fp[k];
+			}
 		}
 		const real* pr = (md.jtype[i] != 0) ? f : n;  // prismatic: the force along the axis
 		b[i] = Fr.R[i][2] * pr[0] + Fr.R[i][5] * pr[1] + Fr.R[i][8] * pr[2];
@@ -104,17 +133,25 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 		tq[i] = tau ? ld(tau, i, B, b) : 0.0;
 		if (q_keep) st(q_keep, i, B, b, q[i]);
 	}
+	// the PLANT's payload (sai2b_set_link_payload with SAI2B_PAYLOAD_PLANT); none: link -1, and a wave-uniform branch
+	// keeps M the call it always was (bias_forces skips its payload block on the link index)
+	const bool loaded = P.plant_payload != nullptr;
+	Payload pl;
+	payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
 		Frames F;
 		fk(P.model, q, F);
 		real M[N * N], L[N * N], dinv[N], bias[N], x[N];
-		bias_forces(P.model, F, dq, with_gravity != 0, bias);
+		bias_forces(P.model, F, dq, with_gravity != 0, bias, pl);
 		if (dbg_bias && s == 0) {
 			UNROLL for (int i = 0; i < N; i++) st(dbg_bias, i, B, b, bias[i]);
 		}
-		mass_matrix(P.model, F, M);
+		if (loaded)
+			mass_matrix(P.model, F, M, pl);
+		else
+			mass_matrix(P.model, F, M);
 		chol<N>(M, L, dinv);
 		UNROLL for (int i = 0; i < N; i++) x[i] = tq[i] - bias[i];
 		solve_lower<N>(L, dinv, x);

@@ -46,6 +46,20 @@ def shard_bounds(global_batch, world, rank):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def shard_rows(a, world, rank):
+    """the columns [lo, hi) of a [rows][global_batch] (or [global_batch]) array or tensor that `rank` owns; None stays None"""
+    if a is None:
+        return None
+    lo, hi = shard_bounds(a.shape[-1], world, rank)
+    part = a[..., lo:hi]
+    return part.contiguous() if hasattr(part, "contiguous") else part.copy()
+
+
+def set_link_payload(ctrl, world, rank, link, mass, com=None, inertia=None, target="both"):
+    """Controller.set_link_payload on this rank's shard of per-robot payload rows given for the whole batch"""
+    ctrl.set_link_payload(link, *[shard_rows(a, world, rank) for a in (mass, com, inertia)], target=target)
+
+
 def node_throughput(robots_per_rank, world, steps, elapsed_max):
     """whole-job control-ticks/sec: every rank's robots x steps over the slowest rank's time"""
     return robots_per_rank * world * steps / elapsed_max

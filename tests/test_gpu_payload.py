@@ -1,0 +1,312 @@
+"""Per-robot payloads on the GPU (sai2b_set_link_payload): robot b of the batch carries payload b % 16 (tests/payload_cases.py),
+and every kernel route is held to 16 CPU oracles, one per payload, each built from the robot's URDF text with the payload as
+one more body on a fixed joint (merged into its link by sai2b_model_from_urdf) and ticking its own robots.
+Bounds: max|tau - tau_oracle| / max|tau_oracle| < 1e-10 over the batch (the bound of smoke()), M to 1e-12 relative, the
+bias vector to 1e-12 and a simulated period to 1e-10 (tests/test_gpu_sim.py), the closed loop to 1e-9 on q and 1e-8 on dq."""
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+import payload_cases as pc
+import sai2_primitives_perso_amd as pkg
+from sai2_primitives_perso_amd import _abi
+
+pytestmark = pytest.mark.gpu
+
+ROUTES = {
+    "default": {},
+    "no_baked": {"SAI2B_NO_BAKED_MODEL": "1"},
+    "prefer_cert": {"SAI2B_PREFER_CERT": "1"},
+    "no_inlane": {"SAI2B_NO_INLANE_SINGULAR": "1"},
+    "sing6": {"SAI2B_FORCE_SING6": "1"},
+    "generic16": {"SAI2B_NO_CERT_PATH": "1", "SAI2B_GENERIC_LANES": "16"},
+    "generic8": {"SAI2B_NO_CERT_PATH": "1", "SAI2B_GENERIC_LANES": "8"},
+    "introspection": {},
+}
+
+
+def _rel(a, b):
+    return np.abs(a - b).max() / np.abs(b).max()
+
+
+def _make(config, B, route, monkeypatch, gravity=True, seed=5, with_payload=True):
+    inp = pkg.workloads.make_inputs(config, B=B, seed=seed)
+    for k, v in ROUTES[route].items():
+        monkeypatch.setenv(k, v)
+    try:
+        g = pkg.Controller(pkg.panda_model(), pkg.task_configs(inp["tasks"]), B, device=0, introspection=route == "introspection")
+    finally:
+        for k in ROUTES[route]:
+            monkeypatch.delenv(k)
+    ol.load_inputs(g, inp)
+    g.enable_gravity_compensation(gravity)
+    if with_payload:
+        g.set_link_payload(6, *pc.rows(B))
+    return inp, g
+
+
+def _oracles(inp, B, gravity=True, scale=None):
+    o = pc.PayloadOracles(pc.texts("panda", scale=scale), ol.task_configs(inp["tasks"]), B)
+    o.load_inputs(inp)
+    o.enable_gravity_compensation(gravity)
+    return o
+
+
+@pytest.mark.parametrize("gravity", (True, False))
+@pytest.mark.parametrize("B", (4096, 4099))
+@pytest.mark.parametrize("config", (2, 3, 4))
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_every_route_matches_the_oracles_with_a_different_payload_per_robot(route, config, B, gravity, monkeypatch):
+    inp, g = _make(config, B, route, monkeypatch, gravity)
+    o = _oracles(inp, B, gravity)
+    tau, ref = g.tick(), o.tick()
+    e = _rel(tau, ref)
+    print(f"payload parity route={route} C{config} B={B} gravity={gravity}: {e:.3e}, work list {g.fallback_count()}")
+    assert e < 1e-10, e
+    if route == "introspection":
+        M, Mo = g.get_model(), o.get_model()
+        assert _rel(M, Mo) < 1e-12, _rel(M, Mo)
+    # a no-op would not pass: the torques without the payloads are far away
+    _, g0 = _make(config, B, route, monkeypatch, gravity, with_payload=False)
+    assert _rel(g0.tick(), ref) > 1e-7
+
+
+@pytest.mark.parametrize("no_task_cert", (False, True))
+@pytest.mark.parametrize("config", (3, 4))
+def test_hand_chained_task_calls_match_the_oracles(config, no_task_cert, monkeypatch):
+    B = 4099
+    if no_task_cert:
+        monkeypatch.setenv("SAI2B_NO_TASK_CERT", "1")
+    inp, g = _make(config, B, "default", monkeypatch)
+    o = _oracles(inp, B)
+    for c in (g, o):
+        N, tau = None, None
+        for t in range(len(inp["tasks"])):
+            c.task_update_model(t, N)
+            N = c.task_nullspaces(t)[2]
+            tau_t = c.task_compute_torques(t, tau)
+            tau = tau_t if tau is None else tau + tau_t
+        c.result = (N, tau)
+    assert _rel(g.result[1], o.result[1]) < 1e-10, _rel(g.result[1], o.result[1])
+    assert np.abs(g.result[0] - o.result[0]).max() < 1e-9
+
+
+def test_full_batch_default_route(monkeypatch):
+    B = 65536
+    inp, g = _make(3, B, "default", monkeypatch)
+    o = _oracles(inp, B)
+    e = _rel(g.tick(), o.tick())
+    assert e < 1e-10, e
+
+
+@pytest.mark.parametrize("robot,link", [("planar_4r", 3), ("six_r", 5), ("sliding_base", 7), ("sliding_base", 3)])
+def test_other_robot_sizes(robot, link):
+    import hp_fixture
+
+    B = 4099
+    text = hp_fixture.urdf_text(robot)
+    model, _ = pkg.model_from_urdf(text, is_file=False)
+    n = int(model.dof)
+    rng = np.random.default_rng(3)
+    q = np.ascontiguousarray(rng.uniform(-0.8, 0.8, size=(n, B)))
+    dq = np.ascontiguousarray(rng.uniform(-0.5, 0.5, size=(n, B)))
+    g = pkg.Controller(model, [pkg.joint_task_config("j", robot_dof=n)], B, device=0)
+    o = pc.PayloadOracles(pc.texts(robot, link=link), [ol.joint_task("j", robot_dof=n)], B)
+    for c in (g, o):
+        c.set_state(q, dq)
+        c.reinitialize()
+        c.set_jt_goals(0, q + 0.1, None, None)
+        c.enable_gravity_compensation(True)
+    # the rows are in the URDF link's frame; the model's link frame has its z along the joint axis: the pose of the one in the other
+    _, links = pkg.model_from_urdf(text, is_file=False)
+    idx, pos, R = pkg.resolve_link_frame(links, pc.link_name(text, link))
+    assert idx == link
+    m, c, I6 = pc.rows(B)
+    I = np.einsum("ij,jkb,lk->ilb", R, np.stack([I6[[0, 3, 4]], I6[[3, 1, 5]], I6[[4, 5, 2]]]), R)
+    g.set_link_payload(link, m, pos[:, None] + R @ c, np.stack([I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]))
+    e = _rel(g.tick(), o.tick())
+    assert e < 1e-10, (robot, link, e)
+    assert _rel(g.get_bias(True), o.get_bias(True)) < 1e-12
+
+
+# ---- plant
+
+def test_bias_and_one_simulated_period_with_the_plant_payload(monkeypatch):
+    B = 4099
+    inp, g = _make(3, B, "default", monkeypatch)
+    o = _oracles(inp, B)
+    for grav in (False, True):
+        assert _rel(g.get_bias(grav), o.get_bias(grav)) < 1e-12
+    tau = o.tick()
+    for c in (g, o):
+        c.sim_step(tau, 0.001, 2, with_gravity=True)
+    (qg, vg), (qo, vo) = g.get_state(), o.get_state()
+    assert np.abs(qg - qo).max() < 1e-10 and np.abs(vg - vo).max() < 1e-10
+    # the plant set alone: the controller's torques are those of an empty hand, the bias is the loaded arm's
+    g.clear_link_payload("controller")
+    o.set_state(inp["q"], inp["dq"]), g.set_state(inp["q"], inp["dq"])
+    assert _rel(g.get_bias(True), o.get_bias(True)) < 1e-12
+    _, g0 = _make(3, B, "default", monkeypatch, with_payload=False)
+    assert np.array_equal(g.tick(), g0.tick())
+
+
+def test_closed_loop_with_a_controller_that_believes_half_the_load(monkeypatch):
+    """200 periods: the controller computes with 1 x the payloads, the plant carries 2 x; against a pair of oracle sets (one
+    computes tau with the believed model, the other steps the real one)"""
+    B = 256
+    inp, g = _make(3, B, "default", monkeypatch, with_payload=False)
+    g.set_link_payload(6, *pc.rows(B), target="controller")
+    g.set_link_payload(6, *pc.rows(B, scale=2.0), target="plant")
+    oa, ob = _oracles(inp, B), _oracles(inp, B, scale=2.0)
+    _, gm = _make(3, B, "default", monkeypatch)  # matched: both sets 1 x
+    for _ in range(200):
+        tau_o = oa.tick()
+        g.tick(), gm.tick()
+        ob.sim_step(tau_o, 0.001, 1, with_gravity=True)
+        g.sim_step(None, 0.001, 1, with_gravity=True)
+        gm.sim_step(None, 0.001, 1, with_gravity=True)
+        q, dq = ob.get_state()
+        oa.set_state(q, dq)
+    (qg, vg), (qo, vo), (qm, _) = g.get_state(), ob.get_state(), gm.get_state()
+    assert np.abs(qg - qo).max() < 1e-9 and np.abs(vg - vo).max() < 1e-8, (np.abs(qg - qo).max(), np.abs(vg - vo).max())
+    assert np.abs(qg - qm).max() > 1e-3
+
+
+# ---- life cycle
+
+def test_set_change_clear_device_rows_reinitialize_and_round_trip(monkeypatch):
+    import torch
+
+    B = 4099
+    inp, g = _make(3, B, "default", monkeypatch)
+    _, g0 = _make(3, B, "default", monkeypatch, with_payload=False)
+    tau0 = g0.tick()
+    m, c, I = pc.rows(B)
+    link, m1, c1, I1 = g.get_link_payload("controller")
+    assert link == 6 and np.array_equal(m1, m) and np.array_equal(c1, c) and np.array_equal(I1, I)
+    assert g.get_link_payload("plant")[0] == 6
+    tau_a = g.tick()
+    # stateless configuration (ki = 0, generators off, regular poses): each tick equals a fresh oracle for that tick's payloads
+    o = _oracles(inp, B)
+    assert _rel(tau_a, o.tick()) < 1e-10
+    # half the robots swap what they hold for another (non-zero) payload: robot b < B / 2 now carries payload (b + 8) % 16
+    mp, cp, Ip = pc.payloads()
+    other = (np.arange(B) + 8) % pc.P
+    m2, c2, I2 = m.copy(), c.copy(), I.copy()
+    h = B // 2
+    m2[:h], c2[:, :h], I2[:, :h] = mp[other[:h]], cp[:, other[:h]], Ip[:, other[:h]]
+    g.set_link_payload(6, m2, c2, I2)
+    tau_b = g.tick()
+    t = pc.texts("panda")
+    o2 = pc.PayloadOracles(t[8:] + t[:8], ol.task_configs(inp["tasks"]), B)
+    o2.load_inputs(inp)
+    o2.enable_gravity_compensation(True)
+    ref_b = np.concatenate([o2.tick()[:, :h], o.tick()[:, h:]], axis=1)
+    assert _rel(tau_b, ref_b) < 1e-10, _rel(tau_b, ref_b)
+    assert np.array_equal(tau_b[:, h:], tau_a[:, h:]) and _rel(tau_b[:, :h], tau_a[:, :h]) > 1e-7
+    # the same rows written by a device producer through the buffer id
+    c = pc.rows(B)[1]
+    g.set_link_payload(6, m, c, I)
+    p = g.device_buffer(_abi.BUF_PAYLOAD)
+    assert p and g.device_buffer(_abi.BUF_PLANT_PAYLOAD)
+    class _Raw:  # zero-copy torch view of the library's payload rows
+        __cuda_array_interface__ = {"data": (int(p), False), "shape": (10, B), "typestr": "<f8", "version": 2}
+
+    g.synchronize()
+    torch.as_tensor(_Raw(), device="cuda").copy_(torch.as_tensor(np.concatenate([m2[None], c2, I2]), device="cuda"))
+    torch.cuda.synchronize()
+    assert np.array_equal(g.tick(), tau_b)
+    # torch tensors as arguments
+    g.set_link_payload(6, torch.from_numpy(m).cuda(), torch.from_numpy(c).cuda(), torch.from_numpy(I).cuda())
+    assert np.array_equal(g.tick(), tau_a)
+    g.reinitialize()
+    ol.load_inputs(g, inp)
+    assert np.array_equal(g.tick(), tau_a)
+    g.clear_link_payload()
+    assert g.get_link_payload("controller")[0] == -1 and not g.device_buffer(_abi.BUF_PAYLOAD)
+    assert np.array_equal(g.tick(), tau0)
+
+
+def test_validation(monkeypatch):
+    B = 64
+    _, g = _make(3, B, "default", monkeypatch, with_payload=False)
+    m, c, I = pc.rows(B)
+    bad = lambda a, v: (lambda x: (x.__setitem__((..., 5), v), x)[1])(a.copy())
+    neg_diag = I.copy()
+    neg_diag[1, 5] = -1e-3
+    for args in ((7, m), (-1, m), (6, bad(m, -1.0)), (6, bad(m, np.nan)), (6, m, bad(c, np.inf)), (6, m, c, bad(I, np.nan)),
+                 (6, m, c, neg_diag)):
+        with pytest.raises(ValueError):
+            g.set_link_payload(*args)
+    with pytest.raises(ValueError):
+        g.set_link_payload(6, m, target="neither")
+    g.set_link_payload(6, m, c, I * np.array([1, 1, 1, -1, -1, -1])[:, None])  # products of inertia may be negative
+
+
+# ---- facades and sharding
+
+def test_link_name_form_of_the_facade_equals_the_index_form():
+    """BatchedRobotModel.setLinkPayload by URDF link NAME: 'link6' of the 6R arm (frame rotated against the model's link
+    frame) and a name that needs no re-expression give the torques of the index form with the rows re-expressed by hand"""
+    import hp_fixture
+
+    B = 130
+    text = hp_fixture.urdf_text("six_r")
+    rng = np.random.default_rng(4)
+    q, dq = rng.uniform(-0.8, 0.8, (6, B)), rng.uniform(-0.5, 0.5, (6, B))
+    m, c, I = pc.rows(B)
+    name = pc.link_name(text, 5)
+    taus = []
+    for by_name in (True, False):
+        model, links = pkg.model_from_urdf(text, is_file=False)
+        robot = pkg.BatchedRobotModel(B, model=model)
+        robot.links = links
+        if by_name:
+            robot.setLinkPayload(name, m, c, I)
+        else:
+            robot.setLinkPayload(5, *pc.model_rows("six_r", 5, m, c, I))
+        robot.setQ(q), robot.setDq(dq)
+        task = pkg.JointTask(robot)
+        ctrl = pkg.RobotController(robot, [task])
+        ctrl.enableGravityCompensation(True)
+        task.setGoalPosition(q + 0.1)
+        taus.append(ctrl.tick())
+    assert np.array_equal(taus[0], taus[1])
+    assert taus[0].shape == (6, B)
+
+
+def test_two_uneven_shards_equal_one_context(monkeypatch):
+    """sharding.set_link_payload: two shards on device 0, 2 050 + 2 049 robots, bit-equal to one context"""
+    from sai2_primitives_perso_amd import sharding
+
+    B, world = 4099, 2
+    inp, g = _make(3, B, "default", monkeypatch)
+    tau = g.tick()
+    m, c, I = pc.rows(B)
+    parts = []
+    for rank in range(world):
+        lo, hi = sharding.shard_bounds(B, world, rank)
+        cut = lambda v: {k: cut(x) for k, x in v.items()} if isinstance(v, dict) else (
+            np.ascontiguousarray(v[..., lo:hi]) if isinstance(v, np.ndarray) and v.ndim and v.shape[-1] == B else v)
+        s = pkg.Controller(pkg.panda_model(), pkg.task_configs(inp["tasks"]), hi - lo, device=0)
+        ol.load_inputs(s, cut(inp))
+        s.enable_gravity_compensation(True)
+        sharding.set_link_payload(s, world, rank, 6, m, c, I)
+        parts.append(s.tick())
+    assert parts[0].shape[1] != parts[1].shape[1]
+    assert np.array_equal(np.concatenate(parts, axis=1), tau)
+
+
+def test_sharded_robot_controller_slices_the_rows(tmp_path):
+    """the C++ ShardedRobotController (tests/cpp/payload_sharded_test.cpp): two shards on device 0, uneven, bit-equal"""
+    import os
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "sai2-primitives-perso_amd", "csrc")
+    out = str(tmp_path / "payload_sharded_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-pthread", "-I", os.path.join(root, "include"),
+                    os.path.join(root, "tests", "cpp", "payload_sharded_test.cpp"), "-o", out, "-L", csrc, "-lsai2b", f"-Wl,-rpath,{csrc}",
+                    "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    r = subprocess.run([out], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr)
