@@ -66,6 +66,7 @@ inline void check(sai2b_ctx* ctx, int rc) {
 
 class RobotController;
 class TemplateTask;
+class BatchedSimulation;
 
 // Stands where the reference takes std::shared_ptr<Sai2Model::Sai2Model>
 class BatchedRobotModel {
@@ -264,6 +265,7 @@ public:
 
 protected:
 	friend class RobotController;
+	friend class BatchedSimulation;  // attachForceSensor reads the task's index
 	inline void syncConfig();
 	// the context this task lives in and its index there: the controller's, or its own
 	inline sai2b_ctx* ctx() const;
@@ -1289,7 +1291,110 @@ public:
 	inline Batch getJointPositions() const;
 	inline Batch getJointVelocities() const;
 
+	// Contact of the plant (sai2b.h "contact in the simulated plant"): what Sai2Simulation's world gives the reference's
+	// examples 07 - 10, as one compliant plane per robot. points_in_link: row-major n x 3, 1 <= n <= 4, in the frame of moving
+	// link `link`; plane_point / plane_normal [3][B] (world, unit normal out of the surface), stiffness [B] (N/m), damping [B]
+	// (s/m, empty: 0), friction [B] (empty: 0). Takes effect at the next integrate(). std::invalid_argument on what
+	// sai2b_set_contact rejects. A sensor attached before (attachForceSensor) stays attached.
+	void setContactPlanes(const int link, const std::vector<double>& points_in_link, const Batch& plane_point, const Batch& plane_normal,
+						  const Batch& stiffness, const Batch& damping = Batch(), const Batch& friction = Batch(),
+						  const double friction_velocity_eps = 1e-3) {
+		checkContactArguments(_dof, (size_t)sai2b_batch(_c), link, points_in_link, plane_point, plane_normal, stiffness, damping, friction,
+							  friction_velocity_eps);
+		sai2b_contact_config cfg;
+		detail::check(nullptr, sai2b_default_contact(&cfg, link, (int)(points_in_link.size() / 3), points_in_link.data()));
+		cfg.friction_velocity_eps = friction_velocity_eps;
+		cfg.sensor_task = _sensor_task;
+		detail::check(_c, sai2b_set_contact(_c, &cfg, plane_point.data(), plane_normal.data(), stiffness.data(),
+											damping.empty() ? nullptr : damping.data(), friction.empty() ? nullptr : friction.data(), 0));
+		_contact = cfg;
+		_has_contact = true;
+		_planes = {plane_point, plane_normal, stiffness, damping, friction};
+	}
+	// What setContactPlanes checks before the device is touched (the conditions of sai2b_set_contact on host arrays, plus the
+	// shapes): std::invalid_argument. Public and static so that callers, and tests without a device, can ask ahead.
+	static void checkContactArguments(const int dof, const size_t B, const int link, const std::vector<double>& points_in_link,
+									  const Batch& plane_point, const Batch& plane_normal, const Batch& stiffness, const Batch& damping,
+									  const Batch& friction, const double friction_velocity_eps) {
+		if (link < 0 || link >= dof) throw std::invalid_argument("setContactPlanes: link must be in [0, dof)");
+		if (points_in_link.empty() || points_in_link.size() % 3 != 0 || points_in_link.size() / 3 > SAI2B_MAX_CONTACT_POINTS)
+			throw std::invalid_argument("setContactPlanes: points_in_link must be n x 3 with n in [1, 4]");
+		if (!(friction_velocity_eps > 0) || !std::isfinite(friction_velocity_eps))
+			throw std::invalid_argument("setContactPlanes: friction_velocity_eps must be finite and > 0");
+		if (plane_point.size() != 3 * B || plane_normal.size() != 3 * B || stiffness.size() != B || (!damping.empty() && damping.size() != B) ||
+			(!friction.empty() && friction.size() != B))
+			throw std::invalid_argument("setContactPlanes: plane_point and plane_normal must be [3][B], stiffness, damping, friction [B]");
+		for (const Batch* a : {&plane_point, &plane_normal, &stiffness, &damping, &friction})
+			for (const double v : *a)
+				if (!std::isfinite(v)) throw std::invalid_argument("setContactPlanes: every value must be finite");
+		for (const double v : points_in_link)
+			if (!std::isfinite(v)) throw std::invalid_argument("setContactPlanes: every value must be finite");
+		for (size_t b = 0; b < B; b++) {
+			const double n = std::sqrt(plane_normal[b] * plane_normal[b] + plane_normal[B + b] * plane_normal[B + b] + plane_normal[2 * B + b] * plane_normal[2 * B + b]);
+			if (!(std::fabs(n - 1.0) <= 1e-9)) throw std::invalid_argument("setContactPlanes: plane_normal must have unit length (within 1e-9)");
+			if (stiffness[b] < 0 || (!damping.empty() && damping[b] < 0) || (!friction.empty() && friction[b] < 0))
+				throw std::invalid_argument("setContactPlanes: stiffness, damping and friction must be >= 0");
+		}
+	}
+	// the same by URDF link NAME: points given in that link's frame (a link behind fixed joints resolves to its moving link)
+	void setContactPlanes(const BatchedRobotModel& robot, const std::string& link_name, const std::vector<double>& points_in_link,
+						  const Batch& plane_point, const Batch& plane_normal, const Batch& stiffness, const Batch& damping = Batch(),
+						  const Batch& friction = Batch(), const double friction_velocity_eps = 1e-3) {
+		const double zero[3] = {0, 0, 0};
+		double fp[3], R[9];
+		const int link = robot.resolveLink(link_name, zero, nullptr, fp, R);
+		std::vector<double> pts(points_in_link.size() - points_in_link.size() % 3);
+		for (size_t k = 0; k + 2 < points_in_link.size(); k += 3)
+			for (int i = 0; i < 3; i++)
+				pts[k + i] = fp[i] + R[3 * i] * points_in_link[k] + R[3 * i + 1] * points_in_link[k + 1] + R[3 * i + 2] * points_in_link[k + 2];
+		if (points_in_link.size() % 3 != 0) pts.clear();
+		setContactPlanes(link, pts, plane_point, plane_normal, stiffness, damping, friction, friction_velocity_eps);
+	}
+	void clearContact() {
+		detail::check(_c, sai2b_clear_contact(_c));
+		_has_contact = false;
+	}
+	// The simulated force / moment sensor: after every integrate() the wrench the robot applies to the surface, in the task's
+	// sensor frame (setForceSensorFrame), is stored into the task's sensed rows on the device; no updateSensedForceAndMoment
+	// is needed. The task must belong to the controller this simulation runs in.
+	void attachForceSensor(const MotionForceTask& task) {
+		if (task.context() != _c) throw std::invalid_argument("attachForceSensor: the task does not belong to this simulation's controller");
+		setSensor(task.index());
+	}
+	void detachForceSensor() { setSensor(-1); }
+	struct ContactState {
+		Batch depth, normal_force;	// [4][B] per point: penetration (> 0 inside the surface) and normal force
+		Batch wrench_world;			// [6][B]: sum F_k and sum (x_k - x_c) x F_k on the robot
+		int robots_in_contact = 0;
+	};
+	ContactState getContactState() const {
+		const size_t B = (size_t)sai2b_batch(_c);
+		ContactState s;
+		s.depth.resize(SAI2B_MAX_CONTACT_POINTS * B), s.normal_force.resize(SAI2B_MAX_CONTACT_POINTS * B), s.wrench_world.resize(6 * B);
+		detail::check(_c, sai2b_get_contact_state(_c, s.depth.data(), s.normal_force.data(), s.wrench_world.data(), &s.robots_in_contact));
+		return s;
+	}
+	int robotsInContact() const {
+		int n = 0;
+		detail::check(_c, sai2b_get_contact_state(_c, nullptr, nullptr, nullptr, &n));
+		return n;
+	}
+
 private:
+	void setSensor(const int task) {
+		if (_has_contact) {
+			sai2b_contact_config cfg = _contact;
+			cfg.sensor_task = task;
+			detail::check(_c, sai2b_set_contact(_c, &cfg, _planes[0].data(), _planes[1].data(), _planes[2].data(),
+												_planes[3].empty() ? nullptr : _planes[3].data(), _planes[4].empty() ? nullptr : _planes[4].data(), 0));
+			_contact = cfg;
+		}  // without planes yet only the index is remembered: it is validated with them (setContactPlanes)
+		_sensor_task = task;
+	}
+	sai2b_contact_config _contact = {};
+	bool _has_contact = false;
+	int _sensor_task = -1;
+	std::vector<Batch> _planes;	 // the host rows of the last setContactPlanes (re-sent when the sensor changes)
 	sai2b_ctx* _c;
 	int _dof = SAI2B_DOF;
 	double _dt;

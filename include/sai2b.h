@@ -28,6 +28,7 @@ extern "C" {
 #define SAI2B_MAX_DOF 8	  /* joints of the largest supported robot; the library holds builds for 4, 6, 7 and 8 */
 #define SAI2B_DOF 7		  /* the Panda's, the default of the helpers that take no robot (source compatibility) */
 #define SAI2B_MAX_TASKS 4 /* tasks in one controller hierarchy */
+#define SAI2B_MAX_CONTACT_POINTS 4 /* contact points of the simulated plant (sai2b_contact_config) */
 #define SAI2B_SH_HISTORY 200 /* SingularityHandler.cpp:16 BUFFER_SIZE */
 
 /* reference src/tasks/TemplateTask.h:19-23 */
@@ -370,7 +371,11 @@ enum sai2b_buffer {
 	 * device-resident producer may rewrite the rows between ticks, ordered with sai2b_stream(); the next tick / sim step
 	 * reads them. Such rows are not inspected. */
 	SAI2B_BUF_PAYLOAD = 8,
-	SAI2B_BUF_PLANT_PAYLOAD = 9
+	SAI2B_BUF_PLANT_PAYLOAD = 9,
+	/* the plant's contact rows (sai2b_set_contact), [9][B] = plane point 3, unit normal 3, stiffness, damping, friction. NULL
+	 * until a contact has been set (and after it is cleared). A device-resident producer may rewrite the rows between steps,
+	 * ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
+	SAI2B_BUF_CONTACT = 10
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -421,6 +426,52 @@ int sai2b_clear_link_payload(sai2b_ctx* ctx, int target);
 /* the rows of ONE target (SAI2B_PAYLOAD_CONTROLLER or SAI2B_PAYLOAD_PLANT) to host arrays, any may be NULL; *link = -1 and
  * zeros when that target has no payload */
 int sai2b_get_link_payload(sai2b_ctx* ctx, int target, int* link, double* mass, double* com, double* inertia);
+
+/* ------------------------------------------------------------------ contact in the simulated plant
+ * A compliant contact model inside sai2b_sim_step and a simulated force / moment sensor, so that a force-controlled closed
+ * loop (tick, sai2b_sim_step(NULL), tick, ...) never leaves the device. Batch-uniform: the moving link the contact geometry
+ * is fixed to, 1 to 4 contact points in that link's frame (one: a probe tip; four corners of a plate: surface-surface
+ * contact with moments), the friction regularisation speed (m/s, > 0) and the MotionForceTask whose sensed rows the sensor
+ * writes (-1: no sensor). Per robot: one plane (point and outward unit normal, world frame), stiffness k (N/m), damping d
+ * (s/m, Hunt-Crossley form) and friction coefficient mu. For point k with world position x and velocity v at the START of
+ * a substep:
+ *     delta = n . (p0 - x)     vn = n . v     f_n = max(0, k max(0, delta) (1 - d vn))     v_t = v - vn n
+ *     F = f_n n - mu f_n v_t / sqrt(|v_t|^2 + eps^2)            (the force ON the robot, world frame)
+ * and the substep is  dq += h M^-1 (tau + sum_k J_k^T F_k - b),  q += h dq. Every piece is continuous in the state. This
+ * law and the integrator are this library's definitions, not sai2-simulation's. The sensor is ideal (contact wrench only):
+ * after the last substep of a period it stores the wrench the robot applies to the environment, in the sensor frame of
+ * `sensor_task` (its sensor_rot / sensor_pos), into that task's SAI2B_BUF_SENSED rows; the next tick consumes them.
+ * sai2b_set_mft_sensed_wrench on that task keeps working (last writer wins, ordered on the ctx stream). */
+typedef struct sai2b_contact_config {
+	int link;					   /* moving link the points are fixed to (0-based, as sai2b_task_config.link) */
+	int n_points;				   /* 1 .. SAI2B_MAX_CONTACT_POINTS */
+	double points[SAI2B_MAX_CONTACT_POINTS][3]; /* in the link's frame, metres */
+	double friction_velocity_eps;  /* m/s, > 0: below it friction fades to zero linearly */
+	int sensor_task;			   /* index of a MotionForceTask, or -1 */
+} sai2b_contact_config;
+/* host only: n_points points ([n_points][3], NULL: one point at the link origin), eps = 1e-3 m/s, no sensor */
+int sai2b_default_contact(sai2b_contact_config* cfg, int link, int n_points, const double* points);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (link outside [0, robot_dof), n_points outside
+ * [1, 4], a non-finite point, eps not > 0, sensor_task neither -1 nor a MotionForceTask of `tasks`) */
+int sai2b_validate_contact(const sai2b_contact_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+						   char* msg, int msg_len);
+/* plane_point [3][B], plane_normal [3][B], stiffness [B], damping [B] (NULL: 0), friction [B] (NULL: 0). Host arrays are
+ * validated (SAI2B_INVALID_ARGUMENT: what sai2b_validate_contact rejects, non-finite anything, negative stiffness / damping /
+ * friction, a normal whose length is not within 1e-9 of 1); DEVICE arrays (on_device != 0) are copied as they are and NOT
+ * inspected. Ordered on the ctx stream; takes effect at the next sai2b_sim_step. sai2b_reinitialize keeps it (plant, not
+ * task state); sai2b_get_bias and every tick kernel never see it. Stiffness 0 for a robot: nothing touches that robot. A
+ * context that never sets a contact, or has cleared it, launches the simulation kernel it would without this feature. */
+int sai2b_set_contact(sai2b_ctx* ctx, const sai2b_contact_config* cfg, const double* plane_point, const double* plane_normal,
+					  const double* stiffness, const double* damping, const double* friction, int on_device);
+/* back to the plant without contact (the rows are kept for a later set, SAI2B_BUF_CONTACT gives NULL, no sensor writes) */
+int sai2b_clear_contact(sai2b_ctx* ctx);
+/* the configuration and the [9][B] rows to the host (either may be NULL); cfg->n_points = 0 and zeros without a contact */
+int sai2b_get_contact(sai2b_ctx* ctx, sai2b_contact_config* cfg, double* rows);
+/* what the last sai2b_sim_step left, from the state after its last substep, host arrays, any NULL: depth [4][B] (delta per
+ * point, > 0 inside the surface; rows of unused points 0), normal_force [4][B], wrench_world [6][B] = sum F_k and
+ * sum (x_k - x_c) x F_k (x_c: the control point of the sensor task, the contact link's origin without one),
+ * *robots_in_contact = robots with some f_n > 0 (counted on the device). Zeros before the first step with a contact. */
+int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* normal_force, double* wrench_world, int* robots_in_contact);
 
 /* ------------------------------------------------------------------ simulation harness
  * What the reference's examples obtain from the external sai2-simulation (examples/05-...cpp:215-236:

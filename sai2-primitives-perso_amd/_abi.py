@@ -24,6 +24,8 @@ OK, INVALID_ARGUMENT, RUNTIME_ERROR, UNSUPPORTED = 0, 1, 2, 3
 # enum sai2b_buffer
 BUF_Q, BUF_DQ, BUF_TAU, BUF_GOALS, BUF_SENSED, BUF_STATE, BUF_TASK_N, BUF_TASK_N_TOTAL = 0, 1, 2, 3, 4, 5, 6, 7
 BUF_PAYLOAD, BUF_PLANT_PAYLOAD = 8, 9  # [10][B] per-robot payload rows of the controller / the plant (sai2b_set_link_payload)
+BUF_CONTACT = 10  # [9][B] contact rows of the plant: plane point 3, normal 3, stiffness, damping, friction (sai2b_set_contact)
+MAX_CONTACT_POINTS = 4
 PAYLOAD_CONTROLLER, PAYLOAD_PLANT, PAYLOAD_BOTH = 1, 2, 3  # enum sai2b_payload_target
 PAYLOAD_TARGETS = {"controller": PAYLOAD_CONTROLLER, "plant": PAYLOAD_PLANT, "both": PAYLOAD_BOTH}
 
@@ -177,6 +179,18 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SAI2B_LIB") or os.path.join(PKG_DIR, "csrc", "libsai2b.so")
 
 # every symbol include/sai2b.h declares (tests check that the built library exports all of them)
+class ContactConfig(C.Structure):
+    """sai2b_contact_config (include/sai2b.h "contact in the simulated plant")"""
+
+    _fields_ = [
+        ("link", _i),
+        ("n_points", _i),
+        ("points", (_d * 3) * MAX_CONTACT_POINTS),
+        ("friction_velocity_eps", _d),
+        ("sensor_task", _i),
+    ]
+
+
 EXPORTS = [
     "sai2b_panda_model",
     "sai2b_model_merge_fixed_body",
@@ -241,6 +255,12 @@ EXPORTS = [
     "sai2b_set_link_payload",
     "sai2b_clear_link_payload",
     "sai2b_get_link_payload",
+    "sai2b_default_contact",
+    "sai2b_validate_contact",
+    "sai2b_set_contact",
+    "sai2b_clear_contact",
+    "sai2b_get_contact",
+    "sai2b_get_contact_state",
 ]
 
 _lib = None
@@ -334,5 +354,11 @@ def load_library():
     lib.sai2b_set_link_payload.argtypes = [vp, _i, _i, vp, vp, vp, _i]
     lib.sai2b_clear_link_payload.argtypes = [vp, _i]
     lib.sai2b_get_link_payload.argtypes = [vp, _i, P(_i), vp, vp, vp]
+    lib.sai2b_default_contact.argtypes = [P(ContactConfig), _i, _i, P(_d)]
+    lib.sai2b_validate_contact.argtypes = [P(ContactConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_set_contact.argtypes = [vp, P(ContactConfig), vp, vp, vp, vp, vp, _i]
+    lib.sai2b_clear_contact.argtypes = [vp]
+    lib.sai2b_get_contact.argtypes = [vp, P(ContactConfig), vp]
+    lib.sai2b_get_contact_state.argtypes = [vp, vp, vp, vp, P(_i)]
     _lib = lib
     return lib

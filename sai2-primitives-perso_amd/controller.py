@@ -255,6 +255,61 @@ class Controller:
                                                  *[C.c_void_p(x.ctypes.data) for x in (m, c, i)]))
         return link.value, m, c, i
 
+    # -- contact in the simulated plant (sai2b.h "contact in the simulated plant")
+    def contact_config(self, link, points=None, sensor_task=-1, friction_velocity_eps=1e-3):
+        """-> ContactConfig: `points` [n][3] in the frame of moving link `link` (None: the link origin), 1 <= n <= 4"""
+        pts = np.zeros((1, 3)) if points is None else np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        cfg = _abi.ContactConfig()
+        rc = self.lib.sai2b_default_contact(C.byref(cfg), int(link), int(pts.shape[0]), pts.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        cfg.sensor_task = int(sensor_task)
+        cfg.friction_velocity_eps = float(friction_velocity_eps)
+        return cfg
+
+    def set_contact(self, link, points, plane_point, plane_normal, stiffness, damping=None, friction=None, sensor_task=-1,
+                    friction_velocity_eps=1e-3):
+        """every robot's own surface for sim_step: contact points [n][3] fixed to `link` (or a ContactConfig as `link`, then
+        `points` is ignored), per robot plane_point [3][B], unit plane_normal [3][B] (out of the surface), stiffness [B] (N/m),
+        damping [B] (s/m, None: 0), friction [B] (None: 0); numpy arrays or torch CUDA tensors. sensor_task: the MotionForceTask
+        whose sensed rows the simulated force / moment sensor writes after every step (-1: none)"""
+        if isinstance(link, _abi.ContactConfig):
+            if points is not None or sensor_task != -1 or friction_velocity_eps != 1e-3:
+                raise ValueError("set_contact: a ContactConfig carries its own points, sensor_task and friction_velocity_eps")
+            cfg = link
+        else:
+            cfg = self.contact_config(link, points, sensor_task, friction_velocity_eps)
+
+        def row(a):
+            if a is None or hasattr(a, "data_ptr"):
+                return a if a is None or a.dim() == 2 else a.view(1, -1)
+            return np.ascontiguousarray(a, dtype=np.float64).reshape(1, -1)
+
+        k, d, mu = row(stiffness), row(damping), row(friction)
+        ins = [self._in(o, r) for o, r in zip((plane_point, plane_normal, k, d, mu), (3, 3, 1, 1, 1))]
+        self._rc(self.lib.sai2b_set_contact(self.h, C.byref(cfg), *[p for p, _ in ins], self._dev(plane_point, plane_normal, k, d, mu)))
+
+    def clear_contact(self):
+        self._rc(self.lib.sai2b_clear_contact(self.h))
+
+    def get_contact(self):
+        """-> (ContactConfig, rows [9][B]); n_points 0 and zeros when the plant has no contact"""
+        cfg, rows = _abi.ContactConfig(), np.empty((9, self.B))
+        self._rc(self.lib.sai2b_get_contact(self.h, C.byref(cfg), C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def get_contact_state(self):
+        """what the last sim_step left: dict depth [4][B], normal_force [4][B], wrench_world [6][B], robots_in_contact"""
+        n = C.c_int()
+        out = [np.empty((r, self.B)) for r in (4, 4, 6)]
+        self._rc(self.lib.sai2b_get_contact_state(self.h, *[C.c_void_p(x.ctypes.data) for x in out], C.byref(n)))
+        return dict(depth=out[0], normal_force=out[1], wrench_world=out[2], robots_in_contact=n.value)
+
+    def robots_in_contact(self):
+        n = C.c_int()
+        self._rc(self.lib.sai2b_get_contact_state(self.h, None, None, None, C.byref(n)))
+        return n.value
+
     # -- the path
     def reinitialize(self):
         self._rc(self.lib.sai2b_reinitialize(self.h))

@@ -108,6 +108,10 @@ struct sai2b_ctx {
 	// per-robot payloads (sai2b_set_link_payload): [0] the controller's rows, [1] the plant's, [10][B] each, created on first use;
 	// h_params.payload / plant_payload point at them while that set is in force
 	double* payload_rows[2] = {nullptr, nullptr};
+	// contact of the plant (sai2b_set_contact): the [9][B] rows, the status rows and the device counter of robots in contact,
+	// created on first use; h_params.contact points at the rows while a contact is in force
+	double* contact_rows = nullptr;
+	sai2b_contact_config contact_cfg = {};
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
@@ -1535,6 +1539,7 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_TASK_N_TOTAL: return task_ok ? ctx->tio[task].Ntot : nullptr;
 		case SAI2B_BUF_PAYLOAD: return (void*)ctx->h_params.payload;
 		case SAI2B_BUF_PLANT_PAYLOAD: return (void*)ctx->h_params.plant_payload;
+		case SAI2B_BUF_CONTACT: return (void*)ctx->h_params.contact;
 	}
 	return nullptr;
 }
@@ -1706,6 +1711,148 @@ extern "C" int sai2b_get_link_payload(sai2b_ctx* ctx, int target, int* link, dou
 	return fetch_rows(ctx, rows, 4, 6, inertia);
 }
 
+// ---- contact in the simulated plant ----
+extern "C" int sai2b_default_contact(sai2b_contact_config* cfg, int link, int n_points, const double* points) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_contact: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->link = link;
+	cfg->n_points = n_points;
+	cfg->friction_velocity_eps = 1e-3;
+	cfg->sensor_task = -1;
+	if (n_points < 1 || n_points > SAI2B_MAX_CONTACT_POINTS)
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_contact: n_points must be in [1, 4]");
+	for (int k = 0; points && k < n_points; k++)
+		for (int a = 0; a < 3; a++) cfg->points[k][a] = points[3 * k + a];
+	return SAI2B_OK;
+}
+static std::string contact_config_error(const sai2b_contact_config* c, const sai2b_task_config* tasks, int n_tasks, int robot_dof) {
+	if (!c) return "contact: null config";
+	if (c->link < 0 || c->link >= robot_dof) return "contact: link must be in [0, dof)";
+	if (c->n_points < 1 || c->n_points > SAI2B_MAX_CONTACT_POINTS) return "contact: n_points must be in [1, 4]";
+	for (int k = 0; k < c->n_points; k++)
+		for (int a = 0; a < 3; a++)
+			if (!std::isfinite(c->points[k][a])) return "contact: points must be finite";
+	if (!(c->friction_velocity_eps > 0) || !std::isfinite(c->friction_velocity_eps)) return "contact: friction_velocity_eps must be finite and > 0";
+	if (c->sensor_task != -1 && (!tasks || c->sensor_task < 0 || c->sensor_task >= n_tasks || tasks[c->sensor_task].type != SAI2B_MOTION_FORCE_TASK))
+		return "contact: sensor_task must be -1 or the index of a MotionForceTask";
+	return "";
+}
+extern "C" int sai2b_validate_contact(const sai2b_contact_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+									  char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? contact_config_error(cfg, tasks, n_tasks, robot_dof) : "contact: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_contact(sai2b_ctx* ctx, const sai2b_contact_config* cfg, const double* plane_point, const double* plane_normal,
+								 const double* stiffness, const double* damping, const double* friction, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
+	const std::string err = contact_config_error(cfg, ctx->cfg, ctx->T, N);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	if (!plane_point || !plane_normal || !stiffness)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: plane_point, plane_normal and stiffness are required");
+	const size_t B = ctx->B;
+	if (!on_device) {
+		for (size_t i = 0; i < 3 * B; i++)
+			if (!std::isfinite(plane_point[i]) || !std::isfinite(plane_normal[i]))
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: plane_point and plane_normal must be finite");
+		for (size_t b = 0; b < B; b++) {
+			const double n2 = plane_normal[b] * plane_normal[b] + plane_normal[B + b] * plane_normal[B + b] + plane_normal[2 * B + b] * plane_normal[2 * B + b];
+			if (!(std::fabs(std::sqrt(n2) - 1.0) <= 1e-9))
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: plane_normal must have unit length (within 1e-9)");
+			if (!std::isfinite(stiffness[b]) || stiffness[b] < 0)
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: stiffness must be finite and >= 0");
+			if (damping && (!std::isfinite(damping[b]) || damping[b] < 0))
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: damping must be finite and >= 0");
+			if (friction && (!std::isfinite(friction[b]) || friction[b] < 0))
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_contact: friction must be finite and >= 0");
+		}
+	}
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	DevParams& hp = ctx->h_params;
+	// three buffers, each created once: a failed allocation leaves the others for the next call, and no contact in force
+	if (!ctx->contact_rows && (rc = dev_alloc(ctx, &ctx->contact_rows, (size_t)sai2b::CONTACT_ROWS * B))) return rc;
+	if (!hp.contact_status && (rc = dev_alloc(ctx, &hp.contact_status, (size_t)sai2b::CONTACT_STATUS_ROWS * B))) return rc;
+	if (!hp.contact_count && (rc = dev_alloc(ctx, &hp.contact_count, 1))) return rc;
+	double* rows = ctx->contact_rows;
+	if ((rc = copy_rows(ctx, rows, plane_point, 3, on_device))) return rc;
+	if ((rc = copy_rows(ctx, rows + 3 * B, plane_normal, 3, on_device))) return rc;
+	if ((rc = copy_rows(ctx, rows + 6 * B, stiffness, 1, on_device))) return rc;
+	const double* opt[2] = {damping, friction};
+	for (int k = 0; k < 2; k++) {
+		if (opt[k]) {
+			if ((rc = copy_rows(ctx, rows + (7 + k) * B, opt[k], 1, on_device))) return rc;
+		} else
+			HIP_TRY(ctx, hipMemsetAsync(rows + (7 + k) * B, 0, B * sizeof(double), ctx->stream));
+	}
+	// everything is written: only now does the contact become the one in force
+	ctx->contact_cfg = *cfg;
+	hp.contact = rows;
+	hp.contact_link = cfg->link, hp.contact_n_points = cfg->n_points, hp.contact_sensor_task = cfg->sensor_task;
+	std::memset(hp.contact_points, 0, sizeof(hp.contact_points));
+	for (int k = 0; k < cfg->n_points; k++)
+		for (int a = 0; a < 3; a++) hp.contact_points[k][a] = cfg->points[k][a];
+	hp.contact_v_eps = cfg->friction_velocity_eps;
+	ctx->params_dirty = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_contact(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	// the status of the last step with a contact does not outlive it: sai2b_get_contact_state gives zeros from here on
+	if (ctx->h_params.contact_status) {
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->h_params.contact_status, 0, (size_t)sai2b::CONTACT_STATUS_ROWS * ctx->B * sizeof(double), ctx->stream));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->h_params.contact_count, 0, sizeof(int), ctx->stream));
+	}
+	ctx->h_params.contact = nullptr;
+	ctx->h_params.contact_sensor_task = -1;
+	ctx->params_dirty = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_contact(sai2b_ctx* ctx, sai2b_contact_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const bool on = ctx->h_params.contact != nullptr;
+	if (cfg) {
+		if (on)
+			*cfg = ctx->contact_cfg;
+		else {
+			std::memset(cfg, 0, sizeof(*cfg));
+			cfg->sensor_task = -1;
+		}
+	}
+	if (!on) {
+		if (rows) std::fill(rows, rows + (size_t)sai2b::CONTACT_ROWS * ctx->B, 0.0);
+		return SAI2B_OK;
+	}
+	return fetch_rows(ctx, ctx->h_params.contact, 0, sai2b::CONTACT_ROWS, rows);
+}
+extern "C" int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* normal_force, double* wrench_world, int* robots_in_contact) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	const double* S = ctx->h_params.contact_status;
+	if (!S) {  // never had a contact
+		if (depth) std::fill(depth, depth + SAI2B_MAX_CONTACT_POINTS * B, 0.0);
+		if (normal_force) std::fill(normal_force, normal_force + SAI2B_MAX_CONTACT_POINTS * B, 0.0);
+		if (wrench_world) std::fill(wrench_world, wrench_world + 6 * B, 0.0);
+		if (robots_in_contact) *robots_in_contact = 0;
+		return SAI2B_OK;
+	}
+	int rc;
+	if ((rc = fetch_rows(ctx, S, 0, SAI2B_MAX_CONTACT_POINTS, depth))) return rc;
+	if ((rc = fetch_rows(ctx, S, SAI2B_MAX_CONTACT_POINTS, SAI2B_MAX_CONTACT_POINTS, normal_force))) return rc;
+	if ((rc = fetch_rows(ctx, S, 2 * SAI2B_MAX_CONTACT_POINTS, 6, wrench_world))) return rc;
+	if (robots_in_contact) {
+		HIP_TRY(ctx, hipMemcpyAsync(robots_in_contact, ctx->h_params.contact_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	return SAI2B_OK;
+}
+
 // ---- simulation harness ----
 extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, double dt, int substeps, int with_gravity) {
 	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "null ctx");
@@ -1727,7 +1874,11 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	// the kernel saves the pose the tasks cached (q_pose) on its way in, when the state buffer still holds it
 	double* q_keep = ctx->q_is_pose ? ctx->q_pose : nullptr;
 	ctx->q_is_pose = false;
-	if (sai2b_launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, nullptr, q_keep, ctx->stream))
+	// the instantiation for what the context has set: plant payload, contact (whose counter starts each step at zero)
+	const DevParams& hp = ctx->h_params;
+	const int forms = (hp.plant_payload ? 1 : 0) | (hp.contact ? 2 : 0);
+	if (hp.contact) HIP_TRY(ctx, hipMemsetAsync(hp.contact_count, 0, sizeof(int), ctx->stream));
+	if (sai2b_launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, forms, nullptr, q_keep, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
 	ctx->models_fresh = false;
@@ -1749,7 +1900,7 @@ extern "C" int sai2b_get_bias(sai2b_ctx* ctx, int with_gravity, double* bias) {
 	if (rc) return rc;
 	if (!ctx->sim_tau && (rc = dev_alloc(ctx, &ctx->sim_tau, (size_t)N * ctx->B))) return rc;
 	// a zero-length step leaves the state as it is and writes the bias vector of the current state
-	if (sai2b_launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->sim_tau, nullptr, ctx->stream))
+	if (sai2b_launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload ? 1 : 0, ctx->sim_tau, nullptr, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	return fetch_rows(ctx, ctx->sim_tau, 0, N, bias);
 }

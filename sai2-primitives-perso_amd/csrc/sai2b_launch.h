@@ -51,8 +51,9 @@ extern "C" int sai2b_launch_otg_reinit(const sai2b::DevParams* d_params, int B, 
 // force / motion space re-parametrisation of MotionForceTask `task` at run time (flags in the kernel's comment)
 extern "C" int sai2b_launch_mft_reparam(const sai2b::DevParams* d_params, int B, int task, int flags, const double* q_pose,
 										hipStream_t stream);
-// simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place
+// simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.
+// forms selects the instantiation: bit 0 = plant payload, bit 1 = contact (the rows, status and counter of DevParams)
 extern "C" int sai2b_launch_sim(const sai2b::DevParams* d_params, int B, const double* tau, double dt, int substeps,
-								int with_gravity, double* dbg_bias, double* q_keep, hipStream_t stream);
+								int with_gravity, int forms, double* dbg_bias, double* q_keep, hipStream_t stream);
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
 extern "C" int sai2b_launch_mft_status(const sai2b::DevParams* d_params, int B, int task, double* out, hipStream_t stream);

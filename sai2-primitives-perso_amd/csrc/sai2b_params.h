@@ -135,6 +135,8 @@ constexpr int POPC_WINDOW = 250, POPC_MAX_COUNTER = 50;	 // POPCExplicitForceCon
 constexpr int IS_NTYPES = 7, IS_COUNT = 8, IS_SIZE = 9, IS_C1 = 10, IS_C2 = 11;
 
 constexpr int PAYLOAD_ROWS = 10;  // rows of a payload buffer: mass, com 3, inertia 6
+constexpr int CONTACT_ROWS = 9;	  // rows of the contact buffer: plane point 3, normal 3, stiffness, damping, friction
+constexpr int CONTACT_STATUS_ROWS = 2 * SAI2B_MAX_CONTACT_POINTS + 6;
 
 struct DevParams {
 	int B;
@@ -154,6 +156,15 @@ struct DevParams {
 	const double* payload;
 	const double* plant_payload;
 	int payload_link, plant_payload_link;
+	// contact of the plant (sai2b_set_contact), again behind everything else: contact [9][B] rows plane point 3, unit normal 3,
+	// stiffness, damping, friction, or NULL; contact_status [2 * 4 + 6][B] and the counter of robots in contact are written by
+	// sim_kernel's contact form; the rest is batch-uniform
+	const double* contact;
+	double* contact_status;
+	int* contact_count;
+	int contact_link, contact_n_points, contact_sensor_task, contact_reserved;
+	double contact_points[SAI2B_MAX_CONTACT_POINTS][3];
+	double contact_v_eps;
 };
 
 }  // namespace sai2b

@@ -19,11 +19,11 @@ namespace sai2b {
 // b(q, dq) = C dq (+ g): Newton-Euler with zero joint accelerations. World-frame angular velocity w,
 // angular acceleration al, linear acceleration a of each joint-frame origin; forces F and moments Nn
 // about the link COMs; backward accumulation to the joint axes.
-// pl: the plant's payload, a second body on link pl.link (none: link < 0)
-template <class MD>
-DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gravity, real* b, const Payload& pl) {
+// pl: the plant's payload, a second body on link pl.link (Payload with link < 0: none; NoPayload: the code without it)
+template <class MD, class PL>
+DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gravity, real* b, const PL& pl) {
 	real F[N][3], Nn[N][3], rc[N][3];
-	real Fp[3] = {0, 0, 0}, Np[3] = {0, 0, 0}, rp[3] = {0, 0, 0};  // the payload's force, moment about its COM, COM from the link origin
+	[[maybe_unused]] real Fp[3] = {0, 0, 0}, Np[3] = {0, 0, 0}, rp[3] = {0, 0, 0};  // the payload's force, moment about its COM, COM from the link origin
 	real w[3] = {0, 0, 0}, al[3] = {0, 0, 0}, a[3] = {0, 0, 0}, o[3] = {0, 0, 0};
 	if (with_gravity) {
 		UNROLL for (int k = 0; k < 3; k++) a[k] = -md.gravity[k];
@@ -71,7 +71,7 @@ DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gr
 			F[i][k] = md.mass[i] * ac[k];
 			Nn[i][k] = Ial[k] + t1[k];
 		}
-		if (pl.link == i) {
+		if constexpr (PL::on) if (pl.link == i) {
 			UNROLL for (int k = 0; k < 3; k++) rp[k] = fma(R[3 * k], pl.c[0], fma(R[3 * k + 1], pl.c[1], R[3 * k + 2] * pl.c[2]));
 			cross3(al, rp, t1);
 			cross3(w, rp, t2);
@@ -105,7 +105,7 @@ DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gr
 			n[k] += Nn[i][k] + t1[k];
 			f[k] += F[i][k];
 		}
-		if (pl.link == i) {
+		if constexpr (PL::on) if (pl.link == i) {
 			cross3(rp, Fp, t1);
 			UNROLL for (int k = 0; k < 3; k++) {
 				n[k] += Np[k] + t1[k];
@@ -117,8 +117,152 @@ DI void bias_forces(const MD& md, const Frames& Fr, const real* dq, bool with_gr
 	}
 }
 
+// ---- contact of the plant (sai2b_set_contact): up to four points fixed to one link against one plane per robot.
+// NoContact: sim_kernel compiles to what it is without the feature. The law (DESIGN "Contact in the simulated plant"):
+//   delta = n . (p0 - x_k), vn = n . v_k, f_n = max(0, k max(0, delta) (1 - d vn)), v_t = v_k - vn n,
+//   F_k = f_n n - mu f_n v_t / sqrt(|v_t|^2 + v_eps^2)      the force ON the robot, world frame
+// continuous in the state everywhere (no jump at touch-down or lift-off, regularised Coulomb friction).
+struct NoContact {
+	static constexpr bool on = false;
+};
+struct Contact {
+	static constexpr bool on = true;
+	real p0[3], n[3], k, d, mu;	 // the robot's own plane: rows of the [9][B] buffer
+};
+constexpr int CONTACT_MAX_POINTS = SAI2B_MAX_CONTACT_POINTS;
+DI void contact_load(const real* rows, int B, int b, Contact& ct) {
+	UNROLL for (int k = 0; k < 3; k++) {
+		ct.p0[k] = ld(rows, k, B, b);
+		ct.n[k] = ld(rows, 3 + k, B, b);
+	}
+	ct.k = ld(rows, 6, B, b);
+	ct.d = ld(rows, 7, B, b);
+	ct.mu = ld(rows, 8, B, b);
+}
+// frame of a batch-uniform link without dynamic register indexing (as frame_pose)
+DI void link_frame(int link, const Frames& F, real* R, real* p) {
+	UNROLL for (int k = 0; k < 9; k++) R[k] = F.R[N - 1][k];
+	UNROLL for (int k = 0; k < 3; k++) p[k] = F.p[N - 1][k];
+	UNROLL for (int i = 0; i < N - 1; i++)
+		if (link == i) {
+			UNROLL for (int k = 0; k < 9; k++) R[k] = F.R[i][k];
+			UNROLL for (int k = 0; k < 3; k++) p[k] = F.p[i][k];
+		}
+}
+// One point: world position x, force Fk on the robot, penetration and normal force. The point's velocity comes from the
+// joints at or below the link, J_k is never formed: a revolute joint contributes dq_i z_i x (x - p_i), a prismatic one dq_i z_i.
+template <class MD>
+DI void contact_point(const MD& md, const DevParams& P, const Contact& ct, const Frames& Fr, const real* Rl, const real* pl, int k,
+					  const real* dq, real* x, real* Fk, real& delta, real& fn) {
+	const double* c = P.contact_points[k];
+	UNROLL for (int a = 0; a < 3; a++) x[a] = fma(Rl[3 * a], c[0], fma(Rl[3 * a + 1], c[1], fma(Rl[3 * a + 2], c[2], pl[a])));
+	real v[3] = {0, 0, 0};
+	UNROLL for (int i = 0; i < N; i++) {
+		const real z[3] = {Fr.R[i][2], Fr.R[i][5], Fr.R[i][8]};
+		const real r[3] = {x[0] - Fr.p[i][0], x[1] - Fr.p[i][1], x[2] - Fr.p[i][2]};
+		real zr[3];
+		cross3(z, r, zr);
+		const bool pris = md.jtype[i] != 0;
+		const real w = i <= P.contact_link ? dq[i] : 0.0;
+		UNROLL for (int a = 0; a < 3; a++) v[a] = fma(w, pris ? z[a] : zr[a], v[a]);
+	}
+	const real* n = ct.n;
+	delta = n[0] * (ct.p0[0] - x[0]) + n[1] * (ct.p0[1] - x[1]) + n[2] * (ct.p0[2] - x[2]);
+	const real vn = n[0] * v[0] + n[1] * v[1] + n[2] * v[2];
+	fn = fmax(0.0, ct.k * fmax(0.0, delta) * (1.0 - ct.d * vn));
+	real vt[3];
+	UNROLL for (int a = 0; a < 3; a++) vt[a] = v[a] - vn * n[a];
+	const real s = ct.mu * fn / sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2] + P.contact_v_eps * P.contact_v_eps);
+	UNROLL for (int a = 0; a < 3; a++) Fk[a] = fn * n[a] - s * vt[a];
+}
+// tc = sum_k J_k^T F_k: row i gets z_i . ((x_k - p_i) x F_k) from a revolute joint, z_i . F_k from a prismatic one
+template <class MD>
+DI void contact_torques(const MD& md, const DevParams& P, const Contact& ct, const Frames& Fr, const real* dq, real* tc) {
+	real Rl[9], pl[3];
+	link_frame(P.contact_link, Fr, Rl, pl);
+	UNROLL for (int i = 0; i < N; i++) tc[i] = 0;
+	UNROLL for (int k = 0; k < CONTACT_MAX_POINTS; k++) {
+		if (k < P.contact_n_points) {  // batch-uniform
+			real x[3], Fk[3], delta, fn;
+			contact_point(md, P, ct, Fr, Rl, pl, k, dq, x, Fk, delta, fn);
+			UNROLL for (int i = 0; i < N; i++) {
+				const real z[3] = {Fr.R[i][2], Fr.R[i][5], Fr.R[i][8]};
+				const real r[3] = {x[0] - Fr.p[i][0], x[1] - Fr.p[i][1], x[2] - Fr.p[i][2]};
+				real m[3];
+				cross3(r, Fk, m);
+				const real* pr = (md.jtype[i] != 0) ? Fk : m;
+				const real t = z[0] * pr[0] + z[1] * pr[1] + z[2] * pr[2];
+				tc[i] += i <= P.contact_link ? t : 0.0;
+			}
+		}
+	}
+}
+// After the last substep: the status rows [2 * 4 + 6][B] (per point delta and f_n, then sum F_k and sum (x_k - x_c) x F_k in
+// the world frame; x_c: the control point of the sensor task, the contact link's origin without one), the count of robots
+// in contact, and the reading of the ideal force / moment sensor: the wrench the robot applies to the environment in the
+// sensor frame of the sensor task (MotionForceTask.cpp:793-828 read backwards), stored into that task's sensed rows.
+template <class MD>
+DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, const real* q, const real* dq, int B, int b) {
+	Frames Fr;
+	fk(md, q, Fr);
+	real Rl[9], pl[3], xc[3], Rc[9];
+	link_frame(P.contact_link, Fr, Rl, pl);
+	const bool sensor = P.contact_sensor_task >= 0;
+	if (sensor) {
+		frame_pose(P.task[P.contact_sensor_task], Fr, xc, Rc);
+	} else {
+		UNROLL for (int a = 0; a < 3; a++) xc[a] = pl[a];
+	}
+	real Ft[3] = {0, 0, 0}, Mt[3] = {0, 0, 0};
+	bool touching = false;
+	UNROLL for (int k = 0; k < CONTACT_MAX_POINTS; k++) {
+		real delta = 0, fn = 0;
+		if (k < P.contact_n_points) {
+			real x[3], Fk[3], m[3];
+			contact_point(md, P, ct, Fr, Rl, pl, k, dq, x, Fk, delta, fn);
+			const real r[3] = {x[0] - xc[0], x[1] - xc[1], x[2] - xc[2]};
+			cross3(r, Fk, m);
+			UNROLL for (int a = 0; a < 3; a++) {
+				Ft[a] += Fk[a];
+				Mt[a] += m[a];
+			}
+			touching = touching || fn > 0;
+		}
+		st(P.contact_status, k, B, b, delta);
+		st(P.contact_status, CONTACT_MAX_POINTS + k, B, b, fn);
+	}
+	UNROLL for (int a = 0; a < 3; a++) {
+		st(P.contact_status, 2 * CONTACT_MAX_POINTS + a, B, b, Ft[a]);
+		st(P.contact_status, 2 * CONTACT_MAX_POINTS + 3 + a, B, b, Mt[a]);
+	}
+	const unsigned long long in_contact = __ballot(touching);
+	if (threadIdx.x == 0 && in_contact) atomicAdd(P.contact_count, __popcll(in_contact));  // lane 0 always has a robot
+	if (sensor) {
+		const DevTask& t = P.task[P.contact_sensor_task];
+		real Rs[9], os[3], ms_w[3], t1[3], fs[3], ms[3];
+		mm<3, 3, 3>(Rc, t.sensor_rot, Rs);
+		mv3(Rc, t.sensor_pos, os);	// o_s - x_c
+		cross3(os, Ft, t1);
+		// -sum (x_k - o_s) x F_k = -(sum (x_k - x_c) x F_k - (o_s - x_c) x sum F_k)
+		UNROLL for (int a = 0; a < 3; a++) {
+			ms_w[a] = t1[a] - Mt[a];
+			t1[a] = -Ft[a];
+		}
+		mv_t<3, 3>(Rs, t1, fs);
+		mv_t<3, 3>(Rs, ms_w, ms);
+		UNROLL for (int a = 0; a < 3; a++) {
+			st(t.sensed, a, B, b, fs[a]);
+			st(t.sensed, 3 + a, B, b, ms[a]);
+		}
+	}
+}
+
+// PL: NoPayload / Payload (the PLANT's payload, sai2b_set_link_payload with SAI2B_PAYLOAD_PLANT), CT: NoContact / Contact;
+// the host launches the instantiation for what the context has set, sim_kernel<NoPayload, NoContact> is the kernel without
+// either feature.
 // q_keep != NULL: the joint positions as they are on entry are saved there first (the pose the tasks cached at
 // their last torque computation: see q_pose in sai2b_host.cpp)
+template <class PL, class CT>
 __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ Pp, const real* __restrict__ tau,
 												 real dt, int substeps, int with_gravity, real* __restrict__ dbg_bias,
 												 real* __restrict__ q_keep) {
@@ -133,11 +277,10 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 		tq[i] = tau ? ld(tau, i, B, b) : 0.0;
 		if (q_keep) st(q_keep, i, B, b, q[i]);
 	}
-	// the PLANT's payload (sai2b_set_link_payload with SAI2B_PAYLOAD_PLANT); none: link -1, and a wave-uniform branch
-	// keeps M the call it always was (bias_forces skips its payload block on the link index)
-	const bool loaded = P.plant_payload != nullptr;
-	Payload pl;
-	payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] PL pl;
+	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] CT ct;
+	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
@@ -148,12 +291,15 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 		if (dbg_bias && s == 0) {
 			UNROLL for (int i = 0; i < N; i++) st(dbg_bias, i, B, b, bias[i]);
 		}
-		if (loaded)
-			mass_matrix(P.model, F, M, pl);
-		else
-			mass_matrix(P.model, F, M);
+		mass_matrix(P.model, F, M, pl);
 		chol<N>(M, L, dinv);
-		UNROLL for (int i = 0; i < N; i++) x[i] = tq[i] - bias[i];
+		if constexpr (CT::on) {
+			real tc[N];
+			contact_torques(P.model, P, ct, F, dq, tc);
+			UNROLL for (int i = 0; i < N; i++) x[i] = (tq[i] + tc[i]) - bias[i];
+		} else {
+			UNROLL for (int i = 0; i < N; i++) x[i] = tq[i] - bias[i];
+		}
 		solve_lower<N>(L, dinv, x);
 		solve_lower_t<N>(L, dinv, x);
 		UNROLL for (int i = 0; i < N; i++) {
@@ -165,6 +311,7 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 		st((real*)P.q, i, B, b, q[i]);
 		st((real*)P.dq, i, B, b, dq[i]);
 	}
+	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b);
 }
 
 // What the tasks' observers read between ticks (MotionForceTask.h:121-165: getCurrentPosition /
@@ -242,9 +389,19 @@ extern "C" int sai2b_launch_mft_status(const sai2b::DevParams* d_params, int B, 
 	return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// forms: bit 0 = the plant carries a payload, bit 1 = the plant has a contact surface
 extern "C" int sai2b_launch_sim(const sai2b::DevParams* d_params, int B, const double* tau, double dt, int substeps,
-								int with_gravity, double* dbg_bias, double* q_keep, hipStream_t stream) {
-	hipLaunchKernelGGL(sai2b::sim_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, tau, dt, substeps, with_gravity,
-					   dbg_bias, q_keep);
+								int with_gravity, int forms, double* dbg_bias, double* q_keep, hipStream_t stream) {
+	using namespace sai2b;
+	const dim3 grid((B + 63) / 64), block(64);
+#define SAI2B_SIM_LAUNCH(PL, CT) \
+	hipLaunchKernelGGL((sim_kernel<PL, CT>), grid, block, 0, stream, d_params, tau, dt, substeps, with_gravity, dbg_bias, q_keep)
+	switch (forms & 3) {
+		case 0: SAI2B_SIM_LAUNCH(NoPayload, NoContact); break;
+		case 1: SAI2B_SIM_LAUNCH(Payload, NoContact); break;
+		case 2: SAI2B_SIM_LAUNCH(NoPayload, Contact); break;
+		default: SAI2B_SIM_LAUNCH(Payload, Contact); break;
+	}
+#undef SAI2B_SIM_LAUNCH
 	return hipGetLastError() == hipSuccess ? 0 : 1;
 }
