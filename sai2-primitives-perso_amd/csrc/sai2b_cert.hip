@@ -27,27 +27,17 @@ __global__ __launch_bounds__(64) void tick_cert_kernel(const DevParams* __restri
 	if (b >= B) return;
 	real* pend = pend_lds + threadIdx.x;
 	real tau[N];
-	// with_comp: bit 0 = JointTask compensation of the tasks above, bit 1 = singular MotionForceTasks go to the work list
-	// instead of through cert::singular_part (SAI2B_NO_INLANE_SINGULAR=1, the A/B switch)
+	// with_comp: TickCertBits (sai2b_params.h)
 	cert::SingPend sp;
 	sp.task = -1, sp.commit = 1, sp.store_t2 = 1, sp.took = 0;
 	PL pl;
 	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
-	const bool mine = cert::tick<MCAP, cert::DM, DevModel, false, S6, PL>(P, P.model, B, b, (with_comp & 1) != 0, pend, tau, nullptr, (with_comp & 2) ? nullptr : &sp, pl);
+	const bool mine = cert::tick<MCAP, cert::DM, DevModel, false, S6, PL>(P, P.model, B, b, (with_comp & TICK_CERT_COMP) != 0, pend, tau, nullptr, (with_comp & TICK_CERT_NO_INLANE) ? nullptr : &sp, pl);
 	{
 		const unsigned long long took = __ballot(sp.took != 0);
 		if (took && threadIdx.x == 0) atomicAdd(&fb_counts[2 + parity], __popcll(took));  // lane 0 is always in range
 	}
-	const unsigned long long declined = __ballot(!mine);
-	if (declined) {
-		int base = 0;
-		if (threadIdx.x == 0) base = atomicAdd(&fb_counts[parity], __popcll(declined));	 // lane 0 is always in range
-		base = __shfl(base, 0);
-		if (!mine) {
-			((gint*)fb_list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
-			return;
-		}
-	}
+	if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
 	cert::flush(P, B, b, pend);
 	cert::flush_singular(P, B, b, sp);
 	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + pend[i * 64]);  // RobotController.cpp:70-72
@@ -64,10 +54,8 @@ __global__ __launch_bounds__(64) void task_cert_kernel(const DevParams* __restri
 													  const double* __restrict__ tau_prec, double* __restrict__ tau_out, double* __restrict__ N_out,
 													  double* __restrict__ Ntot_out, int call_bits, int* __restrict__ tk_counts,
 													  int* __restrict__ tk_list, int parity) {
-	// call_bits: bit 0 = torques (computeTorques), bit 1 = the call commits the once-per-model-update singularity bookkeeping
-	// (updateTaskModel, or a computeTorques that has to update the model itself), bit 2 = singular MotionForceTasks go to the
-	// work list (SAI2B_NO_INLANE_SINGULAR)
-	const int do_torque = call_bits & 1;
+	// call_bits: TaskCertBits (sai2b_params.h)
+	const int do_torque = call_bits & TASK_CERT_TORQUE;
 	__shared__ real pend_lds[(cert::LDS_SLOTS + cert::TASK_EXTRA) * 64];
 	static_assert((cert::LDS_SLOTS + cert::TASK_EXTRA) * 64 * 8 * 4 <= 160 * 1024 || N > 7, "four wavefronts per CU (robots of up to 7 joints)");
 	const DevParams& P = *Pp;
@@ -82,10 +70,11 @@ __global__ __launch_bounds__(64) void task_cert_kernel(const DevParams* __restri
 	io.write_active = do_torque ? 0 : 1;
 	real tau[N];
 	cert::SingPend sp;
-	sp.task = -1, sp.commit = (call_bits >> 1) & 1, sp.store_t2 = do_torque, sp.took = 0;
+	sp.task = -1, sp.commit = (call_bits & TASK_CERT_COMMIT) ? 1 : 0, sp.store_t2 = do_torque, sp.took = 0;
 	PL pl;
 	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
-	const bool mine = cert::tick<MCAP, cert::DM, DevModel, true, false, PL>(P, P.model, B, b, tau_prec != nullptr, pend, tau, &io, (call_bits & 4) ? nullptr : &sp, pl);
+	const bool mine = cert::tick<MCAP, cert::DM, DevModel, true, false, PL>(P, P.model, B, b, tau_prec != nullptr, pend, tau, &io, (call_bits & TASK_CERT_NO_INLANE) ? nullptr : &sp, pl);
+	// (worklist_append, written out: through the helper this kernel comes out with other code, 512 registers and scratch as it is)
 	const unsigned long long declined = __ballot(!mine);
 	if (declined) {
 		int base = 0;
@@ -119,13 +108,7 @@ __global__ __launch_bounds__(64) void range_cert_kernel(const DevParams* __restr
 	PL pl;
 	if constexpr (PL::on) payload_load(P.payload, P.payload_link, B, b, pl);
 	const bool mine = cert::range_tick<MCAP, DevModel, PL>(P, P.model, B, b, inlane != 0, pl);
-	const unsigned long long declined = __ballot(!mine);
-	if (declined) {
-		int base = 0;
-		if (threadIdx.x == 0) base = atomicAdd(&rg_counts[parity], __popcll(declined));  // lane 0 is always in range
-		base = __shfl(base, 0);
-		if (!mine) ((gint*)rg_list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
-	}
+	worklist_append(rg_counts, rg_list, parity, mine, b);
 }
 
 }  // namespace sai2b
@@ -145,69 +128,39 @@ extern "C" int sai2b_debug_read_cstamps(unsigned long long* out, int cap) {
 }
 #endif
 
-// inlane: robots inside a blending region of a 2- or 3-row MotionForceTask stay in the kernel (cert::singular_range)
-extern "C" int sai2b_launch_range_cert(const sai2b::DevParams* d_params, int B, int max_rows, int* rg_counts, int* rg_list, int parity, int inlane,
-									   hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	using sai2b::Payload;
-	if (inlane & 2) {  // bit 1: the context has per-robot payloads
-		if (max_rows <= 3)
-			hipLaunchKernelGGL((sai2b::range_cert_kernel<3, Payload>), grid, block, 0, stream, d_params, rg_counts, rg_list, parity, inlane & 1);
-		else
-			hipLaunchKernelGGL((sai2b::range_cert_kernel<6, Payload>), grid, block, 0, stream, d_params, rg_counts, rg_list, parity, 0);
-		return (int)hipGetLastError();
-	}
-	if (max_rows <= 3)
-		hipLaunchKernelGGL(sai2b::range_cert_kernel<3>, grid, block, 0, stream, d_params, rg_counts, rg_list, parity, inlane);
-	else
-		hipLaunchKernelGGL(sai2b::range_cert_kernel<6>, grid, block, 0, stream, d_params, rg_counts, rg_list, parity, 0);
-	return (int)hipGetLastError();
+namespace sai2b {
+
+// (tables: the instantiations this file has, chosen at run time; [payload][...])
+int launch_range_cert(const DevParams* d_params, int B, int max_rows, bool payload, bool inlane_singular, const WorkList& rg,
+					  hipStream_t stream) {
+	static constexpr decltype(&range_cert_kernel<3>) kernel[2][2] = {{range_cert_kernel<3>, range_cert_kernel<6>},
+																	 {range_cert_kernel<3, Payload>, range_cert_kernel<6, Payload>}};
+	const bool small = max_rows <= 3;
+	// in the lane: robots inside a blending region of a 2- or 3-row MotionForceTask (cert::singular_range)
+	hipLaunchKernelGGL(kernel[payload][!small], dim3((B + 63) / 64), dim3(64), 0, stream, d_params, rg.counts, rg.list, rg.parity,
+					   (small && inlane_singular) ? 1 : 0);
+	return launch_result();
 }
 
-extern "C" int sai2b_launch_task_cert(const sai2b::DevParams* d_params, int B, int task, int max_rows, const double* Nprec_in,
-									  const double* tau_prec, double* tau_out, double* N_out, double* Ntot_out, int do_torque, int* tk_counts,
-									  int* tk_list, int parity, hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	using sai2b::Payload;
-	if (do_torque & 8) {  // bit 3 of the call bits: the context has per-robot payloads
-		do_torque &= 7;
-		if (max_rows <= 3)
-			hipLaunchKernelGGL((sai2b::task_cert_kernel<3, Payload>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-							   do_torque, tk_counts, tk_list, parity);
-		else
-			hipLaunchKernelGGL((sai2b::task_cert_kernel<6, Payload>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-							   do_torque, tk_counts, tk_list, parity);
-		return (int)hipGetLastError();
-	}
-	if (max_rows <= 3)
-		hipLaunchKernelGGL(sai2b::task_cert_kernel<3>, grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-						   do_torque, tk_counts, tk_list, parity);
-	else
-		hipLaunchKernelGGL(sai2b::task_cert_kernel<6>, grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-						   do_torque, tk_counts, tk_list, parity);
-	return (int)hipGetLastError();
+int launch_task_cert(const DevParams* d_params, int B, int task, int max_rows, bool payload, bool inlane_singular, const double* Nprec_in,
+					 const double* tau_prec, double* tau_out, double* N_out, double* Ntot_out, bool commit_sh, bool do_torque,
+					 const WorkList& tk, hipStream_t stream) {
+	static constexpr decltype(&task_cert_kernel<3>) kernel[2][2] = {{task_cert_kernel<3>, task_cert_kernel<6>},
+																	{task_cert_kernel<3, Payload>, task_cert_kernel<6, Payload>}};
+	const int call_bits = (do_torque ? TASK_CERT_TORQUE : 0) | (commit_sh ? TASK_CERT_COMMIT : 0) | (inlane_singular ? 0 : TASK_CERT_NO_INLANE);
+	hipLaunchKernelGGL(kernel[payload][max_rows > 3], dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, Nprec_in, tau_prec, tau_out,
+					   N_out, Ntot_out, call_bits, tk.counts, tk.list, tk.parity);
+	return launch_result();
 }
 
-extern "C" int sai2b_launch_tick_cert(const sai2b::DevParams* d_params, int B, int max_rows, int with_comp, int* fb_counts, int* fb_list,
-									  int parity, hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	// with_comp bit 2: the 6-row instantiation with the singular branch in the lane (cert::tick<.., S6>); bit 3: the payload forms
-	using sai2b::Payload;
-	if (with_comp & 8) {
-		with_comp &= 7;
-		if (max_rows <= 3)
-			hipLaunchKernelGGL((sai2b::tick_cert_kernel<3, false, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		else if (with_comp & 4)
-			hipLaunchKernelGGL((sai2b::tick_cert_kernel<6, true, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		else
-			hipLaunchKernelGGL((sai2b::tick_cert_kernel<6, false, Payload>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		return (int)hipGetLastError();
-	}
-	if (max_rows <= 3)
-		hipLaunchKernelGGL((sai2b::tick_cert_kernel<3>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	else if (with_comp & 4)
-		hipLaunchKernelGGL((sai2b::tick_cert_kernel<6, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	else
-		hipLaunchKernelGGL((sai2b::tick_cert_kernel<6>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	return (int)hipGetLastError();
+int launch_tick_cert(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, hipStream_t stream) {
+	static constexpr decltype(&tick_cert_kernel<3>) kernel[2][3] = {
+		{tick_cert_kernel<3>, tick_cert_kernel<6>, tick_cert_kernel<6, true>},
+		{tick_cert_kernel<3, false, Payload>, tick_cert_kernel<6, false, Payload>, tick_cert_kernel<6, true, Payload>}};
+	const int bits = (with_comp ? TICK_CERT_COMP : 0) | (form.inlane_singular ? 0 : TICK_CERT_NO_INLANE);
+	hipLaunchKernelGGL(kernel[form.payload][form.fast - 3 <= 3 ? 0 : form.sing6 ? 2 : 1], dim3((B + 63) / 64), dim3(64), 0, stream, d_params,
+					   bits, fb.counts, fb.list, fb.parity);
+	return launch_result();
 }
+
+}  // namespace sai2b

@@ -434,6 +434,22 @@ DI void st(real* p, int row, int B, int b, real v) { ((greal*)p)[(size_t)row * B
 DI int ldi(const int* p, int row, int B, int b) { return ((const gint*)p)[(size_t)row * B + b]; }
 DI void sti(int* p, int row, int B, int b, int v) { ((gint*)p)[(size_t)row * B + b] = v; }
 
+// A lane that is not `mine` appends its robot b to the work list of the kernel launched behind (one atomic per wavefront
+// that has such lanes, on counts[parity]) and gets true back: it touches no state and returns. One wavefront per workgroup.
+DI bool worklist_append(int* __restrict__ counts, int* __restrict__ list, int parity, bool mine, int b) {
+	const unsigned long long declined = __ballot(!mine);
+	if (declined) {
+		int base = 0;
+		if (threadIdx.x == 0) base = atomicAdd(&counts[parity], __popcll(declined));  // lane 0 is always in range
+		base = __shfl(base, 0);
+		if (!mine) {
+			((gint*)list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
+			return true;
+		}
+	}
+	return false;
+}
+
 
 // sigma matrices (MotionForceTask.cpp:892-971): sf = sigmaForce / sigmaMoment, sp = sigmaPosition /
 // sigmaOrientation for the 3x3 block `blk` of the partial-task projection

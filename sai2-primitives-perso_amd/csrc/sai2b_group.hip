@@ -75,42 +75,34 @@ extern "C" int sai2b_debug_read_stamps(unsigned long long* out, int cap) {
 }
 #endif
 
+namespace sai2b {
+
 // lanes: 16 or 8. range_only: the pass ahead of the generator kernels (gated JointTasks)
-extern "C" int sai2b_launch_tick_group(const sai2b::DevParams* d_params, int B, int lanes, int range_only, int commit_sh, int with_comp,
-									   int do_torque, const int* fb_count, const int* fb_list, hipStream_t stream) {
+int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_only, bool commit_sh, bool with_comp, bool do_torque,
+					  const int* fb_count, const int* fb_list, hipStream_t stream) {
 	const int gpb = 64 / lanes;
 	int blocks = (B + gpb - 1) / gpb;
 	// the pass over a work list strides over it: one wavefront per SIMD is all this kernel can have resident (512
 	// registers), so more workgroups than SIMDs only add launch cost when the list is short, which it usually is
 	if (fb_count && blocks > 1024) blocks = 1024;
-	const dim3 grid(blocks), block(64);
-	if (lanes == 16) {
-		if (range_only)
-			hipLaunchKernelGGL((sai2b::tick_group_kernel<16, true>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, fb_count, fb_list);
-		else
-			hipLaunchKernelGGL((sai2b::tick_group_kernel<16, false>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, fb_count, fb_list);
-	} else {
-		if (range_only)
-			hipLaunchKernelGGL((sai2b::tick_group_kernel<8, true>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, fb_count, fb_list);
-		else
-			hipLaunchKernelGGL((sai2b::tick_group_kernel<8, false>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, fb_count, fb_list);
-	}
-	return (int)hipGetLastError();
+	static constexpr decltype(&tick_group_kernel<16, false>) kernel[2][2] = {{tick_group_kernel<8, false>, tick_group_kernel<8, true>},
+																			 {tick_group_kernel<16, false>, tick_group_kernel<16, true>}};
+	hipLaunchKernelGGL(kernel[lanes == 16][range_only], dim3(blocks), dim3(64), 0, stream, d_params, commit_sh ? 1 : 0, with_comp ? 1 : 0,
+					   do_torque ? 1 : 0, fb_count, fb_list);
+	return launch_result();
 }
 
 // the TemplateTask calls with a robot spread over `lanes` (16: a short work list, latency; 8: a whole batch, throughput)
-extern "C" int sai2b_launch_task_group(const sai2b::DevParams* d_params, int B, int lanes, int task, const double* Nprec_in, const double* tau_prec,
-									   double* tau_out, double* N_out, double* Ntot_out, int commit_sh, int do_torque, const int* tk_count,
-									   const int* tk_list, hipStream_t stream) {
+int launch_task_group(const DevParams* d_params, int B, int lanes, int task, const double* Nprec_in, const double* tau_prec, double* tau_out,
+					  double* N_out, double* Ntot_out, bool commit_sh, bool do_torque, const int* tk_count, const int* tk_list,
+					  hipStream_t stream) {
 	const int gpb = 64 / lanes;
 	int blocks = (B + gpb - 1) / gpb;
 	if (tk_count && blocks > 1024) blocks = 1024;
-	const dim3 grid(blocks), block(64);
-	if (lanes == 16)
-		hipLaunchKernelGGL((sai2b::task_group_kernel<16>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-						   commit_sh, do_torque, tk_count, tk_list);
-	else
-		hipLaunchKernelGGL((sai2b::task_group_kernel<8>), grid, block, 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
-						   commit_sh, do_torque, tk_count, tk_list);
-	return (int)hipGetLastError();
+	auto* kernel = lanes == 16 ? task_group_kernel<16> : task_group_kernel<8>;
+	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
+					   commit_sh ? 1 : 0, do_torque ? 1 : 0, tk_count, tk_list);
+	return launch_result();
 }
+
+}  // namespace sai2b

@@ -21,6 +21,9 @@ using sai2b::rot_from_rpy;
 using sai2b::sym3_from6;
 using sai2b::DevParams;
 using sai2b::DevTask;
+using sai2b::TickCall;
+using sai2b::TickForm;
+using sai2b::WorkList;
 constexpr int N = SAI2B_N;  // joints of the robots this build serves (sai2b_params.h)
 
 static thread_local std::string g_error;
@@ -43,14 +46,11 @@ struct sai2b_ctx {
 	// lanes per robot of the generic kernel: SAI2B_GENERIC_LANES = 16 / 8 / 1 (1: the one-lane-per-robot kernel),
 	// default 0 = by the amount of work (generic_lanes())
 	int generic_lanes_env = 0;
-	// [4]: [0..1] robots the SVD-free kernel handed to the generic one (alternating by fb_parity), [2..3] robots that went through
-	// the in-lane singular branch of tick_cert_kernel (same alternation)
-	int* fb_counts = nullptr;
-	int* fb_list = nullptr;		// [B] their indices
-	int* rg_counts = nullptr;	// [2], rg_list [B]: the same for the range pass ahead of the trajectory generators
-	int* rg_list = nullptr;
-	int rg_parity = 0;
-	int fb_parity = 0;			// counter set of the last SVD-free launch
+	// work lists (sai2b_launch.h): fb = robots the tick's SVD-free kernel handed to the generic one (counts [4]: with the in-lane
+	// singular branch's), rg = the same for the range pass ahead of the trajectory generators, otg = robots that need the trajectory
+	// planner this tick (sai2b_otg.hip), tk = the task-level SVD-free kernel's (task_cert_kernel; created on first use).
+	// parity: the counter set of the last launch
+	WorkList fb, rg, otg, tk;
 	// How many robots the SVD-free kernel for general hierarchies keeps is a property of the workload (a 6-DOF task
 	// behind a partial JointTask is inside a blending region most of the time): every 8th such tick its count of
 	// declined robots comes back to the host (pinned word, consumed 8 ticks later: cert_tick); above 40 % of the batch the next 64
@@ -78,9 +78,6 @@ struct sai2b_ctx {
 	// (set_state, sim_step) saves q here first.
 	double* q_pose = nullptr;	// [7][B]
 	bool q_is_pose = true;
-	int* otg_counts = nullptr;	// [2][MAX_TASKS] work-list counters of the trajectory planner (sai2b_otg.hip)
-	int* otg_list = nullptr;	// [MAX_TASKS][B] robots that need the planner this tick
-	int otg_parity = 0;
 	// bit t set: task t's goals may have changed since the last OTG update (setters, reinitialize, config
 	// updates); goals_exposed: the caller holds the device pointer of some goals buffer, so always assume it
 	unsigned goals_dirty = ~0u;
@@ -116,9 +113,6 @@ struct sai2b_ctx {
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
 	int last_call_task = 0;	  // the last launch sequence was a task-level call: 1 = task_cert_kernel + work list, 2 = the generic task kernel alone
-	int* tk_count = nullptr;  // work list of the task-level SVD-free kernel (task_cert_kernel): 2 alternating counters + B robot indices
-	int* tk_list = nullptr;
-	int tk_parity = 0;
 	bool no_task_cert = false;	// SAI2B_NO_TASK_CERT=1: the generic task_kernel for every robot (A/B)
 	struct TaskIO {
 		double *Nprec = nullptr, *N = nullptr, *Ntot = nullptr, *tau = nullptr, *tau_prec = nullptr;
@@ -737,18 +731,18 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	if ((rc = dev_alloc(ctx, &ctx->tau, N * Bs))) return rc;
 	hp.q = ctx->q, hp.dq = ctx->dq, hp.tau = ctx->tau;
 	if ((rc = dev_alloc(ctx, &ctx->q_pose, (size_t)N * Bs))) return rc;
-	if ((rc = dev_alloc(ctx, &ctx->fb_counts, 4))) return rc;
-	if ((rc = dev_alloc(ctx, &ctx->fb_list, Bs))) return rc;
-	if ((rc = dev_alloc(ctx, &ctx->rg_counts, 2))) return rc;
-	if ((rc = dev_alloc(ctx, &ctx->rg_list, Bs))) return rc;
+	if ((rc = dev_alloc(ctx, &ctx->fb.counts, 4))) return rc;
+	if ((rc = dev_alloc(ctx, &ctx->fb.list, Bs))) return rc;
+	if ((rc = dev_alloc(ctx, &ctx->rg.counts, 2))) return rc;
+	if ((rc = dev_alloc(ctx, &ctx->rg.list, Bs))) return rc;
 	HIP_TRY(ctx, hipHostMalloc((void**)&ctx->fb_seen, 2 * sizeof(int), hipHostMallocDefault));
 	ctx->fb_seen[0] = ctx->fb_seen[1] = 0;
 	HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fb_seen_ev, hipEventDisableTiming));
-	if ((rc = dev_alloc(ctx, &ctx->otg_counts, 2 * SAI2B_MAX_TASKS + 2))) return rc;  // (+ 2: non-idle robots of a tick, alternating)
+	if ((rc = dev_alloc(ctx, &ctx->otg.counts, 2 * SAI2B_MAX_TASKS + 2))) return rc;  // (+ 2: non-idle robots of a tick, alternating)
 	HIP_TRY(ctx, hipHostMalloc((void**)&ctx->otg_busy_seen, sizeof(int), hipHostMallocDefault));
 	*ctx->otg_busy_seen = 1;
 	HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->otg_seen_ev, hipEventDisableTiming));
-	if ((rc = dev_alloc(ctx, &ctx->otg_list, SAI2B_MAX_TASKS * Bs))) return rc;
+	if ((rc = dev_alloc(ctx, &ctx->otg.list, SAI2B_MAX_TASKS * Bs))) return rc;
 	for (int t = 0; t < n_tasks; t++) {
 		ctx->cfg[t] = tasks[t];
 		normalise_axes(ctx->cfg[t]);
@@ -778,8 +772,8 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	ctx->params_dirty = true;
 	if ((rc = upload_params(ctx))) return rc;
 	// the reference constructs tasks from the model's current state (q = 0 until set_state)
-	if (sai2b_launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b_launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
@@ -912,7 +906,7 @@ extern "C" int sai2b_update_task_config(sai2b_ctx* ctx, int task, const sai2b_ta
 		int rc3 = upload_params(ctx);
 		if (rc3) return rc3;
 		if (reinit_mode >= 0) {
-			if (sai2b_launch_otg_reinit(ctx->d_params, ctx->B, task, reinit_mode, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
+			if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, task, reinit_mode, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
 				return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG enable launch failed");
 			ctx->launches++;
 		}
@@ -920,7 +914,7 @@ extern "C" int sai2b_update_task_config(sai2b_ctx* ctx, int task, const sai2b_ta
 	if (reparam) {
 		int rc4 = upload_params(ctx);
 		if (rc4) return rc4;
-		if (sai2b_launch_mft_reparam(ctx->d_params, ctx->B, task, reparam, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
+		if (sai2b::launch_mft_reparam(ctx->d_params, ctx->B, task, reparam, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "re-parametrisation launch failed");
 		ctx->launches++;
 	}
@@ -1045,8 +1039,8 @@ extern "C" int sai2b_reinitialize(sai2b_ctx* ctx) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	if (sai2b_launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b_launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	ctx->goals_dirty = ~0u;
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1102,6 +1096,18 @@ static int sing6_kind(const sai2b_ctx* ctx) {
 	if (ctx->no_inlane_singular || ctx->no_sing6) return 0;
 	const int ck = cert_kind(ctx);
 	return ck >= 3 + 4 ? ck : 0;
+}
+
+// The first kernel the ticks of this context run now (launch_tick switches sing_mode by what the counters say, and may skip
+// the SVD-free kernel for a while: cert_backoff)
+static TickForm tick_form(const sai2b_ctx* ctx) {
+	TickForm form;
+	form.fast = fast_kind(ctx);
+	if (const int alt = ctx->sing_mode ? sing6_kind(ctx) : 0) form.fast = alt, form.sing6 = true;
+	form.baked = ctx->baked_model;
+	form.payload = ctx->h_params.payload != nullptr;
+	form.inlane_singular = !ctx->no_inlane_singular;
+	return form;
 }
 
 // How many lanes a robot gets in the generic kernel (sai2b_group.hip). 16 = one DPP row per robot: the shortest
@@ -1169,13 +1175,14 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		// for the robots it can certify and only the others take the generic kernel's range pass
 		const int ck = (ctx->introspection || ctx->cert_backoff > 0) ? 0 : cert_kind(ctx);
 		if (ck) {
-			if (sai2b_launch_range_cert(ctx->d_params, ctx->B, ck - 3, ctx->rg_counts, ctx->rg_list, ctx->rg_parity, (ctx->no_inlane_singular ? 0 : 1) | (ctx->h_params.payload ? 2 : 0), ctx->stream) ||
-				sai2b_launch_tick_group(ctx->d_params, ctx->B, 16, 1, 0, with_comp, 0, ctx->rg_counts + ctx->rg_parity, ctx->rg_list, ctx->stream))
+			const TickForm form = tick_form(ctx);
+			if (sai2b::launch_range_cert(ctx->d_params, ctx->B, ck - 3, form.payload, form.inlane_singular, ctx->rg, ctx->stream) ||
+				sai2b::launch_tick_group(ctx->d_params, ctx->B, 16, true, false, with_comp, false, ctx->rg.count(), ctx->rg.list, ctx->stream))
 				return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
-			ctx->rg_parity ^= 1;
+			ctx->rg.parity ^= 1;
 			ctx->launches += 2;
 		} else {
-			if (sai2b_launch_range_pass(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, with_comp, generic_lanes(ctx, true), ctx->stream))
+			if (sai2b::launch_range_pass(ctx->d_params, ctx->B, ctx->introspection, with_comp, generic_lanes(ctx, true), ctx->stream))
 				return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
 			ctx->launches++;
 		}
@@ -1193,19 +1200,18 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 			// (a gated task keeps reading its goals: a robot skipped while they changed must see them later)
 			const int clean_mask = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & ((1u << SAI2B_MAX_TASKS) - 1u));
 			ctx->goals_dirty = 0;
-			if (sai2b_launch_otg(ctx->d_params, ctx->B, ctx->otg_counts, ctx->otg_list, ctx->otg_parity, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
+			if (sai2b::launch_otg(ctx->d_params, ctx->B, ctx->otg, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
 			if (!gated && !ctx->goals_exposed && !ctx->otg_seen_pending) {
-				HIP_TRY(ctx, hipMemcpyAsync(ctx->otg_busy_seen, ctx->otg_counts + 2 * SAI2B_MAX_TASKS + ctx->otg_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+				HIP_TRY(ctx, hipMemcpyAsync(ctx->otg_busy_seen, ctx->otg.counts + 2 * SAI2B_MAX_TASKS + ctx->otg.parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 				HIP_TRY(ctx, hipEventRecord(ctx->otg_seen_ev, ctx->stream));
 				ctx->otg_seen_pending = true;
 				ctx->otg_seen_tick = ctx->otg_tick;
 				ctx->otg_obs_epoch = ctx->goals_epoch;
 			}
-			ctx->otg_parity ^= 1;
+			ctx->otg.parity ^= 1;
 			ctx->launches += 2;
 		}
 	}
-	int fast_now = fast, cert_bits = ctx->no_inlane_singular ? 2 : 0;
 	const bool fast_wanted = fast != 0 && !ctx->introspection && do_torque && commit_sh;
 	if (fast_wanted) {
 		// Which first kernel, by what the last look at the counters said (those of tick k - 8, through two pinned words,
@@ -1234,23 +1240,26 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 				ctx->cert_backoff = 64;
 			}
 		}
-		if (ctx->sing_mode && alt) fast_now = alt, cert_bits |= 4;
-		if (fast_now >= 3 && ctx->cert_backoff > 0) {
-			ctx->cert_backoff--;
-			fast_now = 0;
-		}
 	}
-	const bool fast_launch = fast_wanted && fast_now != 0;
+	TickForm form = tick_form(ctx);	 // (with the mode as the look above left it)
+	if (fast_wanted && form.fast >= 3 && ctx->cert_backoff > 0) {
+		ctx->cert_backoff--;
+		form.fast = 0;
+	}
+	const bool fast_launch = fast_wanted && form.fast != 0;
 	ctx->last_tick_generic_only = do_torque && commit_sh && !fast_launch && !ctx->introspection;
-	if (fast_launch) ctx->fb_parity ^= 1;
+	if (fast_launch) ctx->fb.parity ^= 1;
 	// a long work list (thousands of robots) is throughput, not latency: two robots per DPP row, as for a whole batch
 	const bool long_list = fast_launch && ctx->fb_last_seen > 4096;	 // (16 lanes: 4 robots x 1024 wavefronts in one round)
-	if (sai2b_launch_tick(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast_now, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), commit_sh, (with_comp ? 1 : 0) | cert_bits, do_torque, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !fast_launch || long_list), ctx->stream))
+	TickCall call;
+	call.debug = ctx->introspection, call.commit_sh = commit_sh, call.with_comp = with_comp, call.do_torque = do_torque;
+	call.group = generic_lanes(ctx, !fast_launch || long_list);
+	if (sai2b::launch_tick(ctx->d_params, ctx->B, form, call, ctx->fb, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
 	if (fast_launch && !ctx->fb_seen_pending) {
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen, ctx->fb_counts + ctx->fb_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen + 1, ctx->fb_counts + 2 + ctx->fb_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen + 1, ctx->fb.took(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->fb_seen_ev, ctx->stream));
 		ctx->fb_seen_pending = true;
 		ctx->fb_seen_tick = ctx->cert_tick;
@@ -1368,25 +1377,25 @@ static int launch_task_generic(sai2b_ctx* ctx, int task, const double* Np, const
 	int lanes = ctx->introspection ? 0 : generic_lanes(ctx, count == nullptr);
 	if (!count && ctx->generic_lanes_env == 0) lanes = 0;
 	if (lanes)
-		return sai2b_launch_task_group(ctx->d_params, ctx->B, lanes, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list,
-									   ctx->stream);
-	return sai2b_launch_task(ctx->d_params, ctx->B, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list, ctx->stream);
+		return sai2b::launch_task_group(ctx->d_params, ctx->B, lanes, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list,
+										ctx->stream);
+	return sai2b::launch_task(ctx->d_params, ctx->B, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list, ctx->stream);
 }
 
 static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const double* tp, double* tau_out, double* N_out, double* Ntot_out,
 							int commit_sh, int do_torque) {
 	const int rows = task_cert_rows(ctx, task);
 	if (rows) {
-		if (!ctx->tk_count) {
+		if (!ctx->tk.counts) {
 			int rc;
-			if ((rc = dev_alloc(ctx, &ctx->tk_count, 2))) return rc;
-			if ((rc = dev_alloc(ctx, &ctx->tk_list, (size_t)ctx->B))) return rc;
+			if ((rc = dev_alloc(ctx, &ctx->tk.counts, 2))) return rc;
+			if ((rc = dev_alloc(ctx, &ctx->tk.list, (size_t)ctx->B))) return rc;
 		}
-		ctx->tk_parity ^= 1;
-		if (sai2b_launch_task_cert(ctx->d_params, ctx->B, task, rows, Np, tp, tau_out, N_out, Ntot_out,
-								   (do_torque ? 1 : 0) | (commit_sh ? 2 : 0) | (ctx->no_inlane_singular ? 4 : 0) | (ctx->h_params.payload ? 8 : 0), ctx->tk_count, ctx->tk_list,
-								   ctx->tk_parity, ctx->stream) ||
-			launch_task_generic(ctx, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, ctx->tk_count + ctx->tk_parity, ctx->tk_list))
+		ctx->tk.parity ^= 1;
+		const TickForm form = tick_form(ctx);
+		if (sai2b::launch_task_cert(ctx->d_params, ctx->B, task, rows, form.payload, form.inlane_singular, Np, tp, tau_out, N_out, Ntot_out, commit_sh,
+									do_torque, ctx->tk, ctx->stream) ||
+			launch_task_generic(ctx, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, ctx->tk.count(), ctx->tk.list))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task launch failed");
 		ctx->launches += 2;
 		ctx->last_call_task = 1;
@@ -1430,9 +1439,9 @@ extern "C" int sai2b_task_compute_torques(sai2b_ctx* ctx, int task, const double
 		}
 		const int clean = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & (1u << task));
 		ctx->goals_dirty &= ~(1u << task);
-		if (sai2b_launch_otg(ctx->d_params, ctx->B, ctx->otg_counts, ctx->otg_list, ctx->otg_parity, clean, 1 << task, jerk_mask(ctx), ctx->stream))
+		if (sai2b::launch_otg(ctx->d_params, ctx->B, ctx->otg, clean, 1 << task, jerk_mask(ctx), ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
-		ctx->otg_parity ^= 1;
+		ctx->otg.parity ^= 1;
 		ctx->launches += 2;
 	}
 	const double* tp = nullptr;
@@ -1464,8 +1473,8 @@ extern "C" int sai2b_task_reinitialize(sai2b_ctx* ctx, int task) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	if (sai2b_launch_reinit(ctx->d_params, ctx->B, task, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b_launch_otg_reinit(ctx->d_params, ctx->B, task, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctx->d_params, ctx->B, task, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, task, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	ctx->goals_dirty |= 1u << task;
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1876,9 +1885,8 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	ctx->q_is_pose = false;
 	// the instantiation for what the context has set: plant payload, contact (whose counter starts each step at zero)
 	const DevParams& hp = ctx->h_params;
-	const int forms = (hp.plant_payload ? 1 : 0) | (hp.contact ? 2 : 0);
 	if (hp.contact) HIP_TRY(ctx, hipMemsetAsync(hp.contact_count, 0, sizeof(int), ctx->stream));
-	if (sai2b_launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, forms, nullptr, q_keep, ctx->stream))
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr, nullptr, q_keep, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
 	ctx->models_fresh = false;
@@ -1900,7 +1908,7 @@ extern "C" int sai2b_get_bias(sai2b_ctx* ctx, int with_gravity, double* bias) {
 	if (rc) return rc;
 	if (!ctx->sim_tau && (rc = dev_alloc(ctx, &ctx->sim_tau, (size_t)N * ctx->B))) return rc;
 	// a zero-length step leaves the state as it is and writes the bias vector of the current state
-	if (sai2b_launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload ? 1 : 0, ctx->sim_tau, nullptr, ctx->stream))
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, ctx->sim_tau, nullptr, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	return fetch_rows(ctx, ctx->sim_tau, 0, N, bias);
 }
@@ -1911,7 +1919,7 @@ static int run_status(sai2b_ctx* ctx, int task) {
 	rc = upload_params(ctx);
 	if (rc) return rc;
 	if (!ctx->status_buf && (rc = dev_alloc(ctx, &ctx->status_buf, 68 * (size_t)ctx->B))) return rc;
-	if (sai2b_launch_mft_status(ctx->d_params, ctx->B, task, ctx->status_buf, ctx->stream))
+	if (sai2b::launch_mft_status(ctx->d_params, ctx->B, task, ctx->status_buf, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "status launch failed");
 	return SAI2B_OK;
 }
@@ -2061,9 +2069,8 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	int fast = fast_kind(ctx), cert_bits = ctx->no_inlane_singular ? 2 : 0;
-	if (ctx->sing_mode && sing6_kind(ctx)) fast = sing6_kind(ctx), cert_bits |= 4;	// (the kernel the ticks are running now)
-	const bool two = fast != 0 && !ctx->introspection;
+	const TickForm form = tick_form(ctx);  // (the kernel the ticks are running now)
+	const bool two = form.fast != 0 && !ctx->introspection;
 	// ONE event pair around `steps` back-to-back launches (an event pair per launch costs ~4 us of its own, which made
 	// the two parts add up to more than the step): first the first kernel alone, then the sequence of a tick. The
 	// second figure is what the work-list pass adds to a step, so the two sum to the step by construction.
@@ -2075,10 +2082,10 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 		for (int rep = 0; rep < 2; rep++) {	 // (the first repetition warms the sequence up)
 			HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
 			for (int s = 0; s < steps; s++) {
-				if (two) ctx->fb_parity ^= 1;
-				if (sai2b_launch_tick_part(ctx->d_params, ctx->B, ctx->introspection ? 1 : 0, fast, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), 0, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, !two), ctx->stream))
+				if (two) ctx->fb.parity ^= 1;
+				if (sai2b::launch_tick_part(ctx->d_params, ctx->B, form, ctx->introspection, 0, ctx->fb, generic_lanes(ctx, !two), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
-				if (phase == 1 && sai2b_launch_tick_part(ctx->d_params, ctx->B, 0, fast, (ctx->baked_model ? 1 : 0) | (ctx->h_params.payload ? 2 : 0), 1, 1 | cert_bits, ctx->fb_counts, ctx->fb_list, ctx->fb_parity, generic_lanes(ctx, false), ctx->stream))
+				if (phase == 1 && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, generic_lanes(ctx, false), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 			}
 			HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
@@ -2106,7 +2113,7 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 			*robots = ctx->B;
 			return SAI2B_OK;
 		}
-		HIP_TRY(ctx, hipMemcpyAsync(robots, ctx->tk_count + ctx->tk_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(robots, ctx->tk.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		return SAI2B_OK;
 	}
@@ -2114,7 +2121,7 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 		*robots = ctx->B;
 		return SAI2B_OK;
 	}
-	HIP_TRY(ctx, hipMemcpyAsync(robots, ctx->fb_counts + ctx->fb_parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(robots, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }

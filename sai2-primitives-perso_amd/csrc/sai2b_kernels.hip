@@ -183,16 +183,7 @@ DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb
 	SAI2B_PHASE();
 	const bool ok = certify_nonsingular(J, t0.s_abs_tol, t0.s_max);
 	const bool mine = ok && clean;
-	const unsigned long long declined = __ballot(!mine);
-	if (declined) {
-		int base = 0;
-		if (threadIdx.x == 0) base = atomicAdd(&fb_counts[parity], __popcll(declined));  // lane 0 is always in range
-		base = __shfl(base, 0);
-		if (!mine) {
-			((gint*)fb_list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
-			return;
-		}
-	}
+	if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
 	mft_store_integrators(t0, B, b, in0);
 	SAI2B_PHASE();
 	real tau[N];
@@ -282,16 +273,7 @@ DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __r
 	}
 	SAI2B_PHASE();
 	const bool mine = ok && clean;
-	const unsigned long long declined = __ballot(!mine);
-	if (declined) {
-		int base = 0;
-		if (threadIdx.x == 0) base = atomicAdd(&fb_counts[parity], __popcll(declined));  // lane 0 is always in range
-		base = __shfl(base, 0);
-		if (!mine) {
-			((gint*)fb_list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;
-			return;
-		}
-	}
+	if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
 	// the JointTask law, from its staged rows (late: its results would be live across the model phase)
 	JtEarly jt;
 	if constexpr (FAST == 2) fast_jt_early(P.task[1], rc, StagedRows{P.task[1], B, b, col + S::JG * 64, col + S::JS * 64, N}, jt);
@@ -451,103 +433,66 @@ __global__ __launch_bounds__(64) void reinit_kernel(const DevParams* __restrict_
 	}
 }
 
-}  // namespace sai2b
-
-static void launch_fast(int fast, int baked, dim3 grid, dim3 block, hipStream_t stream, const sai2b::DevParams* d_params,
-						int with_comp, int* fb_counts, int* fb_list, int parity) {
-	if (fast >= 3) {  // general hierarchies (sai2b_cert.hip); fast - 3 = most rows of a partial task; bit 3: the payload form
-		sai2b_launch_tick_cert(d_params, (int)grid.x * 64, fast - 3, with_comp | ((baked & 2) ? 8 : 0), fb_counts, fb_list, parity, stream);
-		return;
-	}
+// the SVD-free first kernel of `form`
+static int launch_fast(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, hipStream_t stream) {
+	if (form.fast >= 3) return launch_tick_cert(d_params, B, form, with_comp, fb, stream);	// general hierarchies (sai2b_cert.hip)
 #if SAI2B_N == 7
-	if (baked & 2) {  // the context has per-robot payloads
-		baked &= 1;
-		if (fast == 2 && baked)
-			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<2, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		else if (fast == 2)
-			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<2, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		else if (baked)
-			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<1, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		else
-			hipLaunchKernelGGL((sai2b::tick_fast_payload_kernel<1, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-		return;
-	}
-	if (fast == 2 && baked)
-		hipLaunchKernelGGL((sai2b::tick_fast_kernel<2, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	else if (fast == 2)
-		hipLaunchKernelGGL((sai2b::tick_fast_kernel<2, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	else if (baked)
-		hipLaunchKernelGGL((sai2b::tick_fast_kernel<1, true>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
-	else
-		hipLaunchKernelGGL((sai2b::tick_fast_kernel<1, false>), grid, block, 0, stream, d_params, with_comp, fb_counts, fb_list, parity);
+	// [payload][FAST - 1][BAKED]
+	static constexpr decltype(&tick_fast_kernel<1, false>) kernel[2][2][2] = {
+		{{tick_fast_kernel<1, false>, tick_fast_kernel<1, true>}, {tick_fast_kernel<2, false>, tick_fast_kernel<2, true>}},
+		{{tick_fast_payload_kernel<1, false>, tick_fast_payload_kernel<1, true>},
+		 {tick_fast_payload_kernel<2, false>, tick_fast_payload_kernel<2, true>}}};
+	hipLaunchKernelGGL(kernel[form.payload][form.fast == 2][form.baked], dim3((B + 63) / 64), dim3(64), 0, stream, d_params,
+					   with_comp ? 1 : 0, fb.counts, fb.list, fb.parity);
 #endif
+	return launch_result();
 }
 
-// with_comp: bit 0 = JointTask compensation, bit 1 (tick_cert_kernel only) = no in-lane singular handling
-// baked: bit 0 = the compile-time Panda, bit 1 = the context has per-robot payloads (the SVD-free kernels' payload forms;
-// the generic kernels find the rows in the parameter block)
-extern "C" int sai2b_launch_tick(const sai2b::DevParams* d_params, int B, int debug, int fast, int baked, int commit_sh,
-								 int with_comp_bits, int do_torque, int* fb_counts, int* fb_list, int parity, int group, hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	const int with_comp = with_comp_bits & 1;
+// the generic kernel: over the work list fb_count / fb_list (or, NULL, the whole batch), `group` lanes per robot
+static int launch_generic(const DevParams* d_params, int B, const TickCall& call, const int* fb_count, const int* fb_list, hipStream_t stream) {
+	if (call.group && !call.debug)
+		return launch_tick_group(d_params, B, call.group, false, call.commit_sh, call.with_comp, call.do_torque, fb_count, fb_list, stream);
+	auto* kernel = call.debug ? tick_kernel<true> : tick_kernel<false>;
+	hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, call.commit_sh ? 1 : 0, call.with_comp ? 1 : 0,
+					   call.do_torque ? 1 : 0, fb_count, fb_list);
+	return launch_result();
+}
+
+int launch_tick(const DevParams* d_params, int B, const TickForm& form, const TickCall& call, const WorkList& fb, hipStream_t stream) {
 	// the fast path produces torques only: introspection and model-only passes use the generic kernel
-	if (debug) {
-		hipLaunchKernelGGL((sai2b::tick_kernel<true>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, nullptr, nullptr);
-	} else if (fast != 0 && do_torque && commit_sh) {
-		launch_fast(fast, baked, grid, block, stream, d_params, fast >= 3 ? with_comp_bits : with_comp, fb_counts, fb_list, parity);
-		if (group)
-			return sai2b_launch_tick_group(d_params, B, group, 0, commit_sh, with_comp, do_torque, (const int*)(fb_counts + parity),
-										   (const int*)fb_list, stream);
-		hipLaunchKernelGGL((sai2b::tick_kernel<false>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque,
-						   (const int*)(fb_counts + parity), (const int*)fb_list);
-	} else {
-		if (group) return sai2b_launch_tick_group(d_params, B, group, 0, commit_sh, with_comp, do_torque, nullptr, nullptr, stream);
-		hipLaunchKernelGGL((sai2b::tick_kernel<false>), grid, block, 0, stream, d_params, commit_sh, with_comp, do_torque, nullptr, nullptr);
-	}
-	return (int)hipGetLastError();
+	if (call.debug || form.fast == 0 || !call.do_torque || !call.commit_sh) return launch_generic(d_params, B, call, nullptr, nullptr, stream);
+	const int rc = launch_fast(d_params, B, form, call.with_comp, fb, stream);
+	return launch_generic(d_params, B, call, fb.count(), fb.list, stream) | rc;
 }
 
 // the range pass of hierarchies with gated generators (same DEBUG variant as the tick that follows, so that
 // both take the same range decisions)
-extern "C" int sai2b_launch_range_pass(const sai2b::DevParams* d_params, int B, int debug, int with_comp, int group, hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	if (!debug && group) return sai2b_launch_tick_group(d_params, B, group, 1, 0, with_comp, 0, nullptr, nullptr, stream);
-	if (debug)
-		hipLaunchKernelGGL((sai2b::tick_kernel<true, true>), grid, block, 0, stream, d_params, 0, with_comp, 0, nullptr, nullptr);
-	else
-		hipLaunchKernelGGL((sai2b::tick_kernel<false, true>), grid, block, 0, stream, d_params, 0, with_comp, 0, nullptr, nullptr);
-	return (int)hipGetLastError();
+int launch_range_pass(const DevParams* d_params, int B, bool debug, bool with_comp, int group, hipStream_t stream) {
+	if (!debug && group) return launch_tick_group(d_params, B, group, true, false, with_comp, false, nullptr, nullptr, stream);
+	auto* kernel = debug ? tick_kernel<true, true> : tick_kernel<false, true>;
+	hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, 0, with_comp ? 1 : 0, 0, nullptr, nullptr);
+	return launch_result();
 }
 
-extern "C" int sai2b_launch_tick_part(const sai2b::DevParams* d_params, int B, int debug, int fast, int baked, int part, int with_comp_bits,
-									  int* fb_counts, int* fb_list, int parity, int group, hipStream_t stream) {
-	const dim3 grid((B + 63) / 64), block(64);
-	if (debug)
-		hipLaunchKernelGGL((sai2b::tick_kernel<true>), grid, block, 0, stream, d_params, 1, 1, 1, nullptr, nullptr);
-	else if (fast == 0 && group)
-		return sai2b_launch_tick_group(d_params, B, group, 0, 1, 1, 1, nullptr, nullptr, stream);
-	else if (fast == 0)
-		hipLaunchKernelGGL((sai2b::tick_kernel<false>), grid, block, 0, stream, d_params, 1, 1, 1, nullptr, nullptr);
-	else if (part == 1 && group)
-		return sai2b_launch_tick_group(d_params, B, group, 0, 1, 1, 1, (const int*)(fb_counts + parity), (const int*)fb_list, stream);
-	else if (part == 1)
-		hipLaunchKernelGGL((sai2b::tick_kernel<false>), grid, block, 0, stream, d_params, 1, 1, 1, (const int*)(fb_counts + parity),
-						   (const int*)fb_list);
-	else
-		launch_fast(fast, baked, grid, block, stream, d_params, fast >= 3 ? with_comp_bits : 1, fb_counts, fb_list, parity);
-	return (int)hipGetLastError();
+int launch_tick_part(const DevParams* d_params, int B, const TickForm& form, bool debug, int part, const WorkList& fb, int group,
+					 hipStream_t stream) {
+	TickCall call;
+	call.debug = debug, call.group = group;
+	if (debug || form.fast == 0) return launch_generic(d_params, B, call, nullptr, nullptr, stream);
+	if (part == 1) return launch_generic(d_params, B, call, fb.count(), fb.list, stream);
+	return launch_fast(d_params, B, form, true, fb, stream);
 }
 
-extern "C" int sai2b_launch_reinit(const sai2b::DevParams* d_params, int B, int only_task, hipStream_t stream) {
-	const int blocks = (B + 63) / 64;
-	hipLaunchKernelGGL(sai2b::reinit_kernel, dim3(blocks), dim3(64), 0, stream, d_params, only_task);
-	return (int)hipGetLastError();
+int launch_reinit(const DevParams* d_params, int B, int only_task, hipStream_t stream) {
+	hipLaunchKernelGGL(reinit_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, only_task);
+	return launch_result();
 }
 
-extern "C" int sai2b_launch_task(const sai2b::DevParams* d_params, int B, int task, const double* Nprec_in, const double* tau_prec,
-								 double* tau_out, double* N_out, double* Ntot_out, int commit_sh, int do_torque, const int* tk_count,
-								 const int* tk_list, hipStream_t stream) {
-	hipLaunchKernelGGL(sai2b::task_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out,
-					   Ntot_out, commit_sh, do_torque, tk_count, tk_list);
-	return (int)hipGetLastError();
+int launch_task(const DevParams* d_params, int B, int task, const double* Nprec_in, const double* tau_prec, double* tau_out, double* N_out,
+				double* Ntot_out, bool commit_sh, bool do_torque, const int* tk_count, const int* tk_list, hipStream_t stream) {
+	hipLaunchKernelGGL(task_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, Nprec_in, tau_prec, tau_out, N_out, Ntot_out,
+					   commit_sh ? 1 : 0, do_torque ? 1 : 0, tk_count, tk_list);
+	return launch_result();
 }
+
+}  // namespace sai2b

@@ -1,59 +1,89 @@
-// sai2b_launch.h — launch entry points shared by sai2b_kernels.hip and sai2b_host.cpp
+// sai2b_launch.h — launch entry points shared by the kernel files and sai2b_host.cpp. Every launcher returns 0 when
+// all its kernels were launched and non-zero otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "sai2b_params.h"
 
-// group: lanes per robot of the generic kernel (16 / 8), or 0 = the one-lane-per-robot generic kernel
-extern "C" int sai2b_launch_tick(const sai2b::DevParams* d_params, int B, int debug, int fast, int baked, int commit_sh,
-								 int with_comp, int do_torque, int* fb_counts, int* fb_list, int parity, int group, hipStream_t stream);
+namespace sai2b {
+
+// Robots a first kernel declined, compacted for the generic kernel behind it. counts: two counters, zero before the
+// first launch, alternating between launches (`parity`): a launch fills [parity] and clears [1 - parity] for the next
+// one. list: [B] robot indices. The tick's list has two more counters at [2..3], alternating alike: robots that went
+// through the in-lane singular branch of tick_cert_kernel. The generators' list (sai2b_otg.hip) is
+// counts [2][SAI2B_MAX_TASKS] + 2 (non-idle robots of a tick, alternating) and list [SAI2B_MAX_TASKS][B].
+struct WorkList {
+	int* counts = nullptr;
+	int* list = nullptr;
+	int parity = 0;
+	int* count() const { return counts + parity; }
+	int* took() const { return counts + 2 + parity; }
+};
+
+// which first kernel a tick runs
+struct TickForm {
+	int fast = 0;  // 0 = the generic kernel alone, 1 = [full MFT], 2 = [full MFT, full JT], 3 + rows = tick_cert_kernel
+				   // (rows: most rows of a partial task of the hierarchy)
+	bool baked = false;			  // robot constants from the compile-time Panda (tick_fast_kernel)
+	bool payload = false;		  // the context has per-robot payloads: the SVD-free kernels' payload forms (the generic
+								  // kernels find the rows in the parameter block)
+	bool inlane_singular = true;  // singular MotionForceTasks stay in the lane (cert::singular_part), not on the work list
+	bool sing6 = false;			  // the 6-row tick_cert_kernel with the singular branch in the lane (cert::tick<.., S6>)
+};
+
+// what a tick call asks for
+struct TickCall {
+	bool debug = false;	 // the introspection instantiation of the generic kernel, no SVD-free kernel
+	bool commit_sh = true, with_comp = true, do_torque = true;
+	int group = 0;	// lanes per robot of the generic kernel (16 / 8), or 0 = the one-lane-per-robot generic kernel
+};
+
+inline int launch_result() { return hipGetLastError() == hipSuccess ? 0 : 1; }
+
+// the SVD-free kernel of `form` (when the call is a plain torque tick) with the generic kernel over its work list
+// behind it, or the generic kernel for the whole batch
+int launch_tick(const DevParams* d_params, int B, const TickForm& form, const TickCall& call, const WorkList& fb, hipStream_t stream);
 // generic tick with a robot spread over `lanes` = 16 or 8 lanes (sai2b_group.hip); fb_count / fb_list as tick_kernel
-extern "C" int sai2b_launch_tick_group(const sai2b::DevParams* d_params, int B, int lanes, int range_only, int commit_sh, int with_comp,
-									   int do_torque, const int* fb_count, const int* fb_list, hipStream_t stream);
-// the SVD-free tick for general hierarchies (sai2b_cert.hip): fills the work list like the fast kernels.
-// max_rows: most rows of a partial task of the hierarchy (selects the instantiation)
-extern "C" int sai2b_launch_tick_cert(const sai2b::DevParams* d_params, int B, int max_rows, int with_comp, int* fb_counts, int* fb_list,
-									  int parity, hipStream_t stream);
+int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_only, bool commit_sh, bool with_comp, bool do_torque,
+					  const int* fb_count, const int* fb_list, hipStream_t stream);
+// the SVD-free tick for general hierarchies (sai2b_cert.hip, form.fast >= 3): fills the work list like the fast kernels
+int launch_tick_cert(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, hipStream_t stream);
 // the range pass ahead of the trajectory generators for certified robots (sai2b_cert.hip: range_cert_kernel); the rest
-// of the batch goes to rg_list for sai2b_launch_tick_group(..., range_only = 1, ...)
-extern "C" int sai2b_launch_range_cert(const sai2b::DevParams* d_params, int B, int max_rows, int* rg_counts, int* rg_list, int parity, int inlane,
-									   hipStream_t stream);
-extern "C" int sai2b_launch_range_pass(const sai2b::DevParams* d_params, int B, int debug, int with_comp, int group, hipStream_t stream);
+// of the batch goes to rg for launch_tick_group(..., range_only = true, ...). max_rows: as TickForm::fast - 3
+int launch_range_cert(const DevParams* d_params, int B, int max_rows, bool payload, bool inlane_singular, const WorkList& rg,
+					  hipStream_t stream);
+int launch_range_pass(const DevParams* d_params, int B, bool debug, bool with_comp, int group, hipStream_t stream);
 // only_task < 0: every task (RobotController::reinitializeTasks); else TemplateTask::reInitializeTask of that one
-extern "C" int sai2b_launch_reinit(const sai2b::DevParams* d_params, int B, int only_task, hipStream_t stream);
-// one task on its own (TemplateTask.h:42-88): model update (do_torque = 0) or the task's torques (do_torque = 1) under
-// a caller-supplied N_prec ([49][B], NULL = identity) and tau_prec ([7][B], NULL = the no-argument computeTorques());
-// N_out / Ntot_out [49][B]: the task's nullspace and N * N_prec; tau_out [7][B]
-extern "C" int sai2b_launch_task_group(const sai2b::DevParams* d_params, int B, int lanes, int task, const double* Nprec_in, const double* tau_prec,
-									   double* tau_out, double* N_out, double* Ntot_out, int commit_sh, int do_torque, const int* tk_count,
-									   const int* tk_list, hipStream_t stream);
-extern "C" int sai2b_launch_task(const sai2b::DevParams* d_params, int B, int task, const double* Nprec_in, const double* tau_prec,
-								 double* tau_out, double* N_out, double* Ntot_out, int commit_sh, int do_torque, const int* tk_count,
-								 const int* tk_list, hipStream_t stream);
-// the same calls through the whitened cascade (sai2b_cert.hip: task_cert_kernel); robots it declines are appended to
-// tk_list (tk_counts: two counters, zero before the first launch, `parity` alternating between launches) for
-// sai2b_launch_task(..., tk_counts + parity, tk_list) behind it. max_rows: rows of the task (<= 3: the small instantiation)
-extern "C" int sai2b_launch_task_cert(const sai2b::DevParams* d_params, int B, int task, int max_rows, const double* Nprec_in,
-									  const double* tau_prec, double* tau_out, double* N_out, double* Ntot_out, int do_torque, int* tk_counts,
-									  int* tk_list, int parity, hipStream_t stream);
-// one kernel of a (fast) tick on its own, for per-kernel timing: part 0 = first kernel, part 1 = the
-// generic kernel over the work list of the SVD-free one. fb_counts: 2 ints, zero before the first
-// launch; fb_list: B ints; parity alternates 0/1 between consecutive launches of the SVD-free kernel
-extern "C" int sai2b_launch_tick_part(const sai2b::DevParams* d_params, int B, int debug, int fast, int baked, int part, int with_comp_bits,
-									  int* fb_counts, int* fb_list, int parity, int group, hipStream_t stream);
+int launch_reinit(const DevParams* d_params, int B, int only_task, hipStream_t stream);
+// one task on its own (TemplateTask.h:42-88): model update (do_torque = false) or the task's torques (do_torque = true)
+// under a caller-supplied N_prec ([N*N][B], NULL = identity) and tau_prec ([N][B], NULL = the no-argument
+// computeTorques()); N_out / Ntot_out [N*N][B]: the task's nullspace and N * N_prec; tau_out [N][B]
+int launch_task_group(const DevParams* d_params, int B, int lanes, int task, const double* Nprec_in, const double* tau_prec, double* tau_out,
+					  double* N_out, double* Ntot_out, bool commit_sh, bool do_torque, const int* tk_count, const int* tk_list,
+					  hipStream_t stream);
+int launch_task(const DevParams* d_params, int B, int task, const double* Nprec_in, const double* tau_prec, double* tau_out, double* N_out,
+				double* Ntot_out, bool commit_sh, bool do_torque, const int* tk_count, const int* tk_list, hipStream_t stream);
+// the same calls through the whitened cascade (sai2b_cert.hip: task_cert_kernel); robots it declines are appended to tk
+// for launch_task(..., tk.count(), tk.list) behind it. max_rows: rows of the task (<= 3: the small instantiation)
+int launch_task_cert(const DevParams* d_params, int B, int task, int max_rows, bool payload, bool inlane_singular, const double* Nprec_in,
+					 const double* tau_prec, double* tau_out, double* N_out, double* Ntot_out, bool commit_sh, bool do_torque,
+					 const WorkList& tk, hipStream_t stream);
+// one kernel of a full tick (commit, compensation, torques) on its own, for per-kernel timing: part 0 = first kernel,
+// part 1 = the generic kernel over the work list of the SVD-free one
+int launch_tick_part(const DevParams* d_params, int B, const TickForm& form, bool debug, int part, const WorkList& fb, int group,
+					 hipStream_t stream);
 // internal OTG (sai2b_otg.hip): one update of every enabled generator; (re)initialisation (modes in the kernel's comment)
 // task_mask bit t: advance task t's generator (all enabled ones: ~0)
-extern "C" int sai2b_launch_otg(const sai2b::DevParams* d_params, int B, int* counts, int* list, int parity, int clean_mask,
-								int task_mask, int jerk_mask, hipStream_t stream);
-// q_pose: [7][B] joint positions the tasks' cached poses correspond to (read in mode 1 only)
-extern "C" int sai2b_launch_otg_reinit(const sai2b::DevParams* d_params, int B, int only_task, int mode, const double* q_pose,
-									   hipStream_t stream);
+int launch_otg(const DevParams* d_params, int B, const WorkList& otg, int clean_mask, int task_mask, int jerk_mask, hipStream_t stream);
+// q_pose: [N][B] joint positions the tasks' cached poses correspond to (read in mode 1 only)
+int launch_otg_reinit(const DevParams* d_params, int B, int only_task, int mode, const double* q_pose, hipStream_t stream);
 // force / motion space re-parametrisation of MotionForceTask `task` at run time (flags in the kernel's comment)
-extern "C" int sai2b_launch_mft_reparam(const sai2b::DevParams* d_params, int B, int task, int flags, const double* q_pose,
-										hipStream_t stream);
+int launch_mft_reparam(const DevParams* d_params, int B, int task, int flags, const double* q_pose, hipStream_t stream);
 // simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.
-// forms selects the instantiation: bit 0 = plant payload, bit 1 = contact (the rows, status and counter of DevParams)
-extern "C" int sai2b_launch_sim(const sai2b::DevParams* d_params, int B, const double* tau, double dt, int substeps,
-								int with_gravity, int forms, double* dbg_bias, double* q_keep, hipStream_t stream);
+// payload / contact select the instantiation: the plant's payload rows, the contact rows, status and counter of DevParams
+int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
+			   double* dbg_bias, double* q_keep, hipStream_t stream);
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
-extern "C" int sai2b_launch_mft_status(const sai2b::DevParams* d_params, int B, int task, double* out, hipStream_t stream);
+int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream);
+
+}  // namespace sai2b

@@ -851,44 +851,33 @@ __global__ __launch_bounds__(64) void mft_reparam_kernel(const DevParams* __rest
 	}
 }
 
-}  // namespace sai2b
-
-extern "C" int sai2b_launch_mft_reparam(const sai2b::DevParams* d_params, int B, int task, int flags, const double* q_pose,
-										hipStream_t stream) {
-	hipLaunchKernelGGL(sai2b::mft_reparam_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, flags, q_pose);
-	return hipGetLastError() == hipSuccess ? 0 : 1;
+int launch_mft_reparam(const DevParams* d_params, int B, int task, int flags, const double* q_pose, hipStream_t stream) {
+	hipLaunchKernelGGL(mft_reparam_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, flags, q_pose);
+	return launch_result();
 }
 
-// counts: [2][SAI2B_MAX_TASKS] ints, zero before the first call; list: [SAI2B_MAX_TASKS][B] ints;
-// parity alternates 0/1 between consecutive calls
 // clean_mask bit t: the host has not written task t's goals / OTG settings since the previous call
 // jerk_mask: tasks whose generator is jerk-limited (host knowledge: DevTask::otg_jerk) — their lists get a third launch
-extern "C" int sai2b_launch_otg(const sai2b::DevParams* d_params, int B, int* counts, int* list, int parity, int clean_mask,
-								int task_mask, int jerk_mask, hipStream_t stream) {
+int launch_otg(const DevParams* d_params, int B, const WorkList& otg, int clean_mask, int task_mask, int jerk_mask, hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);
-	if (jerk_mask & task_mask)
-		hipLaunchKernelGGL(sai2b::otg_kernel<true>, grid, block, 0, stream, d_params, counts, list, parity, clean_mask, task_mask);
-	else
-		hipLaunchKernelGGL(sai2b::otg_kernel<false>, grid, block, 0, stream, d_params, counts, list, parity, clean_mask, task_mask);
+	const int* list = otg.list;
+	auto* kernel = (jerk_mask & task_mask) ? otg_kernel<true> : otg_kernel<false>;
+	hipLaunchKernelGGL(kernel, grid, block, 0, stream, d_params, otg.counts, otg.list, otg.parity, clean_mask, task_mask);
 	const int plan_blocks = (B + 7) / 8 < 2048 ? (B + 7) / 8 : 2048;
-	hipLaunchKernelGGL(sai2b::otg_plan_kernel, dim3(plan_blocks), block, 0, stream, d_params, counts, (const int*)list, parity, task_mask);
+	hipLaunchKernelGGL(otg_plan_kernel, dim3(plan_blocks), block, 0, stream, d_params, otg.counts, list, otg.parity, task_mask);
 	if (jerk_mask & task_mask) {
 		static const bool one_lane = std::getenv("SAI2B_OTG3_ONE_LANE") != nullptr;	 // A/B: round 3's first planner, one lane per robot
-		if (one_lane) {
-			const int blocks3 = (B + 63) / 64 < 256 ? (B + 63) / 64 : 256;
-			hipLaunchKernelGGL(sai2b::otg3_plan_kernel<true>, dim3(blocks3), block, 0, stream, d_params, (const int*)counts, (const int*)list,
-							   parity, task_mask);
-		} else {  // one DoF per lane; the grid strides over the list and bounds the scratch (one block of profiles per lane)
-			const int blocks3 = (B + 7) / 8 < 1024 ? (B + 7) / 8 : 1024;
-			hipLaunchKernelGGL(sai2b::otg3_plan_kernel<false>, dim3(blocks3), block, 0, stream, d_params, (const int*)counts, (const int*)list,
-							   parity, task_mask);
-		}
+		// (else one DoF per lane; the grid strides over the list and bounds the scratch: one block of profiles per lane)
+		const int cap = one_lane ? 256 : 1024, want = one_lane ? (B + 63) / 64 : (B + 7) / 8;
+		auto* plan3 = one_lane ? otg3_plan_kernel<true> : otg3_plan_kernel<false>;
+		hipLaunchKernelGGL(plan3, dim3(want < cap ? want : cap), block, 0, stream, d_params, (const int*)otg.counts, list, otg.parity, task_mask);
 	}
-	return hipGetLastError() == hipSuccess ? 0 : 1;
+	return launch_result();	 // (the last error of the launches above: a later success does not clear it)
 }
 
-extern "C" int sai2b_launch_otg_reinit(const sai2b::DevParams* d_params, int B, int only_task, int mode,
-									   const double* q_pose, hipStream_t stream) {
-	hipLaunchKernelGGL(sai2b::otg_reinit_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, only_task, mode, q_pose);
-	return hipGetLastError() == hipSuccess ? 0 : 1;
+int launch_otg_reinit(const DevParams* d_params, int B, int only_task, int mode, const double* q_pose, hipStream_t stream) {
+	hipLaunchKernelGGL(otg_reinit_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, only_task, mode, q_pose);
+	return launch_result();
 }
+
+}  // namespace sai2b

@@ -138,6 +138,19 @@ constexpr int PAYLOAD_ROWS = 10;  // rows of a payload buffer: mass, com 3, iner
 constexpr int CONTACT_ROWS = 9;	  // rows of the contact buffer: plane point 3, normal 3, stiffness, damping, friction
 constexpr int CONTACT_STATUS_ROWS = 2 * SAI2B_MAX_CONTACT_POINTS + 6;
 
+// the bits of the int tick_cert_kernel (with_comp) and task_cert_kernel (call_bits) take (sai2b_cert.hip)
+enum TickCertBits {
+	TICK_CERT_COMP = 1,		 // JointTask compensation of the tasks above
+	TICK_CERT_NO_INLANE = 2	 // singular MotionForceTasks go to the work list instead of through cert::singular_part
+							 // (SAI2B_NO_INLANE_SINGULAR=1, the A/B switch)
+};
+enum TaskCertBits {
+	TASK_CERT_TORQUE = 1,	  // computeTorques
+	TASK_CERT_COMMIT = 2,	  // the call commits the once-per-model-update singularity bookkeeping (updateTaskModel, or a
+							  // computeTorques that has to update the model itself)
+	TASK_CERT_NO_INLANE = 4	  // as TICK_CERT_NO_INLANE
+};
+
 struct DevParams {
 	int B;
 	int n_tasks;

@@ -382,26 +382,18 @@ __global__ __launch_bounds__(64) void mft_status_kernel(const DevParams* __restr
 	st(out, 25, B, b, sqrt(fmax(oe[0] * soe[0] + oe[1] * soe[1] + oe[2] * soe[2], 0.0)));
 }
 
+int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream) {
+	hipLaunchKernelGGL(mft_status_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, out);
+	return launch_result();
+}
+
+int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
+			   double* dbg_bias, double* q_keep, hipStream_t stream) {
+	static constexpr decltype(&sim_kernel<NoPayload, NoContact>) kernel[2][2] = {
+		{sim_kernel<NoPayload, NoContact>, sim_kernel<Payload, NoContact>}, {sim_kernel<NoPayload, Contact>, sim_kernel<Payload, Contact>}};
+	hipLaunchKernelGGL(kernel[contact][payload], dim3((B + 63) / 64), dim3(64), 0, stream, d_params, tau, dt, substeps, with_gravity, dbg_bias,
+					   q_keep);
+	return launch_result();
+}
+
 }  // namespace sai2b
-
-extern "C" int sai2b_launch_mft_status(const sai2b::DevParams* d_params, int B, int task, double* out, hipStream_t stream) {
-	hipLaunchKernelGGL(sai2b::mft_status_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, task, out);
-	return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-// forms: bit 0 = the plant carries a payload, bit 1 = the plant has a contact surface
-extern "C" int sai2b_launch_sim(const sai2b::DevParams* d_params, int B, const double* tau, double dt, int substeps,
-								int with_gravity, int forms, double* dbg_bias, double* q_keep, hipStream_t stream) {
-	using namespace sai2b;
-	const dim3 grid((B + 63) / 64), block(64);
-#define SAI2B_SIM_LAUNCH(PL, CT) \
-	hipLaunchKernelGGL((sim_kernel<PL, CT>), grid, block, 0, stream, d_params, tau, dt, substeps, with_gravity, dbg_bias, q_keep)
-	switch (forms & 3) {
-		case 0: SAI2B_SIM_LAUNCH(NoPayload, NoContact); break;
-		case 1: SAI2B_SIM_LAUNCH(Payload, NoContact); break;
-		case 2: SAI2B_SIM_LAUNCH(NoPayload, Contact); break;
-		default: SAI2B_SIM_LAUNCH(Payload, Contact); break;
-	}
-#undef SAI2B_SIM_LAUNCH
-	return hipGetLastError() == hipSuccess ? 0 : 1;
-}
