@@ -22,9 +22,9 @@
 namespace sai2b {
 
 // Cholesky factor of an SPD n x n matrix: lower L (row-major, upper part untouched) and the
-// reciprocals of its diagonal.
-template <int n>
-DI void chol(const real* A, real* L, real* dinv) {
+// reciprocals of its diagonal. A is anything indexed [i * n + j] for j <= i (an array, or LdsSym below).
+template <int n, class Mat>
+DI void chol(const Mat& A, real* L, real* dinv) {
 	UNROLL for (int j = 0; j < n; j++) {
 		real s = A[j * n + j];
 		UNROLL for (int k = 0; k < j; k++) s = fma(-L[j * n + k], L[j * n + k], s);
@@ -93,21 +93,32 @@ DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEa
 #define SAI2B_PHASE() do { __builtin_amdgcn_sched_barrier(0); asm volatile("; SAI2B_PHASE_MARK"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
 // ---- Input staging of tick_fast_kernel (used by FAST = 2; FAST = 1 keeps its loads in registers). Every per-robot
-// row the fast tick reads besides q goes global -> LDS by DMA (global_load_lds) at kernel entry, while the model
-// phase runs from q alone, and is read back from LDS after one barrier. The LDS image is [row][64] doubles, one column per lane of the (single-wavefront) workgroup:
-//   dq (N) | JointTask law_goals (3N) and state (N), FAST == 2 only | MotionForceTask law_goals (24) and state (6)
-//   | one pad row when the count is odd | the MotionForceTask istate row IS_NTYPES (64 ints)
-// The force-space rows (MotionForceTask goals 24-29, sensed, state 6-11) are not staged: they stay plain loads
-// after the barrier (StagedRows), which keeps the image within 40 KiB (4 workgroups per CU).
-// PAY: the ten rows of the robot's payload (sai2b_set_link_payload) behind the others, the payload form of the kernel only:
-// 39 168 bytes for FAST = 2, still 4 workgroups per CU
+// row the fast tick reads before its Cholesky part, besides q, goes global -> LDS by DMA (global_load_lds) at kernel
+// entry, while the model phase runs from q alone, and is read back from LDS after one barrier. The LDS image is
+// [row][64] doubles, one column per lane of the (single-wavefront) workgroup:
+//   dq (N) | MotionForceTask law_goals (24) and state (6) | one pad row when the count is odd
+//   | the MotionForceTask istate row IS_NTYPES (64 ints)
+//   | FAST == 2 without payload: 35 rows the DMA never writes, the model phase's results parked by the lane itself
+//     inside the window: M's lower triangle (28, row i (i + 1) / 2 + j) and g (7). M and g are then never live in
+//     registers across the certificate or the control law; fast_tick reads M where it consumes it (LdsSym).
+// 37 632 bytes for FAST = 2. The force-space rows (MotionForceTask goals 24-29, sensed, state 6-11) are not staged: they
+// stay plain loads after the barrier (StagedRows). Nor are the JointTask's law_goals (3N) and state (N): its law is only
+// ever needed as two dot products with the nullspace vector a, so it is evaluated behind a, from plain loads issued
+// before the Gram / Cholesky / nullspace work that hides them (JtLate). That is what makes room for M and g within
+// 40 KiB (4 workgroups per CU).
+// PAY: the payload form of the kernel. Its CRBA needs the robot's payload, which arrives by the DMA, so its model phase
+// stays behind the barrier and nothing is parked: the image is dq | JointTask law_goals and state (FAST == 2) |
+// MotionForceTask rows | the ten payload rows (sai2b_set_link_payload) | pad | istate: 39 168 bytes for FAST = 2.
 template <int FAST, bool PAY = false>
 struct StageLayout {
-	static constexpr int DQ = 0, JG = N, JS = JG + (FAST == 2 ? 3 * N : 0), MG = JS + (FAST == 2 ? N : 0);
+	static constexpr bool JT_STAGED = FAST == 2 && PAY, PARKED = FAST == 2 && !PAY;
+	static constexpr int DQ = 0, JG = N, JS = JG + (JT_STAGED ? 3 * N : 0), MG = JS + (JT_STAGED ? N : 0);
 	static constexpr int MS = MG + 24, PLD = MS + 6, ROWS = PLD + (PAY ? PAYLOAD_ROWS : 0);
 	static constexpr int PAIRS = (ROWS + 1) / 2;  // a 16-byte glds moves two rows (lanes 0-31: row 2i, 32-63: 2i+1)
 	static constexpr int IROW = 2 * PAIRS;		 // the istate row, 256 bytes
-	static constexpr int DOUBLES = IROW * 64 + 32;
+	static constexpr int IMAGE = IROW * 64 + 32;	 // doubles the DMA writes; the parked rows start here
+	static constexpr int MROWS = N * (N + 1) / 2;
+	static constexpr int DOUBLES = IMAGE + (PARKED ? (MROWS + N) * 64 : 0);
 };
 
 // first element of image row k in the batched arrays (the pad row repeats the last one)
@@ -170,12 +181,68 @@ struct StagedRows {
 	DI real state(int k) const { return k < st_rows ? st[k * 64] : ld(t.state, k, B, b); }
 };
 
-// The Cholesky part of the fast tick. J and M are the Jacobian and mass matrix at rc.q, Fu/Ff the task
-// forces of the MotionForceTask law, jt the JointTask law; HAS_JT selects the 2-level form. Ordered to
+// A symmetric N x N matrix parked in the LDS image (StageLayout::PARKED): row i (i + 1) / 2 + j of this lane's column
+// holds element (i, j), j <= i. Indexed like the array it stands in for, lower triangle only.
+struct LdsSym {
+	const real* col;
+	DI real operator[](int k) const {
+		const int i = k / N, j = k % N;
+		return col[(i * (i + 1) / 2 + j) * 64];
+	}
+};
+
+// Where fast_tick gets the second-level JointTask law from. JtGiven: evaluated by the caller (fast_jt_early).
+struct JtGiven {
+	const JtEarly& e;
+	DI void prefetch(const real*) {}
+	DI void project(const real* a, real& af, real& aacc) {
+		UNROLL for (int i = 0; i < N; i++) {
+			af = fma(a[i], e.f[i], af);
+			aacc = fma(a[i], e.ddq[i], aacc);
+		}
+	}
+};
+// JtLate: nothing of the law exists until the nullspace vector does. prefetch() issues the plain loads of its 4N rows
+// and of q; project() evaluates the same fast_jt_early from them (dq from the image), stores the advanced integrators
+// (the caller is past worklist_append: this lane is committed to the fast path) and forms the two dot products.
+struct JtLate {
+	const DevTask& t1;
+	int B, b;
+	const real* dq;	 // image row of dq[0], at this lane's column
+	real lg[3 * N], s[N], q[N];
+	struct Rows {
+		const real *lg, *s;
+		DI real law_goal(int k) const { return lg[k]; }
+		DI real state(int k) const { return s[k]; }
+	};
+	DI void prefetch(const real* qrows) {
+		UNROLL for (int i = 0; i < N; i++) q[i] = ld(qrows, i, B, b);
+		UNROLL for (int k = 0; k < 3 * N; k++) lg[k] = ld(t1.law_goals, k, B, b);
+		UNROLL for (int i = 0; i < N; i++) s[i] = ld(t1.state, i, B, b);
+	}
+	DI void project(const real* a, real& af, real& aacc) {
+		// Nothing in the law depends on a, and arithmetic without a dependency is free to move up to the loads, taking
+		// the wait for them along: a[0] is the last element the back substitution produces, so tie q to it.
+		RobotCtx rc;
+		UNROLL for (int i = 0; i < N; i++) {
+			asm volatile("" : "+v"(q[i]) : "v"(a[0]));
+			rc.q[i] = q[i];
+			rc.dq[i] = dq[i * 64];
+		}
+		JtEarly e;
+		fast_jt_early(t1, rc, Rows{lg, s}, e);
+		UNROLL for (int i = 0; i < N; i++) st(t1.state, i, B, b, e.integ[i]);
+		JtGiven{e}.project(a, af, aacc);
+	}
+};
+
+// The Cholesky part of the fast tick. J and M are the Jacobian and mass matrix at rc.q (M an array or LdsSym: it is
+// read twice, for the bounded-inertia factor and for its own), Fu/Ff the task forces of the MotionForceTask law, jt
+// the JointTask law (JtGiven or JtLate); HAS_JT selects the 2-level form. Ordered to
 // keep few matrices alive at once: bounded-inertia side -> Y = L^-1 J^T -> nullspace vectors -> torques.
-template <bool HAS_JT>
-DI void fast_tick(const DevParams& P, const real* J, const real* M, const real* Fu, const real* Ff, int B, int b,
-				  bool with_comp, const JtEarly& jt, real* tau) {
+template <bool HAS_JT, class Mat, class JT>
+DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* Fu, const real* Ff, int B, int b,
+				  bool with_comp, JT& jt, real* tau) {
 	const DevTask& t0 = P.task[0];
 
 	// bounded inertia estimate shared by the tasks that ask for it (host checks thresholds agree)
@@ -225,6 +292,10 @@ DI void fast_tick(const DevParams& P, const real* J, const real* M, const real* 
 		UNROLL for (int i = 0; i < N; i++) Y[i * 6 + c] = col[i];
 	}
 	SAI2B_PHASE();
+	if constexpr (HAS_JT) {
+		jt.prefetch(P.q);
+		SAI2B_PHASE();
+	}
 	// ---- A = J M^-1 J^T = Y^T Y and its factor: Lambda for FULL decoupling, nullspace for the JT
 	real a[N], bb[N], na2 = 0;
 	if (HAS_JT || mft_full) {
@@ -307,13 +378,10 @@ DI void fast_tick(const DevParams& P, const real* J, const real* M, const real* 
 	UNROLL for (int i = 0; i < N; i++) tau[i] = tau_mft[i];
 	if (!HAS_JT) return;
 
-	// ---- JointTask: the law was evaluated up front (fast_jt_early); project it
+	// ---- JointTask: its law enters only as a . f and a . ddq
 	const DevTask& t1 = P.task[1];
 	real af = 0, aacc = 0;
-	UNROLL for (int i = 0; i < N; i++) {
-		af = fma(a[i], jt.f[i], af);
-		aacc = fma(a[i], jt.ddq[i], aacc);
-	}
+	jt.project(a, af, aacc);
 	if (with_comp) {  // JointTask.cpp:285-292: - Jp^T R M_partial R^T S M^-1 tau_prec;  M^-1 tau_mft = L^-T (Y z)
 		real u[N];
 		UNROLL for (int i = 0; i < N; i++) u[i] = yz[i];

@@ -187,7 +187,8 @@ DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb
 	mft_store_integrators(t0, B, b, in0);
 	SAI2B_PHASE();
 	real tau[N];
-	fast_tick<false>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
+	JtGiven none{jt};
+	fast_tick<false>(P, J, M, Fu, Ff, B, b, with_comp != 0, none, tau);
 	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
 }
 
@@ -223,9 +224,12 @@ DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __r
 	SAI2B_PHASE();
 	if (b >= B) return;
 	const DevTask& t0 = P.task[0];
-	// Window: FK -> frame pose -> Jacobian -> certificate, from q alone. Phase order by register count: the law
-	// comes before CRBA (M is not live across it), and FK runs a second time for CRBA and gravity after the law
-	// rather than keeping the frames or M live across it; the same code on the same q gives the same frames.
+	const real* col = img + threadIdx.x;
+	// Window: FK -> frame pose -> Jacobian -> (CRBA, gravity) -> certificate, from q alone. Without payload the model
+	// phase runs here, while the frames are alive anyway, and parks M and g in this lane's column of the rows behind
+	// the DMA image (S::PARKED): neither is live in registers across the certificate or the control law, and no
+	// barrier is owed for them (a lane reads back only what it wrote). The payload form's CRBA needs rows the DMA
+	// brings, so it keeps the model phase behind the law and evaluates FK a second time there.
 	real J[6 * N], x[3], R[9];
 	{
 		Frames F;
@@ -238,15 +242,22 @@ DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __r
 			jacobian(PandaBaked{}, t0, F, x, J);
 		else
 			jacobian(P.model, t0, F, x, J);
+		if constexpr (S::PARKED) {
+			SAI2B_PHASE();
+			real M[N * N], g[N];
+			fast_model<BAKED>(P, F, PL{}, M, g);
+			real* park = img + S::IMAGE + threadIdx.x;
+			UNROLL for (int i = 0; i < N; i++) UNROLL for (int j = 0; j <= i; j++) park[(i * (i + 1) / 2 + j) * 64] = M[i * N + j];
+			UNROLL for (int i = 0; i < N; i++) park[(S::MROWS + i) * 64] = g[i];
+		}
 	}
 	SAI2B_PHASE();
 	const bool ok = certify_nonsingular(J, t0.s_abs_tol, t0.s_max);
 	SAI2B_PHASE();
 	__syncthreads();  // one wavefront per workgroup: vmcnt(0) + barrier, the DMA-written image is readable from here
-	const real* col = img + threadIdx.x;
 	UNROLL for (int i = 0; i < N; i++) {
 		rc.dq[i] = col[(S::DQ + i) * 64];
-		rc.q[i] = ld(P.q, i, B, b);  // again (an L2 hit): not live across the window
+		if constexpr (!S::PARKED) rc.q[i] = ld(P.q, i, B, b);  // again (an L2 hit): not live across the window
 	}
 	const bool clean = ((const int*)(img + S::IROW * 64))[threadIdx.x] == 0;
 	MftIn in0;
@@ -255,37 +266,50 @@ DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __r
 	real Fu[6], Ff[6];
 	mft_law(t0, rc, J, x, R, in0, Fu, Ff);	// MotionForceTask.cpp:278-503 (integrators not yet stored)
 	SAI2B_PHASE();
-	real M[N * N], g[N];
-	{
-		PL pl;
-		if constexpr (PL::on) {
-			pl.link = P.payload_link;
-			pl.m = col[S::PLD * 64];
-			UNROLL for (int k = 0; k < 3; k++) pl.c[k] = col[(S::PLD + 1 + k) * 64];
-			UNROLL for (int k = 0; k < 6; k++) pl.I[k] = col[(S::PLD + 4 + k) * 64];
-		}
-		Frames F;
-		if constexpr (BAKED)
-			fk(PandaBaked{}, rc.q, F);
-		else
-			fk(P.model, rc.q, F);
-		fast_model<BAKED>(P, F, pl, M, g);
-	}
-	SAI2B_PHASE();
-	const bool mine = ok && clean;
-	if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
-	// the JointTask law, from its staged rows (late: its results would be live across the model phase)
-	JtEarly jt;
-	if constexpr (FAST == 2) fast_jt_early(P.task[1], rc, StagedRows{P.task[1], B, b, col + S::JG * 64, col + S::JS * 64, N}, jt);
-	// committed to the fast path: integrators can go out now
-	mft_store_integrators(t0, B, b, in0);
-	if (FAST == 2) {
-		UNROLL for (int i = 0; i < N; i++) st(P.task[1].state, i, B, b, jt.integ[i]);
-	}
-	SAI2B_PHASE();
 	real tau[N];
-	fast_tick<FAST == 2>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
-	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
+	if constexpr (S::PARKED) {
+		const bool mine = ok && clean;
+		if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
+		mft_store_integrators(t0, B, b, in0);  // committed to the fast path: integrators can go out now
+		SAI2B_PHASE();
+		// the JointTask law and its integrator store are fast_tick's, behind the nullspace vector (JtLate)
+		const real* park = col + S::IMAGE;
+		JtLate jt{P.task[1], B, b, col + S::DQ * 64};
+		fast_tick<FAST == 2>(P, J, LdsSym{park}, Fu, Ff, B, b, with_comp != 0, jt, tau);
+		UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + park[(S::MROWS + i) * 64]);
+	} else {
+		real M[N * N], g[N];
+		{
+			PL pl;
+			if constexpr (PL::on) {
+				pl.link = P.payload_link;
+				pl.m = col[S::PLD * 64];
+				UNROLL for (int k = 0; k < 3; k++) pl.c[k] = col[(S::PLD + 1 + k) * 64];
+				UNROLL for (int k = 0; k < 6; k++) pl.I[k] = col[(S::PLD + 4 + k) * 64];
+			}
+			Frames F;
+			if constexpr (BAKED)
+				fk(PandaBaked{}, rc.q, F);
+			else
+				fk(P.model, rc.q, F);
+			fast_model<BAKED>(P, F, pl, M, g);
+		}
+		SAI2B_PHASE();
+		const bool mine = ok && clean;
+		if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
+		// the JointTask law, from its staged rows (late: its results would be live across the model phase)
+		JtEarly e;
+		if constexpr (FAST == 2) fast_jt_early(P.task[1], rc, StagedRows{P.task[1], B, b, col + S::JG * 64, col + S::JS * 64, N}, e);
+		// committed to the fast path: integrators can go out now
+		mft_store_integrators(t0, B, b, in0);
+		if (FAST == 2) {
+			UNROLL for (int i = 0; i < N; i++) st(P.task[1].state, i, B, b, e.integ[i]);
+		}
+		SAI2B_PHASE();
+		JtGiven jt{e};
+		fast_tick<FAST == 2>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
+		UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
+	}
 }
 
 template <int FAST, bool BAKED>
