@@ -992,12 +992,12 @@ extern "C" int sai2b_set_mft_goals(sai2b_ctx* ctx, int task, const double* pos, 
 	const size_t B = ctx->B;
 	ctx->goals_dirty |= 1u << task;
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
-	if ((rc = copy_rows(ctx, G, pos, 3, on_device))) return rc;
-	if ((rc = copy_rows(ctx, G + 3 * B, rot, 9, on_device))) return rc;
-	if ((rc = copy_rows(ctx, G + 12 * B, lin_vel, 3, on_device))) return rc;
-	if ((rc = copy_rows(ctx, G + 15 * B, ang_vel, 3, on_device))) return rc;
-	if ((rc = copy_rows(ctx, G + 18 * B, lin_acc, 3, on_device))) return rc;
-	return copy_rows(ctx, G + 21 * B, ang_acc, 3, on_device);
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_POS * B, pos, 3, on_device))) return rc;
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_ROT * B, rot, 9, on_device))) return rc;
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_LIN_VEL * B, lin_vel, 3, on_device))) return rc;
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_ANG_VEL * B, ang_vel, 3, on_device))) return rc;
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_LIN_ACC * B, lin_acc, 3, on_device))) return rc;
+	return copy_rows(ctx, G + sai2b::MFT_GOAL_ANG_ACC * B, ang_acc, 3, on_device);
 }
 
 extern "C" int sai2b_set_mft_goal_wrench(sai2b_ctx* ctx, int task, const double* force, const double* moment, int on_device) {
@@ -1005,8 +1005,8 @@ extern "C" int sai2b_set_mft_goal_wrench(sai2b_ctx* ctx, int task, const double*
 	if (rc) return rc;
 	double* G = ctx->h_params.task[task].goals;
 	const size_t B = ctx->B;
-	if ((rc = copy_rows(ctx, G + 24 * B, force, 3, on_device))) return rc;
-	return copy_rows(ctx, G + 27 * B, moment, 3, on_device);
+	if ((rc = copy_rows(ctx, G + sai2b::MFT_GOAL_FORCE * B, force, 3, on_device))) return rc;
+	return copy_rows(ctx, G + sai2b::MFT_GOAL_MOMENT * B, moment, 3, on_device);
 }
 
 extern "C" int sai2b_set_mft_sensed_wrench(sai2b_ctx* ctx, int task, const double* force, const double* moment, int on_device) {
@@ -1972,7 +1972,9 @@ extern "C" int sai2b_get_mft_goals(sai2b_ctx* ctx, int task, double* pos, double
 	if (rc) return rc;
 	const double* G = ctx->h_params.task[task].goals;
 	double* dst[8] = {pos, rot, lin_vel, ang_vel, lin_acc, ang_acc, force, moment};
-	const size_t row0[8] = {0, 3, 12, 15, 18, 21, 24, 27}, rows[8] = {3, 9, 3, 3, 3, 3, 3, 3};
+	using namespace sai2b;
+	const size_t row0[8] = {MFT_GOAL_POS, MFT_GOAL_ROT, MFT_GOAL_LIN_VEL, MFT_GOAL_ANG_VEL, MFT_GOAL_LIN_ACC, MFT_GOAL_ANG_ACC, MFT_GOAL_FORCE, MFT_GOAL_MOMENT};
+	const size_t rows[8] = {3, 9, 3, 3, 3, 3, 3, 3};
 	for (int k = 0; k < 8; k++)
 		if ((rc = fetch_rows(ctx, G, row0[k], rows[k], dst[k]))) return rc;
 	return SAI2B_OK;
@@ -2028,12 +2030,12 @@ extern "C" int sai2b_get_mft_desired(sai2b_ctx* ctx, int task, double* pos, doub
 	int rc = mft_task_check(ctx, task, "sai2b_get_mft_desired");
 	if (rc) return rc;
 	const double* G = ctx->h_params.task[task].law_goals;
-	if ((rc = fetch_rows(ctx, G, 0, 3, pos))) return rc;
-	if ((rc = fetch_rows(ctx, G, 3, 9, rot))) return rc;
-	if ((rc = fetch_rows(ctx, G, 12, 3, lin_vel))) return rc;
-	if ((rc = fetch_rows(ctx, G, 15, 3, ang_vel))) return rc;
-	if ((rc = fetch_rows(ctx, G, 18, 3, lin_acc))) return rc;
-	return fetch_rows(ctx, G, 21, 3, ang_acc);
+	if ((rc = fetch_rows(ctx, G, sai2b::MFT_GOAL_POS, 3, pos))) return rc;
+	if ((rc = fetch_rows(ctx, G, sai2b::MFT_GOAL_ROT, 9, rot))) return rc;
+	if ((rc = fetch_rows(ctx, G, sai2b::MFT_GOAL_LIN_VEL, 3, lin_vel))) return rc;
+	if ((rc = fetch_rows(ctx, G, sai2b::MFT_GOAL_ANG_VEL, 3, ang_vel))) return rc;
+	if ((rc = fetch_rows(ctx, G, sai2b::MFT_GOAL_LIN_ACC, 3, lin_acc))) return rc;
+	return fetch_rows(ctx, G, sai2b::MFT_GOAL_ANG_ACC, 3, ang_acc);
 }
 extern "C" int sai2b_get_otg_status(sai2b_ctx* ctx, int task, double* goal_reached, double* result) {
 	if (!ctx || task < 0 || task >= ctx->T) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_otg_status: bad arguments");

@@ -51,6 +51,80 @@ DI double sel7(const double (&v)[MD], int j) {
 	return r;
 }
 
+// ---- groups of rows of the generator's state, each read and written in one place ----
+// The Cartesian wrapper's reference frame; its goal orientation and angular velocity (GG: Gen or a lane's otgg::LaneState)
+template <class GG> DI void load_cart_ref(const real* S, int B, int b, GG& g) {
+	UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART_REF + i, B, b);
+}
+template <class GG> DI void load_cart_goal(const real* S, int B, int b, GG& g) {
+	UNROLL for (int i = 0; i < 9; i++) g.goal_R[i] = ld(S, OTG_CART_GOAL_R + i, B, b);
+	UNROLL for (int i = 0; i < 3; i++) g.goal_w[i] = ld(S, OTG_CART_GOAL_W + i, B, b);
+}
+template <class GG> DI void store_cart(real* S, int B, int b, const GG& g) {
+	UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART_REF + i, B, b, g.ref[i]);
+	UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART_GOAL_R + i, B, b, g.goal_R[i]);
+	UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART_GOAL_W + i, B, b, g.goal_w[i]);
+}
+// The wrapper's input and Ruckig's stored one
+DI void store_in_ci(real* S, int n, int B, int b, const Gen& g) {
+	store7(S, OTG_IN, n, B, b, g.in.cp);
+	store7(S, OTG_IN + MD, n, B, b, g.in.cv);
+	store7(S, OTG_IN + 2 * MD, n, B, b, g.in.ca);
+	store7(S, OTG_IN + 3 * MD, n, B, b, g.in.tp);
+	store7(S, OTG_IN + 4 * MD, n, B, b, g.in.tv);
+	store7(S, OTG_CI, n, B, b, g.ci.cp);
+	store7(S, OTG_CI + MD, n, B, b, g.ci.cv);
+	store7(S, OTG_CI + 2 * MD, n, B, b, g.ci.ca);
+	store7(S, OTG_CI + 3 * MD, n, B, b, g.ci.tp);
+	store7(S, OTG_CI + 4 * MD, n, B, b, g.ci.tv);
+}
+// One DoF of an acceleration-limited trajectory, the OTG_TRAJ_STRIDE rows from r = OTG_TRAJ + d * OTG_TRAJ_STRIDE, in three
+// pieces (load_traj reads the first only where there is a brake pre-trajectory): its a p v, the start state, the profile
+DI void load_dof_brake(const real* S, int r, int B, int b, otg::Dof& f) {
+	f.brake_a = ld(S, r + 1, B, b), f.brake_p = ld(S, r + 2, B, b), f.brake_v = ld(S, r + 3, B, b);
+}
+DI void load_dof_start(const real* S, int r, int B, int b, otg::Dof& f) { f.p0 = ld(S, r + 4, B, b), f.v0 = ld(S, r + 5, B, b); }
+DI void load_dof_prof(const real* S, int r, int B, int b, otg::Prof& p) {
+	p.t0 = ld(S, r + 6, B, b), p.t1 = ld(S, r + 7, B, b), p.t2 = ld(S, r + 8, B, b), p.t6 = ld(S, r + 9, B, b);
+	p.a0 = ld(S, r + 10, B, b), p.a2 = ld(S, r + 11, B, b), p.a6 = ld(S, r + 12, B, b);
+	p.dur = ((p.t0 + p.t1) + p.t2) + p.t6;	// t_sum.back(), as Profile::check accumulates it
+}
+DI void load_dof(const real* S, int r, int B, int b, otg::Dof& f, otg::Prof& p) {
+	f.brake_t = ld(S, r, B, b);
+	load_dof_brake(S, r, B, b, f);
+	load_dof_start(S, r, B, b, f);
+	load_dof_prof(S, r, B, b, p);
+}
+DI void store_dof(real* S, int r, int B, int b, const otg::Dof& f, const otg::Prof& p) {
+	st(S, r, B, b, f.brake_t), st(S, r + 1, B, b, f.brake_a), st(S, r + 2, B, b, f.brake_p);
+	st(S, r + 3, B, b, f.brake_v), st(S, r + 4, B, b, f.p0), st(S, r + 5, B, b, f.v0);
+	st(S, r + 6, B, b, p.t0), st(S, r + 7, B, b, p.t1), st(S, r + 8, B, b, p.t2), st(S, r + 9, B, b, p.t6);
+	st(S, r + 10, B, b, p.a0), st(S, r + 11, B, b, p.a2), st(S, r + 12, B, b, p.a6);
+}
+// One DoF of a jerk-limited trajectory: the OTG3_STRIDE rows of otg3_traj from r = d * OTG3_STRIDE (what is not stored is zero)
+DI void load_prof3(const real* T3, int r, int B, int b, otg3::Prof& p) {
+	p.brake.duration = ld(T3, r + OTG3_BRAKE, B, b);
+	UNROLL for (int k = 0; k < 2; k++) {
+		p.brake.t[k] = ld(T3, r + OTG3_BRAKE + 1 + k, B, b), p.brake.j[k] = ld(T3, r + OTG3_BRAKE + 3 + k, B, b);
+		p.brake.a[k] = ld(T3, r + OTG3_BRAKE + 5 + k, B, b), p.brake.v[k] = ld(T3, r + OTG3_BRAKE + 7 + k, B, b);
+		p.brake.p[k] = ld(T3, r + OTG3_BRAKE + 9 + k, B, b);
+	}
+	UNROLL for (int k = 0; k < 7; k++) p.t_sum[k] = ld(T3, r + OTG3_TSUM + k, B, b), p.j[k] = ld(T3, r + OTG3_J + k, B, b), p.t[k] = 0;
+	UNROLL for (int k = 0; k < 8; k++) p.a[k] = ld(T3, r + OTG3_A + k, B, b), p.v[k] = ld(T3, r + OTG3_V + k, B, b), p.p[k] = ld(T3, r + OTG3_P + k, B, b);
+	p.pf = p.vf = p.af = 0, p.limits = p.direction = p.control_signs = 0;
+}
+// (plain loops: plan_lane3 keeps them rolled inside its loop over the DoFs)
+DI void store_prof3(real* T3, int r, int B, int b, const otg3::Prof& p) {
+	st(T3, r + OTG3_BRAKE, B, b, p.brake.duration);
+	for (int k = 0; k < 2; k++) {
+		st(T3, r + OTG3_BRAKE + 1 + k, B, b, p.brake.t[k]), st(T3, r + OTG3_BRAKE + 3 + k, B, b, p.brake.j[k]);
+		st(T3, r + OTG3_BRAKE + 5 + k, B, b, p.brake.a[k]), st(T3, r + OTG3_BRAKE + 7 + k, B, b, p.brake.v[k]);
+		st(T3, r + OTG3_BRAKE + 9 + k, B, b, p.brake.p[k]);
+	}
+	for (int k = 0; k < 7; k++) st(T3, r + OTG3_TSUM + k, B, b, p.t_sum[k]), st(T3, r + OTG3_J + k, B, b, p.j[k]);
+	for (int k = 0; k < 8; k++) st(T3, r + OTG3_A + k, B, b, p.a[k]), st(T3, r + OTG3_V + k, B, b, p.v[k]), st(T3, r + OTG3_P + k, B, b, p.p[k]);
+}
+
 // flags and the wrapper's target: enough to decide whether anything happens this tick
 DI void load_head(const real* S, int n, bool cart, int B, int b, Gen& g) {
 	g.goal_reached = ldflag(S, OTG_GOAL_REACHED, B, b);
@@ -58,10 +132,7 @@ DI void load_head(const real* S, int n, bool cart, int B, int b, Gen& g) {
 	g.target_set = ldflag(S, OTG_TARGET_SET, B, b);
 	load7(S, OTG_IN + 3 * MD, n, B, b, g.in.tp);
 	load7(S, OTG_IN + 4 * MD, n, B, b, g.in.tv);
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.goal_R[i] = ld(S, OTG_CART + 9 + i, B, b);
-		UNROLL for (int i = 0; i < 3; i++) g.goal_w[i] = ld(S, OTG_CART + 18 + i, B, b);
-	}
+	if (cart) load_cart_goal(S, B, b, g);
 }
 DI void load_body(const real* S, int n, bool cart, int B, int b, Gen& g) {
 	load7(S, OTG_IN, n, B, b, g.in.cp);
@@ -92,12 +163,7 @@ DI void load_body(const real* S, int n, bool cart, int B, int b, Gen& g) {
 		otg::Dof& f = g.traj.dof[d];
 		otg::Prof& p = g.traj.prof[d];
 		if (d < n) {
-			const int r = OTG_TRAJ + d * OTG_TRAJ_STRIDE;
-			f.brake_t = ld(S, r, B, b), f.brake_a = ld(S, r + 1, B, b), f.brake_p = ld(S, r + 2, B, b);
-			f.brake_v = ld(S, r + 3, B, b), f.p0 = ld(S, r + 4, B, b), f.v0 = ld(S, r + 5, B, b);
-			p.t0 = ld(S, r + 6, B, b), p.t1 = ld(S, r + 7, B, b), p.t2 = ld(S, r + 8, B, b), p.t6 = ld(S, r + 9, B, b);
-			p.a0 = ld(S, r + 10, B, b), p.a2 = ld(S, r + 11, B, b), p.a6 = ld(S, r + 12, B, b);
-			p.dur = ((p.t0 + p.t1) + p.t2) + p.t6;	// t_sum.back(), as Profile::check accumulates it
+			load_dof(S, OTG_TRAJ + d * OTG_TRAJ_STRIDE, B, b, f, p);
 		} else {
 			f = otg::Dof{0, 0, 0, 0, 0, 0, 0, 0};
 			p = otg::Prof{0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -105,21 +171,10 @@ DI void load_body(const real* S, int n, bool cart, int B, int b, Gen& g) {
 		f.pf = f.vf = 0;
 		p.dir = 0;
 	}
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART + i, B, b);
-	}
+	if (cart) load_cart_ref(S, B, b, g);
 }
 DI void store_state(real* S, int n, bool cart, int B, int b, const Gen& g) {
-	store7(S, OTG_IN, n, B, b, g.in.cp);
-	store7(S, OTG_IN + MD, n, B, b, g.in.cv);
-	store7(S, OTG_IN + 2 * MD, n, B, b, g.in.ca);
-	store7(S, OTG_IN + 3 * MD, n, B, b, g.in.tp);
-	store7(S, OTG_IN + 4 * MD, n, B, b, g.in.tv);
-	store7(S, OTG_CI, n, B, b, g.ci.cp);
-	store7(S, OTG_CI + MD, n, B, b, g.ci.cv);
-	store7(S, OTG_CI + 2 * MD, n, B, b, g.ci.ca);
-	store7(S, OTG_CI + 3 * MD, n, B, b, g.ci.tp);
-	store7(S, OTG_CI + 4 * MD, n, B, b, g.ci.tv);
+	store_in_ci(S, n, B, b, g);
 	store7(S, OTG_OUT, n, B, b, g.np);
 	store7(S, OTG_OUT + MD, n, B, b, g.nv);
 	store7(S, OTG_OUT + 2 * MD, n, B, b, g.na);
@@ -130,11 +185,7 @@ DI void store_state(real* S, int n, bool cart, int B, int b, const Gen& g) {
 	st(S, OTG_CI_INIT, B, b, (double)g.ci_init);
 	st(S, OTG_CI_EPOCH, B, b, g.ci_epoch);
 	st(S, OTG_IN_SYNC, B, b, 0.0);
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + i, B, b, g.ref[i]);
-		UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + 9 + i, B, b, g.goal_R[i]);
-		UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART + 18 + i, B, b, g.goal_w[i]);
-	}
+	if (cart) store_cart(S, B, b, g);
 }
 
 // the next state in the layout of the goals (getNext*: OTG_joints.h:142-146, OTG_6dof_cartesian.h:205-227)
@@ -152,13 +203,13 @@ DI void store_desired_cart(real* D, int B, int b, const Gen& g) {
 	otg::mat3_vec(g.ref, g.nv[3], g.nv[4], g.nv[5], w);
 	otg::mat3_vec(g.ref, g.na[3], g.na[4], g.na[5], al);
 	UNROLL for (int k = 0; k < 3; k++) {
-		st(D, k, B, b, g.np[k]);
-		st(D, 12 + k, B, b, g.nv[k]);
-		st(D, 15 + k, B, b, w[k]);
-		st(D, 18 + k, B, b, g.na[k]);
-		st(D, 21 + k, B, b, al[k]);
+		st(D, MFT_GOAL_POS + k, B, b, g.np[k]);
+		st(D, MFT_GOAL_LIN_VEL + k, B, b, g.nv[k]);
+		st(D, MFT_GOAL_ANG_VEL + k, B, b, w[k]);
+		st(D, MFT_GOAL_LIN_ACC + k, B, b, g.na[k]);
+		st(D, MFT_GOAL_ANG_ACC + k, B, b, al[k]);
 	}
-	UNROLL for (int k = 0; k < 9; k++) st(D, 3 + k, B, b, R[k]);
+	UNROLL for (int k = 0; k < 9; k++) st(D, MFT_GOAL_ROT + k, B, b, R[k]);
 }
 
 // goals of one robot as the wrappers' setGoal... calls take them
@@ -172,11 +223,11 @@ DI void load_goals(const DevTask& t, bool cart, int n, int B, int b, Goals& G) {
 		load7(t.goals, n, n, B, b, G.jv);
 	} else {
 		UNROLL for (int k = 0; k < 3; k++) {
-			G.cp[k] = ld(t.goals, k, B, b);
-			G.cv[k] = ld(t.goals, 12 + k, B, b);
-			G.cw[k] = ld(t.goals, 15 + k, B, b);
+			G.cp[k] = ld(t.goals, MFT_GOAL_POS + k, B, b);
+			G.cv[k] = ld(t.goals, MFT_GOAL_LIN_VEL + k, B, b);
+			G.cw[k] = ld(t.goals, MFT_GOAL_ANG_VEL + k, B, b);
 		}
-		UNROLL for (int k = 0; k < 9; k++) G.cR[k] = ld(t.goals, 3 + k, B, b);
+		UNROLL for (int k = 0; k < 9; k++) G.cR[k] = ld(t.goals, MFT_GOAL_ROT + k, B, b);
 	}
 }
 
@@ -241,20 +292,17 @@ DI void load_traj(const real* S, int n, bool cart, int B, int b, Gen& g) {
 	UNROLL for (int d = 0; d < MD; d++) {
 		otg::Dof& f = g.traj.dof[d];
 		otg::Prof& p = g.traj.prof[d];
-		if (d < n) {
+		if (d < n) {  // the rest of a brake pre-trajectory is read only where there is one (at_time)
 			const int r = OTG_TRAJ + d * OTG_TRAJ_STRIDE;
-			f.brake_t = ld(S, r, B, b), f.p0 = ld(S, r + 4, B, b), f.v0 = ld(S, r + 5, B, b);
+			f.brake_t = ld(S, r, B, b);
+			load_dof_start(S, r, B, b, f);
 			f.brake_a = f.brake_p = f.brake_v = 0.0;
-			if (f.brake_t > 0.0) {	// the rest of a brake pre-trajectory is read only where there is one (at_time)
-				f.brake_a = ld(S, r + 1, B, b), f.brake_p = ld(S, r + 2, B, b), f.brake_v = ld(S, r + 3, B, b);
-			}
-			p.t0 = ld(S, r + 6, B, b), p.t1 = ld(S, r + 7, B, b), p.t2 = ld(S, r + 8, B, b), p.t6 = ld(S, r + 9, B, b);
-			p.a0 = ld(S, r + 10, B, b), p.a2 = ld(S, r + 11, B, b), p.a6 = ld(S, r + 12, B, b);
-			p.dur = ((p.t0 + p.t1) + p.t2) + p.t6;
+			if (f.brake_t > 0.0) load_dof_brake(S, r, B, b, f);
+			load_dof_prof(S, r, B, b, p);
 		}
 	}
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART + i, B, b);
+	if (cart) {	 // (not load_cart_ref: otg_kernel<false> keeps its instructions only with the loop written here)
+		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART_REF + i, B, b);
 	}
 }
 
@@ -289,8 +337,8 @@ DI int sample_jerk(const DevTask& t, bool cart, int n, int B, int b, Gen& g) {
 			otg3::integrate(t_in, p0, v0, a0, j0, g.np[d], g.nv[d], g.na[d]);
 			g.ci.cp[d] = g.np[d], g.ci.cv[d] = g.nv[d], g.ci.ca[d] = g.na[d];
 		}
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART + i, B, b);
+	if (cart) {	 // (as in load_traj)
+		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART_REF + i, B, b);
 	}
 	return g.time > duration ? otg::FINISHED : otg::WORKING;
 }
@@ -332,24 +380,11 @@ template <bool JERK> DI void sample_lane(const DevTask& t, bool cart, int n, int
 			otg::cart_finish(g, none);
 		else
 			otg::joints_finish(g, n, none);
-		store7(S, OTG_IN, n, B, b, g.in.cp);
-		store7(S, OTG_IN + MD, n, B, b, g.in.cv);
-		store7(S, OTG_IN + 2 * MD, n, B, b, g.in.ca);
-		store7(S, OTG_IN + 3 * MD, n, B, b, g.in.tp);
-		store7(S, OTG_IN + 4 * MD, n, B, b, g.in.tv);
-		store7(S, OTG_CI, n, B, b, g.ci.cp);
-		store7(S, OTG_CI + MD, n, B, b, g.ci.cv);
-		store7(S, OTG_CI + 2 * MD, n, B, b, g.ci.ca);
-		store7(S, OTG_CI + 3 * MD, n, B, b, g.ci.tp);
-		store7(S, OTG_CI + 4 * MD, n, B, b, g.ci.tv);
+		store_in_ci(S, n, B, b, g);
 		st(S, OTG_IN_SYNC, B, b, 0.0);
 		st(S, OTG_GOAL_REACHED, B, b, (double)g.goal_reached);
 		st(S, OTG_TARGET_SET, B, b, (double)g.target_set);
-		if (cart && !g.goal_reached) {
-			UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + i, B, b, g.ref[i]);
-			UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + 9 + i, B, b, g.goal_R[i]);
-			UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART + 18 + i, B, b, g.goal_w[i]);
-		}
+		if (cart && !g.goal_reached) store_cart(S, B, b, g);
 	}
 	store7(S, OTG_OUT, n, B, b, g.np);
 	store7(S, OTG_OUT + MD, n, B, b, g.nv);
@@ -362,16 +397,32 @@ template <bool JERK> DI void sample_lane(const DevTask& t, bool cart, int n, int
 		store_desired_joints(t.otg_desired, n, B, b, g);
 }
 
+// The lane's DoF of the stored trajectory (sampled when no new calculation is needed) and what else its order has
+DI void load_lane_traj(const DevTask& t, int j, bool active, int B, int b, otgg::LaneGen& g) {
+	load_dof(t.otg_state, OTG_TRAJ + (active ? j : 0) * OTG_TRAJ_STRIDE, B, b, g.f, g.p);
+	g.f.pf = g.f.vf = 0;
+	g.p.dir = 0;
+}
+DI void load_lane_traj(const DevTask& t, int j, bool active, int B, int b, otgg::LaneGen3& g) {
+	load_prof3(t.otg3_traj, (active ? j : 0) * OTG3_STRIDE, B, b, g.p);
+	g.jmax = active ? sel7(t.otg_jmax, j) : 0.0;
+}
+DI void store_lane_traj(const DevTask& t, int j, int B, int b, const otgg::LaneGen& g) {
+	store_dof(t.otg_state, OTG_TRAJ + j * OTG_TRAJ_STRIDE, B, b, g.f, g.p);
+}
+DI void store_lane_traj(const DevTask& t, int j, int B, int b, const otgg::LaneGen3& g) { store_prof3(t.otg3_traj, j * OTG3_STRIDE, B, b, g.p); }
+
 // PLAN, one DoF per lane (sai2b_otg_group.hpp): the whole computeTorques-time sequence
 // setGoal...(goal); update(); (JointTask.cpp:314-315, MotionForceTask.cpp:395-399) for robot b by the
-// caller's group of 8 lanes
-DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
+// caller's group of 8 lanes. LG: otgg::LaneGen (acceleration-limited) or otgg::LaneGen3 (jerk-limited: ruckig's
+// third-order interface, the stored profile travels through otg3_traj)
+template <class LG> DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 	using namespace otgg;
 	real* S = t.otg_state;
 	const int j = lane_j();
 	const bool active = j < n;
 	auto row = [&](int r0) { return active ? ld(S, r0 + j, B, b) : 0.0; };
-	LaneGen g;
+	LG g;
 	g.in_cp = row(OTG_IN), g.in_cv = row(OTG_IN + MD), g.in_ca = row(OTG_IN + 2 * MD), g.in_tp = row(OTG_IN + 3 * MD),
 	g.in_tv = row(OTG_IN + 4 * MD);
 	g.ci_cp = row(OTG_CI), g.ci_cv = row(OTG_CI + MD), g.ci_ca = row(OTG_CI + 2 * MD), g.ci_tp = row(OTG_CI + 3 * MD),
@@ -381,16 +432,7 @@ DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 		g.in_cp = g.ci_cp = g.np, g.in_cv = g.ci_cv = g.nv, g.in_ca = g.ci_ca = g.na;
 		g.ci_tp = g.in_tp, g.ci_tv = g.in_tv;
 	}
-	{
-		const int r = OTG_TRAJ + (active ? j : 0) * OTG_TRAJ_STRIDE;
-		g.f.brake_t = ld(S, r, B, b), g.f.brake_a = ld(S, r + 1, B, b), g.f.brake_p = ld(S, r + 2, B, b);
-		g.f.brake_v = ld(S, r + 3, B, b), g.f.p0 = ld(S, r + 4, B, b), g.f.v0 = ld(S, r + 5, B, b);
-		g.f.pf = g.f.vf = 0;
-		g.p.t0 = ld(S, r + 6, B, b), g.p.t1 = ld(S, r + 7, B, b), g.p.t2 = ld(S, r + 8, B, b), g.p.t6 = ld(S, r + 9, B, b);
-		g.p.a0 = ld(S, r + 10, B, b), g.p.a2 = ld(S, r + 11, B, b), g.p.a6 = ld(S, r + 12, B, b);
-		g.p.dur = ((g.p.t0 + g.p.t1) + g.p.t2) + g.p.t6;
-		g.p.dir = 0;
-	}
+	load_lane_traj(t, j, active, B, b, g);
 	g.time = ld(S, OTG_TIME, B, b);
 	g.duration = ld(S, OTG_DURATION, B, b);
 	g.goal_reached = ldflag(S, OTG_GOAL_REACHED, B, b);
@@ -401,12 +443,14 @@ DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 	g.replanned = 0;
 	const double vmax = active ? sel7(t.otg_vmax, j) : 0.0, amax = active ? sel7(t.otg_amax, j) : 0.0;
 	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART + i, B, b), g.goal_R[i] = ld(S, OTG_CART + 9 + i, B, b);
-		UNROLL for (int i = 0; i < 3; i++) g.goal_w[i] = ld(S, OTG_CART + 18 + i, B, b);
+		// (ref and goal rows interleaved here and in the store below, not the helpers: with their order otg3_plan_kernel<false>
+		// needs 16 B more scratch)
+		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART_REF + i, B, b), g.goal_R[i] = ld(S, OTG_CART_GOAL_R + i, B, b);
+		UNROLL for (int i = 0; i < 3; i++) g.goal_w[i] = ld(S, OTG_CART_GOAL_W + i, B, b);
 		real gR[9], gw[3];
-		UNROLL for (int k = 0; k < 9; k++) gR[k] = ld(t.goals, 3 + k, B, b);
-		UNROLL for (int k = 0; k < 3; k++) gw[k] = ld(t.goals, 15 + k, B, b);
-		const double gp = j < 3 ? ld(t.goals, j, B, b) : 0.0, gv = j < 3 ? ld(t.goals, 12 + j, B, b) : 0.0;
+		UNROLL for (int k = 0; k < 9; k++) gR[k] = ld(t.goals, MFT_GOAL_ROT + k, B, b);
+		UNROLL for (int k = 0; k < 3; k++) gw[k] = ld(t.goals, MFT_GOAL_ANG_VEL + k, B, b);
+		const double gp = j < 3 ? ld(t.goals, MFT_GOAL_POS + j, B, b) : 0.0, gv = j < 3 ? ld(t.goals, MFT_GOAL_LIN_VEL + j, B, b) : 0.0;
 		cart_set_goal_position(g, gp, gv);
 		cart_set_goal_orientation(g, gR, gw);
 	} else {
@@ -421,13 +465,7 @@ DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 	put(OTG_IN, g.in_cp), put(OTG_IN + MD, g.in_cv), put(OTG_IN + 2 * MD, g.in_ca), put(OTG_IN + 3 * MD, g.in_tp), put(OTG_IN + 4 * MD, g.in_tv);
 	put(OTG_CI, g.ci_cp), put(OTG_CI + MD, g.ci_cv), put(OTG_CI + 2 * MD, g.ci_ca), put(OTG_CI + 3 * MD, g.ci_tp), put(OTG_CI + 4 * MD, g.ci_tv);
 	put(OTG_OUT, g.np), put(OTG_OUT + MD, g.nv), put(OTG_OUT + 2 * MD, g.na);
-	if (g.replanned && active) {
-		const int r = OTG_TRAJ + j * OTG_TRAJ_STRIDE;
-		st(S, r, B, b, g.f.brake_t), st(S, r + 1, B, b, g.f.brake_a), st(S, r + 2, B, b, g.f.brake_p);
-		st(S, r + 3, B, b, g.f.brake_v), st(S, r + 4, B, b, g.f.p0), st(S, r + 5, B, b, g.f.v0);
-		st(S, r + 6, B, b, g.p.t0), st(S, r + 7, B, b, g.p.t1), st(S, r + 8, B, b, g.p.t2), st(S, r + 9, B, b, g.p.t6);
-		st(S, r + 10, B, b, g.p.a0), st(S, r + 11, B, b, g.p.a2), st(S, r + 12, B, b, g.p.a6);
-	}
+	if (g.replanned && active) store_lane_traj(t, j, B, b, g);
 	real R[9], w[3], al[3];
 	if (cart) {	 // getNextOrientation / getNextAngular* (OTG_6dof_cartesian.cpp:226-237, .h:222-227)
 		real local[9];
@@ -436,6 +474,7 @@ DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 		otg::mat3_vec(g.ref, gget(g.nv, 3), gget(g.nv, 4), gget(g.nv, 5), w);
 		otg::mat3_vec(g.ref, gget(g.na, 3), gget(g.na, 4), gget(g.na, 5), al);
 	}
+	real* D = t.otg_desired;
 	if (j == 0) {
 		st(S, OTG_TIME, B, b, g.time);
 		if (g.replanned) st(S, OTG_DURATION, B, b, g.duration);
@@ -446,126 +485,20 @@ DI void plan_group(const DevTask& t, bool cart, int n, int B, int b) {
 		st(S, OTG_CI_EPOCH, B, b, g.ci_epoch);
 		st(S, OTG_IN_SYNC, B, b, 0.0);
 		if (cart) {
-			UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + i, B, b, g.ref[i]), st(S, OTG_CART + 9 + i, B, b, g.goal_R[i]);
-			UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART + 18 + i, B, b, g.goal_w[i]);
-			UNROLL for (int k = 0; k < 9; k++) st(t.otg_desired, 3 + k, B, b, R[k]);
-			UNROLL for (int k = 0; k < 3; k++) st(t.otg_desired, 15 + k, B, b, w[k]), st(t.otg_desired, 21 + k, B, b, al[k]);
+			UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART_REF + i, B, b, g.ref[i]), st(S, OTG_CART_GOAL_R + i, B, b, g.goal_R[i]);
+			UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART_GOAL_W + i, B, b, g.goal_w[i]);
+			UNROLL for (int k = 0; k < 9; k++) st(D, MFT_GOAL_ROT + k, B, b, R[k]);
+			UNROLL for (int k = 0; k < 3; k++) st(D, MFT_GOAL_ANG_VEL + k, B, b, w[k]), st(D, MFT_GOAL_ANG_ACC + k, B, b, al[k]);
 		}
 	}
 	if (cart) {
-		if (j < 3) st(t.otg_desired, j, B, b, g.np), st(t.otg_desired, 12 + j, B, b, g.nv), st(t.otg_desired, 18 + j, B, b, g.na);
+		if (j < 3) st(D, MFT_GOAL_POS + j, B, b, g.np), st(D, MFT_GOAL_LIN_VEL + j, B, b, g.nv), st(D, MFT_GOAL_LIN_ACC + j, B, b, g.na);
 	} else if (active && !t.otg_out_is_desired) {
-		st(t.otg_desired, j, B, b, g.np), st(t.otg_desired, n + j, B, b, g.nv), st(t.otg_desired, 2 * n + j, B, b, g.na);
+		st(D, j, B, b, g.np), st(D, n + j, B, b, g.nv), st(D, 2 * n + j, B, b, g.na);
 	}
 }
 
-// PLAN for a JERK-LIMITED generator, one DoF per lane (sai2b_otg_group.hpp: LaneGen3, calculate3): the counterpart of
-// plan_group for ruckig's third-order interface. The stored profile of the lane's DoF travels through otg3_traj.
-DI void plan_group3(const DevTask& t, bool cart, int n, int B, int b) {
-	using namespace otgg;
-	real* S = t.otg_state;
-	real* T3 = t.otg3_traj;
-	const int j = lane_j();
-	const bool active = j < n;
-	auto row = [&](int r0) { return active ? ld(S, r0 + j, B, b) : 0.0; };
-	LaneGen3 g;
-	g.in_cp = row(OTG_IN), g.in_cv = row(OTG_IN + MD), g.in_ca = row(OTG_IN + 2 * MD), g.in_tp = row(OTG_IN + 3 * MD),
-	g.in_tv = row(OTG_IN + 4 * MD);
-	g.ci_cp = row(OTG_CI), g.ci_cv = row(OTG_CI + MD), g.ci_ca = row(OTG_CI + 2 * MD), g.ci_tp = row(OTG_CI + 3 * MD),
-	g.ci_tv = row(OTG_CI + 4 * MD);
-	g.np = row(OTG_OUT), g.nv = row(OTG_OUT + MD), g.na = row(OTG_OUT + 2 * MD);
-	if (ldflag(S, OTG_IN_SYNC, B, b) != 0) {  // see OTG_IN_SYNC
-		g.in_cp = g.ci_cp = g.np, g.in_cv = g.ci_cv = g.nv, g.in_ca = g.ci_ca = g.na;
-		g.ci_tp = g.in_tp, g.ci_tv = g.in_tv;
-	}
-	{	// the stored third-order profile of this lane's DoF (sampled when no new calculation is needed)
-		const int r = (active ? j : 0) * OTG3_STRIDE;
-		otg3::Prof& p = g.p;
-		p.brake.duration = ld(T3, r + OTG3_BRAKE, B, b);
-		UNROLL for (int k = 0; k < 2; k++) {
-			p.brake.t[k] = ld(T3, r + OTG3_BRAKE + 1 + k, B, b), p.brake.j[k] = ld(T3, r + OTG3_BRAKE + 3 + k, B, b);
-			p.brake.a[k] = ld(T3, r + OTG3_BRAKE + 5 + k, B, b), p.brake.v[k] = ld(T3, r + OTG3_BRAKE + 7 + k, B, b);
-			p.brake.p[k] = ld(T3, r + OTG3_BRAKE + 9 + k, B, b);
-		}
-		UNROLL for (int k = 0; k < 7; k++) p.t_sum[k] = ld(T3, r + OTG3_TSUM + k, B, b), p.j[k] = ld(T3, r + OTG3_J + k, B, b), p.t[k] = 0;
-		UNROLL for (int k = 0; k < 8; k++) p.a[k] = ld(T3, r + OTG3_A + k, B, b), p.v[k] = ld(T3, r + OTG3_V + k, B, b), p.p[k] = ld(T3, r + OTG3_P + k, B, b);
-		p.pf = p.vf = p.af = 0, p.limits = p.direction = p.control_signs = 0;
-	}
-	g.time = ld(S, OTG_TIME, B, b);
-	g.duration = ld(S, OTG_DURATION, B, b);
-	g.goal_reached = ldflag(S, OTG_GOAL_REACHED, B, b);
-	g.result = ldflag(S, OTG_RESULT, B, b);
-	g.target_set = ldflag(S, OTG_TARGET_SET, B, b);
-	g.ci_init = ldflag(S, OTG_CI_INIT, B, b);
-	g.ci_epoch = ld(S, OTG_CI_EPOCH, B, b);
-	g.replanned = 0;
-	const double vmax = active ? sel7(t.otg_vmax, j) : 0.0, amax = active ? sel7(t.otg_amax, j) : 0.0;
-	g.jmax = active ? sel7(t.otg_jmax, j) : 0.0;
-	if (cart) {
-		UNROLL for (int i = 0; i < 9; i++) g.ref[i] = ld(S, OTG_CART + i, B, b), g.goal_R[i] = ld(S, OTG_CART + 9 + i, B, b);
-		UNROLL for (int i = 0; i < 3; i++) g.goal_w[i] = ld(S, OTG_CART + 18 + i, B, b);
-		real gR[9], gw[3];
-		UNROLL for (int k = 0; k < 9; k++) gR[k] = ld(t.goals, 3 + k, B, b);
-		UNROLL for (int k = 0; k < 3; k++) gw[k] = ld(t.goals, 15 + k, B, b);
-		const double gp = j < 3 ? ld(t.goals, j, B, b) : 0.0, gv = j < 3 ? ld(t.goals, 12 + j, B, b) : 0.0;
-		cart_set_goal_position(g, gp, gv);
-		cart_set_goal_orientation(g, gR, gw);
-	} else {
-		const double gp = active ? ld(t.goals, j, B, b) : 0.0, gv = active ? ld(t.goals, n + j, B, b) : 0.0;
-		joints_set_goal(g, active, n, gp, gv);
-	}
-	update(g, cart, active, n, t.dt, vmax, amax, t.otg_epoch);
-
-	auto put = [&](int r0, double v) {
-		if (active) st(S, r0 + j, B, b, v);
-	};
-	put(OTG_IN, g.in_cp), put(OTG_IN + MD, g.in_cv), put(OTG_IN + 2 * MD, g.in_ca), put(OTG_IN + 3 * MD, g.in_tp), put(OTG_IN + 4 * MD, g.in_tv);
-	put(OTG_CI, g.ci_cp), put(OTG_CI + MD, g.ci_cv), put(OTG_CI + 2 * MD, g.ci_ca), put(OTG_CI + 3 * MD, g.ci_tp), put(OTG_CI + 4 * MD, g.ci_tv);
-	put(OTG_OUT, g.np), put(OTG_OUT + MD, g.nv), put(OTG_OUT + 2 * MD, g.na);
-	if (g.replanned && active) {
-		const otg3::Prof& p = g.p;
-		const int r = j * OTG3_STRIDE;
-		st(T3, r + OTG3_BRAKE, B, b, p.brake.duration);
-		UNROLL for (int k = 0; k < 2; k++) {
-			st(T3, r + OTG3_BRAKE + 1 + k, B, b, p.brake.t[k]), st(T3, r + OTG3_BRAKE + 3 + k, B, b, p.brake.j[k]);
-			st(T3, r + OTG3_BRAKE + 5 + k, B, b, p.brake.a[k]), st(T3, r + OTG3_BRAKE + 7 + k, B, b, p.brake.v[k]);
-			st(T3, r + OTG3_BRAKE + 9 + k, B, b, p.brake.p[k]);
-		}
-		UNROLL for (int k = 0; k < 7; k++) st(T3, r + OTG3_TSUM + k, B, b, p.t_sum[k]), st(T3, r + OTG3_J + k, B, b, p.j[k]);
-		UNROLL for (int k = 0; k < 8; k++) st(T3, r + OTG3_A + k, B, b, p.a[k]), st(T3, r + OTG3_V + k, B, b, p.v[k]), st(T3, r + OTG3_P + k, B, b, p.p[k]);
-	}
-	real R[9], w[3], al[3];
-	if (cart) {
-		real local[9];
-		otg::vec_to_rot(gget(g.np, 3), gget(g.np, 4), gget(g.np, 5), local);
-		otg::mat3_mul(g.ref, local, R);
-		otg::mat3_vec(g.ref, gget(g.nv, 3), gget(g.nv, 4), gget(g.nv, 5), w);
-		otg::mat3_vec(g.ref, gget(g.na, 3), gget(g.na, 4), gget(g.na, 5), al);
-	}
-	if (j == 0) {
-		st(S, OTG_TIME, B, b, g.time);
-		if (g.replanned) st(S, OTG_DURATION, B, b, g.duration);
-		st(S, OTG_GOAL_REACHED, B, b, (double)g.goal_reached);
-		st(S, OTG_RESULT, B, b, (double)g.result);
-		st(S, OTG_TARGET_SET, B, b, (double)g.target_set);
-		st(S, OTG_CI_INIT, B, b, (double)g.ci_init);
-		st(S, OTG_CI_EPOCH, B, b, g.ci_epoch);
-		st(S, OTG_IN_SYNC, B, b, 0.0);
-		if (cart) {
-			UNROLL for (int i = 0; i < 9; i++) st(S, OTG_CART + i, B, b, g.ref[i]), st(S, OTG_CART + 9 + i, B, b, g.goal_R[i]);
-			UNROLL for (int i = 0; i < 3; i++) st(S, OTG_CART + 18 + i, B, b, g.goal_w[i]);
-			UNROLL for (int k = 0; k < 9; k++) st(t.otg_desired, 3 + k, B, b, R[k]);
-			UNROLL for (int k = 0; k < 3; k++) st(t.otg_desired, 15 + k, B, b, w[k]), st(t.otg_desired, 21 + k, B, b, al[k]);
-		}
-	}
-	if (cart) {
-		if (j < 3) st(t.otg_desired, j, B, b, g.np), st(t.otg_desired, 12 + j, B, b, g.nv), st(t.otg_desired, 18 + j, B, b, g.na);
-	} else if (active && !t.otg_out_is_desired) {
-		st(t.otg_desired, j, B, b, g.np), st(t.otg_desired, n + j, B, b, g.nv), st(t.otg_desired, 2 * n + j, B, b, g.na);
-	}
-}
-
-// PLAN for a JERK-LIMITED generator, one lane per robot (kept as the A/B partner of plan_group3: SAI2B_OTG3_ONE_LANE=1): setGoal...(goal); update(); with ruckig's third-order
+// PLAN for a JERK-LIMITED generator, one lane per robot (kept as the A/B partner of plan_group<LaneGen3>: SAI2B_OTG3_ONE_LANE=1): setGoal...(goal); update(); with ruckig's third-order
 // interface (sai2b_otg3_core.hpp), DoF after DoF out of this lane's scratch memory. The wrapper state travels through
 // the same rows as for the acceleration-limited generator (load_head / load_body / store_state); only the stored
 // trajectory differs (otg3_traj).
@@ -595,20 +528,8 @@ __device__ __noinline__ void plan_lane3(const DevTask& t, bool cart, int n, int 
 		otg::joints_update(g3, n, t.dt, t.otg_vmax, t.otg_amax, t.otg_epoch);
 	}
 	if (g3.replanned) {
-		real* T3 = t.otg3_traj;
 		st(S, OTG_DURATION, B, b, g3.traj.duration);
-		for (int d = 0; d < n; d++) {
-			const otg3::Prof& p = g3.traj.prof[d];
-			const int r = d * OTG3_STRIDE;
-			st(T3, r + OTG3_BRAKE, B, b, p.brake.duration);
-			for (int k = 0; k < 2; k++) {
-				st(T3, r + OTG3_BRAKE + 1 + k, B, b, p.brake.t[k]), st(T3, r + OTG3_BRAKE + 3 + k, B, b, p.brake.j[k]);
-				st(T3, r + OTG3_BRAKE + 5 + k, B, b, p.brake.a[k]), st(T3, r + OTG3_BRAKE + 7 + k, B, b, p.brake.v[k]);
-				st(T3, r + OTG3_BRAKE + 9 + k, B, b, p.brake.p[k]);
-			}
-			for (int k = 0; k < 7; k++) st(T3, r + OTG3_TSUM + k, B, b, p.t_sum[k]), st(T3, r + OTG3_J + k, B, b, p.j[k]);
-			for (int k = 0; k < 8; k++) st(T3, r + OTG3_A + k, B, b, p.a[k]), st(T3, r + OTG3_V + k, B, b, p.v[k]), st(T3, r + OTG3_P + k, B, b, p.p[k]);
-		}
+		for (int d = 0; d < n; d++) store_prof3(t.otg3_traj, d * OTG3_STRIDE, B, b, g3.traj.prof[d]);
 	}
 	{
 		Gen g;
@@ -696,7 +617,7 @@ __global__ __launch_bounds__(64) void otg_plan_kernel(const DevParams* __restric
 			const int e = e0 + threadIdx.x / otgg::G;
 			if (e >= cnt) continue;	 // uniform over the group
 			const int b = ((const gint*)list)[(size_t)t * B + e];
-			plan_group(tk, tk.type == SAI2B_MOTION_FORCE_TASK, tk.otg_n, B, b);
+			plan_group<otgg::LaneGen>(tk, tk.type == SAI2B_MOTION_FORCE_TASK, tk.otg_n, B, b);
 		}
 	}
 }
@@ -727,7 +648,7 @@ __global__ __launch_bounds__(64) void otg3_plan_kernel(const DevParams* __restri
 				const int e = e0 + threadIdx.x / otgg::G;
 				if (e >= cnt) continue;	 // uniform over the group
 				const int b = ((const gint*)list)[(size_t)t * B + e];
-				plan_group3(tk, tk.type == SAI2B_MOTION_FORCE_TASK, tk.otg_n, B, b);
+				plan_group<otgg::LaneGen3>(tk, tk.type == SAI2B_MOTION_FORCE_TASK, tk.otg_n, B, b);
 			}
 		}
 	}
@@ -789,8 +710,8 @@ __global__ __launch_bounds__(64) void otg_reinit_kernel(const DevParams* __restr
 			if (mode == 1) {
 				det_frame_pose(P.model, tk, q, x, R);
 			} else {
-				UNROLL for (int k = 0; k < 3; k++) x[k] = ld(tk.goals, k, B, b);
-				UNROLL for (int k = 0; k < 9; k++) R[k] = ld(tk.goals, 3 + k, B, b);
+				UNROLL for (int k = 0; k < 3; k++) x[k] = ld(tk.goals, MFT_GOAL_POS + k, B, b);
+				UNROLL for (int k = 0; k < 9; k++) R[k] = ld(tk.goals, MFT_GOAL_ROT + k, B, b);
 			}
 			if (!constructed) {	 // OTG_6dof_cartesian.cpp:41
 				UNROLL for (int i = 0; i < 9; i++) g.ref[i] = R[i];
@@ -828,17 +749,17 @@ __global__ __launch_bounds__(64) void mft_reparam_kernel(const DevParams* __rest
 		load_body(S, 6, true, B, b, g);
 		if (flags & 1) {
 			UNROLL for (int k = 0; k < 3; k++) {
-				st(tk.goals, k, B, b, x[k]);
-				st(tk.goals, 12 + k, B, b, 0.0);
-				st(tk.goals, 18 + k, B, b, 0.0);
+				st(tk.goals, MFT_GOAL_POS + k, B, b, x[k]);
+				st(tk.goals, MFT_GOAL_LIN_VEL + k, B, b, 0.0);
+				st(tk.goals, MFT_GOAL_LIN_ACC + k, B, b, 0.0);
 			}
 			otg::cart_reinitialize_linear(g, x);
 		}
 		if (flags & 2) {
-			UNROLL for (int k = 0; k < 9; k++) st(tk.goals, 3 + k, B, b, R[k]);
+			UNROLL for (int k = 0; k < 9; k++) st(tk.goals, MFT_GOAL_ROT + k, B, b, R[k]);
 			UNROLL for (int k = 0; k < 3; k++) {
-				st(tk.goals, 15 + k, B, b, 0.0);
-				st(tk.goals, 21 + k, B, b, 0.0);
+				st(tk.goals, MFT_GOAL_ANG_VEL + k, B, b, 0.0);
+				st(tk.goals, MFT_GOAL_ANG_ACC + k, B, b, 0.0);
 			}
 			otg::cart_reinitialize_angular(g, R);
 		}

@@ -10,6 +10,10 @@
 // shuffles and ballots. Per-DoF arithmetic is sai2b_otg_core.hpp's (the host-tested code); the sums
 // over DoFs are taken in DoF order, like the sequential form.
 //
+// Both orders share everything here but the per-DoF planner calls: the acceleration-limited generator (LaneGen,
+// calculate) and the jerk-limited one (LaneGen3, calculate3; the per-DoF planner is sai2b_otg3_core.hpp's, the code
+// whose host build is bit-equal to the reference's ruckig).
+//
 // A wavefront holds 8 groups. Conditions that are uniform over a group may diverge between groups;
 // every shuffle below reads lanes of the caller's own group, which take the same branch.
 #pragma once
@@ -51,18 +55,107 @@ DI bool gapprox(double a, double b, int lo, int hi, double prec) {
 	return dd <= prec * prec * (na < nb ? na : nb);
 }
 
-// one lane's share of a generator (struct Gen of sai2b_otg_core.hpp, one DoF) + the group-uniform part
-struct LaneGen {
+// one lane's share of a generator's wrapper (struct Gen of sai2b_otg_core.hpp, one DoF) + the group-uniform part
+struct LaneState {
 	double in_cp, in_cv, in_ca, in_tp, in_tv;
 	double ci_cp, ci_cv, ci_ca, ci_tp, ci_tv;
 	double np, nv, na;
-	Dof f;
-	Prof p;
 	// uniform over the group
 	double time, duration, ci_epoch;
 	int goal_reached, result, target_set, ci_init, replanned;
 	double ref[9], goal_R[9], goal_w[3];  // Cartesian wrapper
 };
+// ... and the lane's DoF of the stored trajectory
+struct LaneGen : LaneState {
+	Dof f;
+	Prof p;
+};
+struct LaneGen3 : LaneState {
+	otg3::Prof p;
+	double jmax;
+};
+
+// synchronize (calculator_target.hpp:120-222): every lane sees all candidates (t_min, ends of the blocked intervals)
+// and whether any DoF blocks them; the choice is then made redundantly. False: no candidate is left. Else the limiting
+// DoF, which profile of its block it keeps (0 pmin, 1 aprof, 2 bprof) and the duration.
+template <class Blk> DI bool select_duration(const Blk& bl, bool active, int n, int& limiting, int& best_q, double& duration) {
+	using otg::is_blocked;
+	using otg3::is_blocked;
+	const double c0 = active ? bl.tmin : INFINITY, c1 = (active && bl.a) ? bl.aright : INFINITY,
+				 c2 = (active && bl.b) ? bl.bright : INFINITY;
+	const bool any_interval = gany(active && (bl.a || bl.b));
+	double cand[3][G];
+	UNROLL for (int d = 0; d < G; d++) {
+		cand[0][d] = gget(c0, d);
+		cand[1][d] = gget(c1, d);
+		cand[2][d] = gget(c2, d);
+	}
+	int blocked = 0;
+	UNROLL for (int q = 0; q < 3; q++)
+		UNROLL for (int d = 0; d < G; d++)
+			if (active && is_blocked(bl, cand[q][d])) blocked |= 1 << (q * G + d);
+	blocked = gor(blocked);
+	int best_rank = 1 << 20, best_d = -1;
+	best_q = -1;
+	UNROLL for (int q = 0; q < 3; q++)
+		UNROLL for (int d = 0; d < G; d++) {
+			if (d >= n || (!any_interval && q > 0)) continue;
+			const double t = cand[q][d];
+			int rank = 0;  // position in the reference's stably sorted index array (index = q*n + d)
+			UNROLL for (int oq = 0; oq < 3; oq++)
+				UNROLL for (int od = 0; od < G; od++) {
+					if (od >= n || (!any_interval && oq > 0)) continue;
+					const bool before = (oq < q) || (oq == q && od < d);
+					if (cand[oq][od] < t || (cand[oq][od] == t && before)) rank++;
+				}
+			if (rank < n - 1 || rank >= best_rank) continue;
+			if (((blocked >> (q * G + d)) & 1) || t < 0.0 || isinf(t)) continue;
+			best_rank = rank, best_q = q, best_d = d;
+		}
+	if (best_d < 0) return false;
+	limiting = best_d;
+	double t = 0;
+	UNROLL for (int q = 0; q < 3; q++)
+		UNROLL for (int d = 0; d < G; d++)
+			if (q == best_q && d == best_d) t = cand[q][d];
+	duration = t;
+	return true;
+}
+
+// The collinearity test of the phase synchronisation (calculator_target.hpp:46-118). True: the DoFs' states are
+// multiples of one another, and npc is this lane's control: the limiting DoF's (`control` = amax or jmax, signed by
+// the direction of its profile) scaled like the lane's state.
+DI bool collinear_control(bool active, int limiting, double cp, double cv, double ca, double tp, double tv, double control, bool limiting_up,
+						  double& npc) {
+	const double pd = tp - cp;
+	int which = -1;
+	if (active) {
+		if (fabs(pd) > otg::EPS)
+			which = 0;
+		else if (fabs(cv) > otg::EPS)
+			which = 1;
+		else if (fabs(ca) > otg::EPS)
+			which = 2;
+		else if (fabs(tv) > otg::EPS)
+			which = 3;
+	}
+	const unsigned has = gbits(which >= 0);
+	if (!has) return false;
+	const int scale_dof = __ffs((int)has) - 1;
+	const int w = ggeti(which, scale_dof);
+	const double sv = w == 0 ? pd : w == 1 ? cv : w == 2 ? ca : tv;
+	const double scale = gget(sv, scale_dof);
+	const double pd_scale = gget(pd, scale_dof) / scale, v0_scale = gget(cv, scale_dof) / scale, vf_scale = gget(tv, scale_dof) / scale,
+				 a0_scale = gget(ca, scale_dof) / scale, af_scale = 0.0 / scale;
+	const double scale_limiting = gget(sv, limiting);
+	const double control_lim = gget(control, limiting);
+	const double control_limiting = limiting_up ? control_lim : -control_lim;
+	const bool off = active && (fabs(pd - pd_scale * sv) > otg::EPS || fabs(cv - v0_scale * sv) > otg::EPS || fabs(ca - a0_scale * sv) > otg::EPS ||
+								fabs(tv - vf_scale * sv) > otg::EPS || fabs(0.0 - af_scale * sv) > otg::EPS);
+	if (gany(off)) return false;
+	npc = control_limiting * sv / scale_limiting;
+	return true;
+}
 
 // TargetCalculator::calculate (calculator_target.hpp:249-532), one DoF per lane. Returns the Result;
 // on WORKING f, p and duration hold the new trajectory.
@@ -101,47 +194,8 @@ DI int calculate(bool active, int n, double cp, double cv, double ca, double tp,
 		return otg::WORKING;
 	}
 
-	// synchronize (calculator_target.hpp:120-222): every lane sees all candidates (t_min, ends of the
-	// blocked intervals) and whether any DoF blocks them; the choice is then made redundantly
-	const double c0 = active ? bl.tmin : INFINITY, c1 = (active && bl.a) ? bl.aright : INFINITY,
-				 c2 = (active && bl.b) ? bl.bright : INFINITY;
-	const bool any_interval = gany(active && (bl.a || bl.b));
-	double cand[3][G];
-	UNROLL for (int d = 0; d < G; d++) {
-		cand[0][d] = gget(c0, d);
-		cand[1][d] = gget(c1, d);
-		cand[2][d] = gget(c2, d);
-	}
-	int blocked = 0;
-	UNROLL for (int q = 0; q < 3; q++)
-		UNROLL for (int d = 0; d < G; d++)
-			if (active && otg::is_blocked(bl, cand[q][d])) blocked |= 1 << (q * G + d);
-	blocked = gor(blocked);
-	int best_rank = 1 << 20, best_q = -1, best_d = -1;
-	UNROLL for (int q = 0; q < 3; q++)
-		UNROLL for (int d = 0; d < G; d++) {
-			if (d >= n || (!any_interval && q > 0)) continue;
-			const double t = cand[q][d];
-			int rank = 0;  // position in the reference's stably sorted index array (index = q*n + d)
-			UNROLL for (int oq = 0; oq < 3; oq++)
-				UNROLL for (int od = 0; od < G; od++) {
-					if (od >= n || (!any_interval && oq > 0)) continue;
-					const bool before = (oq < q) || (oq == q && od < d);
-					if (cand[oq][od] < t || (cand[oq][od] == t && before)) rank++;
-				}
-			if (rank < n - 1 || rank >= best_rank) continue;
-			if (((blocked >> (q * G + d)) & 1) || t < 0.0 || isinf(t)) continue;
-			best_rank = rank, best_q = q, best_d = d;
-		}
-	if (best_d < 0) return otg::ERR_SYNCHRONIZATION;
-	const int limiting = best_d;
-	{
-		double t = 0;
-		UNROLL for (int q = 0; q < 3; q++)
-			UNROLL for (int d = 0; d < G; d++)
-				if (q == best_q && d == best_d) t = cand[q][d];
-		duration = t;
-	}
+	int limiting, best_q;
+	if (!select_duration(bl, active, n, limiting, best_q, duration)) return otg::ERR_SYNCHRONIZATION;
 	if (j == limiting) p = best_q == 0 ? bl.pmin : best_q == 1 ? bl.aprof : bl.bprof;
 	if (duration > 7.6e3) return otg::ERR_TRAJECTORY_DURATION;
 	if (duration == 0.0) {
@@ -149,48 +203,21 @@ DI int calculate(bool active, int n, double cp, double cv, double ca, double tp,
 		return otg::WORKING;
 	}
 
-	// phase synchronisation (calculator_target.hpp:398-467), collinearity test :46-118
+	// phase synchronisation (calculator_target.hpp:398-467)
 	{
 		const double pl_t0 = gget(p.t0, limiting), pl_t1 = gget(p.t1, limiting), pl_t2 = gget(p.t2, limiting),
 					 pl_t6 = gget(p.t6, limiting);
 		const int pl_dir = ggeti(p.dir, limiting);
-		const double pd = tp - cp;
-		int which = -1;
-		if (active) {
-			if (fabs(pd) > otg::EPS)
-				which = 0;
-			else if (fabs(cv) > otg::EPS)
-				which = 1;
-			else if (fabs(ca) > otg::EPS)
-				which = 2;
-			else if (fabs(tv) > otg::EPS)
-				which = 3;
-		}
-		const unsigned has = gbits(which >= 0);
-		if (has) {
-			const int scale_dof = __ffs((int)has) - 1;
-			const int w = ggeti(which, scale_dof);
-			const double sv = w == 0 ? pd : w == 1 ? cv : w == 2 ? ca : tv;
-			const double scale = gget(sv, scale_dof);
-			const double pd_scale = gget(pd, scale_dof) / scale, v0_scale = gget(cv, scale_dof) / scale,
-						 vf_scale = gget(tv, scale_dof) / scale, a0_scale = gget(ca, scale_dof) / scale, af_scale = 0.0 / scale;
-			const double scale_limiting = gget(sv, limiting);
-			const double amax_lim = gget(amax, limiting);
-			const double control_limiting = (pl_dir == 0) ? amax_lim : -amax_lim;
-			const bool off = active && (fabs(pd - pd_scale * sv) > otg::EPS || fabs(cv - v0_scale * sv) > otg::EPS ||
-										fabs(ca - a0_scale * sv) > otg::EPS || fabs(tv - vf_scale * sv) > otg::EPS ||
-										fabs(0.0 - af_scale * sv) > otg::EPS);
-			if (!gany(off)) {
-				const double npc = control_limiting * sv / scale_limiting;
-				bool lane_ok = true;
-				if (active && j != limiting) {
-					p.t0 = pl_t0, p.t1 = pl_t1, p.t2 = pl_t2, p.t6 = pl_t6;
-					const double aUp = npc, aDown = -npc, aMax = amax, aMin = -amax;
-					const bool within = (aMin - 1e-12 < aUp) && (aUp < aMax + 1e-12) && (aMin - 1e-12 < aDown) && (aDown < aMax + 1e-12);
-					lane_ok = within && otg::check(p, f, aUp, aDown, vmax, -vmax);
-				}
-				if (!gany(!lane_ok)) return otg::WORKING;
+		double npc;
+		if (collinear_control(active, limiting, cp, cv, ca, tp, tv, amax, pl_dir == 0, npc)) {
+			bool lane_ok = true;
+			if (active && j != limiting) {
+				p.t0 = pl_t0, p.t1 = pl_t1, p.t2 = pl_t2, p.t6 = pl_t6;
+				const double aUp = npc, aDown = -npc, aMax = amax, aMin = -amax;
+				const bool within = (aMin - 1e-12 < aUp) && (aUp < aMax + 1e-12) && (aMin - 1e-12 < aDown) && (aDown < aMax + 1e-12);
+				lane_ok = within && otg::check(p, f, aUp, aDown, vmax, -vmax);
 			}
+			if (!gany(!lane_ok)) return otg::WORKING;
 		}
 	}
 
@@ -210,21 +237,6 @@ DI int calculate(bool active, int n, double cp, double cv, double ca, double tp,
 	}
 	return gany(bad) ? otg::ERR_SYNCHRONIZATION : otg::WORKING;
 }
-
-// ---- the jerk-limited generator, one DoF per lane (round 3): the per-DoF planner is sai2b_otg3_core.hpp's (brake, step 1,
-// step 2, check, sampling: the code whose host build is bit-equal to the reference's ruckig), the couplings between the
-// DoFs are the same shuffles and ballots as above on the third-order profile ----
-struct LaneGen3 {
-	double in_cp, in_cv, in_ca, in_tp, in_tv;
-	double ci_cp, ci_cv, ci_ca, ci_tp, ci_tv;
-	double np, nv, na;
-	otg3::Prof p;
-	double jmax;
-	// uniform over the group
-	double time, duration, ci_epoch;
-	int goal_reached, result, target_set, ci_init, replanned;
-	double ref[9], goal_R[9], goal_w[3];
-};
 
 // TargetCalculator::calculate (calculator_target.hpp:236-532) for finite max_jerk, one DoF per lane
 __device__ __noinline__ int calculate3(bool active, int n, double cp, double cv, double ca, double tp, double tv, double vmax, double amax,
@@ -246,97 +258,33 @@ __device__ __noinline__ int calculate3(bool active, int n, double cp, double cv,
 		if (j == 0) p = bl.pmin;
 		return otg::WORKING;
 	}
-	// synchronize (calculator_target.hpp:120-222), as in calculate() above
-	const double c0 = active ? bl.tmin : INFINITY, c1 = (active && bl.a) ? bl.aright : INFINITY, c2 = (active && bl.b) ? bl.bright : INFINITY;
-	const bool any_interval = gany(active && (bl.a || bl.b));
-	double cand[3][G];
-	UNROLL for (int d = 0; d < G; d++) {
-		cand[0][d] = gget(c0, d);
-		cand[1][d] = gget(c1, d);
-		cand[2][d] = gget(c2, d);
-	}
-	int blocked = 0;
-	UNROLL for (int q = 0; q < 3; q++)
-		UNROLL for (int d = 0; d < G; d++)
-			if (active && otg3::is_blocked(bl, cand[q][d])) blocked |= 1 << (q * G + d);
-	blocked = gor(blocked);
-	int best_rank = 1 << 20, best_q = -1, best_d = -1;
-	UNROLL for (int q = 0; q < 3; q++)
-		UNROLL for (int d = 0; d < G; d++) {
-			if (d >= n || (!any_interval && q > 0)) continue;
-			const double t = cand[q][d];
-			int rank = 0;
-			UNROLL for (int oq = 0; oq < 3; oq++)
-				UNROLL for (int od = 0; od < G; od++) {
-					if (od >= n || (!any_interval && oq > 0)) continue;
-					const bool before = (oq < q) || (oq == q && od < d);
-					if (cand[oq][od] < t || (cand[oq][od] == t && before)) rank++;
-				}
-			if (rank < n - 1 || rank >= best_rank) continue;
-			if (((blocked >> (q * G + d)) & 1) || t < 0.0 || isinf(t)) continue;
-			best_rank = rank, best_q = q, best_d = d;
-		}
-	if (best_d < 0) return otg::ERR_SYNCHRONIZATION;
-	const int limiting = best_d;
-	{
-		double t = 0;
-		UNROLL for (int q = 0; q < 3; q++)
-			UNROLL for (int d = 0; d < G; d++)
-				if (q == best_q && d == best_d) t = cand[q][d];
-		duration = t;
-	}
+	int limiting, best_q;
+	if (!select_duration(bl, active, n, limiting, best_q, duration)) return otg::ERR_SYNCHRONIZATION;
 	if (j == limiting) p = best_q == 0 ? bl.pmin : best_q == 1 ? bl.aprof : bl.bprof;
 	if (duration > 7.6e3) return otg::ERR_TRAJECTORY_DURATION;
 	if (duration == 0.0) {
 		if (active) p = bl.pmin;
 		return otg::WORKING;
 	}
-	// phase synchronisation (calculator_target.hpp:398-467), collinearity test :46-118 with the jerk as control
+	// phase synchronisation (calculator_target.hpp:398-467), with the jerk as control
 	{
 		double plt[7];
 		UNROLL for (int i = 0; i < 7; i++) plt[i] = gget(p.t[i], limiting);
 		const int pl_dir = ggeti(p.direction, limiting), pl_cs = ggeti(p.control_signs, limiting), pl_lim = ggeti(p.limits, limiting);
-		const double pd = tp - cp;
-		int which = -1;
-		if (active) {
-			if (fabs(pd) > otg::EPS)
-				which = 0;
-			else if (fabs(cv) > otg::EPS)
-				which = 1;
-			else if (fabs(ca) > otg::EPS)
-				which = 2;
-			else if (fabs(tv) > otg::EPS)
-				which = 3;
-		}
-		const unsigned has = gbits(which >= 0);
-		if (has) {
-			const int scale_dof = __ffs((int)has) - 1;
-			const int w = ggeti(which, scale_dof);
-			const double sv = w == 0 ? pd : w == 1 ? cv : w == 2 ? ca : tv;
-			const double scale = gget(sv, scale_dof);
-			const double pd_scale = gget(pd, scale_dof) / scale, v0_scale = gget(cv, scale_dof) / scale,
-						 vf_scale = gget(tv, scale_dof) / scale, a0_scale = gget(ca, scale_dof) / scale, af_scale = 0.0 / scale;
-			const double scale_limiting = gget(sv, limiting);
-			const double jmax_lim = gget(jmax, limiting);
-			const double control_limiting = (pl_dir == otg3::UP) ? jmax_lim : -jmax_lim;
-			const bool off = active && (fabs(pd - pd_scale * sv) > otg::EPS || fabs(cv - v0_scale * sv) > otg::EPS ||
-										fabs(ca - a0_scale * sv) > otg::EPS || fabs(tv - vf_scale * sv) > otg::EPS ||
-										fabs(0.0 - af_scale * sv) > otg::EPS);
-			if (!gany(off)) {
-				const double npc = control_limiting * sv / scale_limiting;
-				bool lane_ok = true;
-				if (active && j != limiting) {
-					const double t_profile = duration - p.brake.duration - 0.0;
-					UNROLL for (int i = 0; i < 7; i++) p.t[i] = plt[i];
-					p.control_signs = pl_cs;
-					if (pl_cs == otg3::UDDU)
-						lane_ok = otg3::check_tj<otg3::UDDU, otg3::L_NONE>(p, t_profile, npc, vmax, -vmax, amax, -amax, jmax);
-					else
-						lane_ok = otg3::check_tj<otg3::UDUD, otg3::L_NONE>(p, t_profile, npc, vmax, -vmax, amax, -amax, jmax);
-					p.limits = pl_lim;
-				}
-				if (!gany(!lane_ok)) return otg::WORKING;
+		double npc;
+		if (collinear_control(active, limiting, cp, cv, ca, tp, tv, jmax, pl_dir == otg3::UP, npc)) {
+			bool lane_ok = true;
+			if (active && j != limiting) {
+				const double t_profile = duration - p.brake.duration - 0.0;
+				UNROLL for (int i = 0; i < 7; i++) p.t[i] = plt[i];
+				p.control_signs = pl_cs;
+				if (pl_cs == otg3::UDDU)
+					lane_ok = otg3::check_tj<otg3::UDDU, otg3::L_NONE>(p, t_profile, npc, vmax, -vmax, amax, -amax, jmax);
+				else
+					lane_ok = otg3::check_tj<otg3::UDUD, otg3::L_NONE>(p, t_profile, npc, vmax, -vmax, amax, -amax, jmax);
+				p.limits = pl_lim;
 			}
+			if (!gany(!lane_ok)) return otg::WORKING;
 		}
 	}
 	// time synchronisation (calculator_target.hpp:469-529)
@@ -356,7 +304,8 @@ __device__ __noinline__ int calculate3(bool active, int n, double cp, double cv,
 	return gany(bad) ? otg::ERR_SYNCHRONIZATION : otg::WORKING;
 }
 
-// Ruckig::update (ruckig.hpp:180-216), jerk-limited
+// Ruckig::update (ruckig.hpp:180-216), jerk-limited (two overloads, not one template over the lane state: merged,
+// otg3_plan_kernel<false> needs 16 B more scratch)
 DI int ruckig_update(LaneGen3& g, bool active, int n, double dt, double vmax, double amax, double epoch) {
 	int result = otg::WORKING;
 	g.replanned = 0;

@@ -105,6 +105,12 @@ struct DevTask {
 
 constexpr int MFT_GOAL_ROWS = 30;
 constexpr int MFT_MOTION_GOAL_ROWS = 24;  // pos rot v w a alpha: the rows the OTG replaces
+// rows of a MotionForceTask's goals (and of otg_desired, which has their layout)
+constexpr int MFT_GOAL_POS = 0, MFT_GOAL_ROT = 3, MFT_GOAL_LIN_VEL = 12, MFT_GOAL_ANG_VEL = 15, MFT_GOAL_LIN_ACC = 18, MFT_GOAL_ANG_ACC = 21,
+			  MFT_GOAL_FORCE = 24, MFT_GOAL_MOMENT = 27;
+static_assert(MFT_GOAL_ANG_ACC + 3 == MFT_MOTION_GOAL_ROWS && MFT_MOTION_GOAL_ROWS == 24 && MFT_GOAL_FORCE == MFT_MOTION_GOAL_ROWS &&
+				  MFT_GOAL_MOMENT + 3 == MFT_GOAL_ROWS && MFT_GOAL_ROWS == 30,
+			  "goal rows of a MotionForceTask");
 // rows of otg_state (one OTG_joints / OTG_6dof_cartesian object per robot; sai2b_otg_core.hpp: Gen)
 constexpr int OTG_IN = 0;	  // wrapper _input: cp cv ca tp tv, OTG_MD rows each
 constexpr int OTG_CI = 5 * OTG_MD;	  // Ruckig current_input: cp cv ca tp tv
@@ -120,6 +126,7 @@ constexpr int OTG_TRAJ_STRIDE = 13;
 // brake duration, t[2], j[2], a[2], v[2], p[2]; t_sum[7]; j[7]; a[8]; v[8]; p[8]
 constexpr int OTG3_BRAKE = 0, OTG3_TSUM = 11, OTG3_J = 18, OTG3_A = 25, OTG3_V = 33, OTG3_P = 41, OTG3_STRIDE = 49;
 constexpr int OTG_CART = OTG_TRAJ + OTG_MD * OTG_TRAJ_STRIDE;  // reference frame 9, goal orientation 9, goal angular velocity 3
+constexpr int OTG_CART_REF = OTG_CART, OTG_CART_GOAL_R = OTG_CART + 9, OTG_CART_GOAL_W = OTG_CART + 18;
 constexpr int OTG_IN_SYNC = OTG_CART + 21;
 constexpr int OTG_ACTIVE = OTG_CART + 22;  // gated JointTask only: 1 = the task has a non-empty range this tick
 constexpr int OTG_ROWS = OTG_CART + 23;
