@@ -62,6 +62,14 @@ inline void check(sai2b_ctx* ctx, int rc) {
 	if (rc == SAI2B_INVALID_ARGUMENT) throw std::invalid_argument(msg);
 	throw std::runtime_error(msg);
 }
+// what the masked calls (reinitializeTasks(mask), reInitializeTask(mask), resetRobots) check ahead of the device: a mask entry
+// per robot, q and dq [dof][B] or empty
+inline void checkResetArguments(const int dof, const size_t B, const std::vector<unsigned char>& mask, const Batch& q, const Batch& dq,
+								const char* fn) {
+	if (mask.size() != B) throw std::invalid_argument(std::string(fn) + ": mask must have one entry per robot");
+	if ((!q.empty() && q.size() != (size_t)dof * B) || (!dq.empty() && dq.size() != (size_t)dof * B))
+		throw std::invalid_argument(std::string(fn) + ": q and dq must be [dof][B] (or empty)");
+}
 }  // namespace detail
 
 class RobotController;
@@ -242,6 +250,11 @@ public:
 		return tau;
 	}
 	void reInitializeTask() { detail::check(ctx(), sai2b_task_reinitialize(ctx(), index())); }  // TemplateTask.h:65
+	// the same for the robots with mask[b] != 0 only ([B] bytes); the others are not touched
+	void reInitializeTask(const std::vector<unsigned char>& mask) {
+		detail::checkResetArguments(_robot->dof(), (size_t)B(), mask, {}, {}, "reInitializeTask");
+		detail::check(ctx(), sai2b_reinitialize_robots(ctx(), index(), mask.data(), 0));
+	}
 	Batch getTaskNullspace() const { return nullspace(0); }			  // TemplateTask.h:73
 	Batch getPreviousTasksNullspace() const { return nullspace(1); }  // TemplateTask.h:81
 	const std::shared_ptr<BatchedRobotModel>& getConstRobotModel() const { return _robot; }
@@ -974,6 +987,18 @@ public:
 	}
 	void enableIntrospection(const bool on = true) { detail::check(_ctx, sai2b_enable_introspection(_ctx, on)); }
 	void reinitializeTasks() { detail::check(_ctx, sai2b_reinitialize(_ctx)); }
+	// the same for the robots with mask[b] != 0 only ([B] bytes); the others are not touched
+	void reinitializeTasks(const std::vector<unsigned char>& mask) {
+		detail::checkResetArguments(_robot->dof(), (size_t)_robot->batch(), mask, {}, {}, "reinitializeTasks");
+		detail::check(_ctx, sai2b_reinitialize_robots(_ctx, -1, mask.data(), 0));
+	}
+	// Episode reset of the robots with mask[b] != 0 (sai2b.h: sai2b_reset_robots): the selected columns of q, dq ([dof][B]
+	// each, empty = keep) become their state, their tasks and passivity observers are re-initialised, their stored
+	// torques zeroed. The device state is what changes: the robot model's host copy is not written.
+	void resetRobots(const std::vector<unsigned char>& mask, const Batch& q, const Batch& dq = {}) {
+		detail::checkResetArguments(_robot->dof(), (size_t)_robot->batch(), mask, q, dq, "resetRobots");
+		detail::check(_ctx, sai2b_reset_robots(_ctx, mask.data(), q.empty() ? nullptr : q.data(), dq.empty() ? nullptr : dq.data(), 0));
+	}
 	std::shared_ptr<JointTask> getJointTaskByName(const std::string& task_name) {
 		for (auto& task : _tasks)
 			if (task->getTaskName() == task_name) {
@@ -1116,6 +1141,21 @@ public:
 		});
 	}
 	void reinitializeTasks() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_reinitialize(sh.ctx)); }); }
+	// reinitializeTasks / one task's reInitializeTask / the episode reset for the robots with mask[b] != 0 only
+	// ([B_total] bytes; q, dq [dof][B_total], empty = keep): each shard gets the entries and columns of its robots
+	void reinitializeTasks(const std::vector<unsigned char>& mask) { reInitializeTask(-1, mask); }
+	void reInitializeTask(const int task, const std::vector<unsigned char>& mask) {
+		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "reInitializeTask");
+		if (task < -1 || task >= (int)_cfgs.size()) throw std::invalid_argument("reInitializeTask: no such task");
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_reinitialize_robots(sh.ctx, task, mask.data() + sh.lo, 0)); });
+	}
+	void resetRobots(const std::vector<unsigned char>& mask, const Batch& q, const Batch& dq = {}) {
+		detail::checkResetArguments(_dof, (size_t)_total, mask, q, dq, "resetRobots");
+		forAll([&](Shard& sh) {
+			const Batch qs = slice(q, _dof, sh), dqs = slice(dq, _dof, sh);
+			detail::check(sh.ctx, sai2b_reset_robots(sh.ctx, mask.data() + sh.lo, ptr(qs), ptr(dqs), 0));
+		});
+	}
 	void enableGravityCompensation(const bool on) {
 		forAll([on](Shard& sh) { detail::check(sh.ctx, sai2b_enable_gravity_compensation(sh.ctx, on)); });
 	}

@@ -299,6 +299,20 @@ int sai2b_set_jt_goals(sai2b_ctx* ctx, int task, const double* q_goal, const dou
  * integrators and singularity history cleared. */
 int sai2b_reinitialize(sai2b_ctx* ctx);
 
+/* The same for the robots with mask[b] != 0 only; the others are not touched (every buffer column stays bit-equal, and so
+ * does every later tick). task = -1: every task (RobotController::reinitializeTasks), else that one
+ * (TemplateTask::reInitializeTask). mask: [B] bytes, host, or device when on_device != 0 (then the call is ordered on the
+ * ctx stream under the stream contract below and does not synchronise). One launch, whatever the mask selects. */
+int sai2b_reinitialize_robots(sai2b_ctx* ctx, int task, const unsigned char* mask, int on_device);
+/* Episode reset of the robots with mask[b] != 0: their columns of q and dq ([dof][B], only the selected columns are
+ * read; either may be NULL = keep) become the state, then every task is re-initialised for them as above. Two things
+ * beyond that are this library's definition (the reference has no batch, and its reInitializeTask leaves the observer
+ * alone): the selected robots' passivity observers, where a task has one, are re-initialised
+ * (POPCExplicitForceControl.cpp:10-22), and their columns of SAI2B_BUF_TAU are zeroed, so that a simulation step on the
+ * stored torques does not push a fresh robot with its old episode's. Payload rows, contact rows and the contact-state
+ * outputs are kept for every robot (environment, not episode). All pointers host, or all device (on_device). */
+int sai2b_reset_robots(sai2b_ctx* ctx, const unsigned char* mask, const double* q, const double* dq, int on_device);
+
 /* RobotController::updateControllerTaskModels (RobotController.cpp:53-60) */
 int sai2b_update_task_models(sai2b_ctx* ctx);
 /* RobotController::computeControlTorques (RobotController.cpp:62-74). tau: [7][B]; may be NULL

@@ -216,6 +216,8 @@ EXPORTS = [
     "sai2b_set_mft_sensed_wrench",
     "sai2b_set_jt_goals",
     "sai2b_reinitialize",
+    "sai2b_reinitialize_robots",
+    "sai2b_reset_robots",
     "sai2b_update_task_models",
     "sai2b_compute_control_torques",
     "sai2b_compute_control_torques_ex",
@@ -314,6 +316,8 @@ def load_library():
     lib.sai2b_set_mft_sensed_wrench.argtypes = [vp, _i, vp, vp, _i]
     lib.sai2b_set_jt_goals.argtypes = [vp, _i, vp, vp, vp, _i]
     lib.sai2b_reinitialize.argtypes = [vp]
+    lib.sai2b_reinitialize_robots.argtypes = [vp, _i, vp, _i]
+    lib.sai2b_reset_robots.argtypes = [vp, vp, vp, vp, _i]
     lib.sai2b_update_task_models.argtypes = [vp]
     lib.sai2b_compute_control_torques.argtypes = [vp, vp, _i]
     lib.sai2b_compute_control_torques_ex.argtypes = [vp, vp, _i, _i]

@@ -314,6 +314,45 @@ class Controller:
     def reinitialize(self):
         self._rc(self.lib.sai2b_reinitialize(self.h))
 
+    def _mask(self, mask):
+        """-> (pointer, keepalive) for a [B] mask: numpy bool / uint8 array or contiguous torch CUDA bool / uint8 tensor"""
+        if mask is None:
+            raise ValueError("a mask of one entry per robot is required")
+        if hasattr(mask, "data_ptr"):  # torch tensor
+            if not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (self.B,) or str(mask.dtype) not in ("torch.bool", "torch.uint8"):
+                raise ValueError(f"expected a contiguous bool or uint8 CUDA tensor of shape ({self.B},)")
+            import torch
+
+            s = torch.cuda.current_stream(mask.device).cuda_stream
+            if s != self._caller_stream:
+                self._rc(self.lib.sai2b_set_caller_stream(self.h, C.c_void_p(s)))
+                self._caller_stream = s
+            return C.c_void_p(mask.data_ptr()), mask
+        arr = np.asarray(mask)
+        if arr.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"expected a bool or uint8 mask, got dtype {arr.dtype}")
+        if arr.shape != (self.B,):
+            raise ValueError(f"expected a mask of shape ({self.B},), got {arr.shape}")
+        arr = np.ascontiguousarray(arr).view(np.uint8)
+        return C.c_void_p(arr.ctypes.data), arr
+
+    def reinitialize_robots(self, mask, task=-1):
+        """reinitialize() (task = -1) or task_reinitialize(task) for the robots the mask selects; the others are not touched"""
+        task = int(task)
+        if not (-1 <= task < len(self.tasks)):
+            raise ValueError(f"task must be -1 (every task) or a task index below {len(self.tasks)}")
+        pm, km = self._mask(mask)
+        self._rc(self.lib.sai2b_reinitialize_robots(self.h, task, pm, self._dev(mask)))
+
+    def reset_robots(self, mask, q=None, dq=None):
+        """Episode reset of the robots the mask selects: the selected columns of q, dq ([dof][B], None = keep) become their
+        state, their tasks and passivity observers are re-initialised and their stored torques zeroed; the others are not
+        touched. Mask and rows all numpy or all torch CUDA (then nothing synchronises)."""
+        pm, km = self._mask(mask)
+        pq, kq = self._in(q, self.dof)
+        pd, kd = self._in(dq, self.dof)
+        self._rc(self.lib.sai2b_reset_robots(self.h, pm, pq, pd, self._dev(mask, q, dq)))
+
     def update_task_models(self):
         self._rc(self.lib.sai2b_update_task_models(self.h))
 
@@ -737,9 +776,13 @@ class _TaskBase:
         rc, idx = self._require_owner()
         return rc._ctrl.task_compute_torques(idx, tau_prec, out)
 
-    def reInitializeTask(self):
+    def reInitializeTask(self, mask=None):
+        """mask [B] (bool / uint8): only for the robots it selects"""
         rc, idx = self._require_owner()
-        rc._ctrl.task_reinitialize(idx)
+        if mask is None:
+            rc._ctrl.task_reinitialize(idx)
+        else:
+            rc._ctrl.reinitialize_robots(mask, idx)
 
     def getTaskNullspace(self):
         rc, idx = self._require_owner()
@@ -1433,8 +1476,25 @@ class RobotController:
     def enableGravityCompensation(self, enable=True):
         self._ctrl.enable_gravity_compensation(enable)
 
-    def reinitializeTasks(self):
-        self._ctrl.reinitialize()
+    def reinitializeTasks(self, mask=None):
+        """mask [B] (bool / uint8): only for the robots it selects"""
+        if mask is None:
+            self._ctrl.reinitialize()
+        else:
+            self._ctrl.reinitialize_robots(mask)
+
+    def resetRobots(self, mask, q=None, dq=None):
+        """Controller.reset_robots; the model's host copy of the state follows for the selected robots (host arrays only:
+        with device tensors the state lives on the device, as under BatchedSimulation)"""
+        self._ctrl.reset_robots(mask, q, dq)
+        if not hasattr(mask, "data_ptr"):
+            sel = np.asarray(mask).astype(bool)
+            for name, new in (("_q", q), ("_dq", dq)):
+                cur = getattr(self._robot, name)
+                if new is not None and isinstance(cur, np.ndarray):
+                    cur = np.array(cur, dtype=np.float64)
+                    cur[:, sel] = np.asarray(new, dtype=np.float64)[:, sel]
+                    setattr(self._robot, name, cur)
 
     def getTaskNames(self):
         return [t.getTaskName() for t in self._tasks]

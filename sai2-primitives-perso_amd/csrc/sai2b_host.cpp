@@ -110,6 +110,10 @@ struct sai2b_ctx {
 	double* contact_rows = nullptr;
 	sai2b_contact_config contact_cfg = {};
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
+	// sai2b_reinitialize_robots / sai2b_reset_robots with host arguments: the [B]-byte mask and the [2 * dof][B] q, dq rows are
+	// staged here, created on first use
+	unsigned char* reset_mask = nullptr;
+	double* reset_rows = nullptr;
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
 	int last_call_task = 0;	  // the last launch sequence was a task-level call: 1 = task_cert_kernel + work list, 2 = the generic task kernel alone
@@ -1048,6 +1052,62 @@ extern "C" int sai2b_reinitialize(sai2b_ctx* ctx) {
 	ctx->models_fresh = false;
 	ctx->q_is_pose = true;	// reInitializeTask reads the pose of the current state
 	return SAI2B_OK;
+}
+
+// sai2b_reinitialize_robots (episode = false) and sai2b_reset_robots (episode = true): one launch of reset_subset_kernel
+static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned char* mask, const double* q, const double* dq, int on_device,
+						bool episode) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": null ctx");
+	if (!mask) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": mask is NULL");
+	if (task < -1 || task >= ctx->T) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": task must be -1 (every task) or a task index");
+	if (int rc_ = flush_update(ctx)) return rc_;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc = upload_params(ctx);
+	if (rc) return rc;
+	const size_t B = ctx->B;
+	const unsigned char* d_mask = mask;
+	const double *d_q = q, *d_dq = dq;
+	if (on_device) {
+		if ((rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (!ctx->reset_mask && (rc = dev_alloc(ctx, &ctx->reset_mask, B))) return rc;
+		if ((q || dq) && !ctx->reset_rows && (rc = dev_alloc(ctx, &ctx->reset_rows, 2 * (size_t)N * B))) return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->reset_mask, mask, B, hipMemcpyHostToDevice, ctx->stream));
+		d_mask = ctx->reset_mask;
+		if (q) {
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->reset_rows, q, (size_t)N * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+			d_q = ctx->reset_rows;
+		}
+		if (dq) {
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->reset_rows + (size_t)N * B, dq, (size_t)N * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+			d_dq = ctx->reset_rows + (size_t)N * B;
+		}
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
+	}
+	// q_is_pose is one flag for the batch. While it holds, the state buffer is every robot's cached pose and stays so: a
+	// selected robot's new state is the pose it is re-initialised at. Otherwise the unselected robots' poses live in q_pose
+	// and the kernel moves the selected columns there (one task of several: the other tasks keep theirs, as
+	// sai2b_task_reinitialize has it).
+	int flags = episode ? sai2b::RESET_EPISODE : 0;
+	if (!ctx->q_is_pose && (task < 0 || ctx->T == 1)) flags |= sai2b::RESET_KEEP_POSE;
+	if (sai2b::launch_reset_subset(ctx->d_params, ctx->B, d_mask, d_q, d_dq, ctx->q, ctx->dq, ctx->q_pose, task, flags, ctx->stream))
+		return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
+	// batch-wide and conservative: a dirty flag makes the generator kernel compare goals, and an untouched robot's compare equal
+	ctx->goals_dirty = task < 0 ? ~0u : (ctx->goals_dirty | 1u << task);
+	ctx->goals_epoch++, ctx->otg_all_idle = false;
+	ctx->launches++;
+	ctx->models_fresh = false;
+	for (int t = 0; t < ctx->T; t++)
+		if (task < 0 || t == task || d_q || d_dq) ctx->tio[t].model_fresh = false;
+	return on_device ? caller_after_read(ctx) : SAI2B_OK;
+}
+
+extern "C" int sai2b_reinitialize_robots(sai2b_ctx* ctx, int task, const unsigned char* mask, int on_device) {
+	return reset_subset(ctx, "sai2b_reinitialize_robots", task, mask, nullptr, nullptr, on_device, false);
+}
+
+extern "C" int sai2b_reset_robots(sai2b_ctx* ctx, const unsigned char* mask, const double* q, const double* dq, int on_device) {
+	return reset_subset(ctx, "sai2b_reset_robots", -1, mask, q, dq, on_device, true);
 }
 
 // eligibility of the SVD-free path (sai2b_fast.hpp): [full MFT] or [full MFT, full JT] (any batch size: a robot

@@ -415,9 +415,7 @@ __global__ __launch_bounds__(64) void task_kernel(const DevParams* __restrict__ 
 	}
 }
 
-// RobotController::reinitializeTasks (RobotController.cpp:76-80): MotionForceTask::reInitializeTask
-// (MotionForceTask.cpp:204-245), SingularityHandler ctor state (SingularityHandler.cpp:53-63),
-// JointTask::reInitializeTask (JointTask.cpp:91-107)
+// RobotController::reinitializeTasks (RobotController.cpp:76-80) for every robot: reinit_robot (sai2b_device.hpp)
 __global__ __launch_bounds__(64) void reinit_kernel(const DevParams* __restrict__ Pp, int only_task) {
 	const DevParams& P = *Pp;
 	const int B = P.B;
@@ -425,36 +423,7 @@ __global__ __launch_bounds__(64) void reinit_kernel(const DevParams* __restrict_
 	if (b >= B) return;
 	real q[N];
 	UNROLL for (int i = 0; i < N; i++) q[i] = ld(P.q, i, B, b);
-#pragma unroll 1
-	for (int t = 0; t < P.n_tasks; t++) {
-		const DevTask& tk = P.task[t];
-		if (only_task >= 0 && t != only_task) continue;	 // TemplateTask::reInitializeTask of one task
-		if (tk.type == SAI2B_MOTION_FORCE_TASK) {
-			real x[3], R[9];
-			det_frame_pose(P.model, tk, q, x, R);
-			UNROLL for (int k = 0; k < 3; k++) st(tk.goals, k, B, b, x[k]);
-			UNROLL for (int k = 0; k < 9; k++) st(tk.goals, 3 + k, B, b, R[k]);
-			for (int k = 12; k < MFT_GOAL_ROWS; k++) st(tk.goals, k, B, b, 0.0);
-			for (int k = 0; k < 6; k++) st(tk.sensed, k, B, b, 0.0);
-			for (int k = 0; k < 12; k++) st(tk.state, k, B, b, 0.0);
-			UNROLL for (int i = 0; i < N; i++) {
-				st(tk.state, MFT_QPRIOR + i, B, b, 0.5 * (P.model.q_lower[i] + P.model.q_upper[i]));
-				st(tk.state, MFT_DQPRIOR + i, B, b, 0.0);
-				st(tk.state, MFT_T2DIR + i, B, b, 1.0);
-			}
-			for (int k = 0; k < MFT_ISTATE_ROWS; k++) sti(tk.istate, k, B, b, 0);
-		} else {
-			real cur[N];
-			mv<N, N>(tk.S, q, cur);
-			UNROLL for (int i = 0; i < N; i++)
-				if (i < tk.k0) {
-					st(tk.goals, i, B, b, cur[i]);
-					st(tk.goals, tk.k0 + i, B, b, 0.0);
-					st(tk.goals, 2 * tk.k0 + i, B, b, 0.0);
-					st(tk.state, i, B, b, 0.0);
-				}
-		}
-	}
+	reinit_robot(P, only_task, q, B, b);
 }
 
 // the SVD-free first kernel of `form`

@@ -77,6 +77,11 @@ int launch_tick_part(const DevParams* d_params, int B, const TickForm& form, boo
 int launch_otg(const DevParams* d_params, int B, const WorkList& otg, int clean_mask, int task_mask, int jerk_mask, hipStream_t stream);
 // q_pose: [N][B] joint positions the tasks' cached poses correspond to (read in mode 1 only)
 int launch_otg_reinit(const DevParams* d_params, int B, int only_task, int mode, const double* q_pose, hipStream_t stream);
+// the masked robots' reinit + OTG reinit (mode 0) in one launch (sai2b_otg.hip: reset_subset_kernel). mask [B] device bytes;
+// q_new / dq_new [N][B] device rows or NULL; q_state / dq_state / q_pose: the ctx buffers; flags: RESET_*
+enum { RESET_EPISODE = 1, RESET_KEEP_POSE = 2 };
+int launch_reset_subset(const DevParams* d_params, int B, const unsigned char* mask, const double* q_new, const double* dq_new, double* q_state,
+						double* dq_state, double* q_pose, int only_task, int flags, hipStream_t stream);
 // force / motion space re-parametrisation of MotionForceTask `task` at run time (flags in the kernel's comment)
 int launch_mft_reparam(const DevParams* d_params, int B, int task, int flags, const double* q_pose, hipStream_t stream);
 // simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.

@@ -665,16 +665,8 @@ __global__ __launch_bounds__(64) void otg3_plan_kernel(const DevParams* __restri
 //           when the state buffers move on), and for a JointTask zero the input acceleration
 //           (OTG_joints::disableJerkLimits, :88-91).
 //   mode 2: the same call on a task whose OTG was already on: only the JointTask's zeroing.
-__global__ __launch_bounds__(64) void otg_reinit_kernel(const DevParams* __restrict__ Pp, int only_task, int mode,
-														const double* __restrict__ q_pose) {
-	const DevParams& P = *Pp;
-	const int B = P.B;
-	const int b = blockIdx.x * 64 + threadIdx.x;
-	if (b >= B) return;
-	real q[N];
-	if (mode == 1) {
-		UNROLL for (int i = 0; i < N; i++) q[i] = ld(q_pose, i, B, b);
-	}
+// One robot's share of it (q: the joint positions of q_pose, read in mode 1 only); shared with reset_subset_kernel.
+DI void otg_reinit_robot(const DevParams& P, int only_task, int mode, const real* q, int B, int b) {
 #pragma unroll 1
 	for (int t = 0; t < P.n_tasks; t++) {
 		const DevTask& tk = P.task[t];
@@ -723,6 +715,67 @@ __global__ __launch_bounds__(64) void otg_reinit_kernel(const DevParams* __restr
 			for (int k = MFT_MOTION_GOAL_ROWS; k < MFT_GOAL_ROWS; k++) st(tk.otg_desired, k, B, b, 0.0);
 		}
 		st(S, OTG_CONSTRUCTED, B, b, 1.0);
+	}
+}
+
+__global__ __launch_bounds__(64) void otg_reinit_kernel(const DevParams* __restrict__ Pp, int only_task, int mode,
+														const double* __restrict__ q_pose) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b >= B) return;
+	real q[N];
+	if (mode == 1) {
+		UNROLL for (int i = 0; i < N; i++) q[i] = ld(q_pose, i, B, b);
+	}
+	otg_reinit_robot(P, only_task, mode, q, B, b);
+}
+
+// sai2b_reinitialize_robots / sai2b_reset_robots: the robots with mask[b] != 0 get, in this one launch, what
+// sai2b_set_state + sai2b_reinitialize (only_task >= 0: sai2b_task_reinitialize) give every robot; the others are
+// neither read nor written. One lane per robot, one wavefront per workgroup: a wavefront without a selected robot
+// leaves after its mask load (the vote is uniform over the wavefront, so the exit is a scalar branch), which is what an
+// environment loop with a sparse mask pays for almost all of the batch.
+//   q_new / dq_new  [N][B] or NULL (keep): the selected columns become the state (reset only)
+//   flags           RESET_EPISODE: also re-initialise the passivity observers of the tasks that have one
+//                   (POPCExplicitForceControl.cpp:10-22) and zero the torque columns; RESET_KEEP_POSE: the tasks' cached
+//                   poses live in q_pose (the state has moved on since the last torque computation), so the
+//                   selected columns of q_pose follow the state the tasks were just re-initialised at
+__global__ __launch_bounds__(64) void reset_subset_kernel(const DevParams* __restrict__ Pp, const unsigned char* __restrict__ mask,
+														  const double* __restrict__ q_new, const double* __restrict__ dq_new,
+														  double* __restrict__ q_state, double* __restrict__ dq_state,
+														  double* __restrict__ q_pose, int only_task, int flags) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	const bool selected = b < B && mask[b < B ? b : B - 1] != 0;
+	if (!__any(selected)) return;  // wave-uniform
+	if (!selected) return;
+	real q[N];
+	UNROLL for (int i = 0; i < N; i++) {
+		if (q_new) {
+			q[i] = ld(q_new, i, B, b);
+			st(q_state, i, B, b, q[i]);
+		} else {
+			q[i] = ld(q_state, i, B, b);
+		}
+		if (dq_new) st(dq_state, i, B, b, ld(dq_new, i, B, b));
+		if (flags & RESET_KEEP_POSE) st(q_pose, i, B, b, q[i]);
+		if (flags & RESET_EPISODE) st(P.tau, i, B, b, 0.0);
+	}
+	reinit_robot(P, only_task, q, B, b);
+	otg_reinit_robot(P, only_task, 0, q, B, b);	 // (mode 0 reads the goals reinit_robot has just written, not q)
+	if (flags & RESET_EPISODE) {
+#pragma unroll 1
+		for (int t = 0; t < P.n_tasks; t++) {
+			const DevTask& tk = P.task[t];
+			if (!tk.popc_f) continue;
+			for (int k = 0; k < 3; k++) st(tk.popc_f, k, B, b, 0.0);
+			st(tk.popc_f, 3, B, b, 1.0);  // Rc
+			sti(tk.popc_i, 0, B, b, POPC_MAX_COUNTER);
+			sti(tk.popc_i, 1, B, b, 0);
+			sti(tk.popc_i, 2, B, b, 0);
+		}
 	}
 }
 
@@ -798,6 +851,13 @@ int launch_otg(const DevParams* d_params, int B, const WorkList& otg, int clean_
 
 int launch_otg_reinit(const DevParams* d_params, int B, int only_task, int mode, const double* q_pose, hipStream_t stream) {
 	hipLaunchKernelGGL(otg_reinit_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, only_task, mode, q_pose);
+	return launch_result();
+}
+
+int launch_reset_subset(const DevParams* d_params, int B, const unsigned char* mask, const double* q_new, const double* dq_new, double* q_state,
+						double* dq_state, double* q_pose, int only_task, int flags, hipStream_t stream) {
+	hipLaunchKernelGGL(reset_subset_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, mask, q_new, dq_new, q_state, dq_state, q_pose,
+					   only_task, flags);
 	return launch_result();
 }
 

@@ -60,6 +60,16 @@ def set_link_payload(ctrl, world, rank, link, mass, com=None, inertia=None, targ
     ctrl.set_link_payload(link, *[shard_rows(a, world, rank) for a in (mass, com, inertia)], target=target)
 
 
+def reinitialize_robots(ctrl, world, rank, mask, task=-1):
+    """Controller.reinitialize_robots on this rank's shard of a mask given for the whole batch"""
+    ctrl.reinitialize_robots(shard_rows(mask, world, rank), task)
+
+
+def reset_robots(ctrl, world, rank, mask, q=None, dq=None):
+    """Controller.reset_robots on this rank's shard of a mask and state rows given for the whole batch"""
+    ctrl.reset_robots(*[shard_rows(a, world, rank) for a in (mask, q, dq)])
+
+
 def node_throughput(robots_per_rank, world, steps, elapsed_max):
     """whole-job control-ticks/sec: every rank's robots x steps over the slowest rank's time"""
     return robots_per_rank * world * steps / elapsed_max
