@@ -1477,11 +1477,14 @@ DI bool tick(const DevParams& P, const MD& md, int B, int b, bool with_comp, rea
 			// JointTask::updateTaskModel / computeTorques (JointTask.cpp:218-356)
 			CSTAMP(30);
 			const int k0 = t.k0;
+			// a full JointTask behind tasks that took every joint has no range: computeTorques returns before its
+			// integrator advances (JointTask.cpp:302-306), so the row keeps its value
+			const bool has_range = !t.full_selection || first || wrows < N;
 			if constexpr (TASK) {
 				// what the generic kernel's model pass tells the generator kernels (sai2b_device.hpp: jt_task): a full
 				// JointTask has a range while N_prec leaves a direction, a certified partial one keeps all its rows (an
 				// uncertified one is decided — and this row overwritten — by the generic pass behind)
-				if (t.otg_gated && io->write_active) st(t.otg_state, OTG_ACTIVE, B, b, (!t.full_selection || first || wrows < N) ? 1.0 : 0.0);
+				if (t.otg_gated && io->write_active) st(t.otg_state, OTG_ACTIVE, B, b, has_range ? 1.0 : 0.0);
 			}
 			real va[N], vf[N];
 			{
@@ -1525,7 +1528,7 @@ DI bool tick(const DevParams& P, const MD& md, int B, int b, bool with_comp, rea
 					va[i] = vf[i] = 0;
 					if (i < k0) {  // PD(+I) law of task coordinate i (JointTask.cpp:299-345)
 						const real qd = gq[i], dqd = gdq[i], ddq_d = gddq[i];
-						const real integ = fma(cur[i] - qd, t.dt, integ0[i]);
+						const real integ = has_range ? fma(cur[i] - qd, t.dt, integ0[i]) : integ0[i];
 						pend[(np + i) * 64] = integ;
 						real fi;
 						if (t.use_vsat) {

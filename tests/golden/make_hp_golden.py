@@ -53,20 +53,22 @@ def truth_tasks(cell):
     return config_tasks(cfgs, hierarchy(c["hier"], cfgs[0].robot_dof))
 
 
-def config_tasks(cfgs, specs):
-    """task configs and their hierarchy specs -> the tasks as hp_reference takes them"""
+def config_tasks(cfgs, specs, plain=True):
+    """task configs and their hierarchy specs -> the tasks as hp_reference takes them. plain: the motion law alone, as
+    this fixture has it (tests/golden/make_hp_force_golden.py adds the numbers of the rest)"""
     n = cfgs[0].robot_dof
     out = []
     for cfg, spec in zip(cfgs, specs):
         common = dict(decoupling=int(cfg.dynamic_decoupling_type), bie=float(cfg.bie_threshold))
         if spec[0] == "jt":
             k0 = cfg.task_dof
-            assert not any(cfg.ki[:k0]) and not cfg.use_velocity_saturation
+            assert not plain or (not any(cfg.ki[:k0]) and not cfg.use_velocity_saturation)
             out.append(dict(kind="jt", S=np.array(cfg.joint_selection[: k0 * n]).reshape(k0, n), kp=np.array(cfg.kp[:k0]),
                             kv=np.array(cfg.kv[:k0]), **common))
             continue
-        assert not any(cfg.ki_pos) and not any(cfg.ki_ori) and not cfg.use_velocity_saturation
-        assert cfg.force_space_dimension == 0 and cfg.moment_space_dimension == 0 and not cfg.use_internal_otg
+        assert not plain or (not any(cfg.ki_pos) and not any(cfg.ki_ori) and not cfg.use_velocity_saturation)
+        assert not plain or (cfg.force_space_dimension == 0 and cfg.moment_space_dimension == 0)
+        assert not cfg.use_internal_otg
         out.append(dict(kind="mft", link=spec[1], point=np.array(spec[2], dtype=float), frot=np.eye(3),
                         P=np.array(cfg.partial_projection[:]).reshape(6, 6), rank=cfg.pos_range + cfg.ori_range,
                         kp_pos=np.array(cfg.kp_pos[:]), kv_pos=np.array(cfg.kv_pos[:]), kp_ori=np.array(cfg.kp_ori[:]),
@@ -82,12 +84,12 @@ def _grid(x, bits):
     return np.round(np.asarray(x, dtype=float) * 2.0 ** bits) / 2.0 ** bits
 
 
-def candidates(cell, count):
+def candidates(cell, count, cells=None):
     """poses and goals of `count` candidate robots, in order (deterministic)"""
     import sai2_primitives_perso_amd as pkg
     import urdf_np
 
-    c = CELLS[cell]
+    c = (cells or CELLS)[cell]
     rng = np.random.default_rng([1234, len(cell), sum(map(ord, cell))])
     chain = urdf_np.Chain(urdf_text(c["robot"]), is_file=False)
     n = chain.dof

@@ -74,12 +74,13 @@ def product_model(robot):
     return pkg.model_from_urdf(urdf_text(robot), is_file=False)
 
 
-def product_configs(cell, mk_jt, mk_mft, links=None):
-    """the task configs of a cell, built by the given helpers (the product's, or the oracle's) and the cell's options"""
+def product_configs(cell, mk_jt, mk_mft, links=None, cells=None, apply_opts=None):
+    """the task configs of a cell, built by the given helpers (the product's, or the oracle's) and the cell's options
+    (cells, apply_opts: another table of cells and its way to apply options, tests/hp_force_fixture.py)"""
     import cases
     import sai2_primitives_perso_amd as pkg
 
-    c = CELLS[cell]
+    c = (cells or CELLS)[cell]
     n = 7 if c["robot"] == "panda" else {"planar_4r": 4, "six_r": 6, "sliding_base": 8}[c["robot"]]
     out = []
     for k, spec in enumerate(hierarchy(c["hier"], n)):
@@ -90,34 +91,34 @@ def product_configs(cell, mk_jt, mk_mft, links=None):
         else:
             link, fp, fr = pkg.resolve_link_frame(links, spec[1], spec[2])
             cfg = mk_mft(f"mft{k}", link, fp, fr, spec[3], robot_dof=n)
-        cases.apply_opts(cfg, c["opts"][k])
+        (apply_opts or cases.apply_opts)(cfg, c["opts"][k])
         out.append(cfg)
     return out
 
 
-def load(cell, z=None):
+def load(cell, z=None, fixture=None):
     """the cell's arrays of the fixture, keys without the cell prefix"""
-    z = np.load(FIXTURE) if z is None else z
+    z = np.load(fixture or FIXTURE) if z is None else z
     return {k.split(".", 1)[1]: z[k] for k in z.files if k.split(".", 1)[0] == cell}
 
 
-def kinds(cell):
-    c = CELLS[cell]
+def kinds(cell, cells=None):
+    c = (cells or CELLS)[cell]
     n = 7 if c["robot"] == "panda" else {"planar_4r": 4, "six_r": 6, "sliding_base": 8}[c["robot"]]
     return [s[0] for s in hierarchy(c["hier"], n)]
 
 
-def make(cell, mk_jt, mk_mft, make_ctrl):
+def make(cell, mk_jt, mk_mft, make_ctrl, cells=None, fixture=None, apply_opts=None):
     """a controller (product or oracle, by the helpers given) for the cell's robots, goals loaded, nothing ticked"""
     import oracle_lib as ol
 
-    c = CELLS[cell]
+    c = (cells or CELLS)[cell]
     model, links = product_model(c["robot"])
-    cfgs = product_configs(cell, mk_jt, mk_mft, links)
-    d = load(cell)
+    cfgs = product_configs(cell, mk_jt, mk_mft, links, cells, apply_opts)
+    d = load(cell, fixture=fixture)
     B = d["dq"].shape[1]
     ctrl = make_ctrl(ol.panda_model() if c["robot"] == "panda" and mk_jt is ol.joint_task else model, cfgs, B)
-    for t, k in enumerate(kinds(cell)):
+    for t, k in enumerate(kinds(cell, cells)):
         if k == "mft":
             g = [d[f"mft{t}_{x}"] for x in ("pos", "rot", "v", "w", "a", "alpha")]
             ctrl.set_mft_goals(t, *[np.ascontiguousarray(a) for a in g])
@@ -126,9 +127,10 @@ def make(cell, mk_jt, mk_mft, make_ctrl):
     return ctrl, d
 
 
-def run(ctrl, cell, d, tick=None):
-    """the cell's ticks: per tick (tau, (singular directions, c1, c2) of the MotionForceTask)"""
-    t = kinds(cell).index("mft")
+def run(ctrl, cell, d, tick=None, cells=None, after=None):
+    """the cell's ticks: per tick (tau, (singular directions, c1, c2) of the MotionForceTask); after(ctrl): called behind
+    every tick, its result appended to that tick's tuple"""
+    t = kinds(cell, cells).index("mft")
     out = []
     for k in range(d["q"].shape[0]):
         ctrl.set_state(np.ascontiguousarray(d["q"][k]), np.ascontiguousarray(d["dq"]))
@@ -139,7 +141,7 @@ def run(ctrl, cell, d, tick=None):
             _, _, ro = ctrl.get_mft_singularity(t)
             _, c1, c2 = ctrl.get_mft_sh_state(t)
             state = (ctrl.tasks[t].pos_range + ctrl.tasks[t].ori_range - ro, c1, c2)
-        out.append((tau, tuple(np.asarray(s).astype(int) for s in state)))
+        out.append((tau, tuple(np.asarray(s).astype(int) for s in state)) + (() if after is None else (after(ctrl),)))
     return out
 
 

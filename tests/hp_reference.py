@@ -21,9 +21,20 @@ bias() sums b = C(q, dq) dq + g(q) over the bodies from their velocity-product a
 the body poses along q + t dq; bias_lagrange() is the Lagrangian form from derivatives of M; sim_step() restates the
 integrator (the torque held over the period, `substeps` semi-implicit Euler steps).
 
-HOOKS plants errors for tests/test_hp_reference.py and tests/test_hp_dynamics.py (each must be caught by the checker):
-alpha_rel, flip_vs_type2, no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior; pris_coriolis_half, no_gyroscopic,
-explicit_euler."""
+The task laws in full (MotionForceTask.cpp:278-509 with sigmaForce / Position / Moment / Orientation, getGoalForce /
+Moment and updateSensedForceAndMoment :805-828, JointTask.cpp:294-350, the handler's two arguments
+SingularityHandler.cpp:297-368), read from that text: force and moment spaces of dimension 0-3 in the world or the
+compliant frame, the goal wrench, the sensed wrench through the sensor frame with its lever arm, open- and closed-loop
+force and moment with their integrators and the feedback limit on the norm, the feed-forward whose two gains hang on the
+closed-loop *force* flag, the motion integrators, velocity saturation through the pseudo-inverse of k_v, per-axis gains;
+the JointTask's integrator and per-joint saturation. The passivity observer, the trajectory generators and contact are
+not restated. The held fixtures of these laws are tests/golden/hp_force.npz (tests/test_hp_force_reference.py).
+A force or moment axis is normalised at the working precision, as the reference normalises what it is given.
+
+HOOKS plants errors for tests/test_hp_reference.py, tests/test_hp_force_reference.py and tests/test_hp_dynamics.py (each
+must be caught by the checker): alpha_rel, flip_vs_type2, no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior;
+ff_through_lambda, kff_moment_own_flag, sensor_no_lever, integ_after_use, sat_componentwise, vsat_no_pinv,
+type2_from_fu_only, goal_wrench_not_rotated; pris_coriolis_half, no_gyroscopic, explicit_euler."""
 import copy
 import re
 import xml.etree.ElementTree as ET
@@ -235,9 +246,11 @@ def bie_minv(M, thr):
 
 
 def new_state(model, tasks):
-    """per MotionForceTask: the SingularityHandler's state after construction"""
-    return [dict(types=[], hist=[], c1=0, c2=0, q_prior=(M_(model.lower) + M_(model.upper)) / 2, t2dir=[1] * model.dof)
-            if t["kind"] == "mft" else None for t in tasks]
+    """per MotionForceTask: the SingularityHandler's state after construction and the twelve integrators (position,
+    orientation, force, moment); per JointTask: its integrator"""
+    return [dict(types=[], hist=[], c1=0, c2=0, q_prior=(M_(model.lower) + M_(model.upper)) / 2, t2dir=[1] * model.dof,
+                 integ=zeros(12))
+            if t["kind"] == "mft" else dict(integ=zeros(np.asarray(t["S"]).shape[0])) for t in tasks]
 
 
 def _mft_update(model, t, st, q, M, Minv, MiB, Jw, N_prec, pose0, pert, types_override, out):
@@ -332,27 +345,136 @@ def _mft_update(model, t, st, q, M, Minv, MiB, Jw, N_prec, pose0, pert, types_ov
     return m
 
 
+def _sigma(dim, axis, Rp, Pb):
+    """sigmaForce / sigmaMoment (MotionForceTask.cpp:892-966): the selection of a space of dimension `dim` about `axis`
+    (normalised as parametrizeForceMotionSpaces does, :848), Rp the rotation of the parametrisation, Pb the 3 x 3 block
+    of the partial projection"""
+    if dim == 0:
+        return zeros(3, 3)
+    if dim == 3:
+        return Pb
+    a = M_(axis)
+    a = Rp @ (a / mp.sqrt(a @ a))
+    aa = np.outer(a, a)
+    return Pb @ (aa if dim == 1 else eye(3) - aa) @ Pb.T
+
+
+def _saturate(vec, lim, key, out):
+    """vec scaled down to the norm lim when its norm exceeds it; the decision recorded"""
+    nv = mp.sqrt(vec @ vec)
+    out.setdefault("norms", []).append((nv, lim))
+    out[key] = bool(nv > lim)
+    if "sat_componentwise" in HOOKS:
+        return np.array([min(max(c, -mpf(lim)), mpf(lim)) for c in vec], dtype=object)
+    return vec * (mpf(lim) / nv) if nv > lim else vec
+
+
+def _gain_pinv(kv):
+    """Sai2Model::computePseudoInverse of a diagonal gain matrix: a zero gain gives 0"""
+    if "vsat_no_pinv" in HOOKS:
+        return np.array([1 / c if c != 0 else mpf(1) for c in kv], dtype=object)
+    return np.array([1 / c if c != 0 else mpf(0) for c in kv], dtype=object)
+
+
+def _mft_law(t, st, J, dq, x, R, goal, out):
+    """MotionForceTask::computeTorques up to the singularity handler (MotionForceTask.cpp:306-506), the passivity
+    observer off and the desired motion the goal: (F_u, F_f), the integrators of st advanced"""
+    P = M_(t["P"])
+    Pp, Po = P[:3, :3], P[3:, 3:]
+    Rp = R if t.get("in_frame") else eye(3)
+    sf = _sigma(t.get("fdim", 0), t.get("faxis"), Rp, Pp)
+    sm = _sigma(t.get("mdim", 0), t.get("maxis"), Rp, Po)
+    sp, so = Pp @ (eye(3) - sf) @ Pp.T, Po @ (eye(3) - sm) @ Po.T
+    v, w = J[:3] @ dq, J[3:] @ dq
+    dt = mpf(t.get("dt", 0))
+    late = "integ_after_use" in HOOKS
+    old = st["integ"].copy()
+    new = old.copy()
+    g3 = lambda key: M_(t[key]) if key in t else zeros(3)
+    # goal and sensed wrench (:755-769, :805-828)
+    gf = Rp @ M_(goal["f"]) if "f" in goal else zeros(3)
+    gm = Rp @ M_(goal["m"]) if "m" in goal else zeros(3)
+    if "goal_wrench_not_rotated" in HOOKS and "f" in goal:
+        gf, gm = M_(goal["f"]), M_(goal["m"])
+    fs, ms = zeros(3), zeros(3)
+    if "sf" in goal:
+        Rs, ps = M_(np.asarray(t["sensor_rot"]).reshape(3, 3)), M_(t["sensor_pos"])
+        fc = Rs @ M_(goal["sf"])
+        mc = Rs @ M_(goal["sm"]) + (zeros(3) if "sensor_no_lever" in HOOKS else _cross(ps, fc))
+        fs, ms = R @ fc, R @ mc
+    out.update(sat_f=False, sat_m=False, sat_v=False, sat_w=False)
+    cl_f, cl_m = bool(t.get("cl_force")), bool(t.get("cl_moment"))
+    # force (:327-354; POPCExplicitForceControl.cpp:33-35 with the observer off) and moment (:357-383)
+    if cl_f:
+        new[6:9] = old[6:9] + sf @ (fs - gf) * dt
+        fb = sf @ (-g3("kp_f") * (fs - gf) - g3("ki_f") * (old if late else new)[6:9])
+        fb = _saturate(fb, t["max_f"], "sat_f", out)
+        f_force = sf @ fb - g3("kv_f") * (sf @ v)
+    else:
+        f_force = sf @ (-g3("kv_f") * v)
+    if cl_m:
+        new[9:12] = old[9:12] + sm @ (ms - gm) * dt
+        fb = sm @ (-g3("kp_m") * (ms - gm) - g3("ki_m") * (old if late else new)[9:12])
+        fb = _saturate(fb, t["max_m"], "sat_m", out)
+        f_moment = sm @ (fb - g3("kv_m") * w)
+    else:
+        f_moment = sm @ (-g3("kv_m") * w)
+    # linear motion (:409-437)
+    gpos, grot = M_(goal["pos"]), M_(np.asarray(goal["rot"]).reshape(3, 3))
+    kp, kv, ki = M_(t["kp_pos"]), M_(t["kv_pos"]), g3("ki_pos")
+    new[0:3] = old[0:3] + sp @ (x - gpos) * dt
+    ip = (old if late else new)[0:3]
+    if t.get("vsat"):
+        kvi = _gain_pinv(kv)
+        des = _saturate(-kp * kvi * (sp @ (x - gpos)) - ki * kvi * ip, t["lin_vsat"], "sat_v", out)
+        f_pos = sp @ (M_(goal["a"]) - kv * (v - des))
+    else:
+        f_pos = sp @ (M_(goal["a"]) - kp * (x - gpos) - kv * (v - M_(goal["v"])) - ki * ip)
+    # angular motion (:439-468)
+    kp, kv, ki = M_(t["kp_ori"]), M_(t["kv_ori"]), g3("ki_ori")
+    step = so @ orientation_error(grot, R)
+    new[3:6] = old[3:6] + step * dt
+    io = (old if late else new)[3:6]
+    if t.get("vsat"):
+        kvi = _gain_pinv(kv)
+        des = _saturate(-kp * kvi * step - ki * kvi * io, t["ang_vsat"], "sat_w", out)
+        f_ori = so @ (M_(goal["alpha"]) - kv * (w - des))
+    else:
+        f_ori = so @ (M_(goal["alpha"]) - kp * step - kv * (w - M_(goal["w"])) - ki * io)
+    # feed-forward (:480-487): both halves scaled under the closed-loop *force* flag
+    ff_f, ff_m = sf @ gf, sm @ gm
+    if cl_f:
+        ff_f = ff_f * mpf(t["kff_f"])
+    if cl_m if "kff_moment_own_flag" in HOOKS else cl_f:
+        ff_m = ff_m * mpf(t["kff_m"])
+    st["integ"] = new
+    out["integ"] = new.copy()
+    return np.concatenate([f_pos, f_ori]), np.concatenate([f_force + ff_f, f_moment + ff_m])
+
+
 def _mft_torques(model, t, st, m, q, dq, x, R, goal, out):
+    """SingularityHandler::computeTorques(unit_mass_force, force_related_terms) (SingularityHandler.cpp:297-368)"""
     n = model.dof
+    out["integ"] = st["integ"].copy()
     if t["rank"] == 0:
         return zeros(n)
-    P = M_(t["P"])
-    sp, so = P[:3, :3], P[3:, 3:]  # no force / moment space: sigma_position and sigma_orientation are the projections
-    J = m["J"]
-    v, w = J[:3] @ dq, J[3:] @ dq
-    gpos, grot = M_(goal["pos"]), M_(np.asarray(goal["rot"]).reshape(3, 3))
-    f_pos = sp @ (M_(goal["a"]) - M_(t["kp_pos"]) * (x - gpos) - M_(t["kv_pos"]) * (v - M_(goal["v"])))
-    step = so @ orientation_error(grot, R)
-    f_ori = so @ (M_(goal["alpha"]) - M_(t["kp_ori"]) * step - M_(t["kv_ori"]) * (w - M_(goal["w"])))
-    Fu = np.concatenate([f_pos, f_ori])
+    Fu, Ff = _mft_law(t, st, m["J"], dq, x, R, goal, out)
     ns, sc = m["ns"], m["sc"]
+    out["Ff_norm"] = float(mp.sqrt(Ff @ Ff))
+
+    def through(key, L):
+        Ut = m["U_" + key].T
+        if "ff_through_lambda" in HOOKS:
+            return m["J_" + key].T @ (L @ (Ut @ Fu + Ut @ Ff))
+        return m["J_" + key].T @ (L @ (Ut @ Fu) + Ut @ Ff)
+
     if len(st["types"]) == 0:
-        return m["J_ns"].T @ (m["Lm_ns"] @ (m["U_ns"].T @ Fu)) if ns else zeros(n)
+        return through("ns", m["Lm_ns"]) if ns else zeros(n)
     if t["decoupling"] == IMPEDANCE:
-        return m["J_ns"].T @ (m["U_ns"].T @ Fu) if ns else zeros(n)
+        return through("ns", eye(ns)) if ns else zeros(n)
     if ns == 0:
         return zeros(n)
-    tau_ns = m["J_ns"].T @ (m["Lm_ns"] @ (m["U_ns"].T @ Fu))
+    tau_ns = through("ns", m["Lm_ns"])
     if not t["enforce_handling"]:
         return tau_ns
     V_s, J_post, Lj = m["V_s"], m["J_post"], m["Lm_joint"]
@@ -368,14 +490,15 @@ def _mft_torques(model, t, st, m, q, dq, x, R, goal, out):
                     st["t2dir"][i] = -1
                 elif abs(q[i] - mpf(lo[i])) < t["t2_angle"]:
                     st["t2dir"][i] = 1
-        nF = mp.sqrt(Fu @ Fu)
-        fTd = (Fu / nF if nF > 0 else Fu) @ m["U_s"][:, 0]
+        F = Fu if "type2_from_fu_only" in HOOKS else Fu + Ff
+        nF = mp.sqrt(F @ F)
+        fTd = (F / nF if nF > 0 else F) @ m["U_s"][:, 0]
         ut = np.array([st["t2dir"][i] * abs(fTd) * mpf(t["t2_ratio"]) * mpf(model.effort[i]) for i in range(n)], dtype=object)
         Vt = -V_s if "flip_vs_type2" in HOOKS else V_s
         kv2 = t["kv1"] if "kv1_for_kv2" in HOOKS else t["kv2"]
         tau_j = J_post.T @ (Vt.T @ ut) + J_post.T @ (Lj @ (V_s.T @ (-mpf(kv2) * dq)))
         out["branch"] = 2
-    tau_s = m["J_s"].T @ (m["Lm_s"] @ (m["U_s"].T @ Fu))
+    tau_s = through("s", m["Lm_s"])
     eff = M_(model.effort)
     out["clamped"] = int(sum(abs(tau_s[i]) > eff[i] for i in range(n)))
     if "no_clamp" not in HOOKS:
@@ -406,12 +529,29 @@ def _jt_update(t, M, Minv, MiB, N_prec, out):
     return dict(k=k, Rb=Rb, Jp=Jp, Mp=Mp, Mpm=Mpm, S=S, N_total=N @ N_prec)
 
 
-def _jt_torques(t, m, q, dq, Minv, tau_prec, goal):
+def _jt_torques(t, st, m, q, dq, Minv, tau_prec, goal, out):
+    """JointTask::computeTorques (JointTask.cpp:294-356) with the compensation of :285-292"""
     n = len(q)
-    if m["k"] == 0:
+    out["integ"] = st["integ"].copy()
+    if m["k"] == 0:  # (:302-306: nothing advances)
         return zeros(n)
     S, Rb, Jp = m["S"], m["Rb"], m["Jp"]
-    f = -M_(t["kp"]) * (S @ q - M_(goal["q"])) - M_(t["kv"]) * (S @ dq - M_(goal["dq"]))
+    kp, kv, ki = M_(t["kp"]), M_(t["kv"]), M_(t["ki"]) if "ki" in t else zeros(S.shape[0])
+    e = S @ q - M_(goal["q"])
+    old = st["integ"]
+    st["integ"] = old + e * mpf(t.get("dt", 0))
+    out["integ"] = st["integ"].copy()
+    integ = old if "integ_after_use" in HOOKS else st["integ"]
+    out["sat_jt"] = False
+    if t.get("vsat"):
+        des = -kp * _gain_pinv(kv) * e - ki * _gain_pinv(kv) * integ
+        sat = M_(t["sat"])
+        out["jt_des"] = [(abs(des[i]), sat[i]) for i in range(len(des))]
+        out["sat_jt"] = bool(any(abs(des[i]) > sat[i] for i in range(len(des))))
+        des = np.array([min(max(des[i], -sat[i]), sat[i]) for i in range(len(des))], dtype=object)
+        f = -kv * (S @ dq - des)
+    else:
+        f = -kp * e - kv * (S @ dq - M_(goal["dq"])) - ki * integ
     xx = m["Mp"] @ (Rb.T @ M_(goal["ddq"])) + m["Mpm"] @ (Rb.T @ f)
     tau = Jp.T @ (Rb @ xx)
     return tau - Jp.T @ (Rb @ (m["Mp"] @ (Rb.T @ (S @ (Minv @ tau_prec)))))
@@ -420,7 +560,8 @@ def _jt_torques(t, m, q, dq, Minv, tau_prec, goal):
 def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=None, gravity_comp=False):
     """one tick of the hierarchy: update_task_models() then compute_control_torques() with the compensation terms,
     g(q) added when gravity_comp (RobotController.cpp:70-72).
-    state (new_state) is advanced. pert: additive perturbations of the model quantities {M, Jp[t], x[t], R[t], dq}.
+    state (new_state) is advanced. pert: additive perturbations of the model quantities {M, Jp[t], x[t], R[t], dq}, and
+    where present of the sensed wrench {sf[t], sm[t]} and of the carried integrators {integ[t]} (added to state first).
     types_override[t]: the types of the classification (the perturbed re-evaluations keep the unperturbed decisions).
     kin: the FK quantities of an earlier call at the same q. Returns (tau, info per task, kin)."""
     q, dq = M_(q), M_(dq)
@@ -434,6 +575,11 @@ def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=
         M = M + pert["M"]
         dq = dq + pert["dq"]
         frames = [None if f is None else (f[0], f[1] + pert["x"][t], f[2] + pert["R"][t]) for t, f in enumerate(frames)]
+        if "sf" in pert:
+            goals = [g if pert["sf"][t] is None else dict(g, sf=M_(g["sf"]) + pert["sf"][t], sm=M_(g["sm"]) + pert["sm"][t])
+                     for t, g in enumerate(goals)]
+        for t, d in enumerate(pert.get("integ", [])):
+            state[t]["integ"] = state[t]["integ"] + d
     Minv = inv(M)
     MiB = {}
     n = model.dof
@@ -461,7 +607,7 @@ def tick(model, tasks, state, q, dq, goals, pert=None, types_override=None, kin=
             Jw, x, R = frames[ti]
             tt = _mft_torques(model, t, state[ti], mods[ti], q, dq, x, R, goals[ti], info[ti])
         else:
-            tt = _jt_torques(t, mods[ti], q, dq, Minv, tau, goals[ti])
+            tt = _jt_torques(t, state[ti], mods[ti], q, dq, Minv, tau, goals[ti], info[ti])
         tau = tau + tt
     if gravity_comp:
         tau = tau + kin["g"]
@@ -493,20 +639,62 @@ def perturbation(rng, kin, tasks, dq, Jps):
     return p
 
 
-def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, dirs=16, gravity_comp=False):
+def perturbation_carried(rng, tasks, state, goals):
+    """the same for what a tick carries besides the model: the sensed wrench (force and moment each by eps times its
+    norm) and the integrators (position, orientation, force, moment, and a JointTask's, each by eps times its norm).
+    Drawn from a generator of its own, so the directions of perturbation() are what they were before it existed"""
+
+    def scaled(ref):
+        ref = M_(ref)
+        d = M_(rng.standard_normal(len(ref)))
+        nr = norm_fro(ref)
+        return d * (mpf(EPS) * nr / norm_fro(d)) if nr > 0 else zeros(len(ref))
+
+    p = dict(sf=[], sm=[], integ=[])
+    for t, g, st in zip(tasks, goals, state):
+        has = t["kind"] == "mft" and "sf" in g
+        p["sf"].append(scaled(g["sf"]) if has else None)
+        p["sm"].append(scaled(g["sm"]) if has else None)
+        i = st["integ"]
+        p["integ"].append(np.concatenate([scaled(i[k: k + 3]) for k in range(0, 12, 3)]) if t["kind"] == "mft" else scaled(i))
+    return p
+
+
+INTEG_GROUPS = ("pos", "ori", "force", "moment", "jt")
+
+
+def integ_groups(tasks, info):
+    """the integrators after a tick, by group: the MotionForceTask's four and all JointTasks' together"""
+    (mft,) = [i["integ"] for t, i in zip(tasks, info) if t["kind"] == "mft" and "integ" in i] or [zeros(12)]
+    jt = [i["integ"] for t, i in zip(tasks, info) if t["kind"] == "jt" and "integ" in i]
+    return [mft[0:3], mft[3:6], mft[6:9], mft[9:12], np.concatenate(jt) if jt else zeros(0)]
+
+
+def kappa_emp(model, tasks, state_before, q, dq, goals, tau, info, kin, seed, dirs=16, gravity_comp=False, integ=False):
     """max over `dirs` seeded directions of ||dtau||_inf / (eps max(||tau||_inf, 1)): the error one ulp of noise in M,
-    J N_prec, x / R and dq causes, the classification held at the unperturbed decisions"""
+    J N_prec, x / R, dq, the sensed wrench and the carried integrators causes, the classification held at the
+    unperturbed decisions.
+    integ: returns (kappa, kappa_integ), kappa_integ per group of INTEG_GROUPS the same for the integrators after the
+    tick, plus the one rounding of storing them: (max ||d integ||_inf + eps ||integ||_inf) / (eps max(||integ||_inf, 1))"""
     rng = np.random.default_rng(seed)
+    rng_c = np.random.default_rng([977] + list(np.atleast_1d(seed)))
     Jps = [i.get("Jp") for i in info]
     types = [None if i is None or "types" not in i else i["types"] for i in info]
     worst = mpf(0)
+    groups = integ_groups(tasks, info)
+    worst_i = [mpf(0)] * len(groups)
     for _ in range(dirs):
         st = copy.deepcopy(state_before)
         p = perturbation(rng, kin, tasks, dq, Jps)
-        tp, _, _ = tick(model, tasks, st, q, dq, goals, pert=p, types_override=types, kin=kin, gravity_comp=gravity_comp)
+        p.update(perturbation_carried(rng_c, tasks, st, goals))
+        tp, ip, _ = tick(model, tasks, st, q, dq, goals, pert=p, types_override=types, kin=kin, gravity_comp=gravity_comp)
         worst = max(worst, norm_inf(tp - tau))
-    return float(worst / (mpf(EPS) * max(norm_inf(tau), mpf(1))))
-
+        worst_i = [max(w, norm_inf(a - b)) if len(a) else w for w, a, b in zip(worst_i, integ_groups(tasks, ip), groups)]
+    kap = float(worst / (mpf(EPS) * max(norm_inf(tau), mpf(1))))
+    if not integ:
+        return kap
+    return kap, [float((w + mpf(EPS) * norm_inf(g)) / (mpf(EPS) * max(norm_inf(g), mpf(1)))) if len(g) else 0.0
+                 for w, g in zip(worst_i, groups)]
 
 
 # ---- rigid-body dynamics: the simulation harness (csrc/sai2b_sim.hip) ----

@@ -6,7 +6,12 @@ few control periods on both sides (state, integrators, singularity history and g
 evolving) and torques and joint states are compared every period.
 
 The option vocabulary is the one of the golden cases (tests/cases.py: apply_opts); what the golden cases
-pin one option at a time, this pins in combination."""
+pin one option at a time, this pins in combination.
+
+Inside a singularity-blending region the comparison allows 1e-5 relative: two correct FP64 singular value
+decompositions differ there, and the oracle is a sibling of the kernels. That region is held tightly in
+tests/test_gpu_hp_force.py, where every route's force, integral and saturation laws meet a 40-digit answer
+within 128 eps kappa_emp on every robot (tests/test_gpu_hp_singular.py for the plain motion law)."""
 import os
 import zlib
 
@@ -127,7 +132,9 @@ def _closed_loop(seed):
         e = np.abs(tau_g - tau_o).max(axis=0) / den
         # regular robots: the parity bar with the margin test_certified_generic_path_matches_oracle explains
         # (unfiltered random poses); robots inside a singularity-blending region: Jacobi-SVD vectors of
-        # near-degenerate subspaces differ at 1e-7 between two correct FP64 implementations
+        # near-degenerate subspaces differ at 1e-7 between two correct FP64 implementations (the region is held tightly
+        # elsewhere, against the 40-digit answer: tests/test_gpu_hp_singular.py, and with force spaces, integral gains
+        # and the saturations on, tests/test_gpu_hp_force.py)
         assert e[regular].max() < 1e-8, (what, period, float(e[regular].max()))
         if (~regular).any():
             assert e[~regular].max() < 1e-5, (what, period, float(e[~regular].max()))
