@@ -72,6 +72,70 @@ inline void checkResetArguments(const int dof, const size_t B, const std::vector
 }
 }  // namespace detail
 
+// Observations and episode-end flags (sai2b.h "observations and episode-end flags"): what observe() returns, and the counts
+// of the last observe per reason bit and of robots with a non-zero done byte
+struct Observation {
+	int rows = 0;
+	Batch out;						 // [rows][B]
+	std::vector<unsigned char> done;	 // [B], SAI2B_DONE_* bits
+};
+struct DoneCounts {
+	int reason[SAI2B_DONE_REASONS] = {};
+	int any = 0;
+};
+namespace detail {
+// the host-only validation of an observation configuration against a hierarchy (sai2b_validate_observation)
+inline void checkObservationConfig(const sai2b_observation_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof) {
+	char msg[256];
+	if (sai2b_validate_observation(&cfg, tasks.data(), (int)tasks.size(), dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(msg);
+}
+// what observe(out, done) checks ahead of the device: a configured observation, out [rows][B] and done [B] where given
+inline void checkObserveArguments(const int rows, const size_t B, const Batch* out, const std::vector<unsigned char>* done) {
+	if (rows < 0) throw std::invalid_argument("observe: no observation is configured (setObservation)");
+	if (out && out->size() != (size_t)rows * B) throw std::invalid_argument("observe: out must be [rows][B]");
+	if (done && done->size() != B) throw std::invalid_argument("observe: done must have one entry per robot");
+}
+// the members RobotController and BatchedSimulation share: they act on the controller's context
+class ObservationMembers {
+public:
+	// validates against the controller's tasks, zeroes every robot's episode counter
+	void setObservation(const sai2b_observation_config& cfg) { check(_obs_ctx, sai2b_set_observation(_obs_ctx, &cfg)); }
+	void clearObservation() { check(_obs_ctx, sai2b_clear_observation(_obs_ctx)); }
+	int observationRows() const { return sai2b_observation_rows(_obs_ctx); }  // -1 without an observation
+	// {first row, rows} of a global block (task = -1: enum sai2b_observation_block) or of a per-task block; rows 0: not stored
+	std::pair<int, int> observationLayout(const int block, const int task = -1) const {
+		int first = -1, n = 0;
+		check(_obs_ctx, sai2b_observation_layout(_obs_ctx, block, task, &first, &n));
+		return {first, n};
+	}
+	// one launch; out [rows][B] and done [B] are filled where given (either may be NULL) and must have those sizes
+	void observe(Batch* out, std::vector<unsigned char>* done) {
+		checkObserveArguments(observationRows(), (size_t)sai2b_batch(_obs_ctx), out, done);
+		check(_obs_ctx, sai2b_observe(_obs_ctx, out ? out->data() : nullptr, done ? done->data() : nullptr, 0));
+	}
+	Observation observe() {
+		Observation o;
+		o.rows = observationRows();
+		if (o.rows < 0) throw std::invalid_argument("observe: no observation is configured (setObservation)");
+		o.out.resize((size_t)o.rows * sai2b_batch(_obs_ctx));
+		o.done.resize((size_t)sai2b_batch(_obs_ctx));
+		observe(&o.out, &o.done);
+		return o;
+	}
+	DoneCounts doneCounts() const {
+		int c[SAI2B_DONE_REASONS + 1];
+		check(_obs_ctx, sai2b_get_done_counts(_obs_ctx, c));
+		DoneCounts d;
+		for (int r = 0; r < SAI2B_DONE_REASONS; r++) d.reason[r] = c[r];
+		d.any = c[SAI2B_DONE_REASONS];
+		return d;
+	}
+
+protected:
+	sai2b_ctx* _obs_ctx = nullptr;
+};
+}  // namespace detail
+
 class RobotController;
 class TemplateTask;
 class BatchedSimulation;
@@ -932,7 +996,7 @@ protected:
 };
 
 // reference src/RobotController.{h,cpp}
-class RobotController {
+class RobotController : public detail::ObservationMembers {
 public:
 	RobotController(std::shared_ptr<BatchedRobotModel>& robot, std::vector<std::shared_ptr<TemplateTask>>& tasks) : _robot(robot) {
 		if (tasks.size() == 0) throw std::invalid_argument("RobotController must have at least one task");
@@ -948,6 +1012,7 @@ public:
 			if (msg.find("HIP") != std::string::npos || msg.find("hip") != std::string::npos) throw std::runtime_error(msg);
 			throw std::invalid_argument(msg);
 		}
+		_obs_ctx = _ctx;
 		_tasks = tasks;
 		robot->_controller = this;
 		robot->applyPayloads(_ctx, SAI2B_PAYLOAD_BOTH);
@@ -1210,6 +1275,41 @@ public:
 	Batch tick() {
 		return gatherTau([](Shard& sh, double* tau) { detail::check(sh.ctx, sai2b_tick(sh.ctx, tau, 0)); });
 	}
+	// Observations and episode-end flags of the whole sharded batch (host arrays only): every shard gets the configuration, and
+	// observe() gives each shard its columns of out [rows][B_total] and done [B_total] (either may be NULL)
+	void setObservation(const sai2b_observation_config& cfg) {
+		detail::checkObservationConfig(cfg, _cfgs, _dof);
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_set_observation(sh.ctx, &cfg)); });
+	}
+	void clearObservation() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_observation(sh.ctx)); }); }
+	int observationRows() const { return sai2b_observation_rows(_shards.at(0).ctx); }
+	void observe(Batch* out, std::vector<unsigned char>* done) {
+		const int R = observationRows();
+		detail::checkObserveArguments(R, (size_t)_total, out, done);
+		forAll([&](Shard& sh) {
+			const size_t n = (size_t)(sh.hi - sh.lo);
+			Batch part(out ? (size_t)R * n : 0);
+			detail::check(sh.ctx, sai2b_observe(sh.ctx, out ? part.data() : nullptr, done ? done->data() + sh.lo : nullptr, 0));
+			for (int c = 0; out && c < R; c++) std::copy(part.begin() + c * n, part.begin() + (c + 1) * n, out->begin() + (size_t)c * _total + sh.lo);
+		});
+	}
+	// counts of the last observe over all shards
+	DoneCounts doneCounts() {
+		std::vector<DoneCounts> parts(_shards.size());
+		forAll([&](Shard& sh) {
+			int c[SAI2B_DONE_REASONS + 1];
+			detail::check(sh.ctx, sai2b_get_done_counts(sh.ctx, c));
+			DoneCounts& d = parts[&sh - _shards.data()];
+			for (int r = 0; r < SAI2B_DONE_REASONS; r++) d.reason[r] = c[r];
+			d.any = c[SAI2B_DONE_REASONS];
+		});
+		DoneCounts sum;
+		for (const DoneCounts& d : parts) {
+			for (int r = 0; r < SAI2B_DONE_REASONS; r++) sum.reason[r] += d.reason[r];
+			sum.any += d.any;
+		}
+		return sum;
+	}
 	// ticks with the torques left on the devices (a device-resident consumer, e.g. sai2b_sim_step(ctx(s), NULL, ...))
 	void tickOnDevice() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_tick(sh.ctx, nullptr, 0)); }); }
 	void synchronize() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_synchronize(sh.ctx)); }); }
@@ -1309,7 +1409,7 @@ private:
 // integrate, getJointPositions, getJointVelocities): rigid-body dynamics of the whole batch with the
 // state resident on the device (sai2b_sim_step). Without setJointTorques, integrate() consumes the
 // torques of the controller's last computeControlTorques() without a host round trip.
-class BatchedSimulation {
+class BatchedSimulation : public detail::ObservationMembers {
 public:
 	explicit BatchedSimulation(RobotController& controller, const double timestep = 0.001, const int substeps = 1)
 		: BatchedSimulation(controller.ctx(), timestep, substeps) {}
@@ -1320,6 +1420,7 @@ public:
 	BatchedSimulation(sai2b_ctx* ctx, const double timestep, const int substeps) : _c(ctx), _dt(timestep), _substeps(substeps) {
 		if (timestep <= 0 || substeps < 1) throw std::invalid_argument("simulation timestep must be positive");
 		_dof = sai2b_num_joints(ctx);
+		_obs_ctx = ctx;
 	}
 	void setTimestep(const double dt) {
 		if (dt <= 0) throw std::invalid_argument("simulation timestep must be positive");

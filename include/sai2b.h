@@ -487,6 +487,93 @@ int sai2b_get_contact(sai2b_ctx* ctx, sai2b_contact_config* cfg, double* rows);
  * *robots_in_contact = robots with some f_n > 0 (counted on the device). Zeros before the first step with a contact. */
 int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* normal_force, double* wrench_world, int* robots_in_contact);
 
+/* ------------------------------------------------------------------ observations and episode-end flags
+ * The missing link of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe(out, done), sai2b_reset_robots(done, ..):
+ * ONE launch writes a caller-chosen set of observation rows [rows][B] and one done byte per robot into device (or host)
+ * memory; the byte is a valid mask for sai2b_reset_robots. Everything in the configuration is batch-uniform. A context that
+ * never configures an observation launches exactly the kernels it launches without this feature.
+ *
+ * Row layout: the global blocks that are selected, in the order of their flags below, then for every task of task_mask (in
+ * ascending task index) the selected per-task blocks in the order of their flags. The task quantities are those of
+ * sai2b_get_mft_status / sai2b_get_mft_velocity: computed from the state and goal buffers as they are now. */
+enum sai2b_observation_block {
+	SAI2B_OBS_Q = 1,			 /* dof rows: joint positions */
+	SAI2B_OBS_DQ = 2,			 /* dof rows: joint velocities */
+	SAI2B_OBS_TAU = 4,			 /* dof rows: the stored torques of SAI2B_BUF_TAU */
+	SAI2B_OBS_LIMIT_MARGIN = 8,	 /* 1 row: min_i min(q_i - q_lower_i, q_upper_i - q_i), limits of the context's model */
+	SAI2B_OBS_EPISODE_STEP = 16, /* 1 row: the robot's episode counter (below), as a double */
+	SAI2B_OBS_CONTACT = 32		 /* 14 rows: what the last sai2b_sim_step left (sai2b_get_contact_state): depth 4, normal
+								  * force 4, world wrench 6; zeros when the context has no contact */
+};
+enum sai2b_observation_task_block {
+	SAI2B_OBS_POSE = 1,	 /* 12 rows: position 3, rotation 9 row-major */
+	SAI2B_OBS_TWIST = 2, /* 6 rows: J dq, linear then angular */
+	SAI2B_OBS_ERROR = 4, /* 8 rows: sigma_p (x_goal - x) 3, sigma_o orientationError 3, the two norms sqrt(e^T sigma e) */
+	SAI2B_OBS_SENSED = 8 /* 6 rows: sensed force and moment at the control point, world frame */
+};
+/* Bits of a robot's done byte; each criterion is evaluated only when its bit is set in sai2b_observation_config.criteria.
+ * Every comparison is written so that a NaN operand gives false, and the criteria that read the state (SUCCESS,
+ * JOINT_LIMIT, SPEED, FORCE) are not evaluated for a robot whose q or dq is not finite: such a robot reports NONFINITE
+ * (when enabled) and no accidental other state bit. */
+enum sai2b_done_reason {
+	SAI2B_DONE_SUCCESS = 1,		/* every task of success_task_mask: position-error norm < pos_tolerance and orientation-error
+								 * norm < ori_tolerance, strict, as goalPositionReached / goalOrientationReached
+								 * (MotionForceTask.cpp:548-579) */
+	SAI2B_DONE_JOINT_LIMIT = 2, /* limit margin < joint_limit_margin */
+	SAI2B_DONE_SPEED = 4,		/* some |dq_i| > max_joint_speed[i] */
+	SAI2B_DONE_NONFINITE = 8,	/* some q_i or dq_i is not finite */
+	SAI2B_DONE_FORCE = 16,		/* some task of force_task_mask: norm of the sensed world force > max_sensed_force */
+	SAI2B_DONE_TIMEOUT = 32		/* episode counter >= max_episode_steps */
+};
+#define SAI2B_DONE_REASONS 6
+typedef struct sai2b_observation_config {
+	int blocks;		 /* SAI2B_OBS_Q | ... : the global blocks */
+	int task_mask;	 /* bit t: MotionForceTask t is observed */
+	int task_blocks; /* SAI2B_OBS_POSE | ... : the blocks stored for every observed task */
+	int criteria;	 /* SAI2B_DONE_* bits that are evaluated; 0: the done byte is always 0 */
+	int success_task_mask, force_task_mask;
+	int max_episode_steps;
+	int reserved;
+	double pos_tolerance, ori_tolerance;
+	double joint_limit_margin;
+	double max_joint_speed[SAI2B_MAX_DOF]; /* entries >= dof are ignored */
+	double max_sensed_force;
+} sai2b_observation_config;
+/* host only: nothing observed, every criterion off, thresholds 0 */
+int sai2b_default_observation(sai2b_observation_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: unknown bits in blocks / task_blocks / criteria, a
+ * task in one of the three masks that is not a MotionForceTask of `tasks`, a negative or non-finite threshold,
+ * max_episode_steps < 0 (< 1 with TIMEOUT enabled), SUCCESS or FORCE enabled with an empty task mask */
+int sai2b_validate_observation(const sai2b_observation_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+							   char* msg, int msg_len);
+/* sizeof(sai2b_observation_config) as the library was compiled: a binding that mirrors the struct checks its layout with it */
+int sai2b_sizeof_observation_config(void);
+/* host only, the layout arithmetic: where `block` is stored. task = -1: a global block (enum sai2b_observation_block), else
+ * a per-task block (enum sai2b_observation_task_block) of that task. *n_rows = 0 and *first_row = -1 when the configuration
+ * does not select it; *total_rows: rows of the whole observation. Any output may be NULL. SAI2B_INVALID_ARGUMENT when
+ * `block` is not exactly one known flag or task is outside [-1, SAI2B_MAX_TASKS). */
+int sai2b_observation_config_layout(const sai2b_observation_config* cfg, int robot_dof, int block, int task, int* first_row,
+									int* n_rows, int* total_rows);
+/* validates against the context's tasks, allocates, and zeroes every robot's episode counter (also when called again) */
+int sai2b_set_observation(sai2b_ctx* ctx, const sai2b_observation_config* cfg);
+/* back to a context without an observation: sai2b_observe fails from here on */
+int sai2b_clear_observation(sai2b_ctx* ctx);
+/* rows of the configured observation; -1 without one */
+int sai2b_observation_rows(sai2b_ctx* ctx);
+/* sai2b_observation_config_layout for the context's configuration; SAI2B_INVALID_ARGUMENT without one */
+int sai2b_observation_layout(sai2b_ctx* ctx, int block, int task, int* first_row, int* n_rows);
+/* One launch: out [rows][B] and done [B] bytes (either may be NULL), host memory, or device memory when on_device != 0
+ * (stream contract below: complete when the call returns as far as the caller's stream is concerned, nothing synchronises).
+ * A deferred sai2b_update_task_models is flushed first. SAI2B_INVALID_ARGUMENT without a configured observation (nothing
+ * is launched then).
+ * Episode counter: one int per robot. Every call increments it BEFORE the criteria are evaluated and reports that value in
+ * SAI2B_OBS_EPISODE_STEP; it is stored back as 0 for a robot whose done byte came out non-zero, otherwise as incremented:
+ * it counts the observes since the robot was last reported done. */
+int sai2b_observe(sai2b_ctx* ctx, double* out, unsigned char* done, int on_device);
+/* of the last sai2b_observe, counted on the device: robots per reason bit 0-5 and, last, robots with a non-zero byte.
+ * Zeros before the first observe; SAI2B_INVALID_ARGUMENT without a configured observation. Waits for the ctx stream. */
+int sai2b_get_done_counts(sai2b_ctx* ctx, int counts[7]);
+
 /* ------------------------------------------------------------------ simulation harness
  * What the reference's examples obtain from the external sai2-simulation (examples/05-...cpp:215-236:
  * setJointTorques / integrate / getJointPositions, getJointVelocities): one control period of

@@ -191,6 +191,39 @@ class ContactConfig(C.Structure):
     ]
 
 
+# enum sai2b_observation_block / sai2b_observation_task_block / sai2b_done_reason (sai2b.h "observations and episode-end flags")
+OBS_Q, OBS_DQ, OBS_TAU, OBS_LIMIT_MARGIN, OBS_EPISODE_STEP, OBS_CONTACT = 1, 2, 4, 8, 16, 32
+OBS_POSE, OBS_TWIST, OBS_ERROR, OBS_SENSED = 1, 2, 4, 8
+DONE_SUCCESS, DONE_JOINT_LIMIT, DONE_SPEED, DONE_NONFINITE, DONE_FORCE, DONE_TIMEOUT = 1, 2, 4, 8, 16, 32
+DONE_REASONS = 6
+# name -> flag, in storage order
+OBS_BLOCKS = {"q": OBS_Q, "dq": OBS_DQ, "tau": OBS_TAU, "limit_margin": OBS_LIMIT_MARGIN, "episode_step": OBS_EPISODE_STEP,
+              "contact": OBS_CONTACT}
+OBS_TASK_BLOCKS = {"pose": OBS_POSE, "twist": OBS_TWIST, "error": OBS_ERROR, "sensed": OBS_SENSED}
+DONE_BITS = {"success": DONE_SUCCESS, "joint_limit": DONE_JOINT_LIMIT, "speed": DONE_SPEED, "nonfinite": DONE_NONFINITE,
+             "force": DONE_FORCE, "timeout": DONE_TIMEOUT}
+
+
+class ObservationConfig(C.Structure):
+    """sai2b_observation_config; load_library() checks the size against sai2b_sizeof_observation_config()"""
+
+    _fields_ = [
+        ("blocks", _i),
+        ("task_mask", _i),
+        ("task_blocks", _i),
+        ("criteria", _i),
+        ("success_task_mask", _i),
+        ("force_task_mask", _i),
+        ("max_episode_steps", _i),
+        ("reserved", _i),
+        ("pos_tolerance", _d),
+        ("ori_tolerance", _d),
+        ("joint_limit_margin", _d),
+        ("max_joint_speed", _d * MAX_DOF),
+        ("max_sensed_force", _d),
+    ]
+
+
 EXPORTS = [
     "sai2b_panda_model",
     "sai2b_model_merge_fixed_body",
@@ -263,6 +296,16 @@ EXPORTS = [
     "sai2b_clear_contact",
     "sai2b_get_contact",
     "sai2b_get_contact_state",
+    "sai2b_default_observation",
+    "sai2b_validate_observation",
+    "sai2b_sizeof_observation_config",
+    "sai2b_observation_config_layout",
+    "sai2b_set_observation",
+    "sai2b_clear_observation",
+    "sai2b_observation_rows",
+    "sai2b_observation_layout",
+    "sai2b_observe",
+    "sai2b_get_done_counts",
 ]
 
 _lib = None
@@ -364,5 +407,18 @@ def load_library():
     lib.sai2b_clear_contact.argtypes = [vp]
     lib.sai2b_get_contact.argtypes = [vp, P(ContactConfig), vp]
     lib.sai2b_get_contact_state.argtypes = [vp, vp, vp, vp, P(_i)]
+    lib.sai2b_default_observation.argtypes = [P(ObservationConfig)]
+    lib.sai2b_validate_observation.argtypes = [P(ObservationConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_observation_config.argtypes = []
+    lib.sai2b_observation_config_layout.argtypes = [P(ObservationConfig), _i, _i, _i, P(_i), P(_i), P(_i)]
+    lib.sai2b_set_observation.argtypes = [vp, P(ObservationConfig)]
+    lib.sai2b_clear_observation.argtypes = [vp]
+    lib.sai2b_observation_rows.argtypes = [vp]
+    lib.sai2b_observation_layout.argtypes = [vp, _i, _i, P(_i), P(_i)]
+    lib.sai2b_observe.argtypes = [vp, vp, vp, _i]
+    lib.sai2b_get_done_counts.argtypes = [vp, P(_i)]
+    if lib.sai2b_sizeof_observation_config() != C.sizeof(ObservationConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_observation_config is {lib.sai2b_sizeof_observation_config()} bytes in the library, "
+                           f"{C.sizeof(ObservationConfig)} in the ctypes mirror")
     _lib = lib
     return lib

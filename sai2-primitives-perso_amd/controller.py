@@ -310,6 +310,141 @@ class Controller:
         self._rc(self.lib.sai2b_get_contact_state(self.h, None, None, None, C.byref(n)))
         return n.value
 
+    # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
+    @staticmethod
+    def _flags(names, table, what):
+        """iterable of names (or an int of flags) -> the or of the flags"""
+        if isinstance(names, (int, np.integer)):
+            return int(names)
+        try:
+            return sum({table[n] for n in names})
+        except KeyError as e:
+            raise ValueError(f"unknown {what} {e.args[0]!r}: one of {sorted(table)}") from None
+
+    @staticmethod
+    def _task_bits(tasks):
+        if isinstance(tasks, (int, np.integer)) and not isinstance(tasks, bool):
+            tasks = (tasks,)
+        bits = 0
+        for t in tasks:
+            if not 0 <= int(t) < 31:
+                raise ValueError(f"task index {t} out of range")
+            bits |= 1 << int(t)
+        return bits
+
+    def observation_config(self, blocks=(), tasks=(), task_blocks=(), success_tasks=None, pos_tolerance=0.0, ori_tolerance=0.0,
+                           joint_limit_margin=None, max_joint_speed=None, nonfinite=False, force_tasks=None, max_sensed_force=0.0,
+                           max_episode_steps=None):
+        """-> ObservationConfig. blocks: names of _abi.OBS_BLOCKS ('q', 'dq', 'tau', 'limit_margin', 'episode_step', 'contact');
+        tasks: indices of the observed MotionForceTasks; task_blocks: names of _abi.OBS_TASK_BLOCKS ('pose', 'twist', 'error',
+        'sensed'). A criterion is enabled by giving its argument: success_tasks (with pos_tolerance / ori_tolerance),
+        joint_limit_margin, max_joint_speed (scalar or [dof]), nonfinite=True, force_tasks (with max_sensed_force),
+        max_episode_steps."""
+        cfg = _abi.ObservationConfig()
+        rc = self.lib.sai2b_default_observation(C.byref(cfg))
+        if rc:
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        cfg.blocks = self._flags(blocks, _abi.OBS_BLOCKS, "block")
+        cfg.task_mask = self._task_bits(tasks)
+        cfg.task_blocks = self._flags(task_blocks, _abi.OBS_TASK_BLOCKS, "task block")
+        crit = 0
+        if success_tasks is not None:
+            crit |= _abi.DONE_SUCCESS
+            cfg.success_task_mask = self._task_bits(success_tasks)
+        cfg.pos_tolerance, cfg.ori_tolerance = float(pos_tolerance), float(ori_tolerance)
+        if joint_limit_margin is not None:
+            crit |= _abi.DONE_JOINT_LIMIT
+            cfg.joint_limit_margin = float(joint_limit_margin)
+        if max_joint_speed is not None:
+            crit |= _abi.DONE_SPEED
+            v = np.broadcast_to(np.asarray(max_joint_speed, dtype=np.float64), (self.dof,))
+            for i in range(self.dof):
+                cfg.max_joint_speed[i] = float(v[i])
+        if nonfinite:
+            crit |= _abi.DONE_NONFINITE
+        if force_tasks is not None:
+            crit |= _abi.DONE_FORCE
+            cfg.force_task_mask = self._task_bits(force_tasks)
+        cfg.max_sensed_force = float(max_sensed_force)
+        if max_episode_steps is not None:
+            crit |= _abi.DONE_TIMEOUT
+            cfg.max_episode_steps = int(max_episode_steps)
+        cfg.criteria = crit
+        return cfg
+
+    def set_observation(self, cfg=None, **kwargs):
+        """configure what observe() stores and which criteria end an episode (an ObservationConfig, or the arguments of
+        observation_config); every robot's episode counter restarts at zero"""
+        if cfg is None:
+            cfg = self.observation_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_observation: an ObservationConfig or keyword arguments, not both")
+        self._rc(self.lib.sai2b_set_observation(self.h, C.byref(cfg)))
+
+    def clear_observation(self):
+        self._rc(self.lib.sai2b_clear_observation(self.h))
+
+    def observation_rows(self):
+        """rows of the configured observation; -1 without one"""
+        return self.lib.sai2b_observation_rows(self.h)
+
+    def observation_layout(self):
+        """dict name -> slice of rows of observe()'s output: the global blocks by their names, the per-task blocks as
+        'pose0', 'twist0', ... with the task index; only what the configuration stores"""
+        first, n = C.c_int(), C.c_int()
+        out = {}
+        for name, flag in _abi.OBS_BLOCKS.items():
+            self._rc(self.lib.sai2b_observation_layout(self.h, flag, -1, C.byref(first), C.byref(n)))
+            if n.value:
+                out[name] = slice(first.value, first.value + n.value)
+        for t in range(len(self.tasks)):
+            for name, flag in _abi.OBS_TASK_BLOCKS.items():
+                self._rc(self.lib.sai2b_observation_layout(self.h, flag, t, C.byref(first), C.byref(n)))
+                if n.value:
+                    out[f"{name}{t}"] = slice(first.value, first.value + n.value)
+        return out
+
+    def observe(self, out=None, done=None):
+        """one launch -> (rows [observation_rows()][B] float64, done [B] uint8 with the _abi.DONE_* bits). out / done: numpy
+        arrays or torch CUDA tensors to fill (both of one kind; a torch pair never leaves the device and nothing synchronises),
+        None: a new numpy array, False: not wanted (None is returned in its place)"""
+        rows = self.observation_rows()
+        if rows < 0:
+            raise ValueError("sai2b_observe: no observation is configured (sai2b_set_observation)")
+        given = [o for o in (out, done) if o is not None and o is not False]
+        dev = self._dev(*given)
+        if dev and (out is None or done is None):
+            raise ValueError("observe: with a device tensor pass the other argument as a tensor too, or False")
+        if out is None:
+            out = np.empty((rows, self.B))
+        if done is None:
+            done = np.zeros(self.B, dtype=np.uint8)
+        po = pd = None
+        if out is not False:
+            if hasattr(out, "data_ptr"):
+                po, _ = self._in(out, rows)
+            else:
+                if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (rows, self.B)):
+                    raise ValueError(f"out must be a C-contiguous float64 array of shape ({rows}, {self.B})")
+                po = C.c_void_p(out.ctypes.data)
+        if done is not False:
+            if hasattr(done, "data_ptr"):
+                if str(done.dtype) != "torch.uint8":
+                    raise ValueError("done must be a uint8 tensor (it receives the reason bits)")
+                pd, _ = self._mask(done)
+            else:
+                if not (isinstance(done, np.ndarray) and done.dtype == np.uint8 and done.flags.c_contiguous and done.shape == (self.B,)):
+                    raise ValueError(f"done must be a C-contiguous uint8 array of shape ({self.B},)")
+                pd = C.c_void_p(done.ctypes.data)
+        self._rc(self.lib.sai2b_observe(self.h, po, pd, dev))
+        return (None if out is False else out), (None if done is False else done)
+
+    def done_counts(self):
+        """of the last observe(): dict reason name -> robots with that bit, and 'any' -> robots with a non-zero byte"""
+        c = (C.c_int * 7)()
+        self._rc(self.lib.sai2b_get_done_counts(self.h, c))
+        return dict(zip(list(_abi.DONE_BITS) + ["any"], list(c)))
+
     # -- the path
     def reinitialize(self):
         self._rc(self.lib.sai2b_reinitialize(self.h))

@@ -475,6 +475,18 @@ DI void sigma_pair(const DevTask& t, int blk, int dim, const real* axis, const r
 	mm_nt<3, 3, 3>(T, Pb, sp);
 }
 
+// Sensed wrench at the control point in the world frame (MotionForceTask.cpp:805-828) from the sensor-frame force sfc and
+// moment smc of the task's sensed rows; R: the compliant frame's orientation in the world
+DI void sensed_wrench_world(const DevTask& t, const real* R, const real* sfc, const real* smc, real* fs_w, real* ms_w) {
+	real fs_c[3], ms_c[3], tmp[3];
+	mv3(t.sensor_rot, sfc, fs_c);
+	mv3(t.sensor_rot, smc, ms_c);
+	cross3(t.sensor_pos, fs_c, tmp);
+	UNROLL for (int k = 0; k < 3; k++) ms_c[k] += tmp[k];
+	mv3(R, fs_c, fs_w);
+	mv3(R, ms_c, ms_w);
+}
+
 // Where a task's per-robot input rows come from: row k of `law_goals`, `goals`, `sensed` and `state`. HbmRows
 // reads the batched arrays; the fast kernel's StagedRows (sai2b_fast.hpp) reads an LDS image of most of them.
 struct HbmRows {

@@ -110,6 +110,16 @@ struct sai2b_ctx {
 	double* contact_rows = nullptr;
 	sai2b_contact_config contact_cfg = {};
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
+	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
+	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
+	// obs_done stage the results of a call with host arguments (obs_out_rows: rows obs_out has room for)
+	bool obs_on = false;
+	sai2b_observation_config obs_cfg = {};
+	sai2b::ObsParams obs;
+	int obs_rows = 0, obs_out_rows = 0;
+	int *obs_steps = nullptr, *obs_counts = nullptr;
+	double* obs_out = nullptr;
+	unsigned char* obs_done = nullptr;
 	// sai2b_reinitialize_robots / sai2b_reset_robots with host arguments: the [B]-byte mask and the [2 * dof][B] q, dq rows are
 	// staged here, created on first use
 	unsigned char* reset_mask = nullptr;
@@ -1919,6 +1929,183 @@ extern "C" int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* no
 		HIP_TRY(ctx, hipMemcpyAsync(robots_in_contact, ctx->h_params.contact_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	}
+	return SAI2B_OK;
+}
+
+// ---- observations and episode-end flags ----
+namespace {
+constexpr int OBS_ALL_BLOCKS = SAI2B_OBS_Q | SAI2B_OBS_DQ | SAI2B_OBS_TAU | SAI2B_OBS_LIMIT_MARGIN | SAI2B_OBS_EPISODE_STEP | SAI2B_OBS_CONTACT;
+constexpr int OBS_ALL_TASK_BLOCKS = SAI2B_OBS_POSE | SAI2B_OBS_TWIST | SAI2B_OBS_ERROR | SAI2B_OBS_SENSED;
+constexpr int OBS_ALL_CRITERIA = (1 << SAI2B_DONE_REASONS) - 1;
+constexpr int OBS_TASK_BLOCK_ROWS[sai2b::OBS_TASK_BLOCKS] = {12, 6, 8, 6};	// POSE, TWIST, ERROR, SENSED
+// first rows of the global blocks and of every observed task's blocks; returns the rows of the whole observation
+int observation_rows(const sai2b_observation_config& c, int row_global[sai2b::OBS_GLOBAL_BLOCKS], int row_task[SAI2B_MAX_TASKS]) {
+	const int global_rows[sai2b::OBS_GLOBAL_BLOCKS] = {N, N, N, 1, 1, sai2b::CONTACT_STATUS_ROWS};
+	int rows = 0;
+	for (int k = 0; k < sai2b::OBS_GLOBAL_BLOCKS; k++) {
+		row_global[k] = (c.blocks >> k) & 1 ? rows : -1;
+		if ((c.blocks >> k) & 1) rows += global_rows[k];
+	}
+	int per_task = 0;
+	for (int k = 0; k < sai2b::OBS_TASK_BLOCKS; k++)
+		if ((c.task_blocks >> k) & 1) per_task += OBS_TASK_BLOCK_ROWS[k];
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		const bool on = ((c.task_mask >> t) & 1) && per_task > 0;
+		row_task[t] = on ? rows : -1;
+		if (on) rows += per_task;
+	}
+	return rows;
+}
+int single_bit_index(int v, int n_bits) {
+	for (int k = 0; k < n_bits; k++)
+		if (v == 1 << k) return k;
+	return -1;
+}
+std::string observation_config_error(const sai2b_observation_config* c, const sai2b_task_config* tasks, int n_tasks) {
+	if (!c) return "observation: null config";
+	if (c->blocks & ~OBS_ALL_BLOCKS) return "observation: unknown bits in blocks";
+	if (c->task_blocks & ~OBS_ALL_TASK_BLOCKS) return "observation: unknown bits in task_blocks";
+	if (c->criteria & ~OBS_ALL_CRITERIA) return "observation: unknown bits in criteria";
+	const int masks[3] = {c->task_mask, c->success_task_mask, c->force_task_mask};
+	const char* mask_name[3] = {"task_mask", "success_task_mask", "force_task_mask"};
+	for (int m = 0; m < 3; m++)
+		for (int t = 0; t < 32; t++)
+			if (((unsigned)masks[m] >> t) & 1u)
+				if (!tasks || t >= n_tasks || t >= SAI2B_MAX_TASKS || tasks[t].type != SAI2B_MOTION_FORCE_TASK)
+					return std::string("observation: ") + mask_name[m] + " selects a task that is not a MotionForceTask";
+	const double thr[4] = {c->pos_tolerance, c->ori_tolerance, c->joint_limit_margin, c->max_sensed_force};
+	for (double v : thr)
+		if (!std::isfinite(v) || v < 0) return "observation: thresholds must be finite and >= 0";
+	for (int i = 0; i < N; i++)
+		if (!std::isfinite(c->max_joint_speed[i]) || c->max_joint_speed[i] < 0) return "observation: max_joint_speed must be finite and >= 0";
+	if (c->max_episode_steps < 0) return "observation: max_episode_steps must be >= 0";
+	if ((c->criteria & SAI2B_DONE_TIMEOUT) && c->max_episode_steps < 1) return "observation: TIMEOUT needs max_episode_steps >= 1";
+	if ((c->criteria & SAI2B_DONE_SUCCESS) && !c->success_task_mask) return "observation: SUCCESS needs a task in success_task_mask";
+	if ((c->criteria & SAI2B_DONE_FORCE) && !c->force_task_mask) return "observation: FORCE needs a task in force_task_mask";
+	return "";
+}
+}  // namespace
+extern "C" int sai2b_default_observation(sai2b_observation_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_observation: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_observation_config(void) { return (int)sizeof(sai2b_observation_config); }
+extern "C" int sai2b_validate_observation(const sai2b_observation_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+										  char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? observation_config_error(cfg, tasks, n_tasks) : "observation: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_observation_config_layout(const sai2b_observation_config* cfg, int robot_dof, int block, int task, int* first_row,
+											   int* n_rows, int* total_rows) {
+	if (!cfg || robot_dof != N) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_observation_config_layout: bad arguments");
+	const int k = single_bit_index(block, task < 0 ? sai2b::OBS_GLOBAL_BLOCKS : sai2b::OBS_TASK_BLOCKS);
+	if (k < 0 || task < -1 || task >= SAI2B_MAX_TASKS)
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_observation_config_layout: block must be one known flag and task -1 or a task index");
+	int row_global[sai2b::OBS_GLOBAL_BLOCKS], row_task[SAI2B_MAX_TASKS];
+	const int rows = observation_rows(*cfg, row_global, row_task);
+	int first = -1, n = 0;
+	if (task < 0) {
+		const int global_rows[sai2b::OBS_GLOBAL_BLOCKS] = {N, N, N, 1, 1, sai2b::CONTACT_STATUS_ROWS};
+		if (row_global[k] >= 0) first = row_global[k], n = global_rows[k];
+	} else if (row_task[task] >= 0 && ((cfg->task_blocks >> k) & 1)) {
+		first = row_task[task], n = OBS_TASK_BLOCK_ROWS[k];
+		for (int j = 0; j < k; j++)
+			if ((cfg->task_blocks >> j) & 1) first += OBS_TASK_BLOCK_ROWS[j];
+	}
+	if (first_row) *first_row = first;
+	if (n_rows) *n_rows = n;
+	if (total_rows) *total_rows = rows;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_observation(sai2b_ctx* ctx, const sai2b_observation_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_observation: null ctx");
+	const std::string err = observation_config_error(cfg, ctx->cfg, ctx->T);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	const size_t B = ctx->B;
+	if (!ctx->obs_steps && (rc = dev_alloc(ctx, &ctx->obs_steps, B))) return rc;
+	if (!ctx->obs_counts && (rc = dev_alloc(ctx, &ctx->obs_counts, (size_t)sai2b::OBS_COUNTS))) return rc;
+	// a new configuration starts every robot's episode (stream-ordered behind observes already enqueued)
+	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_steps, 0, B * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, sai2b::OBS_COUNTS * sizeof(int), ctx->stream));
+	sai2b::ObsParams o;
+	o.blocks = cfg->blocks, o.task_mask = cfg->task_mask, o.task_blocks = cfg->task_blocks;
+	o.criteria = cfg->criteria, o.success_mask = cfg->success_task_mask, o.force_mask = cfg->force_task_mask;
+	o.max_steps = cfg->max_episode_steps;
+	o.pos_tol = cfg->pos_tolerance, o.ori_tol = cfg->ori_tolerance, o.limit_margin = cfg->joint_limit_margin, o.max_force = cfg->max_sensed_force;
+	for (int i = 0; i < N; i++) o.max_speed[i] = cfg->max_joint_speed[i];
+	ctx->obs_rows = observation_rows(*cfg, o.row_global, o.row_task);
+	ctx->obs = o;
+	ctx->obs_cfg = *cfg;
+	ctx->obs_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_observation(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_observation: null ctx");
+	ctx->obs_on = false;
+	ctx->obs_rows = 0;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_observation_rows(sai2b_ctx* ctx) { return ctx && ctx->obs_on ? ctx->obs_rows : -1; }
+extern "C" int sai2b_observation_layout(sai2b_ctx* ctx, int block, int task, int* first_row, int* n_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_observation_layout: null ctx");
+	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_observation_layout: no observation is configured (sai2b_set_observation)");
+	const int rc = sai2b_observation_config_layout(&ctx->obs_cfg, N, block, task, first_row, n_rows, nullptr);
+	return rc ? set_error(ctx, rc, g_error) : SAI2B_OK;
+}
+extern "C" int sai2b_observe(sai2b_ctx* ctx, double* out, unsigned char* done, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_observe: null ctx");
+	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_observe: no observation is configured (sai2b_set_observation)");
+	int rc = flush_update(ctx);	 // a deferred model update happens before anything is observed
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if ((rc = upload_params(ctx))) return rc;
+	const size_t B = ctx->B;
+	const bool want_out = out && ctx->obs_rows > 0;
+	double* d_out = want_out ? out : nullptr;
+	unsigned char* d_done = done;
+	if (on_device) {
+		// device results are written on the ctx stream: what the caller's stream still does with those buffers comes first
+		if ((want_out || done) && (rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (want_out) {
+			if (ctx->obs_out_rows < ctx->obs_rows) {  // a configuration with more rows: the smaller staging buffer goes
+				if (ctx->obs_out) {
+					HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)ctx->obs_out), ctx->allocs.end());
+					HIP_TRY(ctx, hipFree(ctx->obs_out));
+					ctx->obs_out = nullptr, ctx->obs_out_rows = 0;
+				}
+				if ((rc = dev_alloc(ctx, &ctx->obs_out, (size_t)ctx->obs_rows * B))) return rc;
+				ctx->obs_out_rows = ctx->obs_rows;
+			}
+			d_out = ctx->obs_out;
+		}
+		if (done) {
+			if (!ctx->obs_done && (rc = dev_alloc(ctx, &ctx->obs_done, B))) return rc;
+			d_done = ctx->obs_done;
+		}
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, sai2b::OBS_COUNTS * sizeof(int), ctx->stream));
+	if (sai2b::launch_observe(ctx->d_params, ctx->B, ctx->obs, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
+		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_observe: launch failed");
+	ctx->launches++;
+	if (on_device) return (want_out || done) ? caller_after_read(ctx) : SAI2B_OK;
+	if (want_out) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)ctx->obs_rows * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (done) HIP_TRY(ctx, hipMemcpyAsync(done, d_done, B, hipMemcpyDeviceToHost, ctx->stream));
+	if (want_out || done) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_done_counts(sai2b_ctx* ctx, int counts[7]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_done_counts: bad arguments");
+	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_done_counts: no observation is configured (sai2b_set_observation)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->obs_counts, sai2b::OBS_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }
 

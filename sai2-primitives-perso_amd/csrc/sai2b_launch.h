@@ -91,4 +91,21 @@ int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, i
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
 int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream);
 
+// sai2b_observe (sai2b_observe.hip: observe_kernel): the kernel's own parameter block, passed by value as a kernel argument
+// (batch-uniform, read with scalar loads); DevParams is not touched by the feature. Rows are first rows of the [rows][B]
+// output, -1 = block not stored.
+constexpr int OBS_GLOBAL_BLOCKS = 6, OBS_TASK_BLOCKS = 4, OBS_COUNTS = SAI2B_DONE_REASONS + 1;
+struct ObsParams {
+	int blocks = 0, task_mask = 0, task_blocks = 0;	 // what is stored (sai2b_observation_config)
+	int criteria = 0, success_mask = 0, force_mask = 0, max_steps = 0;
+	int row_global[OBS_GLOBAL_BLOCKS] = {-1, -1, -1, -1, -1, -1};  // Q, DQ, TAU, LIMIT_MARGIN, EPISODE_STEP, CONTACT
+	int row_task[SAI2B_MAX_TASKS] = {-1, -1, -1, -1};			   // first row of task t's blocks (stored in flag order)
+	double pos_tol = 0, ori_tol = 0, limit_margin = 0, max_force = 0;
+	double max_speed[N] = {};
+};
+// out [rows][B] or NULL, done [B] bytes or NULL, steps [B] episode counters, counts [OBS_COUNTS] zeroed by the caller on the
+// stream ahead of the launch
+int launch_observe(const DevParams* d_params, int B, const ObsParams& obs, double* out, unsigned char* done, int* steps, int* counts,
+				   hipStream_t stream);
+
 }  // namespace sai2b

@@ -352,17 +352,12 @@ __global__ __launch_bounds__(64) void mft_status_kernel(const DevParams* __restr
 	mv3(sp, e, se);
 	mv3(so, oe, soe);
 	// sensed wrench at the control point, world frame (MotionForceTask.cpp:805-828)
-	real sfc[3], smc[3], fs_c[3], ms_c[3], tmp[3], fs_w[3], ms_w[3];
+	real sfc[3], smc[3], fs_w[3], ms_w[3];
 	UNROLL for (int k = 0; k < 3; k++) {
 		sfc[k] = ld(t.sensed, k, B, b);
 		smc[k] = ld(t.sensed, 3 + k, B, b);
 	}
-	mv3(t.sensor_rot, sfc, fs_c);
-	mv3(t.sensor_rot, smc, ms_c);
-	cross3(t.sensor_pos, fs_c, tmp);
-	UNROLL for (int k = 0; k < 3; k++) ms_c[k] += tmp[k];
-	mv3(R, fs_c, fs_w);
-	mv3(R, ms_c, ms_w);
+	sensed_wrench_world(t, R, sfc, smc, fs_w, ms_w);
 	UNROLL for (int k = 0; k < 3; k++) {
 		st(out, k, B, b, x[k]);
 		st(out, 12 + k, B, b, fs_w[k]);

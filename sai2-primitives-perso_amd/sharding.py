@@ -70,6 +70,22 @@ def reset_robots(ctrl, world, rank, mask, q=None, dq=None):
     ctrl.reset_robots(*[shard_rows(a, world, rank) for a in (mask, q, dq)])
 
 
+def observe(ctrl, world, rank, out=None, done=None):
+    """Controller.observe on this rank's shard, written into this rank's columns [lo, hi) of host arrays given for the whole
+    batch: out [rows][global_batch] float64, done [global_batch] uint8 (one of the two may be None: not wanted). -> (lo, hi)"""
+    if out is None and done is None:
+        raise ValueError("observe: give out, done or both (the arrays of the whole batch this rank's columns are written into)")
+    lo, hi = shard_bounds((out if out is not None else done).shape[-1], world, rank)
+    if hi - lo != ctrl.B:
+        raise ValueError(f"rank {rank} owns {hi - lo} robots of the arrays given, its controller has {ctrl.B}")
+    part_out, part_done = ctrl.observe(out=None if out is not None else False, done=None if done is not None else False)
+    if out is not None:
+        out[:, lo:hi] = part_out
+    if done is not None:
+        done[lo:hi] = part_done
+    return lo, hi
+
+
 def node_throughput(robots_per_rank, world, steps, elapsed_max):
     """whole-job control-ticks/sec: every rank's robots x steps over the slowest rank's time"""
     return robots_per_rank * world * steps / elapsed_max
