@@ -1521,7 +1521,93 @@ public:
 		return n;
 	}
 
+	// Joint dynamics of the plant (sai2b.h "joint dynamics of the simulated plant"): per robot and joint, [dof][B] each, empty =
+	// that effect off: armature (>= 0), viscous damping (>= 0), Coulomb friction level (>= 0), torque limit (> 0, +inf: none),
+	// lower and upper joint limit (q_lower < q_upper, -inf / +inf: none). Batch-uniform per joint, one value for all joints or
+	// dof values: stop_stiffness (>= 0), stop_damping (>= 0, Hunt-Crossley form), friction_velocity_eps (> 0). Takes effect at
+	// the next integrate(). std::invalid_argument on what sai2b_set_joint_dynamics rejects.
+	struct JointDynamics {
+		Batch armature, damping, friction, torque_limit, q_lower, q_upper;
+		std::vector<double> stop_stiffness = {0.0}, stop_damping = {0.0}, friction_velocity_eps = {1e-2};
+	};
+	void setJointDynamics(const JointDynamics& jd) {
+		checkJointDynamicsArguments(_dof, (size_t)sai2b_batch(_c), jd);
+		const sai2b_joint_dynamics_config cfg = jointDynamicsConfig(_dof, jd);
+		auto p = [](const Batch& a) { return a.empty() ? nullptr : a.data(); };
+		detail::check(_c, sai2b_set_joint_dynamics(_c, &cfg, p(jd.armature), p(jd.damping), p(jd.friction), p(jd.torque_limit), p(jd.q_lower),
+												   p(jd.q_upper), 0));
+	}
+	// torque limits and joint limits of the robot's model (effort, q_lower, q_upper of sai2b_robot_model) for every robot of the
+	// batch; what else `jd` sets is kept, its own torque_limit / q_lower / q_upper are replaced
+	void setJointDynamicsFromModel(const BatchedRobotModel& robot) { setJointDynamicsFromModel(robot, JointDynamics()); }
+	void setJointDynamicsFromModel(const BatchedRobotModel& robot, JointDynamics jd) {
+		if (robot.dof() != _dof) throw std::invalid_argument("setJointDynamicsFromModel: the model is not this simulation's robot");
+		const size_t B = (size_t)sai2b_batch(_c);
+		const sai2b_robot_model& m = robot.model();
+		jd.torque_limit.assign((size_t)_dof * B, 0.0), jd.q_lower.assign((size_t)_dof * B, 0.0), jd.q_upper.assign((size_t)_dof * B, 0.0);
+		for (int i = 0; i < _dof; i++)
+			for (size_t b = 0; b < B; b++)
+				jd.torque_limit[i * B + b] = m.effort[i], jd.q_lower[i * B + b] = m.q_lower[i], jd.q_upper[i * B + b] = m.q_upper[i];
+		setJointDynamics(jd);
+	}
+	// What setJointDynamics checks before the device is touched (the conditions of sai2b_set_joint_dynamics on host arrays, plus
+	// the shapes): std::invalid_argument. Public and static so that callers, and tests without a device, can ask ahead.
+	static void checkJointDynamicsArguments(const int dof, const size_t B, const JointDynamics& jd) {
+		const size_t NB = (size_t)dof * B;
+		for (const Batch* a : {&jd.armature, &jd.damping, &jd.friction, &jd.torque_limit, &jd.q_lower, &jd.q_upper})
+			if (!a->empty() && a->size() != NB) throw std::invalid_argument("setJointDynamics: every row must be [dof][B] or empty");
+		for (const std::vector<double>* v : {&jd.stop_stiffness, &jd.stop_damping, &jd.friction_velocity_eps})
+			if (v->size() != 1 && v->size() != (size_t)dof)
+				throw std::invalid_argument("setJointDynamics: stop_stiffness, stop_damping and friction_velocity_eps take one value or dof values");
+		const sai2b_joint_dynamics_config cfg = jointDynamicsConfig(dof, jd);
+		char msg[256];
+		if (sai2b_validate_joint_dynamics(&cfg, dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(std::string("setJointDynamics: ") + msg);
+		for (const Batch* a : {&jd.armature, &jd.damping, &jd.friction})
+			for (const double v : *a)
+				if (!std::isfinite(v) || v < 0) throw std::invalid_argument("setJointDynamics: armature, damping and friction must be finite and >= 0");
+		for (const double v : jd.torque_limit)
+			if (!(v > 0)) throw std::invalid_argument("setJointDynamics: torque_limit must be > 0 (+inf: none)");
+		for (size_t i = 0; i < NB; i++) {
+			const double lo = jd.q_lower.empty() ? -INFINITY : jd.q_lower[i], hi = jd.q_upper.empty() ? INFINITY : jd.q_upper[i];
+			if (std::isnan(lo) || std::isnan(hi)) throw std::invalid_argument("setJointDynamics: q_lower and q_upper must not be NaN");
+			if (!(lo < hi)) throw std::invalid_argument("setJointDynamics: q_lower must be below q_upper");
+		}
+	}
+	void clearJointDynamics() { detail::check(_c, sai2b_clear_joint_dynamics(_c)); }
+	struct JointDynamicsState {
+		Batch applied_torque, stop_torque, dissipative_torque;	// [dof][B]: the saturated command, sl - su and -g dq at the final state
+		int robots_saturated = 0, robots_at_stop = 0;
+	};
+	JointDynamicsState getJointDynamicsState() const {
+		const size_t NB = (size_t)_dof * sai2b_batch(_c);
+		JointDynamicsState s;
+		s.applied_torque.resize(NB), s.stop_torque.resize(NB), s.dissipative_torque.resize(NB);
+		detail::check(_c, sai2b_get_joint_dynamics_state(_c, s.applied_torque.data(), s.stop_torque.data(), s.dissipative_torque.data(),
+														 &s.robots_saturated, &s.robots_at_stop));
+		return s;
+	}
+	int robotsSaturated() const {
+		int n = 0;
+		detail::check(_c, sai2b_get_joint_dynamics_state(_c, nullptr, nullptr, nullptr, &n, nullptr));
+		return n;
+	}
+	int robotsAtStop() const {
+		int n = 0;
+		detail::check(_c, sai2b_get_joint_dynamics_state(_c, nullptr, nullptr, nullptr, nullptr, &n));
+		return n;
+	}
+
 private:
+	static sai2b_joint_dynamics_config jointDynamicsConfig(const int dof, const JointDynamics& jd) {
+		sai2b_joint_dynamics_config cfg = {};
+		for (int i = 0; i < SAI2B_MAX_DOF; i++) cfg.friction_velocity_eps[i] = 1e-2;
+		for (int i = 0; i < dof && i < SAI2B_MAX_DOF; i++) {
+			cfg.stop_stiffness[i] = jd.stop_stiffness[jd.stop_stiffness.size() == 1 ? 0 : i];
+			cfg.stop_damping[i] = jd.stop_damping[jd.stop_damping.size() == 1 ? 0 : i];
+			cfg.friction_velocity_eps[i] = jd.friction_velocity_eps[jd.friction_velocity_eps.size() == 1 ? 0 : i];
+		}
+		return cfg;
+	}
 	void setSensor(const int task) {
 		if (_has_contact) {
 			sai2b_contact_config cfg = _contact;

@@ -309,8 +309,9 @@ int sai2b_reinitialize_robots(sai2b_ctx* ctx, int task, const unsigned char* mas
  * beyond that are this library's definition (the reference has no batch, and its reInitializeTask leaves the observer
  * alone): the selected robots' passivity observers, where a task has one, are re-initialised
  * (POPCExplicitForceControl.cpp:10-22), and their columns of SAI2B_BUF_TAU are zeroed, so that a simulation step on the
- * stored torques does not push a fresh robot with its old episode's. Payload rows, contact rows and the contact-state
- * outputs are kept for every robot (environment, not episode). All pointers host, or all device (on_device). */
+ * stored torques does not push a fresh robot with its old episode's. Payload rows, contact rows, the contact-state
+ * outputs, the joint-dynamics rows and their status are kept for every robot (environment, not episode). All pointers
+ * host, or all device (on_device). */
 int sai2b_reset_robots(sai2b_ctx* ctx, const unsigned char* mask, const double* q, const double* dq, int on_device);
 
 /* RobotController::updateControllerTaskModels (RobotController.cpp:53-60) */
@@ -389,7 +390,13 @@ enum sai2b_buffer {
 	/* the plant's contact rows (sai2b_set_contact), [9][B] = plane point 3, unit normal 3, stiffness, damping, friction. NULL
 	 * until a contact has been set (and after it is cleared). A device-resident producer may rewrite the rows between steps,
 	 * ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
-	SAI2B_BUF_CONTACT = 10
+	SAI2B_BUF_CONTACT = 10,
+	/* the plant's joint-dynamics rows (sai2b_set_joint_dynamics), [6][dof][B] = armature, damping, friction, torque limit,
+	 * lower limit, upper limit, and what the last step left, [3][dof][B] = applied, stop and dissipative torque. NULL until
+	 * joint dynamics have been set (and after they are cleared). A device-resident producer may rewrite the rows between
+	 * steps, ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
+	SAI2B_BUF_JOINT_DYNAMICS = 11,
+	SAI2B_BUF_JOINT_DYNAMICS_STATE = 12
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -486,6 +493,60 @@ int sai2b_get_contact(sai2b_ctx* ctx, sai2b_contact_config* cfg, double* rows);
  * sum (x_k - x_c) x F_k (x_c: the control point of the sensor task, the contact link's origin without one),
  * *robots_in_contact = robots with some f_n > 0 (counted on the device). Zeros before the first step with a contact. */
 int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* normal_force, double* wrench_world, int* robots_in_contact);
+
+/* ------------------------------------------------------------------ joint dynamics of the simulated plant
+ * Armature, viscous damping, Coulomb friction, actuator saturation and joint stops inside sai2b_sim_step, different for every
+ * robot of the batch. Per robot and joint i, rows [dof][B] each: armature a_i >= 0 (reflected rotor inertia, kg m^2 for a
+ * revolute joint, kg for a prismatic one), damping d_i >= 0, Coulomb friction level f_i >= 0, torque limit t_i > 0 (+inf: none),
+ * lower and upper limit lo_i < hi_i (-inf / +inf: none). Batch-uniform, per joint (sai2b_joint_dynamics_config): stop stiffness
+ * k_i >= 0, stop damping c_i >= 0 (Hunt-Crossley form, s/rad or s/m) and the friction regularisation speed e_i > 0 (rad/s or
+ * m/s). One substep of length h from the state (q, dq) at its START, the commanded torque tau held over the period:
+ *     ts_i = min(max(tau_i, -t_i), t_i)                                  actuator saturation
+ *     sl_i = max(0, k_i max(0, lo_i - q_i) (1 - c_i dq_i))               lower stop, pushes +
+ *     su_i = max(0, k_i max(0, q_i - hi_i) (1 + c_i dq_i))               upper stop, pushes -
+ *     g_i  = d_i + f_i / sqrt(dq_i^2 + e_i^2)                            damping + regularised Coulomb friction as a
+ *                                                                        state-dependent damper: torque = -g_i dq_i
+ *     (M + diag(a) + h diag(g)) dq+ = (M + diag(a)) dq + h (ts + sl - su + tc - b)
+ *     q+ = q + h dq+
+ * M and b are the plant's (with its payload, if it has one), tc is the contact torque of the section above when a contact is
+ * set and zero otherwise. Every piece is continuous in the state. The dissipative term is taken at the NEW velocity
+ * (linear-implicit), so a large friction slope f / e or a large d on a light outer link does not limit the step; the stop
+ * spring is explicit, as the contact spring is. With a = d = f = 0, t = +inf and lo, hi = -/+inf the step is algebraically
+ * the one of a context without joint dynamics, dq += h M^-1 (tau - b), but not bit-equal to it: a context gets this kernel
+ * only after it asks for it. This law is this library's definition, not sai2-simulation's.
+ * SAI2B_OBS_LIMIT_MARGIN and SAI2B_DONE_JOINT_LIMIT keep reading the limits of the context's MODEL (sai2b_robot_model), not
+ * these rows; the tick kernels, the singularity handling and sai2b_get_bias never see joint dynamics. */
+typedef struct sai2b_joint_dynamics_config {
+	double stop_stiffness[SAI2B_MAX_DOF], stop_damping[SAI2B_MAX_DOF], friction_velocity_eps[SAI2B_MAX_DOF]; /* entries >= dof are ignored */
+} sai2b_joint_dynamics_config;
+/* host only: k = 0, c = 0, e = 1e-2 for every joint */
+int sai2b_default_joint_dynamics(sai2b_joint_dynamics_config* cfg, int robot_dof);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (a negative or non-finite stop_stiffness or
+ * stop_damping, a friction_velocity_eps that is not finite and > 0, among the first robot_dof entries) */
+int sai2b_validate_joint_dynamics(const sai2b_joint_dynamics_config* cfg, int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_joint_dynamics_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_joint_dynamics_config(void);
+/* armature, damping, friction, torque_limit, q_lower, q_upper: [dof][B] each; NULL = that effect off (zeros for armature,
+ * damping and friction, +inf for the torque limit, -inf / +inf for the limits). Host arrays are validated
+ * (SAI2B_INVALID_ARGUMENT: what sai2b_validate_joint_dynamics rejects, a negative or non-finite armature, damping or friction,
+ * a NaN limit, a torque limit that is not > 0, q_lower >= q_upper); DEVICE arrays (on_device != 0) are copied as they are and
+ * NOT inspected. Ordered on the ctx stream; takes effect at the next sai2b_sim_step. sai2b_reinitialize, sai2b_reset_robots and
+ * sai2b_reinitialize_robots keep the rows and the status (environment, not episode). A context that never sets joint
+ * dynamics, or has cleared them, launches the simulation kernel it would without this feature. */
+int sai2b_set_joint_dynamics(sai2b_ctx* ctx, const sai2b_joint_dynamics_config* cfg, const double* armature, const double* damping,
+							 const double* friction, const double* torque_limit, const double* q_lower, const double* q_upper,
+							 int on_device);
+/* back to the plant without joint dynamics (the rows are kept for a later set, the two buffer ids give NULL) */
+int sai2b_clear_joint_dynamics(sai2b_ctx* ctx);
+/* the configuration and the [6][dof][B] rows to the host (either may be NULL); without joint dynamics: the default
+ * configuration and the neutral rows (0, 0, 0, +inf, -inf, +inf) */
+int sai2b_get_joint_dynamics(sai2b_ctx* ctx, sai2b_joint_dynamics_config* cfg, double* rows);
+/* what the last sai2b_sim_step left, host arrays [dof][B], any NULL: the applied torque ts, and from the state after the last
+ * substep the stop torque sl - su and the dissipative torque -g_i dq_i. *robots_saturated = robots with some |tau_i| > t_i in
+ * that call, *robots_at_stop = robots with a non-zero stop torque at the final state (both counted on the device). Zeros
+ * before the first step with joint dynamics and after they are cleared. */
+int sai2b_get_joint_dynamics_state(sai2b_ctx* ctx, double* applied_torque, double* stop_torque, double* dissipative_torque,
+								   int* robots_saturated, int* robots_at_stop);
 
 /* ------------------------------------------------------------------ observations and episode-end flags
  * The missing link of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe(out, done), sai2b_reset_robots(done, ..):

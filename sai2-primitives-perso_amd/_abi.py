@@ -26,6 +26,9 @@ BUF_Q, BUF_DQ, BUF_TAU, BUF_GOALS, BUF_SENSED, BUF_STATE, BUF_TASK_N, BUF_TASK_N
 BUF_PAYLOAD, BUF_PLANT_PAYLOAD = 8, 9  # [10][B] per-robot payload rows of the controller / the plant (sai2b_set_link_payload)
 BUF_CONTACT = 10  # [9][B] contact rows of the plant: plane point 3, normal 3, stiffness, damping, friction (sai2b_set_contact)
 MAX_CONTACT_POINTS = 4
+BUF_JOINT_DYNAMICS = 11  # [6][dof][B] rows of the plant's joint dynamics (sai2b_set_joint_dynamics)
+BUF_JOINT_DYNAMICS_STATE = 12  # [3][dof][B]: applied, stop and dissipative torque of the last sim step
+JOINT_DYNAMICS_ROWS = ("armature", "damping", "friction", "torque_limit", "q_lower", "q_upper")
 PAYLOAD_CONTROLLER, PAYLOAD_PLANT, PAYLOAD_BOTH = 1, 2, 3  # enum sai2b_payload_target
 PAYLOAD_TARGETS = {"controller": PAYLOAD_CONTROLLER, "plant": PAYLOAD_PLANT, "both": PAYLOAD_BOTH}
 
@@ -224,6 +227,16 @@ class ObservationConfig(C.Structure):
     ]
 
 
+class JointDynamicsConfig(C.Structure):
+    """sai2b_joint_dynamics_config; load_library() checks the size against sai2b_sizeof_joint_dynamics_config()"""
+
+    _fields_ = [
+        ("stop_stiffness", _d * MAX_DOF),
+        ("stop_damping", _d * MAX_DOF),
+        ("friction_velocity_eps", _d * MAX_DOF),
+    ]
+
+
 EXPORTS = [
     "sai2b_panda_model",
     "sai2b_model_merge_fixed_body",
@@ -306,6 +319,13 @@ EXPORTS = [
     "sai2b_observation_layout",
     "sai2b_observe",
     "sai2b_get_done_counts",
+    "sai2b_default_joint_dynamics",
+    "sai2b_validate_joint_dynamics",
+    "sai2b_sizeof_joint_dynamics_config",
+    "sai2b_set_joint_dynamics",
+    "sai2b_clear_joint_dynamics",
+    "sai2b_get_joint_dynamics",
+    "sai2b_get_joint_dynamics_state",
 ]
 
 _lib = None
@@ -417,6 +437,16 @@ def load_library():
     lib.sai2b_observation_layout.argtypes = [vp, _i, _i, P(_i), P(_i)]
     lib.sai2b_observe.argtypes = [vp, vp, vp, _i]
     lib.sai2b_get_done_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_default_joint_dynamics.argtypes = [P(JointDynamicsConfig), _i]
+    lib.sai2b_validate_joint_dynamics.argtypes = [P(JointDynamicsConfig), _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_joint_dynamics_config.argtypes = []
+    lib.sai2b_set_joint_dynamics.argtypes = [vp, P(JointDynamicsConfig), vp, vp, vp, vp, vp, vp, _i]
+    lib.sai2b_clear_joint_dynamics.argtypes = [vp]
+    lib.sai2b_get_joint_dynamics.argtypes = [vp, P(JointDynamicsConfig), vp]
+    lib.sai2b_get_joint_dynamics_state.argtypes = [vp, vp, vp, vp, P(_i), P(_i)]
+    if lib.sai2b_sizeof_joint_dynamics_config() != C.sizeof(JointDynamicsConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_joint_dynamics_config is {lib.sai2b_sizeof_joint_dynamics_config()} bytes in the library, "
+                           f"{C.sizeof(JointDynamicsConfig)} in the ctypes mirror")
     if lib.sai2b_sizeof_observation_config() != C.sizeof(ObservationConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_observation_config is {lib.sai2b_sizeof_observation_config()} bytes in the library, "
                            f"{C.sizeof(ObservationConfig)} in the ctypes mirror")

@@ -133,6 +133,7 @@ class Controller:
         self.lib = _abi.load_library()
         self.B = int(batch)
         self.dof = int(model.dof)  # joints of the robot: the library routes to its build for that size
+        self.model = model
         self.tasks = list(tasks)
         arr = (TaskConfig * len(self.tasks))(*self.tasks)
         self.h = self.lib.sai2b_create(C.byref(model), arr, len(self.tasks), self.B, int(device))
@@ -308,6 +309,88 @@ class Controller:
     def robots_in_contact(self):
         n = C.c_int()
         self._rc(self.lib.sai2b_get_contact_state(self.h, None, None, None, C.byref(n)))
+        return n.value
+
+    # -- joint dynamics of the simulated plant (sai2b.h "joint dynamics of the simulated plant")
+    def joint_dynamics_config(self, stop_stiffness=0.0, stop_damping=0.0, friction_velocity_eps=1e-2):
+        """-> JointDynamicsConfig: each a scalar or [dof] (batch-uniform, per joint)"""
+        cfg = _abi.JointDynamicsConfig()
+        if self.lib.sai2b_default_joint_dynamics(C.byref(cfg), self.dof):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        for name, v in (("stop_stiffness", stop_stiffness), ("stop_damping", stop_damping), ("friction_velocity_eps", friction_velocity_eps)):
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (self.dof,)):
+                raise ValueError(f"{name}: expected a scalar or {self.dof} values")
+            getattr(cfg, name)[: self.dof] = [float(x) for x in np.broadcast_to(a, (self.dof,))]
+        msg = C.create_string_buffer(256)
+        if self.lib.sai2b_validate_joint_dynamics(C.byref(cfg), self.dof, msg, 256):
+            raise ValueError(msg.value.decode())
+        return cfg
+
+    def _joint_row(self, a, name):
+        """a scalar, [dof] or [dof][B] -> [dof][B] float64; a torch CUDA tensor [dof][B] passes as it is"""
+        if a is None or hasattr(a, "data_ptr"):
+            return a
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 1 and a.shape == (self.dof,):
+            a = a[:, None]
+        elif a.ndim not in (0, 2) or (a.ndim == 2 and a.shape != (self.dof, self.B)):
+            raise ValueError(f"{name}: expected a scalar, {self.dof} values or an array of shape ({self.dof}, {self.B})")
+        return np.ascontiguousarray(np.broadcast_to(a, (self.dof, self.B)))
+
+    def set_joint_dynamics(self, armature=None, damping=None, friction=None, torque_limit=None, q_lower=None, q_upper=None,
+                           stop_stiffness=0.0, stop_damping=0.0, friction_velocity_eps=1e-2, limits=None):
+        """every robot's own joints for sim_step: armature, damping, Coulomb friction level, torque limit and joint limits, each
+        a scalar, [dof] or [dof][B] (numpy; broadcast) or a torch CUDA tensor [dof][B]; None: that effect off.
+        torque_limit="model" takes the effort limits and limits="model" the q_lower / q_upper of the context's model.
+        stop_stiffness, stop_damping, friction_velocity_eps: scalars or [dof], batch-uniform; or a
+        JointDynamicsConfig as `stop_stiffness`"""
+        if isinstance(torque_limit, str) or isinstance(limits, str):
+            model = self.model
+            if isinstance(torque_limit, str):
+                if torque_limit != "model":
+                    raise ValueError("torque_limit must be an array or 'model'")
+                torque_limit = np.array(model.effort[: self.dof])
+            if isinstance(limits, str):
+                if limits != "model" or q_lower is not None or q_upper is not None:
+                    raise ValueError("limits must be 'model', without q_lower / q_upper")
+                q_lower, q_upper = np.array(model.q_lower[: self.dof]), np.array(model.q_upper[: self.dof])
+        elif limits is not None:
+            raise ValueError("limits must be 'model' or None")
+        if isinstance(stop_stiffness, _abi.JointDynamicsConfig):
+            cfg = stop_stiffness
+        else:
+            cfg = self.joint_dynamics_config(stop_stiffness, stop_damping, friction_velocity_eps)
+        objs = [self._joint_row(o, n) for o, n in zip((armature, damping, friction, torque_limit, q_lower, q_upper), _abi.JOINT_DYNAMICS_ROWS)]
+        ins = [self._in(o, self.dof) for o in objs]
+        self._rc(self.lib.sai2b_set_joint_dynamics(self.h, C.byref(cfg), *[p for p, _ in ins], self._dev(*objs)))
+
+    def clear_joint_dynamics(self):
+        self._rc(self.lib.sai2b_clear_joint_dynamics(self.h))
+
+    def get_joint_dynamics(self):
+        """-> (JointDynamicsConfig, rows [6][dof][B]); the defaults and the neutral rows when the plant has no joint dynamics"""
+        cfg, rows = _abi.JointDynamicsConfig(), np.empty((6, self.dof, self.B))
+        self._rc(self.lib.sai2b_get_joint_dynamics(self.h, C.byref(cfg), C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def get_joint_dynamics_state(self):
+        """what the last sim_step left: dict applied_torque, stop_torque, dissipative_torque [dof][B], robots_saturated,
+        robots_at_stop"""
+        ns, na = C.c_int(), C.c_int()
+        out = [np.empty((self.dof, self.B)) for _ in range(3)]
+        self._rc(self.lib.sai2b_get_joint_dynamics_state(self.h, *[C.c_void_p(x.ctypes.data) for x in out], C.byref(ns), C.byref(na)))
+        return dict(applied_torque=out[0], stop_torque=out[1], dissipative_torque=out[2], robots_saturated=ns.value,
+                    robots_at_stop=na.value)
+
+    def robots_saturated(self):
+        n = C.c_int()
+        self._rc(self.lib.sai2b_get_joint_dynamics_state(self.h, None, None, None, C.byref(n), None))
+        return n.value
+
+    def robots_at_stop(self):
+        n = C.c_int()
+        self._rc(self.lib.sai2b_get_joint_dynamics_state(self.h, None, None, None, None, C.byref(n)))
         return n.value
 
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
@@ -1679,3 +1762,40 @@ class BatchedSimulation:
 
     def getJointVelocities(self):
         return self._c._ctrl.get_state()[1]
+
+    # -- joint dynamics of the plant (Controller.set_joint_dynamics)
+    def setJointDynamics(self, *args, **kwargs):
+        self._c._ctrl.set_joint_dynamics(*args, **kwargs)
+
+    def clearJointDynamics(self):
+        self._c._ctrl.clear_joint_dynamics()
+
+    def getJointDynamicsState(self):
+        return self._c._ctrl.get_joint_dynamics_state()
+
+    # -- contact of the plant (Controller.set_contact); the force sensor writes the sensed rows of one MotionForceTask
+    def setContactPlanes(self, *args, **kwargs):
+        self._c._ctrl.set_contact(*args, **kwargs)
+
+    def clearContact(self):
+        self._c._ctrl.clear_contact()
+
+    def _sensor(self, task):
+        cfg, rows = self._c._ctrl.get_contact()
+        if cfg.n_points == 0:
+            raise ValueError("no contact is set (setContactPlanes)")
+        cfg.sensor_task = int(task)
+        self._c._ctrl.set_contact(cfg, None, rows[0:3], rows[3:6], rows[6], rows[7], rows[8])
+
+    def attachForceSensor(self, task):
+        """the MotionForceTask (index in the controller's hierarchy) whose sensed rows the simulated sensor writes"""
+        self._sensor(task)
+
+    def detachForceSensor(self):
+        self._sensor(-1)
+
+    def getContactState(self):
+        return self._c._ctrl.get_contact_state()
+
+    def robotsInContact(self):
+        return self._c._ctrl.robots_in_contact()

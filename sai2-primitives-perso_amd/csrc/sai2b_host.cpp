@@ -109,6 +109,13 @@ struct sai2b_ctx {
 	// created on first use; h_params.contact points at the rows while a contact is in force
 	double* contact_rows = nullptr;
 	sai2b_contact_config contact_cfg = {};
+	// joint dynamics of the plant (sai2b_set_joint_dynamics): the [6][dof][B] rows, the [3][dof][B] status rows and the two device
+	// counters, created on first use; joint_on: sai2b_sim_step launches sim_joint_kernel with `joint` as its argument
+	bool joint_on = false;
+	sai2b_joint_dynamics_config joint_cfg = {};
+	sai2b::JointParams joint;
+	double *joint_rows = nullptr, *joint_status = nullptr;
+	int* joint_counts = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -1619,6 +1626,8 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_PAYLOAD: return (void*)ctx->h_params.payload;
 		case SAI2B_BUF_PLANT_PAYLOAD: return (void*)ctx->h_params.plant_payload;
 		case SAI2B_BUF_CONTACT: return (void*)ctx->h_params.contact;
+		case SAI2B_BUF_JOINT_DYNAMICS: return ctx->joint_on ? (void*)ctx->joint_rows : nullptr;
+		case SAI2B_BUF_JOINT_DYNAMICS_STATE: return ctx->joint_on ? (void*)ctx->joint_status : nullptr;
 	}
 	return nullptr;
 }
@@ -1932,6 +1941,134 @@ extern "C" int sai2b_get_contact_state(sai2b_ctx* ctx, double* depth, double* no
 	return SAI2B_OK;
 }
 
+// ---- joint dynamics of the simulated plant ----
+extern "C" int sai2b_default_joint_dynamics(sai2b_joint_dynamics_config* cfg, int robot_dof) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_joint_dynamics: null config");
+	if (robot_dof != N) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "joint dynamics: this build serves another robot size");
+	std::memset(cfg, 0, sizeof(*cfg));
+	for (int i = 0; i < SAI2B_MAX_DOF; i++) cfg->friction_velocity_eps[i] = 1e-2;
+	return SAI2B_OK;
+}
+static std::string joint_dynamics_config_error(const sai2b_joint_dynamics_config* c) {
+	if (!c) return "joint dynamics: null config";
+	for (int i = 0; i < N; i++) {
+		if (!std::isfinite(c->stop_stiffness[i]) || c->stop_stiffness[i] < 0) return "joint dynamics: stop_stiffness must be finite and >= 0";
+		if (!std::isfinite(c->stop_damping[i]) || c->stop_damping[i] < 0) return "joint dynamics: stop_damping must be finite and >= 0";
+		if (!std::isfinite(c->friction_velocity_eps[i]) || !(c->friction_velocity_eps[i] > 0))
+			return "joint dynamics: friction_velocity_eps must be finite and > 0";
+	}
+	return "";
+}
+extern "C" int sai2b_validate_joint_dynamics(const sai2b_joint_dynamics_config* cfg, int robot_dof, char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? joint_dynamics_config_error(cfg) : "joint dynamics: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_joint_dynamics_config(void) { return (int)sizeof(sai2b_joint_dynamics_config); }
+extern "C" int sai2b_set_joint_dynamics(sai2b_ctx* ctx, const sai2b_joint_dynamics_config* cfg, const double* armature, const double* damping,
+										const double* friction, const double* torque_limit, const double* q_lower, const double* q_upper,
+										int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_dynamics: null ctx");
+	const std::string err = joint_dynamics_config_error(cfg);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_dynamics: " + err);
+	const size_t B = ctx->B, NB = (size_t)N * B;
+	if (!on_device) {
+		const double* nonneg[3] = {armature, damping, friction};
+		const char* nonneg_name[3] = {"armature", "damping", "friction"};
+		for (int k = 0; k < 3; k++)
+			for (size_t i = 0; nonneg[k] && i < NB; i++)
+				if (!std::isfinite(nonneg[k][i]) || nonneg[k][i] < 0)
+					return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string("sai2b_set_joint_dynamics: ") + nonneg_name[k] + " must be finite and >= 0");
+		for (size_t i = 0; torque_limit && i < NB; i++)
+			if (!(torque_limit[i] > 0)) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_dynamics: torque_limit must be > 0 (+inf: none)");
+		for (size_t i = 0; i < NB; i++) {
+			const double lo = q_lower ? q_lower[i] : -INFINITY, hi = q_upper ? q_upper[i] : INFINITY;
+			if (std::isnan(lo) || std::isnan(hi)) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_dynamics: q_lower and q_upper must not be NaN");
+			if (!(lo < hi)) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_dynamics: q_lower must be below q_upper");
+		}
+	}
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// three buffers, each created once: a failed allocation leaves the others for the next call, and the context as it was
+	if (!ctx->joint_rows && (rc = dev_alloc(ctx, &ctx->joint_rows, (size_t)sai2b::JOINT_ROWS * NB))) return rc;
+	if (!ctx->joint_status && (rc = dev_alloc(ctx, &ctx->joint_status, (size_t)sai2b::JOINT_STATUS_ROWS * NB))) return rc;
+	if (!ctx->joint_counts && (rc = dev_alloc(ctx, &ctx->joint_counts, (size_t)sai2b::JOINT_COUNTS))) return rc;
+	const double* src[sai2b::JOINT_ROWS] = {armature, damping, friction, torque_limit, q_lower, q_upper};
+	const double neutral[sai2b::JOINT_ROWS] = {0, 0, 0, INFINITY, -INFINITY, INFINITY};
+	std::vector<double> fill;
+	for (int r = 0; r < sai2b::JOINT_ROWS; r++) {
+		double* dst = ctx->joint_rows + (size_t)r * NB;
+		if (src[r]) {
+			if ((rc = copy_rows(ctx, dst, src[r], N, on_device))) return rc;
+		} else if (neutral[r] == 0) {
+			HIP_TRY(ctx, hipMemsetAsync(dst, 0, NB * sizeof(double), ctx->stream));
+		} else {
+			fill.assign(NB, neutral[r]);
+			if ((rc = copy_rows(ctx, dst, fill.data(), N, 0))) return rc;
+		}
+	}
+	// everything is written: only now do the joint dynamics become the ones in force
+	ctx->joint_cfg = *cfg;
+	sai2b::JointParams& J = ctx->joint;
+	J.rows = ctx->joint_rows, J.status = ctx->joint_status, J.counts = ctx->joint_counts;
+	for (int i = 0; i < N; i++) J.stop_k[i] = cfg->stop_stiffness[i], J.stop_c[i] = cfg->stop_damping[i], J.v_eps[i] = cfg->friction_velocity_eps[i];
+	ctx->joint_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_joint_dynamics(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_joint_dynamics: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	// the status of the last step with joint dynamics does not outlive them: sai2b_get_joint_dynamics_state gives zeros from here on
+	if (ctx->joint_status) {
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->joint_status, 0, (size_t)sai2b::JOINT_STATUS_ROWS * N * ctx->B * sizeof(double), ctx->stream));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->joint_counts, 0, sai2b::JOINT_COUNTS * sizeof(int), ctx->stream));
+	}
+	ctx->joint_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_joint_dynamics(sai2b_ctx* ctx, sai2b_joint_dynamics_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_joint_dynamics: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) {
+		if (ctx->joint_on)
+			*cfg = ctx->joint_cfg;
+		else
+			sai2b_default_joint_dynamics(cfg, N);
+	}
+	if (!ctx->joint_on) {
+		const size_t NB = (size_t)N * ctx->B;
+		const double neutral[sai2b::JOINT_ROWS] = {0, 0, 0, INFINITY, -INFINITY, INFINITY};
+		for (int r = 0; rows && r < sai2b::JOINT_ROWS; r++) std::fill(rows + r * NB, rows + (r + 1) * NB, neutral[r]);
+		return SAI2B_OK;
+	}
+	return fetch_rows(ctx, ctx->joint_rows, 0, (size_t)sai2b::JOINT_ROWS * N, rows);
+}
+extern "C" int sai2b_get_joint_dynamics_state(sai2b_ctx* ctx, double* applied_torque, double* stop_torque, double* dissipative_torque,
+											  int* robots_saturated, int* robots_at_stop) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_joint_dynamics_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	double* dst[sai2b::JOINT_STATUS_ROWS] = {applied_torque, stop_torque, dissipative_torque};
+	int* cnt[sai2b::JOINT_COUNTS] = {robots_saturated, robots_at_stop};
+	const size_t NB = (size_t)N * ctx->B;
+	if (!ctx->joint_status) {  // never had joint dynamics
+		for (double* d : dst)
+			if (d) std::fill(d, d + NB, 0.0);
+		for (int* c : cnt)
+			if (c) *c = 0;
+		return SAI2B_OK;
+	}
+	int rc;
+	for (int r = 0; r < sai2b::JOINT_STATUS_ROWS; r++)
+		if ((rc = fetch_rows(ctx, ctx->joint_status, (size_t)r * N, N, dst[r]))) return rc;
+	for (int k = 0; k < sai2b::JOINT_COUNTS; k++)
+		if (cnt[k]) HIP_TRY(ctx, hipMemcpyAsync(cnt[k], ctx->joint_counts + k, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (robots_saturated || robots_at_stop) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
 // ---- observations and episode-end flags ----
 namespace {
 constexpr int OBS_ALL_BLOCKS = SAI2B_OBS_Q | SAI2B_OBS_DQ | SAI2B_OBS_TAU | SAI2B_OBS_LIMIT_MARGIN | SAI2B_OBS_EPISODE_STEP | SAI2B_OBS_CONTACT;
@@ -2133,7 +2270,10 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	// the instantiation for what the context has set: plant payload, contact (whose counter starts each step at zero)
 	const DevParams& hp = ctx->h_params;
 	if (hp.contact) HIP_TRY(ctx, hipMemsetAsync(hp.contact_count, 0, sizeof(int), ctx->stream));
-	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr, nullptr, q_keep, ctx->stream))
+	// joint dynamics: sim_joint_kernel, its two counters zeroed alike
+	if (ctx->joint_on) HIP_TRY(ctx, hipMemsetAsync(ctx->joint_counts, 0, sai2b::JOINT_COUNTS * sizeof(int), ctx->stream));
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr,
+						  ctx->joint_on ? &ctx->joint : nullptr, nullptr, q_keep, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
 	ctx->models_fresh = false;
@@ -2155,7 +2295,7 @@ extern "C" int sai2b_get_bias(sai2b_ctx* ctx, int with_gravity, double* bias) {
 	if (rc) return rc;
 	if (!ctx->sim_tau && (rc = dev_alloc(ctx, &ctx->sim_tau, (size_t)N * ctx->B))) return rc;
 	// a zero-length step leaves the state as it is and writes the bias vector of the current state
-	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, ctx->sim_tau, nullptr, ctx->stream))
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, nullptr, ctx->sim_tau, nullptr, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	return fetch_rows(ctx, ctx->sim_tau, 0, N, bias);
 }

@@ -84,10 +84,21 @@ int launch_reset_subset(const DevParams* d_params, int B, const unsigned char* m
 						double* dq_state, double* q_pose, int only_task, int flags, hipStream_t stream);
 // force / motion space re-parametrisation of MotionForceTask `task` at run time (flags in the kernel's comment)
 int launch_mft_reparam(const DevParams* d_params, int B, int task, int flags, const double* q_pose, hipStream_t stream);
+// joint dynamics of the plant (sai2b_set_joint_dynamics, sai2b_sim.hip: sim_joint_kernel): the kernel's own parameter block,
+// passed by value as a kernel argument like ObsParams; DevParams is not touched by the feature.
+constexpr int JOINT_ROWS = 6, JOINT_STATUS_ROWS = 3, JOINT_COUNTS = 2;
+enum { JOINT_ARMATURE = 0, JOINT_DAMPING, JOINT_FRICTION, JOINT_TORQUE_LIMIT, JOINT_LOWER, JOINT_UPPER };
+struct JointParams {
+	const double* rows = nullptr;  // [JOINT_ROWS][N][B]
+	double* status = nullptr;	   // [JOINT_STATUS_ROWS][N][B]: applied, stop and dissipative torque
+	int* counts = nullptr;		   // [JOINT_COUNTS]: robots saturated, robots at a stop; zeroed by the caller ahead of the launch
+	double stop_k[N] = {}, stop_c[N] = {}, v_eps[N] = {};
+};
 // simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.
-// payload / contact select the instantiation: the plant's payload rows, the contact rows, status and counter of DevParams
+// payload / contact select the instantiation: the plant's payload rows, the contact rows, status and counter of DevParams;
+// joint != NULL: sim_joint_kernel (the same two selectors) instead of sim_kernel, dbg_bias must be NULL then
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   double* dbg_bias, double* q_keep, hipStream_t stream);
+			   const JointParams* joint, double* dbg_bias, double* q_keep, hipStream_t stream);
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
 int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream);
 

@@ -314,6 +314,110 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b);
 }
 
+// ---- joint dynamics of the plant (sai2b_set_joint_dynamics): armature, damping, Coulomb friction, actuator saturation and
+// joint stops, per robot and joint. The law (DESIGN "Joint dynamics in the simulated plant"), from the state at the start
+// of a substep:
+//   ts_i = min(max(tau_i, -t_i), t_i)
+//   sl_i = max(0, k_i max(0, lo_i - q_i) (1 - c_i dq_i)),  su_i = max(0, k_i max(0, q_i - hi_i) (1 + c_i dq_i))
+//   g_i  = d_i + f_i / sqrt(dq_i^2 + e_i^2)                 torque of damping + regularised Coulomb friction: -g_i dq_i
+//   (M + diag(a) + h diag(g)) dq+ = (M + diag(a)) dq + h (ts + sl - su + tc - b),   q+ = q + h dq+
+// continuous in the state everywhere; the dissipative term at the new velocity (linear-implicit), the stop spring explicit.
+// Infinite limits give zero stop torques (max(0, -inf) = 0, k finite) and an infinite torque limit gives ts = tau.
+struct JointRows {
+	real a[N], d[N], f[N], lo[N], hi[N];  // the robot's own rows of the [6][N][B] buffer (the torque limit is used up on entry)
+};
+DI real joint_stop_torque(const JointParams& J, const JointRows& jr, int i, real q, real dq) {
+	const real sl = fmax(0.0, J.stop_k[i] * fmax(0.0, jr.lo[i] - q) * (1.0 - J.stop_c[i] * dq));
+	const real su = fmax(0.0, J.stop_k[i] * fmax(0.0, q - jr.hi[i]) * (1.0 + J.stop_c[i] * dq));
+	return sl - su;
+}
+DI real joint_dissipation(const JointParams& J, const JointRows& jr, int i, real dq) {
+	return jr.d[i] + jr.f[i] / sqrt(dq * dq + J.v_eps[i] * J.v_eps[i]);
+}
+// After the last substep: the status rows [3][N][B] (applied torque, stop torque and dissipative torque at the final state)
+// and the two counters, one ballot and one atomic each
+DI void joint_report(const JointParams& J, const JointRows& jr, const real* ts, bool saturated, const real* q, const real* dq, int B, int b) {
+	bool at_stop = false;
+	UNROLL for (int i = 0; i < N; i++) {
+		const real s = joint_stop_torque(J, jr, i, q[i], dq[i]);
+		at_stop = at_stop || s != 0.0;
+		st(J.status, i, B, b, ts[i]);
+		st(J.status, N + i, B, b, s);
+		st(J.status, 2 * N + i, B, b, -joint_dissipation(J, jr, i, dq[i]) * dq[i]);
+	}
+	const unsigned long long sat = __ballot(saturated), stop = __ballot(at_stop);
+	if (threadIdx.x == 0 && sat) atomicAdd(J.counts, __popcll(sat));  // lane 0 always has a robot
+	if (threadIdx.x == 0 && stop) atomicAdd(J.counts + 1, __popcll(stop));
+}
+
+// sim_kernel's step with the joint terms: PL / CT as there, launched instead of it by a context that has joint dynamics set.
+// a + h g goes on the diagonal ahead of the factorisation, (M + diag(a)) dq is formed from the unmodified M, and the two
+// triangular solves return the new velocity itself.
+template <class PL, class CT>
+__global__ __launch_bounds__(64) void sim_joint_kernel(const DevParams* __restrict__ Pp, const real* __restrict__ tau, real dt, int substeps,
+													   int with_gravity, real* __restrict__ q_keep, const JointParams J) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b >= B) return;
+	real q[N], dq[N], ts[N];
+	JointRows jr;
+	bool saturated = false;
+	UNROLL for (int i = 0; i < N; i++) {
+		q[i] = ld(P.q, i, B, b);
+		dq[i] = ld(P.dq, i, B, b);
+		const real tq = tau ? ld(tau, i, B, b) : 0.0;
+		if (q_keep) st(q_keep, i, B, b, q[i]);
+		jr.a[i] = ld(J.rows, JOINT_ARMATURE * N + i, B, b);
+		jr.d[i] = ld(J.rows, JOINT_DAMPING * N + i, B, b);
+		jr.f[i] = ld(J.rows, JOINT_FRICTION * N + i, B, b);
+		jr.lo[i] = ld(J.rows, JOINT_LOWER * N + i, B, b);
+		jr.hi[i] = ld(J.rows, JOINT_UPPER * N + i, B, b);
+		const real lim = ld(J.rows, JOINT_TORQUE_LIMIT * N + i, B, b);
+		saturated = saturated || fabs(tq) > lim;
+		ts[i] = fmin(fmax(tq, -lim), lim);
+	}
+	[[maybe_unused]] PL pl;
+	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] CT ct;
+	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	const real h = dt / substeps;
+#pragma unroll 1
+	for (int s = 0; s < substeps; s++) {
+		Frames F;
+		fk(P.model, q, F);
+		real M[N * N], L[N * N], dinv[N], x[N];
+		bias_forces(P.model, F, dq, with_gravity != 0, x, pl);
+		if constexpr (CT::on) {
+			real tc[N];
+			contact_torques(P.model, P, ct, F, dq, tc);
+			UNROLL for (int i = 0; i < N; i++) x[i] = ((ts[i] + joint_stop_torque(J, jr, i, q[i], dq[i])) + tc[i]) - x[i];
+		} else {
+			UNROLL for (int i = 0; i < N; i++) x[i] = (ts[i] + joint_stop_torque(J, jr, i, q[i], dq[i])) - x[i];
+		}
+		mass_matrix(P.model, F, M, pl);
+		UNROLL for (int i = 0; i < N; i++) {
+			real m = jr.a[i] * dq[i];
+			UNROLL for (int j = 0; j < N; j++) m = fma(M[i * N + j], dq[j], m);
+			x[i] = fma(h, x[i], m);
+		}
+		UNROLL for (int i = 0; i < N; i++) M[i * N + i] += fma(h, joint_dissipation(J, jr, i, dq[i]), jr.a[i]);
+		chol<N>(M, L, dinv);
+		solve_lower<N>(L, dinv, x);
+		solve_lower_t<N>(L, dinv, x);
+		UNROLL for (int i = 0; i < N; i++) {
+			dq[i] = x[i];
+			q[i] = fma(h, dq[i], q[i]);
+		}
+	}
+	UNROLL for (int i = 0; i < N; i++) {
+		st((real*)P.q, i, B, b, q[i]);
+		st((real*)P.dq, i, B, b, dq[i]);
+	}
+	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b);
+	joint_report(J, jr, ts, saturated, q, dq, B, b);
+}
+
 // What the tasks' observers read between ticks (MotionForceTask.h:121-165: getCurrentPosition /
 // Orientation, getSensedForce/MomentControlWorldFrame; MotionForceTask.cpp:540-579: getPositionError,
 // getOrientationError, goalPositionReached, goalOrientationReached), computed from the state and goal
@@ -383,7 +487,16 @@ int launch_mft_status(const DevParams* d_params, int B, int task, double* out, h
 }
 
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   double* dbg_bias, double* q_keep, hipStream_t stream) {
+			   const JointParams* joint, double* dbg_bias, double* q_keep, hipStream_t stream) {
+	if (joint) {
+		static constexpr decltype(&sim_joint_kernel<NoPayload, NoContact>) joint_kernel[2][2] = {
+			{sim_joint_kernel<NoPayload, NoContact>, sim_joint_kernel<Payload, NoContact>},
+			{sim_joint_kernel<NoPayload, Contact>, sim_joint_kernel<Payload, Contact>}};
+		if (dbg_bias) return 1;
+		hipLaunchKernelGGL(joint_kernel[contact][payload], dim3((B + 63) / 64), dim3(64), 0, stream, d_params, tau, dt, substeps, with_gravity,
+						   q_keep, *joint);
+		return launch_result();
+	}
 	static constexpr decltype(&sim_kernel<NoPayload, NoContact>) kernel[2][2] = {
 		{sim_kernel<NoPayload, NoContact>, sim_kernel<Payload, NoContact>}, {sim_kernel<NoPayload, Contact>, sim_kernel<Payload, Contact>}};
 	hipLaunchKernelGGL(kernel[contact][payload], dim3((B + 63) / 64), dim3(64), 0, stream, d_params, tau, dt, substeps, with_gravity, dbg_bias,
