@@ -136,6 +136,53 @@ protected:
 };
 }  // namespace detail
 
+// Actions (sai2b.h "actions"): the counts of the last applyAction
+struct ActionCounts {
+	int rejected = 0, clipped = 0, limited = 0;
+};
+namespace detail {
+// the host-only validation of an action configuration against a hierarchy (sai2b_validate_action)
+inline void checkActionConfig(const sai2b_action_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof) {
+	char msg[256];
+	if (sai2b_validate_action(&cfg, tasks.data(), (int)tasks.size(), dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(msg);
+}
+// what applyAction(action, mask) checks ahead of the device: a configured action, action [rows][B], mask [B] or empty
+inline void checkActionArguments(const int rows, const size_t B, const Batch& action, const std::vector<unsigned char>& mask) {
+	if (rows < 0) throw std::invalid_argument("applyAction: no action is configured (setAction)");
+	if (action.size() != (size_t)rows * B) throw std::invalid_argument("applyAction: action must be [rows][B]");
+	if (!mask.empty() && mask.size() != B) throw std::invalid_argument("applyAction: mask must have one entry per robot");
+}
+// the members RobotController and BatchedSimulation share: they act on the controller's context
+class ActionMembers {
+public:
+	// validates against the controller's tasks
+	void setAction(const sai2b_action_config& cfg) { check(_act_ctx, sai2b_set_action(_act_ctx, &cfg)); }
+	void clearAction() { check(_act_ctx, sai2b_clear_action(_act_ctx)); }
+	int actionRows() const { return sai2b_action_rows(_act_ctx); }  // -1 without an action
+	// {first row, rows} of a block (enum sai2b_action_block; ignored for a JointTask) of a task; rows 0: not read
+	std::pair<int, int> actionLayout(const int block, const int task) const {
+		int first = -1, n = 0;
+		check(_act_ctx, sai2b_action_layout(_act_ctx, block, task, &first, &n));
+		return {first, n};
+	}
+	// one launch: action [rows][B] to the goal rows of the configured tasks, for the robots with mask[b] != 0 (empty: every robot)
+	void applyAction(const Batch& action, const std::vector<unsigned char>& mask = {}) {
+		checkActionArguments(actionRows(), (size_t)sai2b_batch(_act_ctx), action, mask);
+		check(_act_ctx, sai2b_apply_action(_act_ctx, action.data(), mask.empty() ? nullptr : mask.data(), 0));
+	}
+	ActionCounts actionCounts() const {
+		int c[3];
+		check(_act_ctx, sai2b_get_action_counts(_act_ctx, c));
+		ActionCounts a;
+		a.rejected = c[0], a.clipped = c[1], a.limited = c[2];
+		return a;
+	}
+
+protected:
+	sai2b_ctx* _act_ctx = nullptr;
+};
+}  // namespace detail
+
 class RobotController;
 class TemplateTask;
 class BatchedSimulation;
@@ -996,7 +1043,7 @@ protected:
 };
 
 // reference src/RobotController.{h,cpp}
-class RobotController : public detail::ObservationMembers {
+class RobotController : public detail::ObservationMembers, public detail::ActionMembers {
 public:
 	RobotController(std::shared_ptr<BatchedRobotModel>& robot, std::vector<std::shared_ptr<TemplateTask>>& tasks) : _robot(robot) {
 		if (tasks.size() == 0) throw std::invalid_argument("RobotController must have at least one task");
@@ -1012,7 +1059,7 @@ public:
 			if (msg.find("HIP") != std::string::npos || msg.find("hip") != std::string::npos) throw std::runtime_error(msg);
 			throw std::invalid_argument(msg);
 		}
-		_obs_ctx = _ctx;
+		_obs_ctx = _act_ctx = _ctx;
 		_tasks = tasks;
 		robot->_controller = this;
 		robot->applyPayloads(_ctx, SAI2B_PAYLOAD_BOTH);
@@ -1310,6 +1357,34 @@ public:
 		}
 		return sum;
 	}
+	// Actions of the whole sharded batch (host arrays only): every shard gets the configuration, applyAction() gives each shard
+	// its columns of action [rows][B_total] and of mask [B_total] (empty: every robot), the counts are summed over the shards
+	void setAction(const sai2b_action_config& cfg) {
+		detail::checkActionConfig(cfg, _cfgs, _dof);
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_set_action(sh.ctx, &cfg)); });
+	}
+	void clearAction() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_action(sh.ctx)); }); }
+	int actionRows() const { return sai2b_action_rows(_shards.at(0).ctx); }
+	void applyAction(const Batch& action, const std::vector<unsigned char>& mask = {}) {
+		const int R = actionRows();
+		detail::checkActionArguments(R, (size_t)_total, action, mask);
+		forAll([&](Shard& sh) {
+			const Batch part = slice(action, R, sh);
+			detail::check(sh.ctx, sai2b_apply_action(sh.ctx, part.data(), mask.empty() ? nullptr : mask.data() + sh.lo, 0));
+		});
+	}
+	ActionCounts actionCounts() {
+		std::vector<ActionCounts> parts(_shards.size());
+		forAll([&](Shard& sh) {
+			int c[3];
+			detail::check(sh.ctx, sai2b_get_action_counts(sh.ctx, c));
+			ActionCounts& a = parts[&sh - _shards.data()];
+			a.rejected = c[0], a.clipped = c[1], a.limited = c[2];
+		});
+		ActionCounts sum;
+		for (const ActionCounts& a : parts) sum.rejected += a.rejected, sum.clipped += a.clipped, sum.limited += a.limited;
+		return sum;
+	}
 	// ticks with the torques left on the devices (a device-resident consumer, e.g. sai2b_sim_step(ctx(s), NULL, ...))
 	void tickOnDevice() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_tick(sh.ctx, nullptr, 0)); }); }
 	void synchronize() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_synchronize(sh.ctx)); }); }
@@ -1409,7 +1484,7 @@ private:
 // integrate, getJointPositions, getJointVelocities): rigid-body dynamics of the whole batch with the
 // state resident on the device (sai2b_sim_step). Without setJointTorques, integrate() consumes the
 // torques of the controller's last computeControlTorques() without a host round trip.
-class BatchedSimulation : public detail::ObservationMembers {
+class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers {
 public:
 	explicit BatchedSimulation(RobotController& controller, const double timestep = 0.001, const int substeps = 1)
 		: BatchedSimulation(controller.ctx(), timestep, substeps) {}
@@ -1420,7 +1495,7 @@ public:
 	BatchedSimulation(sai2b_ctx* ctx, const double timestep, const int substeps) : _c(ctx), _dt(timestep), _substeps(substeps) {
 		if (timestep <= 0 || substeps < 1) throw std::invalid_argument("simulation timestep must be positive");
 		_dof = sai2b_num_joints(ctx);
-		_obs_ctx = ctx;
+		_obs_ctx = _act_ctx = ctx;
 	}
 	void setTimestep(const double dt) {
 		if (dt <= 0) throw std::invalid_argument("simulation timestep must be positive");

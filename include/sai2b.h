@@ -635,6 +635,93 @@ int sai2b_observe(sai2b_ctx* ctx, double* out, unsigned char* done, int on_devic
  * Zeros before the first observe; SAI2B_INVALID_ARGUMENT without a configured observation. Waits for the ctx stream. */
 int sai2b_get_done_counts(sai2b_ctx* ctx, int counts[7]);
 
+/* ------------------------------------------------------------------ actions
+ * The link between a policy and the controller in the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe, policy,
+ * sai2b_apply_action, sai2b_reset_robots: ONE launch maps an action [rows][B] in device (or host) memory to the goal rows of
+ * the chosen tasks. Everything in the configuration is batch-uniform. A context that never configures an action launches
+ * exactly the kernels it launches without this feature.
+ *
+ * Row layout: tasks in ascending index; within a MotionForceTask the selected blocks in the order of their flags below, 3
+ * rows each; a JointTask takes task_dof rows.
+ *
+ * Per robot, with a = the task's slice of the action (every component limited to [-1, 1] first when clip_actions):
+ *   position     p = base + pos_scale o a; each component clamped into [pos_lower, pos_upper]; then, with x the robot's
+ *                current position and e = p - x, if |e| > max_pos_lead: p = x + e max_pos_lead / |e| (box first, then lead:
+ *                the lead may take p out of the box again by at most the distance from x to the box). p -> goal position rows.
+ *   orientation  w = ori_scale a, R_new = exp([w]x) R_base: the delta is a rotation vector in the WORLD frame.
+ *                exp = I + A [w]x + B [w]x^2, th2 = w.w, A = sin th / th, B = 2 sin^2(th / 2) / th2; for th2 < 1e-8 the series
+ *                A = 1 - th2 / 6, B = 1/2 - th2 / 24 (truncation below 1e-18). Evaluated as R_base + (A [w]x + B [w]x^2) R_base:
+ *                a zero action leaves the nine rows equal (==) to the base. NO re-orthonormalisation: in DELTA_GOAL mode
+ *                the goal rotation collects the rounding of one 3 x 3 product per apply; the drift from orthonormal is
+ *                measured in DESIGN.md §8h.
+ *   force/moment goal force / moment rows = force_scale a / moment_scale a, in every mode.
+ *   JointTask    g = base + jt_scale o a, clamped into [jt_lower, jt_upper] -> goal position rows.
+ * base: DELTA_GOAL the goal rows as they are, DELTA_CURRENT the robot as it is now, ABSOLUTE 0 (orientation: the identity).
+ * Goal velocity and acceleration rows are never touched (MotionForceTask::setGoalPosition does not touch them either).
+ *
+ * A robot with an action component that is not finite gets NONE of its goal rows written (they stay bit-equal) and is
+ * counted as rejected; so is a robot whose q is not finite when the configuration reads the state (a DELTA_CURRENT task, or
+ * a finite max_pos_lead). Every comparison is written so that a NaN operand gives "reject" or "false". */
+enum sai2b_action_mode {		 /* per task */
+	SAI2B_ACT_NONE = 0,			 /* the task takes no rows */
+	SAI2B_ACT_DELTA_GOAL = 1,	 /* base = the task's goal rows as they are (accumulating) */
+	SAI2B_ACT_DELTA_CURRENT = 2, /* base = the robot as it is now: MotionForceTask pose by forward kinematics of SAI2B_BUF_Q (as
+								  * sai2b_observe computes it, not the cached pose), JointTask S q */
+	SAI2B_ACT_ABSOLUTE = 3
+};
+enum sai2b_action_block { /* MotionForceTask only, 3 rows each; a JointTask always takes task_dof rows */
+	SAI2B_ACT_POSITION = 1,
+	SAI2B_ACT_ORIENTATION = 2,
+	SAI2B_ACT_FORCE = 4,
+	SAI2B_ACT_MOMENT = 8
+};
+typedef struct sai2b_action_task {
+	int mode, blocks;
+	double pos_scale[3], ori_scale, force_scale, moment_scale; /* metres, rad, N, Nm per unit action */
+	double pos_lower[3], pos_upper[3];						   /* world box for the goal position; -inf / +inf: none */
+	double max_pos_lead;									   /* bound on |goal - current position|; +inf: none */
+	double jt_scale[SAI2B_MAX_DOF], jt_lower[SAI2B_MAX_DOF], jt_upper[SAI2B_MAX_DOF]; /* per task row; entries >= task_dof are ignored */
+} sai2b_action_task;
+typedef struct sai2b_action_config {
+	int clip_actions; /* nonzero: every component is limited to [-1, 1] before scaling */
+	int reserved;
+	sai2b_action_task task[SAI2B_MAX_TASKS];
+} sai2b_action_config;
+/* host only: every task NONE with no block, scales 1, limits -inf / +inf, lead +inf, no clipping */
+int sai2b_default_action(sai2b_action_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: an unknown mode or unknown block bits, blocks on a
+ * JointTask, a MotionForceTask with a mode and no block, a mode on a task index >= n_tasks, a scale that is negative or not
+ * finite, lower >= upper or a NaN limit, a lead that is not > 0, no task with a mode at all */
+int sai2b_validate_action(const sai2b_action_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+						  int msg_len);
+/* sizeof(sai2b_action_config) as the library was compiled: a binding that mirrors the struct checks its layout with it */
+int sai2b_sizeof_action_config(void);
+/* host only, the layout arithmetic: where `block` (one flag of enum sai2b_action_block; ignored for a JointTask) of `task` is
+ * read from. *n_rows = 0 and *first_row = -1 when the configuration does not select it; *total_rows: rows of the whole
+ * action. Any output may be NULL. SAI2B_INVALID_ARGUMENT when task is outside [0, n_tasks) or, for a MotionForceTask, block
+ * is not exactly one known flag. */
+int sai2b_action_config_layout(const sai2b_action_config* cfg, const sai2b_task_config* tasks, int n_tasks, int block, int task,
+							   int* first_row, int* n_rows, int* total_rows);
+/* validates against the context's tasks and allocates the device counters */
+int sai2b_set_action(sai2b_ctx* ctx, const sai2b_action_config* cfg);
+/* back to a context without an action: sai2b_apply_action fails from here on */
+int sai2b_clear_action(sai2b_ctx* ctx);
+/* rows of the configured action; -1 without one */
+int sai2b_action_rows(sai2b_ctx* ctx);
+/* sai2b_action_config_layout for the context's configuration; SAI2B_INVALID_ARGUMENT without one */
+int sai2b_action_layout(sai2b_ctx* ctx, int block, int task, int* first_row, int* n_rows);
+/* One launch, whatever is configured: action [rows][B]; mask [B] bytes or NULL = every robot, a robot with mask[b] == 0 is not
+ * touched and not counted. All pointers host, or all device when on_device != 0 (stream contract below: the inputs are read
+ * before anything the caller enqueues on its stream after the call, nothing synchronises). A deferred
+ * sai2b_update_task_models is flushed first. The tasks with a mode are marked as the goal setters mark them, so the internal
+ * trajectory generators see the new goals at the next tick. SAI2B_INVALID_ARGUMENT without a configured action (nothing is
+ * launched then). */
+int sai2b_apply_action(sai2b_ctx* ctx, const double* action, const unsigned char* mask, int on_device);
+/* of the last sai2b_apply_action, counted on the device: robots rejected, robots with some component clipped to +-1, robots
+ * whose goal was limited by a box, the lead or a joint clamp (a rejected robot counts as rejected only). Zeros before the
+ * first apply; SAI2B_INVALID_ARGUMENT without a configured action. Waits for the ctx stream. */
+int sai2b_get_action_counts(sai2b_ctx* ctx, int counts[3]);
+
 /* ------------------------------------------------------------------ simulation harness
  * What the reference's examples obtain from the external sai2-simulation (examples/05-...cpp:215-236:
  * setJointTorques / integrate / getJointPositions, getJointVelocities): one control period of

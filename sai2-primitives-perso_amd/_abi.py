@@ -237,6 +237,43 @@ class JointDynamicsConfig(C.Structure):
     ]
 
 
+# enum sai2b_action_mode / sai2b_action_block (sai2b.h "actions"); name -> value, blocks in row order
+ACT_NONE, ACT_DELTA_GOAL, ACT_DELTA_CURRENT, ACT_ABSOLUTE = 0, 1, 2, 3
+ACT_POSITION, ACT_ORIENTATION, ACT_FORCE, ACT_MOMENT = 1, 2, 4, 8
+ACT_MODES = {"none": ACT_NONE, "delta_goal": ACT_DELTA_GOAL, "delta_current": ACT_DELTA_CURRENT, "absolute": ACT_ABSOLUTE}
+ACT_BLOCKS = {"position": ACT_POSITION, "orientation": ACT_ORIENTATION, "force": ACT_FORCE, "moment": ACT_MOMENT}
+ACT_COUNTS = ("rejected", "clipped", "limited")
+
+
+class ActionTask(C.Structure):
+    """sai2b_action_task"""
+
+    _fields_ = [
+        ("mode", _i),
+        ("blocks", _i),
+        ("pos_scale", _d * 3),
+        ("ori_scale", _d),
+        ("force_scale", _d),
+        ("moment_scale", _d),
+        ("pos_lower", _d * 3),
+        ("pos_upper", _d * 3),
+        ("max_pos_lead", _d),
+        ("jt_scale", _d * MAX_DOF),
+        ("jt_lower", _d * MAX_DOF),
+        ("jt_upper", _d * MAX_DOF),
+    ]
+
+
+class ActionConfig(C.Structure):
+    """sai2b_action_config; load_library() checks the size against sai2b_sizeof_action_config()"""
+
+    _fields_ = [
+        ("clip_actions", _i),
+        ("reserved", _i),
+        ("task", ActionTask * MAX_TASKS),
+    ]
+
+
 EXPORTS = [
     "sai2b_panda_model",
     "sai2b_model_merge_fixed_body",
@@ -326,6 +363,16 @@ EXPORTS = [
     "sai2b_clear_joint_dynamics",
     "sai2b_get_joint_dynamics",
     "sai2b_get_joint_dynamics_state",
+    "sai2b_default_action",
+    "sai2b_validate_action",
+    "sai2b_sizeof_action_config",
+    "sai2b_action_config_layout",
+    "sai2b_set_action",
+    "sai2b_clear_action",
+    "sai2b_action_rows",
+    "sai2b_action_layout",
+    "sai2b_apply_action",
+    "sai2b_get_action_counts",
 ]
 
 _lib = None
@@ -450,5 +497,18 @@ def load_library():
     if lib.sai2b_sizeof_observation_config() != C.sizeof(ObservationConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_observation_config is {lib.sai2b_sizeof_observation_config()} bytes in the library, "
                            f"{C.sizeof(ObservationConfig)} in the ctypes mirror")
+    lib.sai2b_default_action.argtypes = [P(ActionConfig)]
+    lib.sai2b_validate_action.argtypes = [P(ActionConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_action_config.argtypes = []
+    lib.sai2b_action_config_layout.argtypes = [P(ActionConfig), P(TaskConfig), _i, _i, _i, P(_i), P(_i), P(_i)]
+    lib.sai2b_set_action.argtypes = [vp, P(ActionConfig)]
+    lib.sai2b_clear_action.argtypes = [vp]
+    lib.sai2b_action_rows.argtypes = [vp]
+    lib.sai2b_action_layout.argtypes = [vp, _i, _i, P(_i), P(_i)]
+    lib.sai2b_apply_action.argtypes = [vp, vp, vp, _i]
+    lib.sai2b_get_action_counts.argtypes = [vp, P(_i)]
+    if lib.sai2b_sizeof_action_config() != C.sizeof(ActionConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_action_config is {lib.sai2b_sizeof_action_config()} bytes in the library, "
+                           f"{C.sizeof(ActionConfig)} in the ctypes mirror")
     _lib = lib
     return lib

@@ -528,6 +528,94 @@ class Controller:
         self._rc(self.lib.sai2b_get_done_counts(self.h, c))
         return dict(zip(list(_abi.DONE_BITS) + ["any"], list(c)))
 
+    # -- actions (sai2b.h "actions")
+    def action_config(self, tasks=None, clip_actions=False):
+        """-> ActionConfig. tasks: dict task index -> dict of that task's settings, every other task takes no rows:
+        mode ('delta_goal', 'delta_current', 'absolute'), for a MotionForceTask blocks (names of _abi.ACT_BLOCKS: 'position',
+        'orientation', 'force', 'moment'), pos_scale / pos_lower / pos_upper (scalar or [3]), ori_scale, force_scale,
+        moment_scale, max_pos_lead; for a JointTask jt_scale / jt_lower / jt_upper (scalar or [task_dof]) or
+        jt_limits='model': the model's joint limits (a full joint task only)."""
+        cfg = _abi.ActionConfig()
+        if self.lib.sai2b_default_action(C.byref(cfg)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        cfg.clip_actions = int(bool(clip_actions))
+        for t, settings in dict(tasks or {}).items():
+            if not 0 <= int(t) < _abi.MAX_TASKS:
+                raise ValueError(f"task index {t} out of range")
+            a, s = cfg.task[int(t)], dict(settings)
+            mode = s.pop("mode", "none")
+            if isinstance(mode, str) and mode not in _abi.ACT_MODES:
+                raise ValueError(f"unknown mode {mode!r}: one of {sorted(_abi.ACT_MODES)}")
+            a.mode = _abi.ACT_MODES[mode] if isinstance(mode, str) else int(mode)
+            a.blocks = self._flags(s.pop("blocks", ()), _abi.ACT_BLOCKS, "block")
+            k0 = self.tasks[int(t)].task_dof if int(t) < len(self.tasks) and self.tasks[int(t)].type == _abi.JOINT_TASK else 0
+            if "jt_limits" in s:
+                if s.pop("jt_limits") != "model" or "jt_lower" in s or "jt_upper" in s:
+                    raise ValueError("jt_limits must be 'model', without jt_lower / jt_upper")
+                if k0 != self.dof:
+                    raise ValueError("jt_limits='model' is for a full joint task")
+                s["jt_lower"], s["jt_upper"] = list(self.model.q_lower)[:k0], list(self.model.q_upper)[:k0]
+            for name in ("pos_scale", "pos_lower", "pos_upper", "jt_scale", "jt_lower", "jt_upper"):
+                if name in s:
+                    n = 3 if name.startswith("pos") else k0
+                    v = np.broadcast_to(np.asarray(s.pop(name), dtype=np.float64), (n,))
+                    for i in range(n):
+                        getattr(a, name)[i] = float(v[i])
+            for name in ("ori_scale", "force_scale", "moment_scale", "max_pos_lead"):
+                if name in s:
+                    setattr(a, name, float(s.pop(name)))
+            if s:
+                raise ValueError(f"unknown action setting {sorted(s)[0]!r} of task {t}")
+        return cfg
+
+    def set_action(self, cfg=None, **kwargs):
+        """configure what apply_action() maps (an ActionConfig, or the arguments of action_config)"""
+        if cfg is None:
+            cfg = self.action_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_action: an ActionConfig or keyword arguments, not both")
+        self._rc(self.lib.sai2b_set_action(self.h, C.byref(cfg)))
+
+    def clear_action(self):
+        self._rc(self.lib.sai2b_clear_action(self.h))
+
+    def action_rows(self):
+        """rows of the configured action; -1 without one"""
+        return self.lib.sai2b_action_rows(self.h)
+
+    def action_layout(self):
+        """dict name -> slice of rows of the action: 'position0', 'orientation0', 'force0', 'moment0' with the index of the
+        MotionForceTask, 'joints1' with that of the JointTask; only what the configuration reads"""
+        first, n = C.c_int(), C.c_int()
+        out = {}
+        for t, task in enumerate(self.tasks):
+            blocks = {"joints": _abi.ACT_POSITION} if task.type == _abi.JOINT_TASK else _abi.ACT_BLOCKS
+            for name, flag in blocks.items():
+                self._rc(self.lib.sai2b_action_layout(self.h, flag, t, C.byref(first), C.byref(n)))
+                if n.value:
+                    out[f"{name}{t}"] = slice(first.value, first.value + n.value)
+        return out
+
+    def apply_action(self, action, mask=None):
+        """one launch: action [action_rows()][B] to the goal rows of the configured tasks, for the robots mask selects ([B]
+        bool / uint8, None: every robot). numpy arrays, or torch CUDA tensors (then nothing leaves the device and nothing
+        synchronises)"""
+        rows = self.action_rows()
+        if rows < 0:
+            raise ValueError("sai2b_apply_action: no action is configured (sai2b_set_action)")
+        dev = self._dev(action, mask)
+        pa, ka = self._in(action, rows)
+        if pa is None:
+            raise ValueError(f"an action of shape ({rows}, {self.B}) is required")
+        pm, km = self._mask(mask) if mask is not None else (None, None)
+        self._rc(self.lib.sai2b_apply_action(self.h, pa, pm, dev))
+
+    def action_counts(self):
+        """of the last apply_action(): dict 'rejected', 'clipped', 'limited' -> robots"""
+        c = (C.c_int * 3)()
+        self._rc(self.lib.sai2b_get_action_counts(self.h, c))
+        return dict(zip(_abi.ACT_COUNTS, list(c)))
+
     # -- the path
     def reinitialize(self):
         self._rc(self.lib.sai2b_reinitialize(self.h))

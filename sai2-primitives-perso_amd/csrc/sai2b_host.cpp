@@ -127,6 +127,16 @@ struct sai2b_ctx {
 	int *obs_steps = nullptr, *obs_counts = nullptr;
 	double* obs_out = nullptr;
 	unsigned char* obs_done = nullptr;
+	// actions (sai2b_set_action): the configuration in force and what action_kernel takes from it, the device counters of the
+	// last apply, created on first use; act_in / act_mask stage the inputs of a call with host arguments (act_in_rows: rows
+	// act_in has room for)
+	bool act_on = false;
+	sai2b_action_config act_cfg = {};
+	sai2b::ActParams act;
+	int act_rows = 0, act_in_rows = 0;
+	int* act_counts = nullptr;
+	double* act_in = nullptr;
+	unsigned char* act_mask = nullptr;
 	// sai2b_reinitialize_robots / sai2b_reset_robots with host arguments: the [B]-byte mask and the [2 * dof][B] q, dq rows are
 	// staged here, created on first use
 	unsigned char* reset_mask = nullptr;
@@ -2242,6 +2252,202 @@ extern "C" int sai2b_get_done_counts(sai2b_ctx* ctx, int counts[7]) {
 	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_done_counts: no observation is configured (sai2b_set_observation)");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->obs_counts, sai2b::OBS_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
+// ---- actions ----
+namespace {
+constexpr int ACT_ALL_BLOCKS = SAI2B_ACT_POSITION | SAI2B_ACT_ORIENTATION | SAI2B_ACT_FORCE | SAI2B_ACT_MOMENT;
+int action_task_rows(const sai2b_action_task& a, const sai2b_task_config& t) {
+	if (a.mode == SAI2B_ACT_NONE) return 0;
+	if (t.type == SAI2B_JOINT_TASK) return t.task_dof;
+	int rows = 0;
+	for (int k = 0; k < sai2b::ACT_BLOCKS; k++)
+		if ((a.blocks >> k) & 1) rows += 3;
+	return rows;
+}
+// first action row of every task (-1: the task takes none); returns the rows of the whole action
+int action_rows(const sai2b_action_config& c, const sai2b_task_config* tasks, int n_tasks, int row_task[SAI2B_MAX_TASKS]) {
+	int rows = 0;
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		const int n = t < n_tasks ? action_task_rows(c.task[t], tasks[t]) : 0;
+		row_task[t] = n ? rows : -1;
+		rows += n;
+	}
+	return rows;
+}
+bool bad_scale(double v) { return !std::isfinite(v) || v < 0; }
+std::string action_config_error(const sai2b_action_config* c, const sai2b_task_config* tasks, int n_tasks) {
+	if (!c) return "action: null config";
+	if (!tasks || n_tasks < 1 || n_tasks > SAI2B_MAX_TASKS) return "action: no tasks to validate against";
+	bool any = false;
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		const sai2b_action_task& a = c->task[t];
+		const std::string who = "action: task " + std::to_string(t) + ": ";
+		if (a.mode < SAI2B_ACT_NONE || a.mode > SAI2B_ACT_ABSOLUTE) return who + "unknown mode";
+		if (a.blocks & ~ACT_ALL_BLOCKS) return who + "unknown bits in blocks";
+		if (a.mode == SAI2B_ACT_NONE) continue;
+		if (t >= n_tasks) return who + "a mode on a task the hierarchy does not have";
+		any = true;
+		if (tasks[t].type == SAI2B_JOINT_TASK) {
+			if (a.blocks) return who + "blocks are for a MotionForceTask (a JointTask takes task_dof rows)";
+			for (int i = 0; i < tasks[t].task_dof && i < SAI2B_MAX_DOF; i++) {
+				if (bad_scale(a.jt_scale[i])) return who + "jt_scale must be finite and >= 0";
+				if (!(a.jt_lower[i] < a.jt_upper[i])) return who + "jt_lower must be < jt_upper (and neither a NaN)";
+			}
+			continue;
+		}
+		if (tasks[t].type != SAI2B_MOTION_FORCE_TASK) return who + "not a JointTask or MotionForceTask";
+		if (!a.blocks) return who + "a MotionForceTask with a mode needs a block";
+		if (bad_scale(a.pos_scale[0]) || bad_scale(a.pos_scale[1]) || bad_scale(a.pos_scale[2])) return who + "pos_scale must be finite and >= 0";
+		if (bad_scale(a.ori_scale)) return who + "ori_scale must be finite and >= 0";
+		if (bad_scale(a.force_scale)) return who + "force_scale must be finite and >= 0";
+		if (bad_scale(a.moment_scale)) return who + "moment_scale must be finite and >= 0";
+		for (int k = 0; k < 3; k++)
+			if (!(a.pos_lower[k] < a.pos_upper[k])) return who + "pos_lower must be < pos_upper (and neither a NaN)";
+		if (!(a.max_pos_lead > 0)) return who + "max_pos_lead must be > 0";
+	}
+	if (!any) return "action: no task has a mode";
+	return "";
+}
+}  // namespace
+extern "C" int sai2b_default_action(sai2b_action_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_action: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	for (sai2b_action_task& a : cfg->task) {
+		a.ori_scale = a.force_scale = a.moment_scale = 1.0;
+		a.max_pos_lead = INFINITY;
+		for (int k = 0; k < 3; k++) a.pos_scale[k] = 1.0, a.pos_lower[k] = -INFINITY, a.pos_upper[k] = INFINITY;
+		for (int i = 0; i < SAI2B_MAX_DOF; i++) a.jt_scale[i] = 1.0, a.jt_lower[i] = -INFINITY, a.jt_upper[i] = INFINITY;
+	}
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_action_config(void) { return (int)sizeof(sai2b_action_config); }
+extern "C" int sai2b_validate_action(const sai2b_action_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+									 int msg_len) {
+	const std::string err = robot_dof == N ? action_config_error(cfg, tasks, n_tasks) : "action: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_action_config_layout(const sai2b_action_config* cfg, const sai2b_task_config* tasks, int n_tasks, int block, int task,
+										  int* first_row, int* n_rows, int* total_rows) {
+	if (!cfg || !tasks || n_tasks < 1 || n_tasks > SAI2B_MAX_TASKS)
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_action_config_layout: bad arguments");
+	if (task < 0 || task >= n_tasks) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_action_config_layout: task must be a task index");
+	const bool joint = tasks[task].type == SAI2B_JOINT_TASK;
+	const int k = joint ? 0 : single_bit_index(block, sai2b::ACT_BLOCKS);
+	if (k < 0) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_action_config_layout: block must be one known flag");
+	int row_task[SAI2B_MAX_TASKS];
+	const int rows = action_rows(*cfg, tasks, n_tasks, row_task);
+	const sai2b_action_task& a = cfg->task[task];
+	int first = -1, n = 0;
+	if (row_task[task] >= 0) {
+		if (joint) {
+			first = row_task[task], n = tasks[task].task_dof;
+		} else if ((a.blocks >> k) & 1) {
+			first = row_task[task], n = 3;
+			for (int j = 0; j < k; j++)
+				if ((a.blocks >> j) & 1) first += 3;
+		}
+	}
+	if (first_row) *first_row = first;
+	if (n_rows) *n_rows = n;
+	if (total_rows) *total_rows = rows;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_action(sai2b_ctx* ctx, const sai2b_action_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_action: null ctx");
+	const std::string err = action_config_error(cfg, ctx->cfg, ctx->T);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	if (!ctx->act_counts && (rc = dev_alloc(ctx, &ctx->act_counts, (size_t)sai2b::ACT_COUNTS))) return rc;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->act_counts, 0, sai2b::ACT_COUNTS * sizeof(int), ctx->stream));
+	sai2b::ActParams p;
+	int row_task[SAI2B_MAX_TASKS];
+	p.rows = ctx->act_rows = action_rows(*cfg, ctx->cfg, ctx->T, row_task);
+	p.clip = cfg->clip_actions != 0;
+	for (int t = 0; t < ctx->T; t++) {
+		const sai2b_action_task& a = cfg->task[t];
+		sai2b::ActTask& d = p.task[t];
+		if (a.mode == SAI2B_ACT_NONE) continue;
+		const bool joint = ctx->cfg[t].type == SAI2B_JOINT_TASK;
+		d.mode = a.mode, d.blocks = joint ? 0 : a.blocks, d.row = row_task[t];
+		for (int k = 0; k < 3; k++) d.pos_scale[k] = a.pos_scale[k], d.pos_lower[k] = a.pos_lower[k], d.pos_upper[k] = a.pos_upper[k];
+		d.ori_scale = a.ori_scale, d.force_scale = a.force_scale, d.moment_scale = a.moment_scale, d.max_lead = a.max_pos_lead;
+		for (int i = 0; i < N; i++) d.jt_scale[i] = a.jt_scale[i], d.jt_lower[i] = a.jt_lower[i], d.jt_upper[i] = a.jt_upper[i];
+		const bool lead = !joint && (a.blocks & SAI2B_ACT_POSITION) && a.max_pos_lead < INFINITY;
+		if (a.mode == SAI2B_ACT_DELTA_CURRENT || lead) p.need_state = 1;
+		if (!joint && (a.mode == SAI2B_ACT_DELTA_CURRENT || lead)) p.need_pose = 1;
+	}
+	ctx->act = p;
+	ctx->act_cfg = *cfg;
+	ctx->act_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_action(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_action: null ctx");
+	ctx->act_on = false;
+	ctx->act_rows = 0;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_action_rows(sai2b_ctx* ctx) { return ctx && ctx->act_on ? ctx->act_rows : -1; }
+extern "C" int sai2b_action_layout(sai2b_ctx* ctx, int block, int task, int* first_row, int* n_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_action_layout: null ctx");
+	if (!ctx->act_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_action_layout: no action is configured (sai2b_set_action)");
+	const int rc = sai2b_action_config_layout(&ctx->act_cfg, ctx->cfg, ctx->T, block, task, first_row, n_rows, nullptr);
+	return rc ? set_error(ctx, rc, g_error) : SAI2B_OK;
+}
+extern "C" int sai2b_apply_action(sai2b_ctx* ctx, const double* action, const unsigned char* mask, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_apply_action: null ctx");
+	if (!ctx->act_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_apply_action: no action is configured (sai2b_set_action)");
+	if (!action) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_apply_action: action is NULL");
+	int rc = flush_update(ctx);	 // DELTA_CURRENT reads the state: a deferred model update happens first
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if ((rc = upload_params(ctx))) return rc;
+	const size_t B = ctx->B;
+	const double* d_action = action;
+	const unsigned char* d_mask = mask;
+	if (on_device) {
+		if ((rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (ctx->act_in_rows < ctx->act_rows) {	 // a configuration with more rows: the smaller staging buffer goes
+			if (ctx->act_in) {
+				HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+				ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)ctx->act_in), ctx->allocs.end());
+				HIP_TRY(ctx, hipFree(ctx->act_in));
+				ctx->act_in = nullptr, ctx->act_in_rows = 0;
+			}
+			if ((rc = dev_alloc(ctx, &ctx->act_in, (size_t)ctx->act_rows * B))) return rc;
+			ctx->act_in_rows = ctx->act_rows;
+		}
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->act_in, action, (size_t)ctx->act_rows * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		d_action = ctx->act_in;
+		if (mask) {
+			if (!ctx->act_mask && (rc = dev_alloc(ctx, &ctx->act_mask, B))) return rc;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->act_mask, mask, B, hipMemcpyHostToDevice, ctx->stream));
+			d_mask = ctx->act_mask;
+		}
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->act_counts, 0, sai2b::ACT_COUNTS * sizeof(int), ctx->stream));
+	if (sai2b::launch_action(ctx->d_params, ctx->B, ctx->act, d_action, d_mask, ctx->act_counts, ctx->stream))
+		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_apply_action: launch failed");
+	// as the goal setters: the generators of the tasks that took rows compare their goals at the next tick
+	for (int t = 0; t < ctx->T; t++)
+		if (ctx->act_cfg.task[t].mode != SAI2B_ACT_NONE) ctx->goals_dirty |= 1u << t;
+	ctx->goals_epoch++, ctx->otg_all_idle = false;
+	ctx->launches++;
+	return on_device ? caller_after_read(ctx) : SAI2B_OK;
+}
+extern "C" int sai2b_get_action_counts(sai2b_ctx* ctx, int counts[3]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_action_counts: bad arguments");
+	if (!ctx->act_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_action_counts: no action is configured (sai2b_set_action)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->act_counts, sai2b::ACT_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }

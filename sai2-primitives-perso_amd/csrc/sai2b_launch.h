@@ -119,4 +119,23 @@ struct ObsParams {
 int launch_observe(const DevParams* d_params, int B, const ObsParams& obs, double* out, unsigned char* done, int* steps, int* counts,
 				   hipStream_t stream);
 
+// sai2b_apply_action (sai2b_action.hip: action_kernel): its own parameter block, passed by value as a kernel argument like
+// ObsParams; DevParams is not touched by the feature. Per task what sai2b_action_task holds, with the task's first action row.
+constexpr int ACT_BLOCKS = 4, ACT_COUNTS = 3;  // counts: rejected, clipped, limited
+struct ActTask {
+	int mode = 0, blocks = 0, row = -1, reserved = 0;
+	double pos_scale[3] = {}, ori_scale = 0, force_scale = 0, moment_scale = 0;
+	double pos_lower[3] = {}, pos_upper[3] = {}, max_lead = 0;
+	double jt_scale[N] = {}, jt_lower[N] = {}, jt_upper[N] = {};
+};
+struct ActParams {
+	int rows = 0, clip = 0;
+	int need_state = 0;	 // some task reads q: DELTA_CURRENT, or a finite lead
+	int need_pose = 0;	 // some MotionForceTask reads the current pose: fk() is computed, once for all tasks
+	ActTask task[SAI2B_MAX_TASKS];
+};
+// action [rows][B], mask [B] bytes or NULL, counts [ACT_COUNTS] zeroed by the caller on the stream ahead of the launch
+int launch_action(const DevParams* d_params, int B, const ActParams& act, const double* action, const unsigned char* mask, int* counts,
+				  hipStream_t stream);
+
 }  // namespace sai2b

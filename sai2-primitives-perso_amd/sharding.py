@@ -86,6 +86,12 @@ def observe(ctrl, world, rank, out=None, done=None):
     return lo, hi
 
 
+def apply_action(ctrl, world, rank, action, mask=None):
+    """Controller.apply_action on this rank's shard of an action [rows][global_batch] and mask [global_batch] given for the
+    whole batch"""
+    ctrl.apply_action(shard_rows(action, world, rank), shard_rows(mask, world, rank))
+
+
 def node_throughput(robots_per_rank, world, steps, elapsed_max):
     """whole-job control-ticks/sec: every rank's robots x steps over the slowest rank's time"""
     return robots_per_rank * world * steps / elapsed_max
