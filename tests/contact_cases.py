@@ -32,8 +32,10 @@ def model(robot):
     return m
 
 
-def draw(robot, B, n_points, seed=0):
-    """-> dict model, link, points, q, dq, tau [n][B], rows [9][B]"""
+def draw(robot, B, n_points, seed=0, link=None):
+    """-> dict model, link, points, q, dq, tau [n][B], rows [9][B]. link: the contact link (default: the last one); it is not
+    part of the seed, so every link of a robot gets the same states, torques, normals and gains, the planes placed against
+    its own points"""
     m = model(robot)
     n = int(m.dof)
     rng = np.random.default_rng([zlib.crc32(robot.encode()), B, n_points, seed])
@@ -41,7 +43,8 @@ def draw(robot, B, n_points, seed=0):
     q = np.ascontiguousarray((lo + (hi - lo) * rng.uniform(0.2, 0.8, (B, n))).T)
     dq = rng.normal(0, 0.8, (n, B))
     tau = rng.normal(0, 5, (n, B))
-    link, pts = n - 1, points(n_points)
+    link, pts = n - 1 if link is None else int(link), points(n_points)
+    assert 0 <= link < n
     rows = np.zeros((9, B))
     nrm = rng.normal(size=(3, B))
     rows[3:6] = nrm / np.linalg.norm(nrm, axis=0)

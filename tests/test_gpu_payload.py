@@ -29,7 +29,7 @@ def _rel(a, b):
     return np.abs(a - b).max() / np.abs(b).max()
 
 
-def _make(config, B, route, monkeypatch, gravity=True, seed=5, with_payload=True):
+def _make(config, B, route, monkeypatch, gravity=True, seed=5, with_payload=True, link=6):
     inp = pkg.workloads.make_inputs(config, B=B, seed=seed)
     for k, v in ROUTES[route].items():
         monkeypatch.setenv(k, v)
@@ -41,12 +41,13 @@ def _make(config, B, route, monkeypatch, gravity=True, seed=5, with_payload=True
     ol.load_inputs(g, inp)
     g.enable_gravity_compensation(gravity)
     if with_payload:
-        g.set_link_payload(6, *pc.rows(B))
+        # the rows are in the URDF link's frame, which is the model's on link 6; pc.model_rows carries them over on the others
+        g.set_link_payload(link, *(pc.rows(B) if link == 6 else pc.model_rows("panda", link, *pc.rows(B))))
     return inp, g
 
 
-def _oracles(inp, B, gravity=True, scale=None):
-    o = pc.PayloadOracles(pc.texts("panda", scale=scale), ol.task_configs(inp["tasks"]), B)
+def _oracles(inp, B, gravity=True, scale=None, link=6):
+    o = pc.PayloadOracles(pc.texts("panda", link=link, scale=scale), ol.task_configs(inp["tasks"]), B)
     o.load_inputs(inp)
     o.enable_gravity_compensation(gravity)
     return o
