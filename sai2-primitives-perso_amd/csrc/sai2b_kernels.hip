@@ -9,9 +9,34 @@
 #include "sai2b_device.hpp"
 #include "sai2b_fast.hpp"
 #include "sai2b_baked_panda.h"
+#include "sai2b_baked_panda_model.h"
 #include "sai2b_launch.h"
 
 namespace sai2b {
+
+#if SAI2B_N == 7
+// The model phase of the BAKED kernels: overloads on PandaBaked that the calls below take in place of the generic templates
+// of sai2b_device.hpp. They run the generated straight-line forms (sai2b_baked_panda_model.h), which keep only the nonzero
+// terms of the Panda's constants; the payload forms keep payload_terms() and their selects as the generic ones have them.
+DI void fk(const PandaBaked&, const real* q, Frames& F) {
+	real sn[N], cs[N];
+	UNROLL for (int i = 0; i < N; i++) sincos_joint(q[i], &sn[i], &cs[i]);
+	panda_fk(sn, cs, F);
+}
+DI void jacobian(const PandaBaked&, const DevTask& t, const Frames& F, const real* x, real* J) { panda_jacobian(F, t.link, x, J); }
+DI void mass_matrix(const PandaBaked&, const Frames& F, real* M, const NoPayload& = NoPayload{}) { panda_mass_matrix(F, M); }
+DI void mass_matrix(const PandaBaked&, const Frames& F, real* M, const Payload& pl) {
+	PayloadTerms pt;
+	payload_terms(pl, F, pt);
+	panda_mass_matrix_payload(F, pl.link, pt, M);
+}
+DI void gravity_vector(const PandaBaked&, const Frames& F, real* g, const NoPayload& = NoPayload{}) { panda_gravity_vector(F, g); }
+DI void gravity_vector(const PandaBaked&, const Frames& F, real* g, const Payload& pl) {
+	PayloadTerms pt;
+	payload_terms(pl, F, pt);
+	panda_gravity_vector_payload(F, pl.link, pt, g);
+}
+#endif
 
 // Generic tick: Jacobi-SVD based, any hierarchy (the reference's control flow, projector form).
 // fb_count != NULL: the fallback pass behind tick_fast_kernel — lane i of the grid takes robot
@@ -199,8 +224,9 @@ DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb
 // fb_counts: two counters alternating between ticks (`parity`): this launch fills [parity] and clears
 // [1 - parity] for the next one (the generic pass that read it finished before this kernel started).
 // BAKED selects where the robot constants come from: false = the ctx's parameter block (any robot),
-// true = the compile-time Panda literals of sai2b_baked_panda.h (chosen by the host only when the ctx
-// model is bit-equal to them): no scalar loads from the parameter block for the model phase.
+// true = the stock Panda (chosen by the host only when the ctx model is bit-equal to sai2b_baked_panda.h): the model
+// phase is the straight-line code of sai2b_baked_panda_model.h, written out at build time from the nonzero terms of those
+// constants (the PandaBaked overloads at the top of this file), with no loads from the parameter block.
 // PL = Payload: the form for contexts with per-robot payloads (tick_fast_payload_kernel below); its ten rows join the staged
 // image (StageLayout<FAST, true>), so nothing of them is live, and no global load is issued, before the model phase reads
 // them from LDS. img: the kernel's LDS image.
