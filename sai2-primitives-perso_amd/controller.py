@@ -765,6 +765,13 @@ class Controller:
         self._rc(self.lib.sai2b_get_fallback_count(self.h, C.byref(n)))
         return n.value
 
+    def worklist_state(self):
+        """-> dict(last_seen, pending): the work list's length at the host's last look (that of the tick 8 before it; -1: none
+        yet) and how the request under way is answered (0: none, 1: mapped host words, 2: copies)"""
+        v = [C.c_int(), C.c_int()]
+        self._rc(self.lib.sai2b_get_worklist_state(self.h, C.byref(v[0]), C.byref(v[1])))
+        return {"last_seen": v[0].value, "pending": v[1].value}
+
     def counters(self):
         a, b = C.c_longlong(), C.c_longlong()
         self.lib.sai2b_counters(self.h, C.byref(a), C.byref(b))

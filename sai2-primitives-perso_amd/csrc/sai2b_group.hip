@@ -17,13 +17,19 @@ namespace sai2b {
 template <int G, bool RANGE>
 __global__ __launch_bounds__(64) SAI2B_GROUP_OCC void tick_group_kernel(const DevParams* __restrict__ Pp, int commit_sh, int with_comp,
 														   int do_torque, const int* __restrict__ fb_count,
-														   const int* __restrict__ fb_list) {
+														   const int* __restrict__ fb_list, unsigned long long* report, unsigned stamp) {
 	constexpr int GPB = 64 / G;	 // robots per workgroup (one wavefront)
 	__shared__ real pads[GPB][grp::PAD_DOUBLES];
 	const DevParams& P = *Pp;
 	const int gi = grp::group<G>();
 	if (fb_count) {
 		const int cnt = *(const gint*)fb_count;
+		// the list's counts for the host (mapped host memory, one lane, two tagged 8-byte words: never a torn pair)
+		if (report && blockIdx.x == 0 && threadIdx.x == 0) {
+			const unsigned long long tag = (unsigned long long)stamp << 32;
+			__hip_atomic_store(report, tag | (unsigned)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+			__hip_atomic_store(report + 1, tag | (unsigned)((const gint*)fb_count)[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		}
 #pragma unroll 1
 		// entry e -> workgroup e % gridDim.x: a short list gives every robot a wavefront of its own (robots of one
 		// wavefront that take different branches run one after the other)
@@ -79,7 +85,7 @@ namespace sai2b {
 
 // lanes: 16 or 8. range_only: the pass ahead of the generator kernels (gated JointTasks)
 int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_only, bool commit_sh, bool with_comp, bool do_torque,
-					  const int* fb_count, const int* fb_list, hipStream_t stream) {
+					  const int* fb_count, const int* fb_list, hipStream_t stream, unsigned long long* report, unsigned stamp) {
 	const int gpb = 64 / lanes;
 	int blocks = (B + gpb - 1) / gpb;
 	// the pass over a work list strides over it: one wavefront per SIMD is all this kernel can have resident (512
@@ -88,7 +94,7 @@ int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_on
 	static constexpr decltype(&tick_group_kernel<16, false>) kernel[2][2] = {{tick_group_kernel<8, false>, tick_group_kernel<8, true>},
 																			 {tick_group_kernel<16, false>, tick_group_kernel<16, true>}};
 	hipLaunchKernelGGL(kernel[lanes == 16][range_only], dim3(blocks), dim3(64), 0, stream, d_params, commit_sh ? 1 : 0, with_comp ? 1 : 0,
-					   do_torque ? 1 : 0, fb_count, fb_list);
+					   do_torque ? 1 : 0, fb_count, fb_list, fb_count ? report : nullptr, stamp);
 	return launch_result();
 }
 

@@ -61,6 +61,14 @@ struct sai2b_ctx {
 	bool sing_mode = false, no_sing6 = false, force_sing6 = false;
 	hipEvent_t fb_seen_ev = nullptr;
 	bool fb_seen_pending = false;
+	// The same counts without copy kernels: two 8-byte words in mapped, coherent pinned memory (fb.report is their device
+	// address) that the pass over the work list writes itself: [0] = stamp << 32 | declined, [1] = stamp << 32 | in-lane
+	// singular. The host asks with a fresh stamp and, 8 ticks on, waits until both tags carry it. fb_seen_by_copy: the
+	// pending request went through fb_seen and the event instead (the one-lane generic kernel as the pass does not take
+	// the pointer).
+	unsigned long long* fb_report = nullptr;
+	unsigned fb_stamp = 0;
+	bool fb_seen_by_copy = false;
 	// The route of a tick is a function of the tick index: the counts recorded at tick k (counted in ticks that want the
 	// SVD-free kernel) are consumed at tick k + 8, waiting for the read-back if it has not arrived (it has, at that
 	// distance, unless the caller never fetches a result); the next probe is recorded there.
@@ -763,6 +771,9 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	hp.q = ctx->q, hp.dq = ctx->dq, hp.tau = ctx->tau;
 	if ((rc = dev_alloc(ctx, &ctx->q_pose, (size_t)N * Bs))) return rc;
 	if ((rc = dev_alloc(ctx, &ctx->fb.counts, 4))) return rc;
+	HIP_TRY(ctx, hipHostMalloc((void**)&ctx->fb_report, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+	ctx->fb_report[0] = ctx->fb_report[1] = 0;
+	HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->fb.report, ctx->fb_report, 0));
 	if ((rc = dev_alloc(ctx, &ctx->fb.list, Bs))) return rc;
 	if ((rc = dev_alloc(ctx, &ctx->rg.counts, 2))) return rc;
 	if ((rc = dev_alloc(ctx, &ctx->rg.list, Bs))) return rc;
@@ -847,6 +858,7 @@ extern "C" void sai2b_destroy(sai2b_ctx* ctx) {
 	if (ctx->otg_seen_ev) (void)hipEventDestroy(ctx->otg_seen_ev);
 	if (ctx->otg_busy_seen) (void)hipHostFree(ctx->otg_busy_seen);
 	if (ctx->fb_seen) (void)hipHostFree(ctx->fb_seen);
+	if (ctx->fb_report) (void)hipHostFree(ctx->fb_report);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -1197,6 +1209,33 @@ static TickForm tick_form(const sai2b_ctx* ctx) {
 	return form;
 }
 
+// The counts of the pending request (launch_tick), waiting for them if they have not arrived: 0 and d / took filled, or an error
+static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took) {
+	if (ctx->fb_seen_by_copy) {
+		if (hipEventQuery(ctx->fb_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->fb_seen_ev));
+		*d = ctx->fb_seen[0], *took = ctx->fb_seen[1];
+		return SAI2B_OK;
+	}
+	const unsigned long long want = ctx->fb_stamp;
+	unsigned long long w0 = 0, w1 = 0;
+	auto arrived = [&] {
+		w0 = __atomic_load_n(&ctx->fb_report[0], __ATOMIC_ACQUIRE), w1 = __atomic_load_n(&ctx->fb_report[1], __ATOMIC_ACQUIRE);
+		return (w0 >> 32) == want && (w1 >> 32) == want;
+	};
+	if (!arrived()) {
+		// (at a distance of 8 ticks they have, unless the caller never fetches a result)
+		const auto t0 = std::chrono::steady_clock::now();
+		for (unsigned spin = 0; !arrived(); spin++)
+			if ((spin & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+		if (!arrived()) {
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+			if (!arrived()) return set_error(ctx, SAI2B_RUNTIME_ERROR, "the work list's counts did not reach the host");
+		}
+	}
+	*d = (long long)(unsigned)w0, *took = (long long)(unsigned)w1;
+	return SAI2B_OK;
+}
+
 // How many lanes a robot gets in the generic kernel (sai2b_group.hip). 16 = one DPP row per robot: the shortest
 // critical path, what the (usually short) work list behind the SVD-free kernel wants; 8 = two robots per row:
 // fewer idle lanes, better when the whole batch runs the generic kernel and fills the machine anyway.
@@ -1312,9 +1351,9 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		const int alt = sing6_kind(ctx);
 		ctx->cert_tick++;
 		if (ctx->fb_seen_pending && ctx->cert_tick - ctx->fb_seen_tick >= 8) {
-			if (hipEventQuery(ctx->fb_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->fb_seen_ev));
-			ctx->fb_seen_pending = false;
-			const long long d = ctx->fb_seen[0], took = ctx->fb_seen[1];
+			long long d = 0, took = 0;
+			ctx->fb_seen_pending = false;  // (also when they never arrive: the next tick asks afresh)
+			if (int rc_ = fb_counts_arrived(ctx, &d, &took)) return rc_;
 			ctx->fb_last_seen = (int)d;
 			if (ctx->sing_mode) {
 				if (d * 5 > (long long)ctx->B * 2)
@@ -1341,13 +1380,24 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	TickCall call;
 	call.debug = ctx->introspection, call.commit_sh = commit_sh, call.with_comp = with_comp, call.do_torque = do_torque;
 	call.group = generic_lanes(ctx, !fast_launch || long_list);
+	// the pass over the work list reports the list's counts when asked (the lanes-per-robot pass takes the request; the
+	// one-lane generic kernel as the pass does not: two copies behind it, as before)
+	const bool ask = fast_launch && !ctx->fb_seen_pending;
+	const bool by_copy = ask && call.group == 0;
+	if (ask && !by_copy) {
+		if (++ctx->fb_stamp == 0) ctx->fb_stamp = 1;
+		call.stamp = ctx->fb_stamp;
+	}
 	if (sai2b::launch_tick(ctx->d_params, ctx->B, form, call, ctx->fb, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
-	if (fast_launch && !ctx->fb_seen_pending) {
+	if (by_copy) {
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen + 1, ctx->fb.took(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->fb_seen_ev, ctx->stream));
+	}
+	if (ask) {
+		ctx->fb_seen_by_copy = by_copy;
 		ctx->fb_seen_pending = true;
 		ctx->fb_seen_tick = ctx->cert_tick;
 	}
@@ -2718,6 +2768,13 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 	}
 	HIP_TRY(ctx, hipMemcpyAsync(robots, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
+extern "C" int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending) {
+	if (!ctx) return SAI2B_INVALID_ARGUMENT;
+	if (last_seen) *last_seen = ctx->fb_last_seen;
+	if (pending) *pending = ctx->fb_seen_pending ? (ctx->fb_seen_by_copy ? 2 : 1) : 0;
 	return SAI2B_OK;
 }
 

@@ -468,9 +468,12 @@ static int launch_fast(const DevParams* d_params, int B, const TickForm& form, b
 }
 
 // the generic kernel: over the work list fb_count / fb_list (or, NULL, the whole batch), `group` lanes per robot
-static int launch_generic(const DevParams* d_params, int B, const TickCall& call, const int* fb_count, const int* fb_list, hipStream_t stream) {
+// report: where the pass over a work list tells the host the list's counts, when the call asks (TickCall::stamp)
+static int launch_generic(const DevParams* d_params, int B, const TickCall& call, const int* fb_count, const int* fb_list, hipStream_t stream,
+						  unsigned long long* report = nullptr) {
 	if (call.group && !call.debug)
-		return launch_tick_group(d_params, B, call.group, false, call.commit_sh, call.with_comp, call.do_torque, fb_count, fb_list, stream);
+		return launch_tick_group(d_params, B, call.group, false, call.commit_sh, call.with_comp, call.do_torque, fb_count, fb_list, stream,
+								 call.stamp ? report : nullptr, call.stamp);
 	auto* kernel = call.debug ? tick_kernel<true> : tick_kernel<false>;
 	hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, call.commit_sh ? 1 : 0, call.with_comp ? 1 : 0,
 					   call.do_torque ? 1 : 0, fb_count, fb_list);
@@ -481,7 +484,7 @@ int launch_tick(const DevParams* d_params, int B, const TickForm& form, const Ti
 	// the fast path produces torques only: introspection and model-only passes use the generic kernel
 	if (call.debug || form.fast == 0 || !call.do_torque || !call.commit_sh) return launch_generic(d_params, B, call, nullptr, nullptr, stream);
 	const int rc = launch_fast(d_params, B, form, call.with_comp, fb, stream);
-	return launch_generic(d_params, B, call, fb.count(), fb.list, stream) | rc;
+	return launch_generic(d_params, B, call, fb.count(), fb.list, stream, fb.report) | rc;
 }
 
 // the range pass of hierarchies with gated generators (same DEBUG variant as the tick that follows, so that

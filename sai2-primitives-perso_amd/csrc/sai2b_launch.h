@@ -12,10 +12,13 @@ namespace sai2b {
 // one. list: [B] robot indices. The tick's list has two more counters at [2..3], alternating alike: robots that went
 // through the in-lane singular branch of tick_cert_kernel. The generators' list (sai2b_otg.hip) is
 // counts [2][SAI2B_MAX_TASKS] + 2 (non-idle robots of a tick, alternating) and list [SAI2B_MAX_TASKS][B].
+// report: the mapped host words through which the pass over the tick's list tells the host the list's counts (device address;
+// two 8-byte words, see tick_group_kernel). The tick's list alone has them.
 struct WorkList {
 	int* counts = nullptr;
 	int* list = nullptr;
 	int parity = 0;
+	unsigned long long* report = nullptr;
 	int* count() const { return counts + parity; }
 	int* took() const { return counts + 2 + parity; }
 };
@@ -36,6 +39,7 @@ struct TickCall {
 	bool debug = false;	 // the introspection instantiation of the generic kernel, no SVD-free kernel
 	bool commit_sh = true, with_comp = true, do_torque = true;
 	int group = 0;	// lanes per robot of the generic kernel (16 / 8), or 0 = the one-lane-per-robot generic kernel
+	unsigned stamp = 0;	 // != 0: the host asks for the work list's counts, tagged with it (WorkList::report)
 };
 
 inline int launch_result() { return hipGetLastError() == hipSuccess ? 0 : 1; }
@@ -44,8 +48,9 @@ inline int launch_result() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 // behind it, or the generic kernel for the whole batch
 int launch_tick(const DevParams* d_params, int B, const TickForm& form, const TickCall& call, const WorkList& fb, hipStream_t stream);
 // generic tick with a robot spread over `lanes` = 16 or 8 lanes (sai2b_group.hip); fb_count / fb_list as tick_kernel
+// report != NULL (with a work list): workgroup 0 writes {stamp << 32 | count, stamp << 32 | fb_count[2]} there, system scope
 int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_only, bool commit_sh, bool with_comp, bool do_torque,
-					  const int* fb_count, const int* fb_list, hipStream_t stream);
+					  const int* fb_count, const int* fb_list, hipStream_t stream, unsigned long long* report = nullptr, unsigned stamp = 0);
 // the SVD-free tick for general hierarchies (sai2b_cert.hip, form.fast >= 3): fills the work list like the fast kernels
 int launch_tick_cert(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, hipStream_t stream);
 // the range pass ahead of the trajectory generators for certified robots (sai2b_cert.hip: range_cert_kernel); the rest
