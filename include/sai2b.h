@@ -804,8 +804,12 @@ int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots);
 /* What the host knows of the tick's work list (diagnostics, tests). last_seen: the list's length at the host's last look,
  * which is that of the tick 8 before the look (-1: never looked). pending: 0 = no request for the counts is under way,
  * 1 = one is, answered by the pass over the list through mapped host words, 2 = one is, answered by two copies behind
- * the pass (the one-lane generic kernel as the pass, SAI2B_GENERIC_LANES=1). Any pointer may be NULL. */
-int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending);
+ * the pass (the one-lane generic kernel as the pass, SAI2B_GENERIC_LANES=1). form: what the last tick launched: 0 = the generic
+ * kernel alone, 1 = an SVD-free kernel and the generic kernel over its work list behind it, 2 = one launch in which every
+ * wavefront serves the robots it declines itself (the headline hierarchies without payload, while the last look found no
+ * wavefront with more than four declined robots; SAI2B_NO_SELF_SERVE=1 keeps form 1). wmax: the largest number of robots one
+ * wavefront declined, of the same look as last_seen (-1: not known). Any pointer may be NULL. */
+int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending, int* form, int* wmax);
 
 /* number of kernel launches and robots processed since creation (bench bookkeeping) */
 int sai2b_counters(const sai2b_ctx* ctx, long long* launches, long long* ticks);

@@ -465,7 +465,7 @@ def load_library():
     lib.sai2b_get_model.argtypes = [vp, _i, vp, vp, vp, vp]
     lib.sai2b_profile_tick.argtypes = [vp, _i, P(_d), P(_d)]
     lib.sai2b_get_fallback_count.argtypes = [vp, P(_i)]
-    lib.sai2b_get_worklist_state.argtypes = [vp, P(_i), P(_i)]
+    lib.sai2b_get_worklist_state.argtypes = [vp, P(_i), P(_i), P(_i), P(_i)]
     lib.sai2b_counters.argtypes = [vp, P(C.c_longlong), P(C.c_longlong)]
     lib.sai2b_set_link_payload.argtypes = [vp, _i, _i, vp, vp, vp, _i]
     lib.sai2b_clear_link_payload.argtypes = [vp, _i]

@@ -766,11 +766,13 @@ class Controller:
         return n.value
 
     def worklist_state(self):
-        """-> dict(last_seen, pending): the work list's length at the host's last look (that of the tick 8 before it; -1: none
-        yet) and how the request under way is answered (0: none, 1: mapped host words, 2: copies)"""
-        v = [C.c_int(), C.c_int()]
-        self._rc(self.lib.sai2b_get_worklist_state(self.h, C.byref(v[0]), C.byref(v[1])))
-        return {"last_seen": v[0].value, "pending": v[1].value}
+        """-> dict(last_seen, pending, form, wmax): the work list's length at the host's last look (that of the tick 8 before
+        it; -1: none yet), how the request under way is answered (0: none, 1: mapped host words, 2: copies), what the last tick
+        launched (0: the generic kernel alone, 1: an SVD-free kernel and the pass over its work list, 2: one launch, every
+        wavefront serving the robots it declines) and the most robots one wavefront declined at that look (-1: not known)"""
+        v = [C.c_int() for _ in range(4)]
+        self._rc(self.lib.sai2b_get_worklist_state(self.h, *[C.byref(x) for x in v]))
+        return {"last_seen": v[0].value, "pending": v[1].value, "form": v[2].value, "wmax": v[3].value}
 
     def counters(self):
         a, b = C.c_longlong(), C.c_longlong()

@@ -436,11 +436,15 @@ DI void sti(int* p, int row, int B, int b, int v) { ((gint*)p)[(size_t)row * B +
 
 // A lane that is not `mine` appends its robot b to the work list of the kernel launched behind (one atomic per wavefront
 // that has such lanes, on counts[parity]) and gets true back: it touches no state and returns. One wavefront per workgroup.
-DI bool worklist_append(int* __restrict__ counts, int* __restrict__ list, int parity, bool mine, int b) {
+// wmax != NULL (the tick's list behind tick_fast_kernel): wmax[parity] keeps the largest number of such lanes in one wavefront.
+DI bool worklist_append(int* __restrict__ counts, int* __restrict__ list, int parity, bool mine, int b, int* wmax = nullptr) {
 	const unsigned long long declined = __ballot(!mine);
 	if (declined) {
 		int base = 0;
-		if (threadIdx.x == 0) base = atomicAdd(&counts[parity], __popcll(declined));  // lane 0 is always in range
+		if (threadIdx.x == 0) {	 // lane 0 is always in range
+			base = atomicAdd(&counts[parity], __popcll(declined));
+			if (wmax) atomicMax(&wmax[parity], __popcll(declined));
+		}
 		base = __shfl(base, 0);
 		if (!mine) {
 			((gint*)list)[base + __popcll(declined & ((1ull << threadIdx.x) - 1ull))] = b;

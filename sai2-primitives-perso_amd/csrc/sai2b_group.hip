@@ -24,11 +24,13 @@ __global__ __launch_bounds__(64) SAI2B_GROUP_OCC void tick_group_kernel(const De
 	const int gi = grp::group<G>();
 	if (fb_count) {
 		const int cnt = *(const gint*)fb_count;
-		// the list's counts for the host (mapped host memory, one lane, two tagged 8-byte words: never a torn pair)
+		// the list's counts for the host (mapped host memory, one lane, three tagged 8-byte words: never a torn set; the third is the
+		// largest number of robots one wavefront declined, by which the host chooses the one-launch form, sai2b_self.hip)
 		if (report && blockIdx.x == 0 && threadIdx.x == 0) {
 			const unsigned long long tag = (unsigned long long)stamp << 32;
 			__hip_atomic_store(report, tag | (unsigned)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 			__hip_atomic_store(report + 1, tag | (unsigned)((const gint*)fb_count)[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+			__hip_atomic_store(report + 2, tag | (unsigned)((const gint*)fb_count)[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 		}
 #pragma unroll 1
 		// entry e -> workgroup e % gridDim.x: a short list gives every robot a wavefront of its own (robots of one

@@ -61,9 +61,10 @@ struct sai2b_ctx {
 	bool sing_mode = false, no_sing6 = false, force_sing6 = false;
 	hipEvent_t fb_seen_ev = nullptr;
 	bool fb_seen_pending = false;
-	// The same counts without copy kernels: two 8-byte words in mapped, coherent pinned memory (fb.report is their device
-	// address) that the pass over the work list writes itself: [0] = stamp << 32 | declined, [1] = stamp << 32 | in-lane
-	// singular. The host asks with a fresh stamp and, 8 ticks on, waits until both tags carry it. fb_seen_by_copy: the
+	// The same counts without copy kernels: three 8-byte words in mapped, coherent pinned memory (fb.report is their device
+	// address) that the pass over the work list writes itself (in the self form: a launch of one lane behind the asking tick):
+	// [0] = stamp << 32 | declined, [1] = stamp << 32 | in-lane singular, [2] = stamp << 32 | most declined robots of one
+	// wavefront. The host asks with a fresh stamp and, 8 ticks on, waits until all tags carry it. fb_seen_by_copy: the
 	// pending request went through fb_seen and the event instead (the one-lane generic kernel as the pass does not take
 	// the pointer).
 	unsigned long long* fb_report = nullptr;
@@ -75,6 +76,12 @@ struct sai2b_ctx {
 	long long cert_tick = 0, fb_seen_tick = 0;
 	int cert_backoff = 0;
 	int fb_last_seen = -1;		// length of the work list when the host last looked (-1: never)
+	// The headline tick in one launch (tick_self_kernel, sai2b_self.hip: a wavefront serves the robots it declines itself) while
+	// the last look said that this costs no wavefront more than one round of four robots: fb_last_wmax = the largest number of
+	// robots one wavefront declined, the third word of that look (-1: not known, the look went through the copies). Before
+	// any look the form is self. SAI2B_NO_SELF_SERVE=1 keeps the two launches. last_tick_form: sai2b_get_worklist_state
+	int fb_last_wmax = -1, last_tick_form = 0;
+	bool no_self_serve = false;
 	bool last_tick_generic_only = false;
 	// sai2b_update_task_models() is deferred: the reference's loop is update -> goal setters -> computeControlTorques,
 	// and the fused tick (with the SVD-free kernels in front) does both at once. Any other call in between runs the
@@ -747,6 +754,8 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	const char* pc = std::getenv("SAI2B_PREFER_CERT");
 	ctx->prefer_cert = pc && pc[0] == '1';
 	if (const char* gl = std::getenv("SAI2B_GENERIC_LANES")) ctx->generic_lanes_env = std::atoi(gl);
+	const char* nss = std::getenv("SAI2B_NO_SELF_SERVE");
+	ctx->no_self_serve = nss && nss[0] == '1';
 	DevParams& hp = ctx->h_params;
 	std::memset(&hp, 0, sizeof(hp));
 	hp.B = batch, hp.n_tasks = n_tasks;
@@ -770,9 +779,9 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	if ((rc = dev_alloc(ctx, &ctx->tau, N * Bs))) return rc;
 	hp.q = ctx->q, hp.dq = ctx->dq, hp.tau = ctx->tau;
 	if ((rc = dev_alloc(ctx, &ctx->q_pose, (size_t)N * Bs))) return rc;
-	if ((rc = dev_alloc(ctx, &ctx->fb.counts, 4))) return rc;
-	HIP_TRY(ctx, hipHostMalloc((void**)&ctx->fb_report, 2 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-	ctx->fb_report[0] = ctx->fb_report[1] = 0;
+	if ((rc = dev_alloc(ctx, &ctx->fb.counts, 6))) return rc;
+	HIP_TRY(ctx, hipHostMalloc((void**)&ctx->fb_report, 3 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+	ctx->fb_report[0] = ctx->fb_report[1] = ctx->fb_report[2] = 0;
 	HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->fb.report, ctx->fb_report, 0));
 	if ((rc = dev_alloc(ctx, &ctx->fb.list, Bs))) return rc;
 	if ((rc = dev_alloc(ctx, &ctx->rg.counts, 2))) return rc;
@@ -1206,21 +1215,27 @@ static TickForm tick_form(const sai2b_ctx* ctx) {
 	form.baked = ctx->baked_model;
 	form.payload = ctx->h_params.payload != nullptr;
 	form.inlane_singular = !ctx->no_inlane_singular;
+	// One launch (sai2b_self.hip) for the two headline kernels without payload, while the generic kernel is the lanes-per-robot
+	// one and the last look found a short list (long_list's bound) of which no wavefront holds more than one round of four
+	// robots. Speed only: each robot runs the same per-robot code either way.
+	form.self = N == 7 && (form.fast == 1 || form.fast == 2) && !form.payload && ctx->generic_lanes_env != 1 && !ctx->no_self_serve &&
+				(ctx->fb_last_seen < 0 || (ctx->fb_last_seen <= 4096 && ctx->fb_last_wmax >= 0 && ctx->fb_last_wmax <= 4));
 	return form;
 }
 
-// The counts of the pending request (launch_tick), waiting for them if they have not arrived: 0 and d / took filled, or an error
-static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took) {
+// The counts of the pending request (launch_tick), waiting for them if they have not arrived: 0 and d / took / wmax filled, or an error
+static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took, long long* wmax) {
 	if (ctx->fb_seen_by_copy) {
 		if (hipEventQuery(ctx->fb_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->fb_seen_ev));
-		*d = ctx->fb_seen[0], *took = ctx->fb_seen[1];
+		*d = ctx->fb_seen[0], *took = ctx->fb_seen[1], *wmax = -1;
 		return SAI2B_OK;
 	}
 	const unsigned long long want = ctx->fb_stamp;
-	unsigned long long w0 = 0, w1 = 0;
+	unsigned long long w0 = 0, w1 = 0, w2 = 0;
 	auto arrived = [&] {
 		w0 = __atomic_load_n(&ctx->fb_report[0], __ATOMIC_ACQUIRE), w1 = __atomic_load_n(&ctx->fb_report[1], __ATOMIC_ACQUIRE);
-		return (w0 >> 32) == want && (w1 >> 32) == want;
+		w2 = __atomic_load_n(&ctx->fb_report[2], __ATOMIC_ACQUIRE);
+		return (w0 >> 32) == want && (w1 >> 32) == want && (w2 >> 32) == want;
 	};
 	if (!arrived()) {
 		// (at a distance of 8 ticks they have, unless the caller never fetches a result)
@@ -1232,7 +1247,7 @@ static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took) {
 			if (!arrived()) return set_error(ctx, SAI2B_RUNTIME_ERROR, "the work list's counts did not reach the host");
 		}
 	}
-	*d = (long long)(unsigned)w0, *took = (long long)(unsigned)w1;
+	*d = (long long)(unsigned)w0, *took = (long long)(unsigned)w1, *wmax = (long long)(unsigned)w2;
 	return SAI2B_OK;
 }
 
@@ -1351,10 +1366,10 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		const int alt = sing6_kind(ctx);
 		ctx->cert_tick++;
 		if (ctx->fb_seen_pending && ctx->cert_tick - ctx->fb_seen_tick >= 8) {
-			long long d = 0, took = 0;
+			long long d = 0, took = 0, wmax = -1;
 			ctx->fb_seen_pending = false;  // (also when they never arrive: the next tick asks afresh)
-			if (int rc_ = fb_counts_arrived(ctx, &d, &took)) return rc_;
-			ctx->fb_last_seen = (int)d;
+			if (int rc_ = fb_counts_arrived(ctx, &d, &took, &wmax)) return rc_;
+			ctx->fb_last_seen = (int)d, ctx->fb_last_wmax = (int)wmax;
 			if (ctx->sing_mode) {
 				if (d * 5 > (long long)ctx->B * 2)
 					ctx->cert_backoff = 64;
@@ -1373,6 +1388,8 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 		form.fast = 0;
 	}
 	const bool fast_launch = fast_wanted && form.fast != 0;
+	form.self = form.self && fast_launch;
+	ctx->last_tick_form = !fast_launch ? 0 : (form.self ? 2 : 1);
 	ctx->last_tick_generic_only = do_torque && commit_sh && !fast_launch && !ctx->introspection;
 	if (fast_launch) ctx->fb.parity ^= 1;
 	// a long work list (thousands of robots) is throughput, not latency: two robots per DPP row, as for a whole batch
@@ -1380,8 +1397,8 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	TickCall call;
 	call.debug = ctx->introspection, call.commit_sh = commit_sh, call.with_comp = with_comp, call.do_torque = do_torque;
 	call.group = generic_lanes(ctx, !fast_launch || long_list);
-	// the pass over the work list reports the list's counts when asked (the lanes-per-robot pass takes the request; the
-	// one-lane generic kernel as the pass does not: two copies behind it, as before)
+	// the pass over the work list reports the list's counts when asked (the lanes-per-robot pass takes the request, and so does
+	// the self form, with a launch of one lane behind it; the one-lane generic kernel as the pass does not: two copies behind it)
 	const bool ask = fast_launch && !ctx->fb_seen_pending;
 	const bool by_copy = ask && call.group == 0;
 	if (ask && !by_copy) {
@@ -2707,7 +2724,10 @@ extern "C" int sai2b_get_model(sai2b_ctx* ctx, int task, double* M, double* J, d
 // Bench bookkeeping: run `steps` fused ticks with HIP events around EACH kernel launch of the tick on
 // the ctx stream and return the average duration per launch in milliseconds: first kernel of the tick
 // (the SVD-free kernel when the hierarchy is eligible, else the generic kernel) and, when there is
-// one, the generic kernel over its work list behind it (0 otherwise).
+// one, the generic kernel over its work list behind it (0 otherwise). In the self form (tick_self_kernel) the tick is one
+// kernel: while it declines nothing, that kernel is the first figure and the second is 0. When the last tick declined robots,
+// the first figure is the SVD-free kernel by itself, as in the two-launch form, and the second what the self kernel takes
+// beyond it, which is what serving those robots inside the launch adds to a step.
 extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, double* second_ms) {
 	if (!ctx || steps < 1) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_profile_tick: bad arguments");
 	if (int rc_ = flush_update(ctx)) return rc_;
@@ -2715,7 +2735,15 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 	int rc = upload_params(ctx);
 	if (rc) return rc;
 	const TickForm form = tick_form(ctx);  // (the kernel the ticks are running now)
-	const bool two = form.fast != 0 && !ctx->introspection;
+	const bool self = form.self && !ctx->introspection;
+	int declined = 0;
+	if (self) {
+		HIP_TRY(ctx, hipMemcpyAsync(&declined, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	const bool two = form.fast != 0 && !ctx->introspection && (!self || declined > 0);
+	TickForm alone = form;	// the SVD-free kernel by itself
+	alone.self = false;
 	// ONE event pair around `steps` back-to-back launches (an event pair per launch costs ~4 us of its own, which made
 	// the two parts add up to more than the step): first the first kernel alone, then the sequence of a tick. The
 	// second figure is what the work-list pass adds to a step, so the two sum to the step by construction.
@@ -2727,10 +2755,11 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 		for (int rep = 0; rep < 2; rep++) {	 // (the first repetition warms the sequence up)
 			HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
 			for (int s = 0; s < steps; s++) {
-				if (two) ctx->fb.parity ^= 1;
-				if (sai2b::launch_tick_part(ctx->d_params, ctx->B, form, ctx->introspection, 0, ctx->fb, generic_lanes(ctx, !two), ctx->stream))
+				if (two || self) ctx->fb.parity ^= 1;
+				if (sai2b::launch_tick_part(ctx->d_params, ctx->B, (two && phase == 0) ? alone : form, ctx->introspection, 0, ctx->fb,
+											generic_lanes(ctx, !two), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
-				if (phase == 1 && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, generic_lanes(ctx, false), ctx->stream))
+				if (phase == 1 && !self && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, generic_lanes(ctx, false), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 			}
 			HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
@@ -2742,7 +2771,7 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 	}
 	(void)hipEventDestroy(e0);
 	(void)hipEventDestroy(e1);
-	ctx->launches += (two ? 6 : 2) * (long long)steps;
+	ctx->launches += (two ? (self ? 4 : 6) : 2) * (long long)steps;
 	ctx->ticks += (two ? 4 : 2) * (long long)steps * ctx->B;
 	if (first_ms) *first_ms = part_ms[0];
 	if (second_ms) *second_ms = two ? std::max(0.0, part_ms[1] - part_ms[0]) : 0.0;
@@ -2771,10 +2800,12 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 	return SAI2B_OK;
 }
 
-extern "C" int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending) {
+extern "C" int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending, int* form, int* wmax) {
 	if (!ctx) return SAI2B_INVALID_ARGUMENT;
 	if (last_seen) *last_seen = ctx->fb_last_seen;
 	if (pending) *pending = ctx->fb_seen_pending ? (ctx->fb_seen_by_copy ? 2 : 1) : 0;
+	if (form) *form = ctx->last_tick_form;
+	if (wmax) *wmax = ctx->fb_last_wmax;
 	return SAI2B_OK;
 }
 

@@ -7,36 +7,10 @@
 #include <hip/hip_runtime.h>
 
 #include "sai2b_device.hpp"
-#include "sai2b_fast.hpp"
-#include "sai2b_baked_panda.h"
-#include "sai2b_baked_panda_model.h"
+#include "sai2b_fast_body.hpp"
 #include "sai2b_launch.h"
 
 namespace sai2b {
-
-#if SAI2B_N == 7
-// The model phase of the BAKED kernels: overloads on PandaBaked that the calls below take in place of the generic templates
-// of sai2b_device.hpp. They run the generated straight-line forms (sai2b_baked_panda_model.h), which keep only the nonzero
-// terms of the Panda's constants; the payload forms keep payload_terms() and their selects as the generic ones have them.
-DI void fk(const PandaBaked&, const real* q, Frames& F) {
-	real sn[N], cs[N];
-	UNROLL for (int i = 0; i < N; i++) sincos_joint(q[i], &sn[i], &cs[i]);
-	panda_fk(sn, cs, F);
-}
-DI void jacobian(const PandaBaked&, const DevTask& t, const Frames& F, const real* x, real* J) { panda_jacobian(F, t.link, x, J); }
-DI void mass_matrix(const PandaBaked&, const Frames& F, real* M, const NoPayload& = NoPayload{}) { panda_mass_matrix(F, M); }
-DI void mass_matrix(const PandaBaked&, const Frames& F, real* M, const Payload& pl) {
-	PayloadTerms pt;
-	payload_terms(pl, F, pt);
-	panda_mass_matrix_payload(F, pl.link, pt, M);
-}
-DI void gravity_vector(const PandaBaked&, const Frames& F, real* g, const NoPayload& = NoPayload{}) { panda_gravity_vector(F, g); }
-DI void gravity_vector(const PandaBaked&, const Frames& F, real* g, const Payload& pl) {
-	PayloadTerms pt;
-	payload_terms(pl, F, pt);
-	panda_gravity_vector_payload(F, pl.link, pt, g);
-}
-#endif
 
 // Generic tick: Jacobi-SVD based, any hierarchy (the reference's control flow, projector form).
 // fb_count != NULL: the fallback pass behind tick_fast_kernel — lane i of the grid takes robot
@@ -131,213 +105,7 @@ __global__ __launch_bounds__(64) void tick_kernel(const DevParams* __restrict__ 
 	}
 }
 
-#if SAI2B_N == 7  // the SVD-free kernels are for 7-joint robots (6-DOF task + a one-dimensional nullspace)
-// [full MFT] (FAST = 1) with its inputs loaded into registers up front, as before the staged path: at C2's 4 096
-// robots (one wavefront per 16 SIMDs, nothing to contend for HBM) the staged form measured 13 % slower.
-// M and g of the headline kernels' model phase. PL = NoPayload: the code this was before payloads existed.
-template <bool BAKED, class PL>
-DI void fast_model(const DevParams& P, const Frames& F, const PL& pl, real* M, real* g) {
-	if constexpr (BAKED)
-		mass_matrix(PandaBaked{}, F, M, pl);
-	else
-		mass_matrix(P.model, F, M, pl);
-	if (P.gravity_comp) {
-		if constexpr (BAKED)
-			gravity_vector(PandaBaked{}, F, g, pl);
-		else
-			gravity_vector(P.model, F, g, pl);
-	}
-	else {
-		UNROLL for (int i = 0; i < N; i++) g[i] = 0;
-	}
-}
-
-template <bool BAKED, class PL>
-DI void tick_fast1_loads(const DevParams& P, int with_comp, int* __restrict__ fb_counts, int* __restrict__ fb_list, int parity,
-						 int b) {
-	const int B = P.B;
-	RobotCtx rc;
-	UNROLL for (int i = 0; i < N; i++) {
-		rc.q[i] = ld(P.q, i, B, b);
-		rc.dq[i] = ld(P.dq, i, B, b);
-	}
-	const DevTask& t0 = P.task[0];
-	const bool clean = ldi(t0.istate, IS_NTYPES, B, b) == 0;
-	// Phase order keeps the live set small and gives every load a phase of arithmetic to hide behind:
-	// FK/Jacobian -> MFT law -> CRBA -> certificate.
-	JtEarly jt;
-	MftIn in0;
-	mft_load(t0, B, b, in0);
-	SAI2B_PHASE();
-	real J[6 * N], M[N * N], g[N], Fu[6], Ff[6];
-	{
-		Frames F;
-		if constexpr (BAKED)
-			fk(PandaBaked{}, rc.q, F);
-		else
-			fk(P.model, rc.q, F);
-		real x[3], R[9];
-		frame_pose(t0, F, x, R);
-		if constexpr (BAKED)
-			jacobian(PandaBaked{}, t0, F, x, J);
-		else
-			jacobian(P.model, t0, F, x, J);
-		SAI2B_PHASE();
-		mft_law(t0, rc, J, x, R, in0, Fu, Ff);	// MotionForceTask.cpp:278-503 (integrators not yet stored)
-		SAI2B_PHASE();
-		if constexpr (PL::on) {	 // (the ten rows are loaded here, not with the other inputs: nothing of them is live across the law)
-			PL pl;
-			payload_load(P.payload, P.payload_link, B, b, pl);
-			fast_model<BAKED>(P, F, pl, M, g);
-		} else {	// spelled out as it was before payloads: the register allocation of this form follows the text
-			if constexpr (BAKED)
-				mass_matrix(PandaBaked{}, F, M);
-			else
-				mass_matrix(P.model, F, M);
-			if (P.gravity_comp) {
-				if constexpr (BAKED)
-					gravity_vector(PandaBaked{}, F, g);
-				else
-					gravity_vector(P.model, F, g);
-			}
-			else {
-				UNROLL for (int i = 0; i < N; i++) g[i] = 0;
-			}
-		}
-	}
-	SAI2B_PHASE();
-	const bool ok = certify_nonsingular(J, t0.s_abs_tol, t0.s_max);
-	const bool mine = ok && clean;
-	if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
-	mft_store_integrators(t0, B, b, in0);
-	SAI2B_PHASE();
-	real tau[N];
-	JtGiven none{jt};
-	fast_tick<false>(P, J, M, Fu, Ff, B, b, with_comp != 0, none, tau);
-	UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
-}
-
-// FAST = 1: hierarchy [full MFT]; FAST = 2: [full MFT, full JT] — the SVD-free path of
-// sai2b_fast.hpp. A robot takes it only when it is certified non-singular (and is not leaving a
-// singular region); otherwise its lane touches no state and appends the robot to the work list of
-// the generic kernel launched right behind (one atomic per wavefront that has such robots).
-// fb_counts: two counters alternating between ticks (`parity`): this launch fills [parity] and clears
-// [1 - parity] for the next one (the generic pass that read it finished before this kernel started).
-// BAKED selects where the robot constants come from: false = the ctx's parameter block (any robot),
-// true = the stock Panda (chosen by the host only when the ctx model is bit-equal to sai2b_baked_panda.h): the model
-// phase is the straight-line code of sai2b_baked_panda_model.h, written out at build time from the nonzero terms of those
-// constants (the PandaBaked overloads at the top of this file), with no loads from the parameter block.
-// PL = Payload: the form for contexts with per-robot payloads (tick_fast_payload_kernel below); its ten rows join the staged
-// image (StageLayout<FAST, true>), so nothing of them is live, and no global load is issued, before the model phase reads
-// them from LDS. img: the kernel's LDS image.
-template <int FAST, bool BAKED, class PL>
-DI void tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __restrict__ fb_counts, int* __restrict__ fb_list,
-					   int parity, real* img) {
-	const DevParams& P = *Pp;
-	const int B = P.B;
-	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
-	// Inputs: q in registers (FK needs it and nothing else), every other row by DMA into the LDS image (StageLayout,
-	// sai2b_fast.hpp). q is waited for before the DMA is issued, and the window up to the barrier issues no other
-	// global load and touches no scratch, so the DMA lands behind the kinematics and the barrier retires it.
-	using S = StageLayout<FAST, PL::on>;
-	RobotCtx rc;
-	UNROLL for (int i = 0; i < N; i++) {
-		rc.q[i] = ld(P.q, i, B, min(b, B - 1));
-		asm volatile("" : "+v"(rc.q[i]));  // the wait for q goes here, ahead of the DMA
-	}
-	SAI2B_PHASE();
-	stage_issue<FAST, PL::on>(P, img, b0);
-	SAI2B_PHASE();
-	if (b >= B) return;
-	const DevTask& t0 = P.task[0];
-	const real* col = img + threadIdx.x;
-	// Window: FK -> frame pose -> Jacobian -> (CRBA, gravity) -> certificate, from q alone. Without payload the model
-	// phase runs here, while the frames are alive anyway, and parks M and g in this lane's column of the rows behind
-	// the DMA image (S::PARKED): neither is live in registers across the certificate or the control law, and no
-	// barrier is owed for them (a lane reads back only what it wrote). The payload form's CRBA needs rows the DMA
-	// brings, so it keeps the model phase behind the law and evaluates FK a second time there.
-	real J[6 * N], x[3], R[9];
-	{
-		Frames F;
-		if constexpr (BAKED)
-			fk(PandaBaked{}, rc.q, F);
-		else
-			fk(P.model, rc.q, F);
-		frame_pose(t0, F, x, R);
-		if constexpr (BAKED)
-			jacobian(PandaBaked{}, t0, F, x, J);
-		else
-			jacobian(P.model, t0, F, x, J);
-		if constexpr (S::PARKED) {
-			SAI2B_PHASE();
-			real M[N * N], g[N];
-			fast_model<BAKED>(P, F, PL{}, M, g);
-			real* park = img + S::IMAGE + threadIdx.x;
-			UNROLL for (int i = 0; i < N; i++) UNROLL for (int j = 0; j <= i; j++) park[(i * (i + 1) / 2 + j) * 64] = M[i * N + j];
-			UNROLL for (int i = 0; i < N; i++) park[(S::MROWS + i) * 64] = g[i];
-		}
-	}
-	SAI2B_PHASE();
-	const bool ok = certify_nonsingular(J, t0.s_abs_tol, t0.s_max);
-	SAI2B_PHASE();
-	__syncthreads();  // one wavefront per workgroup: vmcnt(0) + barrier, the DMA-written image is readable from here
-	UNROLL for (int i = 0; i < N; i++) {
-		rc.dq[i] = col[(S::DQ + i) * 64];
-		if constexpr (!S::PARKED) rc.q[i] = ld(P.q, i, B, b);  // again (an L2 hit): not live across the window
-	}
-	const bool clean = ((const int*)(img + S::IROW * 64))[threadIdx.x] == 0;
-	MftIn in0;
-	mft_load(t0, StagedRows{t0, B, b, col + S::MG * 64, col + S::MS * 64, 6}, in0);
-	SAI2B_PHASE();
-	real Fu[6], Ff[6];
-	mft_law(t0, rc, J, x, R, in0, Fu, Ff);	// MotionForceTask.cpp:278-503 (integrators not yet stored)
-	SAI2B_PHASE();
-	real tau[N];
-	if constexpr (S::PARKED) {
-		const bool mine = ok && clean;
-		if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
-		mft_store_integrators(t0, B, b, in0);  // committed to the fast path: integrators can go out now
-		SAI2B_PHASE();
-		// the JointTask law and its integrator store are fast_tick's, behind the nullspace vector (JtLate)
-		const real* park = col + S::IMAGE;
-		JtLate jt{P.task[1], B, b, col + S::DQ * 64};
-		fast_tick<FAST == 2>(P, J, LdsSym{park}, Fu, Ff, B, b, with_comp != 0, jt, tau);
-		UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + park[(S::MROWS + i) * 64]);
-	} else {
-		real M[N * N], g[N];
-		{
-			PL pl;
-			if constexpr (PL::on) {
-				pl.link = P.payload_link;
-				pl.m = col[S::PLD * 64];
-				UNROLL for (int k = 0; k < 3; k++) pl.c[k] = col[(S::PLD + 1 + k) * 64];
-				UNROLL for (int k = 0; k < 6; k++) pl.I[k] = col[(S::PLD + 4 + k) * 64];
-			}
-			Frames F;
-			if constexpr (BAKED)
-				fk(PandaBaked{}, rc.q, F);
-			else
-				fk(P.model, rc.q, F);
-			fast_model<BAKED>(P, F, pl, M, g);
-		}
-		SAI2B_PHASE();
-		const bool mine = ok && clean;
-		if (worklist_append(fb_counts, fb_list, parity, mine, b)) return;
-		// the JointTask law, from its staged rows (late: its results would be live across the model phase)
-		JtEarly e;
-		if constexpr (FAST == 2) fast_jt_early(P.task[1], rc, StagedRows{P.task[1], B, b, col + S::JG * 64, col + S::JS * 64, N}, e);
-		// committed to the fast path: integrators can go out now
-		mft_store_integrators(t0, B, b, in0);
-		if (FAST == 2) {
-			UNROLL for (int i = 0; i < N; i++) st(P.task[1].state, i, B, b, e.integ[i]);
-		}
-		SAI2B_PHASE();
-		JtGiven jt{e};
-		fast_tick<FAST == 2>(P, J, M, Fu, Ff, B, b, with_comp != 0, jt, tau);
-		UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + g[i]);
-	}
-}
-
+#if SAI2B_N == 7  // the SVD-free kernels are for 7-joint robots: their per-lane body is sai2b_fast_body.hpp
 template <int FAST, bool BAKED>
 __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restrict__ Pp, int with_comp,
 														  int* __restrict__ fb_counts, int* __restrict__ fb_list,
@@ -346,7 +114,9 @@ __global__ __launch_bounds__(64) void tick_fast_kernel(const DevParams* __restri
 	const int B = P.B;
 	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
 	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
-	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
+	// [4 + ..]: the largest number of declined robots in one wavefront (worklist_append through fast_declined)
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0, ((gint*)fb_counts)[4 + (1 - parity)] = 0;
 	if constexpr (FAST == 1) {
 		if (b < B) tick_fast1_loads<BAKED, NoPayload>(P, with_comp, fb_counts, fb_list, parity, b);
 		return;
@@ -363,7 +133,9 @@ __global__ __launch_bounds__(64) void tick_fast_payload_kernel(const DevParams* 
 	const int B = P.B;
 	const int b0 = blockIdx.x * 64, b = b0 + threadIdx.x;
 	// (and the in-lane branch's count of the next launch: tick_cert_kernel<6, S6> may follow this kernel and adds to it)
-	if (blockIdx.x == 0 && threadIdx.x == 0) ((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0;
+	// [4 + ..]: the largest number of declined robots in one wavefront (worklist_append through fast_declined)
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		((gint*)fb_counts)[1 - parity] = 0, ((gint*)fb_counts)[2 + (1 - parity)] = 0, ((gint*)fb_counts)[4 + (1 - parity)] = 0;
 	if constexpr (FAST == 1) {
 		if (b < B) tick_fast1_loads<BAKED, Payload>(P, with_comp, fb_counts, fb_list, parity, b);
 		return;
@@ -483,6 +255,7 @@ static int launch_generic(const DevParams* d_params, int B, const TickCall& call
 int launch_tick(const DevParams* d_params, int B, const TickForm& form, const TickCall& call, const WorkList& fb, hipStream_t stream) {
 	// the fast path produces torques only: introspection and model-only passes use the generic kernel
 	if (call.debug || form.fast == 0 || !call.do_torque || !call.commit_sh) return launch_generic(d_params, B, call, nullptr, nullptr, stream);
+	if (form.self) return launch_tick_self(d_params, B, form, call.with_comp, fb, call.stamp, stream);
 	const int rc = launch_fast(d_params, B, form, call.with_comp, fb, stream);
 	return launch_generic(d_params, B, call, fb.count(), fb.list, stream, fb.report) | rc;
 }
@@ -502,6 +275,7 @@ int launch_tick_part(const DevParams* d_params, int B, const TickForm& form, boo
 	call.debug = debug, call.group = group;
 	if (debug || form.fast == 0) return launch_generic(d_params, B, call, nullptr, nullptr, stream);
 	if (part == 1) return launch_generic(d_params, B, call, fb.count(), fb.list, stream);
+	if (form.self) return launch_tick_self(d_params, B, form, true, fb, 0, stream);
 	return launch_fast(d_params, B, form, true, fb, stream);
 }
 

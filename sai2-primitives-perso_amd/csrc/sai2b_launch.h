@@ -12,8 +12,10 @@ namespace sai2b {
 // one. list: [B] robot indices. The tick's list has two more counters at [2..3], alternating alike: robots that went
 // through the in-lane singular branch of tick_cert_kernel. The generators' list (sai2b_otg.hip) is
 // counts [2][SAI2B_MAX_TASKS] + 2 (non-idle robots of a tick, alternating) and list [SAI2B_MAX_TASKS][B].
+// The tick's list also has counts[4..5], alternating alike: the largest number of robots one wavefront of tick_fast_kernel /
+// tick_self_kernel declined.
 // report: the mapped host words through which the pass over the tick's list tells the host the list's counts (device address;
-// two 8-byte words, see tick_group_kernel). The tick's list alone has them.
+// three 8-byte words, see tick_group_kernel). The tick's list alone has them.
 struct WorkList {
 	int* counts = nullptr;
 	int* list = nullptr;
@@ -32,6 +34,8 @@ struct TickForm {
 								  // kernels find the rows in the parameter block)
 	bool inlane_singular = true;  // singular MotionForceTasks stay in the lane (cert::singular_part), not on the work list
 	bool sing6 = false;			  // the 6-row tick_cert_kernel with the singular branch in the lane (cert::tick<.., S6>)
+	bool self = false;			  // fast = 1 | 2 without payload: one launch, each wavefront serves the robots it declines itself
+								  // (tick_self_kernel, sai2b_self.hip) instead of the generic kernel over a work list behind
 };
 
 // what a tick call asks for
@@ -48,9 +52,13 @@ inline int launch_result() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 // behind it, or the generic kernel for the whole batch
 int launch_tick(const DevParams* d_params, int B, const TickForm& form, const TickCall& call, const WorkList& fb, hipStream_t stream);
 // generic tick with a robot spread over `lanes` = 16 or 8 lanes (sai2b_group.hip); fb_count / fb_list as tick_kernel
-// report != NULL (with a work list): workgroup 0 writes {stamp << 32 | count, stamp << 32 | fb_count[2]} there, system scope
+// report != NULL (with a work list): workgroup 0 writes {stamp << 32 | count, stamp << 32 | fb_count[2], stamp << 32 | fb_count[4]}
+// there, system scope
 int launch_tick_group(const DevParams* d_params, int B, int lanes, bool range_only, bool commit_sh, bool with_comp, bool do_torque,
 					  const int* fb_count, const int* fb_list, hipStream_t stream, unsigned long long* report = nullptr, unsigned stamp = 0);
+// the tick of form.self in one launch (sai2b_self.hip); stamp != 0: a one-lane launch behind it writes fb.report as above
+int launch_tick_self(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, unsigned stamp,
+					 hipStream_t stream);
 // the SVD-free tick for general hierarchies (sai2b_cert.hip, form.fast >= 3): fills the work list like the fast kernels
 int launch_tick_cert(const DevParams* d_params, int B, const TickForm& form, bool with_comp, const WorkList& fb, hipStream_t stream);
 // the range pass ahead of the trajectory generators for certified robots (sai2b_cert.hip: range_cert_kernel); the rest

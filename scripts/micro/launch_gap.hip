@@ -106,6 +106,9 @@ int main() {
 	bulk = pass ? d_bulk : nullptr;
 	std::printf("---- A %s\n", pass ? "writes 14 MB per launch (dirty lines in the L2s at its end)" : "writes nothing");
 	timed("1. A alone", [&](unsigned k) { A(0, nullptr, nullptr, k); });
+	// 1b is the price of every form in which tail workgroups wait for the fast ones: 1 024 workgroups adding to ONE word cost
+	// ~11 us (28.4 against 17.2 us) whether or not anything spins on it (4). tick_self_kernel (csrc/sai2b_self.hip) has no such
+	// word: a wavefront serves the robots it declines itself.
 	timed("1b. A alone + finished counter", [&](unsigned k) { A(0, d_fin, nullptr, k); });
 	for (int g : {1024, 16, 1}) {
 		char name[96];
