@@ -23,7 +23,7 @@
 //
 // State (integrators) is written only once the robot is known to finish here: the values wait in LDS
 // (PEND_SLOTS doubles per lane). Partial tasks of up to 6 rows (the kernel's instantiations: MCAP = 3 and 6);
-// the host routes anything else to the generic kernel (sai2b_host.cpp: cert_kind).
+// the host routes anything else to the generic kernel (sai2b_tick_policy.h: cert_kind).
 #pragma once
 #include "sai2b_device.hpp"
 #include "sai2b_fast.hpp"

@@ -38,51 +38,27 @@ struct sai2b_ctx {
 	bool models_fresh = false;	// update_task_models() ran for the current state
 	bool params_dirty = true;
 	bool baked_model = false;  // the ctx model is bit-equal to the compile-time Panda constants
-	bool no_fast_path = false;	// SAI2B_NO_FAST_PATH=1 in the environment: always run the generic kernel
 	bool blocking_sync = false;	// SAI2B_BLOCKING_SYNC=1: sai2b_synchronize() blocks without polling first
-	bool no_cert_path = false;	// SAI2B_NO_CERT_PATH=1: no SVD-free kernel for general hierarchies (sai2b_cert.hpp)
-	bool no_inlane_singular = false;  // SAI2B_NO_INLANE_SINGULAR=1: singular MotionForceTasks of tick_cert_kernel<3> go to the work list
-	bool prefer_cert = false;	// SAI2B_PREFER_CERT=1 (diagnostic): sai2b_cert.hpp also where sai2b_fast.hpp applies
-	// lanes per robot of the generic kernel: SAI2B_GENERIC_LANES = 16 / 8 / 1 (1: the one-lane-per-robot kernel),
-	// default 0 = by the amount of work (generic_lanes())
-	int generic_lanes_env = 0;
+	// what a tick launches (sai2b_tick_policy.h): the switches of the environment, and the state of the route (the singular mode,
+	// the back-off, the pending request for the work list's counts and what the last look said)
+	sai2b::RouteSwitches sw;
+	sai2b::TickRoute route;
 	// work lists (sai2b_launch.h): fb = robots the tick's SVD-free kernel handed to the generic one (counts [4]: with the in-lane
 	// singular branch's), rg = the same for the range pass ahead of the trajectory generators, otg = robots that need the trajectory
 	// planner this tick (sai2b_otg.hip), tk = the task-level SVD-free kernel's (task_cert_kernel; created on first use).
 	// parity: the counter set of the last launch
 	WorkList fb, rg, otg, tk;
-	// How many robots the SVD-free kernel for general hierarchies keeps is a property of the workload (a 6-DOF task
-	// behind a partial JointTask is inside a blending region most of the time): every 8th such tick its count of
-	// declined robots comes back to the host (pinned word, consumed 8 ticks later: cert_tick); above 40 % of the batch the next 64
-	// ticks run the generic kernel alone, then the SVD-free kernel is tried again. Results are the same either way.
-	int* fb_seen = nullptr;		// pinned host words: [0] declined, [1] through the in-lane singular branch
-	// many robots inside a blending region of a 4- to 6-row MotionForceTask: the 6-row SVD-free kernel with the singular branch in
-	// the lane runs instead of the hierarchy's usual first kernel (launch_tick); SAI2B_NO_SING6=1 switches the mode off
-	bool sing_mode = false, no_sing6 = false, force_sing6 = false;
+	// The counts of the tick's work list come back to the host every 8th tick that wants the SVD-free kernel (route.look). By
+	// copies: two pinned host words, [0] declined, [1] through the in-lane singular branch, and an event behind them.
+	int* fb_seen = nullptr;
 	hipEvent_t fb_seen_ev = nullptr;
-	bool fb_seen_pending = false;
 	// The same counts without copy kernels: three 8-byte words in mapped, coherent pinned memory (fb.report is their device
 	// address) that the pass over the work list writes itself (in the self form: a launch of one lane behind the asking tick):
 	// [0] = stamp << 32 | declined, [1] = stamp << 32 | in-lane singular, [2] = stamp << 32 | most declined robots of one
-	// wavefront. The host asks with a fresh stamp and, 8 ticks on, waits until all tags carry it. fb_seen_by_copy: the
-	// pending request went through fb_seen and the event instead (the one-lane generic kernel as the pass does not take
+	// wavefront. The host asks with a fresh stamp (route.stamp) and, 8 ticks on, waits until all tags carry it. route.by_copy:
+	// the pending request went through fb_seen and the event instead (the one-lane generic kernel as the pass does not take
 	// the pointer).
 	unsigned long long* fb_report = nullptr;
-	unsigned fb_stamp = 0;
-	bool fb_seen_by_copy = false;
-	// The route of a tick is a function of the tick index: the counts recorded at tick k (counted in ticks that want the
-	// SVD-free kernel) are consumed at tick k + 8, waiting for the read-back if it has not arrived (it has, at that
-	// distance, unless the caller never fetches a result); the next probe is recorded there.
-	long long cert_tick = 0, fb_seen_tick = 0;
-	int cert_backoff = 0;
-	int fb_last_seen = -1;		// length of the work list when the host last looked (-1: never)
-	// The headline tick in one launch (tick_self_kernel, sai2b_self.hip: a wavefront serves the robots it declines itself) while
-	// the last look said that this costs no wavefront more than one round of four robots: fb_last_wmax = the largest number of
-	// robots one wavefront declined, the third word of that look (-1: not known, the look went through the copies). Before
-	// any look the form is self. SAI2B_NO_SELF_SERVE=1 keeps the two launches. last_tick_form: sai2b_get_worklist_state
-	int fb_last_wmax = -1, last_tick_form = 0;
-	bool no_self_serve = false;
-	bool last_tick_generic_only = false;
 	// sai2b_update_task_models() is deferred: the reference's loop is update -> goal setters -> computeControlTorques,
 	// and the fused tick (with the SVD-free kernels in front) does both at once. Any other call in between runs the
 	// pending model update first (flush_update), so nothing observable changes.
@@ -98,13 +74,13 @@ struct sai2b_ctx {
 	unsigned goals_dirty = ~0u;
 	// Every generator idle (goal reached, goals untouched since): an update is a no-op for every robot, and stays one until the
 	// host touches a goal or a generator's configuration — the generator kernels are not launched at all then. Known from the
-	// count of non-idle robots otg_kernel leaves behind (read back every 8th tick, consumed 8 ticks later: otg_tick) of a tick
+	// count of non-idle robots otg_kernel leaves behind (read back every 8th tick, consumed 8 ticks later: otg_look) of a tick
 	// launched with the goals as they still are (goals_epoch). SAI2B_NO_OTG_IDLE_SKIP=1 switches it off.
-	bool otg_all_idle = false, no_otg_idle_skip = false, otg_seen_pending = false;
+	bool otg_all_idle = false, no_otg_idle_skip = false;
 	unsigned long long goals_epoch = 0, otg_obs_epoch = 0;
 	int* otg_busy_seen = nullptr;  // pinned host word
 	hipEvent_t otg_seen_ev = nullptr;
-	long long otg_tick = 0, otg_seen_tick = 0;	// as cert_tick / fb_seen_tick: recorded at tick k, consumed at tick k + 8
+	sai2b::DelayedLook otg_look;  // as route.look: recorded at tick k, consumed at tick k + 8
 	bool goals_exposed = false;
 	sai2b_robot_model model;
 	sai2b_task_config cfg[SAI2B_MAX_TASKS];
@@ -159,7 +135,6 @@ struct sai2b_ctx {
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
 	int last_call_task = 0;	  // the last launch sequence was a task-level call: 1 = task_cert_kernel + work list, 2 = the generic task kernel alone
-	bool no_task_cert = false;	// SAI2B_NO_TASK_CERT=1: the generic task_kernel for every robot (A/B)
 	struct TaskIO {
 		double *Nprec = nullptr, *N = nullptr, *Ntot = nullptr, *tau = nullptr, *tau_prec = nullptr;
 		bool nprec_given = false;  // false: identity (the value a task is constructed with)
@@ -734,28 +709,10 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_out, hipEventDisableTiming));
 	ctx->B = batch, ctx->T = n_tasks, ctx->device = device;
 	ctx->model = *model;
-	const char* nf = std::getenv("SAI2B_NO_FAST_PATH");
-	ctx->no_fast_path = nf && nf[0] == '1';
-	const char* bs = std::getenv("SAI2B_BLOCKING_SYNC");
-	ctx->blocking_sync = bs && bs[0] == '1';
-	const char* nc = std::getenv("SAI2B_NO_CERT_PATH");
-	ctx->no_cert_path = nc && nc[0] == '1';
-	const char* ntc = std::getenv("SAI2B_NO_TASK_CERT");
-	ctx->no_task_cert = ntc && ntc[0] == '1';
-	const char* nis = std::getenv("SAI2B_NO_INLANE_SINGULAR");
-	ctx->no_inlane_singular = nis && nis[0] == '1';
-	const char* nois = std::getenv("SAI2B_NO_OTG_IDLE_SKIP");
-	ctx->no_otg_idle_skip = nois && nois[0] == '1';
-	const char* ns6 = std::getenv("SAI2B_NO_SING6");
-	ctx->no_sing6 = ns6 && ns6[0] == '1';
-	const char* fs6 = std::getenv("SAI2B_FORCE_SING6");	 // testing aid: that kernel from the first tick on, whatever the counts
-	ctx->force_sing6 = fs6 && fs6[0] == '1';
-	ctx->sing_mode = ctx->force_sing6;
-	const char* pc = std::getenv("SAI2B_PREFER_CERT");
-	ctx->prefer_cert = pc && pc[0] == '1';
-	if (const char* gl = std::getenv("SAI2B_GENERIC_LANES")) ctx->generic_lanes_env = std::atoi(gl);
-	const char* nss = std::getenv("SAI2B_NO_SELF_SERVE");
-	ctx->no_self_serve = nss && nss[0] == '1';
+	ctx->sw = sai2b::route_switches_from_env();
+	ctx->route = sai2b::TickRoute(ctx->sw);
+	ctx->blocking_sync = sai2b::env_flag("SAI2B_BLOCKING_SYNC");
+	ctx->no_otg_idle_skip = sai2b::env_flag("SAI2B_NO_OTG_IDLE_SKIP");
 	DevParams& hp = ctx->h_params;
 	std::memset(&hp, 0, sizeof(hp));
 	hp.B = batch, hp.n_tasks = n_tasks;
@@ -768,8 +725,7 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 						   std::memcmp(m.inertia, PB::inertia, sizeof(m.inertia)) == 0 &&
 						   std::memcmp(m.gravity, PB::gravity, sizeof(m.gravity)) == 0 &&
 						   std::memcmp(m.jtype, PB::jtype, sizeof(m.jtype)) == 0;
-		if (const char* e = std::getenv("SAI2B_NO_BAKED_MODEL"))
-			if (e[0] == '1') ctx->baked_model = false;
+		if (sai2b::env_flag("SAI2B_NO_BAKED_MODEL")) ctx->baked_model = false;
 	}
 	const size_t Bs = (size_t)batch;
 	int rc;
@@ -1158,79 +1114,24 @@ extern "C" int sai2b_reset_robots(sai2b_ctx* ctx, const unsigned char* mask, con
 	return reset_subset(ctx, "sai2b_reset_robots", -1, mask, q, dq, on_device, true);
 }
 
-// eligibility of the SVD-free path (sai2b_fast.hpp): [full MFT] or [full MFT, full JT] (any batch size: a robot
-// the kernel declines goes to the generic kernel on its own, lanes past the batch just exit)
-// 3 + r: the SVD-free kernel for general hierarchies (sai2b_cert.hpp): any robot size and joint type, any sequence
-// of tasks whose rows can all be independent (at most N of them, a full JointTask only at the bottom); r = most
-// rows a partial task brings (selects the kernel's instantiation)
-static int cert_kind(const sai2b_ctx* ctx) {
-	if (ctx->no_fast_path || ctx->no_cert_path || ctx->T < 1) return 0;
-	int rows = 0, max_rows = 0, slots = N;  // deferred stores per robot (sai2b_cert.hpp: PEND_SLOTS = 36)
-	for (int t = 0; t < ctx->T; t++) {
-		const DevTask& d = ctx->h_params.task[t];
-		if (d.type == SAI2B_MOTION_FORCE_TASK) {
-			// the passivity observer mutates per-robot state inside the law: generic kernel only
-			if (ctx->cfg[t].passivity_enabled && ctx->cfg[t].closed_loop_force) return 0;
-			rows += d.rank;
-			max_rows = std::max(max_rows, d.rank);
-			slots += 12;
-		} else {
-			if (d.full_selection && t != ctx->T - 1) return 0;
-			rows += d.full_selection ? 0 : d.k0;
-			if (!d.full_selection) max_rows = std::max(max_rows, d.k0);
-			slots += d.k0;
-		}
-	}
-	// (the kernel is instantiated for partial tasks of up to 6 rows)
-	return (rows <= N && slots <= 36 && max_rows <= 6) ? 3 + max_rows : 0;
-}
-static int fast_kind(const sai2b_ctx* ctx) {
-	// these two kernels are written for 7 revolute joints (a 6-DOF task leaves a one-dimensional nullspace)
-	bool arm7 = N == 7;
-	for (int i = 0; i < N; i++)
-		if (ctx->model.joint_type[i] != SAI2B_REVOLUTE) arm7 = false;
-	if (!arm7 || ctx->no_fast_path || ctx->T > 2 || ctx->cfg[0].type != SAI2B_MOTION_FORCE_TASK ||
-		!ctx->h_params.task[0].full_projection || ctx->h_params.task[0].rank != 6 ||
-		(ctx->cfg[0].passivity_enabled && ctx->cfg[0].closed_loop_force))
-		return cert_kind(ctx);
-	if (ctx->prefer_cert && cert_kind(ctx)) return cert_kind(ctx);
-	if (ctx->T == 1) return 1;
-	return (ctx->cfg[1].type == SAI2B_JOINT_TASK && ctx->h_params.task[1].full_selection) ? 2 : cert_kind(ctx);
-}
-
-// The kernel for batches with many robots inside a blending region of a 4- to 6-row MotionForceTask: tick_cert_kernel<6, S6>
-// (cert::singular_streamed); 0 when the hierarchy has no such task or is not the SVD-free kernel's
-static int sing6_kind(const sai2b_ctx* ctx) {
-	if (ctx->no_inlane_singular || ctx->no_sing6) return 0;
-	const int ck = cert_kind(ctx);
-	return ck >= 3 + 4 ? ck : 0;
-}
-
-// The first kernel the ticks of this context run now (launch_tick switches sing_mode by what the counters say, and may skip
-// the SVD-free kernel for a while: cert_backoff)
-static TickForm tick_form(const sai2b_ctx* ctx) {
-	TickForm form;
-	form.fast = fast_kind(ctx);
-	if (const int alt = ctx->sing_mode ? sing6_kind(ctx) : 0) form.fast = alt, form.sing6 = true;
-	form.baked = ctx->baked_model;
-	form.payload = ctx->h_params.payload != nullptr;
-	form.inlane_singular = !ctx->no_inlane_singular;
-	// One launch (sai2b_self.hip) for the two headline kernels without payload, while the generic kernel is the lanes-per-robot
-	// one and the last look found a short list (long_list's bound) of which no wavefront holds more than one round of four
-	// robots. Speed only: each robot runs the same per-robot code either way.
-	form.self = N == 7 && (form.fast == 1 || form.fast == 2) && !form.payload && ctx->generic_lanes_env != 1 && !ctx->no_self_serve &&
-				(ctx->fb_last_seen < 0 || (ctx->fb_last_seen <= 4096 && ctx->fb_last_wmax >= 0 && ctx->fb_last_wmax <= 4));
-	return form;
+// the hierarchy, the kinds of kernel it is eligible for and what a call asks for, as sai2b_tick_policy.h takes them
+static sai2b::Hierarchy hierarchy(const sai2b_ctx* ctx) { return sai2b::Hierarchy{&ctx->h_params, ctx->cfg, ctx->T, ctx->model.joint_type}; }
+static sai2b::RouteKinds route_kinds(const sai2b_ctx* ctx) { return sai2b::route_kinds(ctx->sw, hierarchy(ctx)); }
+static sai2b::TickAsk tick_ask(const sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torque, unsigned gated) {
+	sai2b::TickAsk a;
+	a.introspection = ctx->introspection, a.commit_sh = commit_sh, a.with_comp = with_comp, a.do_torque = do_torque;
+	a.payload = ctx->h_params.payload != nullptr, a.baked = ctx->baked_model, a.gated = gated;
+	return a;
 }
 
 // The counts of the pending request (launch_tick), waiting for them if they have not arrived: 0 and d / took / wmax filled, or an error
 static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took, long long* wmax) {
-	if (ctx->fb_seen_by_copy) {
+	if (ctx->route.by_copy) {
 		if (hipEventQuery(ctx->fb_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->fb_seen_ev));
 		*d = ctx->fb_seen[0], *took = ctx->fb_seen[1], *wmax = -1;
 		return SAI2B_OK;
 	}
-	const unsigned long long want = ctx->fb_stamp;
+	const unsigned long long want = ctx->route.stamp;
 	unsigned long long w0 = 0, w1 = 0, w2 = 0;
 	auto arrived = [&] {
 		w0 = __atomic_load_n(&ctx->fb_report[0], __ATOMIC_ACQUIRE), w1 = __atomic_load_n(&ctx->fb_report[1], __ATOMIC_ACQUIRE);
@@ -1249,15 +1150,6 @@ static int fb_counts_arrived(sai2b_ctx* ctx, long long* d, long long* took, long
 	}
 	*d = (long long)(unsigned)w0, *took = (long long)(unsigned)w1, *wmax = (long long)(unsigned)w2;
 	return SAI2B_OK;
-}
-
-// How many lanes a robot gets in the generic kernel (sai2b_group.hip). 16 = one DPP row per robot: the shortest
-// critical path, what the (usually short) work list behind the SVD-free kernel wants; 8 = two robots per row:
-// fewer idle lanes, better when the whole batch runs the generic kernel and fills the machine anyway.
-static int generic_lanes(const sai2b_ctx* ctx, bool whole_batch) {
-	if (ctx->generic_lanes_env == 1) return 0;
-	if (ctx->generic_lanes_env == 8 || ctx->generic_lanes_env == 16) return ctx->generic_lanes_env;
-	return (whole_batch && ctx->B >= 16384) ? 8 : 16;
 }
 
 // tasks whose generator is jerk-limited: their planner work lists take a launch of their own (sai2b_otg.hip)
@@ -1309,30 +1201,24 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	const unsigned gated = refresh_otg_gating(ctx);
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	const int fast = fast_kind(ctx);
-	if (do_torque && gated) {
-		// which robots' gated tasks are active this tick: the task models of the current state, nothing committed.
-		// Where the SVD-free kernel for general hierarchies applies (and keeps most of the batch), its cascade decides
-		// for the robots it can certify and only the others take the generic kernel's range pass
-		const int ck = (ctx->introspection || ctx->cert_backoff > 0) ? 0 : cert_kind(ctx);
-		if (ck) {
-			const TickForm form = tick_form(ctx);
-			if (sai2b::launch_range_cert(ctx->d_params, ctx->B, ck - 3, form.payload, form.inlane_singular, ctx->rg, ctx->stream) ||
-				sai2b::launch_tick_group(ctx->d_params, ctx->B, 16, true, false, with_comp, false, ctx->rg.count(), ctx->rg.list, ctx->stream))
-				return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
-			ctx->rg.parity ^= 1;
-			ctx->launches += 2;
-		} else {
-			if (sai2b::launch_range_pass(ctx->d_params, ctx->B, ctx->introspection, with_comp, generic_lanes(ctx, true), ctx->stream))
-				return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
-			ctx->launches++;
-		}
+	const sai2b::RouteKinds kinds = route_kinds(ctx);
+	const sai2b::TickAsk ask = tick_ask(ctx, commit_sh, with_comp, do_torque, gated);
+	// which robots' gated tasks are active this tick
+	const sai2b::RangePlan range = sai2b::plan_range(ctx->route, ctx->sw, kinds, ctx->B, ask);
+	if (range.run && range.cert) {
+		if (sai2b::launch_range_cert(ctx->d_params, ctx->B, range.max_rows, range.payload, range.inlane_singular, ctx->rg, ctx->stream) ||
+			sai2b::launch_tick_group(ctx->d_params, ctx->B, 16, true, false, with_comp, false, ctx->rg.count(), ctx->rg.list, ctx->stream))
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
+		ctx->rg.parity ^= 1;
+		ctx->launches += 2;
+	} else if (range.run) {
+		if (sai2b::launch_range_pass(ctx->d_params, ctx->B, ctx->introspection, with_comp, range.lanes, ctx->stream))
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
+		ctx->launches++;
 	}
 	if (do_torque && any_otg(ctx)) {  // the generators advance once per torque computation, before the law
-		ctx->otg_tick++;
-		if (ctx->otg_seen_pending && ctx->otg_tick - ctx->otg_seen_tick >= 8) {
+		if (ctx->otg_look.advance()) {
 			if (hipEventQuery(ctx->otg_seen_ev) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ctx->otg_seen_ev));
-			ctx->otg_seen_pending = false;
 			if (*ctx->otg_busy_seen == 0 && ctx->otg_obs_epoch == ctx->goals_epoch) ctx->otg_all_idle = true;
 		}
 		// (see otg_all_idle: exact, not a heuristic — an idle generator's update neither reads nor writes anything)
@@ -1342,81 +1228,31 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 			const int clean_mask = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & ((1u << SAI2B_MAX_TASKS) - 1u));
 			ctx->goals_dirty = 0;
 			if (sai2b::launch_otg(ctx->d_params, ctx->B, ctx->otg, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
-			if (!gated && !ctx->goals_exposed && !ctx->otg_seen_pending) {
+			if (!gated && !ctx->goals_exposed && !ctx->otg_look.pending) {
 				HIP_TRY(ctx, hipMemcpyAsync(ctx->otg_busy_seen, ctx->otg.counts + 2 * SAI2B_MAX_TASKS + ctx->otg.parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 				HIP_TRY(ctx, hipEventRecord(ctx->otg_seen_ev, ctx->stream));
-				ctx->otg_seen_pending = true;
-				ctx->otg_seen_tick = ctx->otg_tick;
+				ctx->otg_look.ask();
 				ctx->otg_obs_epoch = ctx->goals_epoch;
 			}
 			ctx->otg.parity ^= 1;
 			ctx->launches += 2;
 		}
 	}
-	const bool fast_wanted = fast != 0 && !ctx->introspection && do_torque && commit_sh;
-	if (fast_wanted) {
-		// Which first kernel, by what the last look at the counters said (those of tick k - 8, through two pinned words,
-		// see cert_tick): the hierarchy's own SVD-free kernel; while more than 20 480 robots leave it for the work list
-		// and the hierarchy has a 4- to 6-row MotionForceTask, the 6-row kernel with the singular branch in the lane (until
-		// fewer than 15 360 either take that branch or leave); and the generic kernel alone for 64 ticks whenever a kernel for
-		// general hierarchies keeps less than 60 % of the batch. The numbers are the measured break-even on the Panda
-		// (scripts/micro/sing6_crossover.py: 65 536 robots, 14 890 declined: 173 us against 215 us with the 6-row kernel;
-		// 22 382 declined: 238 against 195): the in-lane 6-row branch costs every wavefront ~100 us whatever the batch, a pass
-		// over the work list ~60 us per round of 4 096 robots (16 lanes each) or ~450 us per 65 536 in its throughput form.
-		const int alt = sing6_kind(ctx);
-		ctx->cert_tick++;
-		if (ctx->fb_seen_pending && ctx->cert_tick - ctx->fb_seen_tick >= 8) {
-			long long d = 0, took = 0, wmax = -1;
-			ctx->fb_seen_pending = false;  // (also when they never arrive: the next tick asks afresh)
-			if (int rc_ = fb_counts_arrived(ctx, &d, &took, &wmax)) return rc_;
-			ctx->fb_last_seen = (int)d, ctx->fb_last_wmax = (int)wmax;
-			if (ctx->sing_mode) {
-				if (d * 5 > (long long)ctx->B * 2)
-					ctx->cert_backoff = 64;
-				else if (d + took < 15360 && !ctx->force_sing6)
-					ctx->sing_mode = false;
-			} else if (alt && d > 20480) {
-				ctx->sing_mode = true;
-			} else if (fast >= 3 && d * 5 > (long long)ctx->B * 2) {
-				ctx->cert_backoff = 64;
-			}
-		}
+	// the work list's counts of 8 ticks ago, when this tick is the one to look at them
+	if (sai2b::look_due(ctx->route, kinds, ask)) {
+		long long d = 0, took = 0, wmax = -1;
+		if (int rc_ = fb_counts_arrived(ctx, &d, &took, &wmax)) return rc_;
+		sai2b::observe(ctx->route, ctx->sw, kinds, ctx->B, d, took, wmax);
 	}
-	TickForm form = tick_form(ctx);	 // (with the mode as the look above left it)
-	if (fast_wanted && form.fast >= 3 && ctx->cert_backoff > 0) {
-		ctx->cert_backoff--;
-		form.fast = 0;
-	}
-	const bool fast_launch = fast_wanted && form.fast != 0;
-	form.self = form.self && fast_launch;
-	ctx->last_tick_form = !fast_launch ? 0 : (form.self ? 2 : 1);
-	ctx->last_tick_generic_only = do_torque && commit_sh && !fast_launch && !ctx->introspection;
-	if (fast_launch) ctx->fb.parity ^= 1;
-	// a long work list (thousands of robots) is throughput, not latency: two robots per DPP row, as for a whole batch
-	const bool long_list = fast_launch && ctx->fb_last_seen > 4096;	 // (16 lanes: 4 robots x 1024 wavefronts in one round)
-	TickCall call;
-	call.debug = ctx->introspection, call.commit_sh = commit_sh, call.with_comp = with_comp, call.do_torque = do_torque;
-	call.group = generic_lanes(ctx, !fast_launch || long_list);
-	// the pass over the work list reports the list's counts when asked (the lanes-per-robot pass takes the request, and so does
-	// the self form, with a launch of one lane behind it; the one-lane generic kernel as the pass does not: two copies behind it)
-	const bool ask = fast_launch && !ctx->fb_seen_pending;
-	const bool by_copy = ask && call.group == 0;
-	if (ask && !by_copy) {
-		if (++ctx->fb_stamp == 0) ctx->fb_stamp = 1;
-		call.stamp = ctx->fb_stamp;
-	}
-	if (sai2b::launch_tick(ctx->d_params, ctx->B, form, call, ctx->fb, ctx->stream))
+	const sai2b::TickPlan plan = sai2b::plan(ctx->route, ctx->sw, kinds, ctx->B, ask);
+	if (plan.fast_launch) ctx->fb.parity ^= 1;
+	if (sai2b::launch_tick(ctx->d_params, ctx->B, plan.form, plan.call, ctx->fb, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
-	if (by_copy) {
+	if (plan.by_copy) {
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen, ctx->fb.count(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->fb_seen + 1, ctx->fb.took(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipEventRecord(ctx->fb_seen_ev, ctx->stream));
-	}
-	if (ask) {
-		ctx->fb_seen_by_copy = by_copy;
-		ctx->fb_seen_pending = true;
-		ctx->fb_seen_tick = ctx->cert_tick;
 	}
 	if (do_torque) ctx->q_is_pose = true;  // computeTorques caches the tasks' current pose
 	return SAI2B_OK;
@@ -1505,19 +1341,6 @@ static int task_io(sai2b_ctx* ctx, int task, const char* fn) {
 	return SAI2B_OK;
 }
 
-// Rows of a task when the SVD-free task-level kernel (sai2b_cert.hip: task_cert_kernel) can serve it, else 0: the
-// eligibility of cert_kind() for this one task. Not with introspection (its outputs come from the generic kernel) nor
-// a passivity observer (it mutates state inside the law).
-static int task_cert_rows(const sai2b_ctx* ctx, int task) {
-	if (ctx->no_task_cert || ctx->no_fast_path || ctx->no_cert_path || ctx->introspection) return 0;
-	const DevTask& d = ctx->h_params.task[task];
-	if (d.type == SAI2B_MOTION_FORCE_TASK) {
-		if (ctx->cfg[task].passivity_enabled && ctx->cfg[task].closed_loop_force) return 0;
-		return (d.rank >= 1 && d.rank <= 6) ? d.rank : 0;
-	}
-	if (d.full_selection) return 1;	 // (a full JointTask brings no level of its own: the small instantiation)
-	return d.k0 <= 6 ? d.k0 : 0;
-}
 // one TemplateTask call on the device: the SVD-free kernel with the generic one over the robots it declined, or the
 // generic one for every robot
 // the generic form of a task-level call: a robot spread over 16 lanes (a work list) or 8 (a whole batch), or — SAI2B_GENERIC_LANES=1,
@@ -1528,8 +1351,8 @@ static int launch_task_generic(sai2b_ctx* ctx, int task, const double* Np, const
 	// A whole batch stays on the one-lane kernel unless SAI2B_GENERIC_LANES asks otherwise: without the row-space chain of a
 	// controller tick every JointTask behind another task takes the 7 x 7 Jacobi, and 65 536 robots through the hand-chained
 	// [MFT, JT] cost 1 111 us per period with 8 lanes per robot against 692 us with one (profiles/r03_bench_task_level.txt)
-	int lanes = ctx->introspection ? 0 : generic_lanes(ctx, count == nullptr);
-	if (!count && ctx->generic_lanes_env == 0) lanes = 0;
+	int lanes = ctx->introspection ? 0 : sai2b::generic_lanes(ctx->sw, ctx->B, count == nullptr);
+	if (!count && ctx->sw.generic_lanes_env == 0) lanes = 0;
 	if (lanes)
 		return sai2b::launch_task_group(ctx->d_params, ctx->B, lanes, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list,
 										ctx->stream);
@@ -1538,7 +1361,7 @@ static int launch_task_generic(sai2b_ctx* ctx, int task, const double* Np, const
 
 static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const double* tp, double* tau_out, double* N_out, double* Ntot_out,
 							int commit_sh, int do_torque) {
-	const int rows = task_cert_rows(ctx, task);
+	const int rows = sai2b::task_cert_rows(ctx->sw, hierarchy(ctx), task, ctx->introspection);
 	if (rows) {
 		if (!ctx->tk.counts) {
 			int rc;
@@ -1546,8 +1369,7 @@ static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const do
 			if ((rc = dev_alloc(ctx, &ctx->tk.list, (size_t)ctx->B))) return rc;
 		}
 		ctx->tk.parity ^= 1;
-		const TickForm form = tick_form(ctx);
-		if (sai2b::launch_task_cert(ctx->d_params, ctx->B, task, rows, form.payload, form.inlane_singular, Np, tp, tau_out, N_out, Ntot_out, commit_sh,
+		if (sai2b::launch_task_cert(ctx->d_params, ctx->B, task, rows, ctx->h_params.payload != nullptr, !ctx->sw.no_inlane_singular, Np, tp, tau_out, N_out, Ntot_out, commit_sh,
 									do_torque, ctx->tk, ctx->stream) ||
 			launch_task_generic(ctx, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, ctx->tk.count(), ctx->tk.list))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task launch failed");
@@ -2734,7 +2556,8 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	const TickForm form = tick_form(ctx);  // (the kernel the ticks are running now)
+	// (the kernel the ticks are running now)
+	const TickForm form = sai2b::tick_form(ctx->route, ctx->sw, route_kinds(ctx), ctx->baked_model, ctx->h_params.payload != nullptr);
 	const bool self = form.self && !ctx->introspection;
 	int declined = 0;
 	if (self) {
@@ -2757,9 +2580,9 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 			for (int s = 0; s < steps; s++) {
 				if (two || self) ctx->fb.parity ^= 1;
 				if (sai2b::launch_tick_part(ctx->d_params, ctx->B, (two && phase == 0) ? alone : form, ctx->introspection, 0, ctx->fb,
-											generic_lanes(ctx, !two), ctx->stream))
+											sai2b::generic_lanes(ctx->sw, ctx->B, !two), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
-				if (phase == 1 && !self && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, generic_lanes(ctx, false), ctx->stream))
+				if (phase == 1 && !self && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, sai2b::generic_lanes(ctx->sw, ctx->B, false), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 			}
 			HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
@@ -2791,7 +2614,7 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 		return SAI2B_OK;
 	}
-	if (ctx->last_tick_generic_only) {	// no SVD-free kernel ran in front: every robot took the generic kernel
+	if (ctx->route.last_generic_only) {	// no SVD-free kernel ran in front: every robot took the generic kernel
 		*robots = ctx->B;
 		return SAI2B_OK;
 	}
@@ -2802,10 +2625,10 @@ extern "C" int sai2b_get_fallback_count(sai2b_ctx* ctx, int* robots) {
 
 extern "C" int sai2b_get_worklist_state(const sai2b_ctx* ctx, int* last_seen, int* pending, int* form, int* wmax) {
 	if (!ctx) return SAI2B_INVALID_ARGUMENT;
-	if (last_seen) *last_seen = ctx->fb_last_seen;
-	if (pending) *pending = ctx->fb_seen_pending ? (ctx->fb_seen_by_copy ? 2 : 1) : 0;
-	if (form) *form = ctx->last_tick_form;
-	if (wmax) *wmax = ctx->fb_last_wmax;
+	if (last_seen) *last_seen = ctx->route.last_seen;
+	if (pending) *pending = ctx->route.pending();
+	if (form) *form = ctx->route.last_form;
+	if (wmax) *wmax = ctx->route.last_wmax;
 	return SAI2B_OK;
 }
 

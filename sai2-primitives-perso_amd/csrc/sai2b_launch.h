@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sai2b_params.h"
+#include "sai2b_tick_policy.h"  // TickForm, TickCall
 
 namespace sai2b {
 
@@ -23,27 +24,6 @@ struct WorkList {
 	unsigned long long* report = nullptr;
 	int* count() const { return counts + parity; }
 	int* took() const { return counts + 2 + parity; }
-};
-
-// which first kernel a tick runs
-struct TickForm {
-	int fast = 0;  // 0 = the generic kernel alone, 1 = [full MFT], 2 = [full MFT, full JT], 3 + rows = tick_cert_kernel
-				   // (rows: most rows of a partial task of the hierarchy)
-	bool baked = false;			  // robot constants from the compile-time Panda (tick_fast_kernel)
-	bool payload = false;		  // the context has per-robot payloads: the SVD-free kernels' payload forms (the generic
-								  // kernels find the rows in the parameter block)
-	bool inlane_singular = true;  // singular MotionForceTasks stay in the lane (cert::singular_part), not on the work list
-	bool sing6 = false;			  // the 6-row tick_cert_kernel with the singular branch in the lane (cert::tick<.., S6>)
-	bool self = false;			  // fast = 1 | 2 without payload: one launch, each wavefront serves the robots it declines itself
-								  // (tick_self_kernel, sai2b_self.hip) instead of the generic kernel over a work list behind
-};
-
-// what a tick call asks for
-struct TickCall {
-	bool debug = false;	 // the introspection instantiation of the generic kernel, no SVD-free kernel
-	bool commit_sh = true, with_comp = true, do_torque = true;
-	int group = 0;	// lanes per robot of the generic kernel (16 / 8), or 0 = the one-lane-per-robot generic kernel
-	unsigned stamp = 0;	 // != 0: the host asks for the work list's counts, tagged with it (WorkList::report)
 };
 
 inline int launch_result() { return hipGetLastError() == hipSuccess ? 0 : 1; }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """compare_kernel_isa.py <dir A> <dir B>: is the device code of two states of csrc/ the same? Each directory holds
-<unit>_n<N>.s for the five device translation units and N = 4, 6, 7, 8, made in csrc/ of either state with
+<unit>_n<N>.s for the eight device translation units of the Makefile and N = 4, 6, 7, 8, made in csrc/ of either state with
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSAI2B_N=<N> -include sai2b_dof_rename.h --cuda-device-only -S <unit>.hip
   (sai2b_otg.hip: with -ffp-contract=off, as the Makefile builds it)
@@ -10,7 +10,7 @@ tests/test_fast_kernel_isa.py filters them). Exit status 0 when every kernel of 
 import re
 import sys
 
-UNITS = ["sai2b_kernels", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim"]
+UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action"]
 
 
 def kernels(path):
