@@ -17,6 +17,7 @@
 #define SAI2_PRIMITIVES_BATCHED_H_
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <condition_variable>
 #include <exception>
@@ -1593,6 +1594,87 @@ public:
 	int robotsInContact() const {
 		int n = 0;
 		detail::check(_c, sai2b_get_contact_state(_c, nullptr, nullptr, nullptr, &n));
+		return n;
+	}
+
+	// External wrench on a link of the plant (sai2b.h "external wrench on a link of the simulated plant"): per robot a force
+	// [3][B] (N) and a couple [3][B] (N m, empty: 0) on moving link `link` at point_in_link, world components or (frame =
+	// SAI2B_WRENCH_LINK) components that turn with the link; steps [B]: the robot's remaining pushed periods (> 0 counted down by
+	// every integrate(), < 0 until changed, 0 off; empty: -1). sensor: the MotionForceTask whose sensed rows read the wrench
+	// after every integrate() (nullptr: none). Takes effect at the next integrate(). std::invalid_argument on what
+	// sai2b_set_external_wrench rejects.
+	void setExternalWrench(const int link, const Batch& force, const Batch& moment = Batch(), const Batch& steps = Batch(),
+						   const std::array<double, 3>& point_in_link = {0.0, 0.0, 0.0}, const int frame = SAI2B_WRENCH_WORLD,
+						   const MotionForceTask* sensor = nullptr) {
+		checkExternalWrenchArguments(_dof, (size_t)sai2b_batch(_c), link, force, moment, steps, point_in_link, frame);
+		if (sensor && sensor->context() != _c)
+			throw std::invalid_argument("setExternalWrench: the sensor task does not belong to this simulation's controller");
+		sai2b_external_wrench_config cfg;
+		detail::check(nullptr, sai2b_default_external_wrench(&cfg, link));
+		cfg.frame = frame;
+		for (int a = 0; a < 3; a++) cfg.point[a] = point_in_link[a];
+		cfg.sensor_task = sensor ? sensor->index() : -1;
+		detail::check(_c, sai2b_set_external_wrench(_c, &cfg, force.data(), moment.empty() ? nullptr : moment.data(),
+													steps.empty() ? nullptr : steps.data(), 0));
+	}
+	// What setExternalWrench checks before the device is touched (the conditions of sai2b_set_external_wrench on host arrays,
+	// plus the shapes): std::invalid_argument. Public and static so that callers, and tests without a device, can ask ahead.
+	static void checkExternalWrenchArguments(const int dof, const size_t B, const int link, const Batch& force, const Batch& moment,
+											 const Batch& steps, const std::array<double, 3>& point_in_link, const int frame) {
+		sai2b_external_wrench_config cfg;
+		detail::check(nullptr, sai2b_default_external_wrench(&cfg, link));
+		cfg.frame = frame;
+		for (int a = 0; a < 3; a++) cfg.point[a] = point_in_link[a];
+		char msg[256];
+		if (sai2b_validate_external_wrench(&cfg, nullptr, 0, dof, msg, sizeof(msg)) != SAI2B_OK)
+			throw std::invalid_argument(std::string("setExternalWrench: ") + msg);
+		if (force.size() != 3 * B || (!moment.empty() && moment.size() != 3 * B) || (!steps.empty() && steps.size() != B))
+			throw std::invalid_argument("setExternalWrench: force and moment must be [3][B], steps [B]");
+		for (const Batch* a : {&force, &moment})
+			for (const double v : *a)
+				if (!std::isfinite(v)) throw std::invalid_argument("setExternalWrench: force and moment must be finite");
+		for (const double v : steps)
+			if (std::isnan(v)) throw std::invalid_argument("setExternalWrench: steps must not be NaN");
+	}
+	// the same by URDF link NAME: the point given in that link's frame (a link behind fixed joints resolves to its moving link).
+	// With SAI2B_WRENCH_LINK the components of force and moment are those of the NAMED link's frame too: they are turned into
+	// the moving link's frame here (turnedRows), so a tool reaction given for a tool behind a rotated fixed joint turns with it.
+	void setExternalWrench(const BatchedRobotModel& robot, const std::string& link_name, const std::array<double, 3>& point_in_link,
+						   const Batch& force, const Batch& moment = Batch(), const Batch& steps = Batch(), const int frame = SAI2B_WRENCH_WORLD,
+						   const MotionForceTask* sensor = nullptr) {
+		double fp[3], R[9];
+		const int link = robot.resolveLink(link_name, point_in_link.data(), nullptr, fp, R);
+		if (frame == SAI2B_WRENCH_LINK)
+			setExternalWrench(link, turnedRows(R, force), turnedRows(R, moment), steps, {fp[0], fp[1], fp[2]}, frame, sensor);
+		else
+			setExternalWrench(link, force, moment, steps, {fp[0], fp[1], fp[2]}, frame, sensor);
+	}
+	// R (row-major 3 x 3) applied to every column of rows [3][B]; rows of another size (empty: none given) pass as they are and
+	// are judged by checkExternalWrenchArguments
+	static Batch turnedRows(const double R[9], const Batch& rows) {
+		if (rows.empty() || rows.size() % 3 != 0) return rows;
+		const size_t B = rows.size() / 3;
+		Batch out(rows.size());
+		for (size_t b = 0; b < B; b++)
+			for (int i = 0; i < 3; i++) out[i * B + b] = R[3 * i] * rows[b] + R[3 * i + 1] * rows[B + b] + R[3 * i + 2] * rows[2 * B + b];
+		return out;
+	}
+	void clearExternalWrench() { detail::check(_c, sai2b_clear_external_wrench(_c)); }
+	struct ExternalWrenchState {
+		Batch wrench_world;	 // [6][B]: F_w and M_w about the application point, zeros for a robot that was not pushed
+		Batch torque;		 // [dof][B]: the joint torques of the wrench
+		int robots_pushed = 0;
+	};
+	ExternalWrenchState getExternalWrenchState() const {
+		const size_t B = (size_t)sai2b_batch(_c);
+		ExternalWrenchState s;
+		s.wrench_world.resize(6 * B), s.torque.resize((size_t)_dof * B);
+		detail::check(_c, sai2b_get_external_wrench_state(_c, s.wrench_world.data(), s.torque.data(), &s.robots_pushed));
+		return s;
+	}
+	int robotsPushed() const {
+		int n = 0;
+		detail::check(_c, sai2b_get_external_wrench_state(_c, nullptr, nullptr, &n));
 		return n;
 	}
 

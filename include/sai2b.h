@@ -396,7 +396,13 @@ enum sai2b_buffer {
 	 * joint dynamics have been set (and after they are cleared). A device-resident producer may rewrite the rows between
 	 * steps, ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
 	SAI2B_BUF_JOINT_DYNAMICS = 11,
-	SAI2B_BUF_JOINT_DYNAMICS_STATE = 12
+	SAI2B_BUF_JOINT_DYNAMICS_STATE = 12,
+	/* the plant's external-wrench rows (sai2b_set_external_wrench), [7][B] = force 3, moment 3, remaining pushed periods, and
+	 * what the last step left, [6 + dof][B] = F_w 3, M_w 3, the joint torques tx. NULL until an external wrench has been set
+	 * (and after it is cleared). A device-resident producer may rewrite the rows between steps, ordered with sai2b_stream();
+	 * the next sai2b_sim_step reads them. Such rows are not inspected. */
+	SAI2B_BUF_EXTERNAL_WRENCH = 13,
+	SAI2B_BUF_EXTERNAL_WRENCH_STATE = 14
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -547,6 +553,67 @@ int sai2b_get_joint_dynamics(sai2b_ctx* ctx, sai2b_joint_dynamics_config* cfg, d
  * before the first step with joint dynamics and after they are cleared. */
 int sai2b_get_joint_dynamics_state(sai2b_ctx* ctx, double* applied_torque, double* stop_torque, double* dissipative_torque,
 								   int* robots_saturated, int* robots_at_stop);
+
+/* ------------------------------------------------------------------ external wrench on a link of the simulated plant
+ * A force and a moment applied to one link of every robot inside sai2b_sim_step, different for every robot and timed per
+ * robot: a random shove, a hand guiding the end effector, a tool reaction that turns with the link, a load the controller
+ * does not know about. Batch-uniform (sai2b_external_wrench_config): the moving link, the application point c in that link's
+ * frame, the frame the rows are given in and the MotionForceTask whose sensed rows the ideal sensor writes (-1: none). Per
+ * robot, one device buffer of rows [7][B]: rows 0-2 the force F (N), rows 3-5 the moment M (a pure couple, N m), row 6
+ * `steps`, the robot's remaining pushed periods, stored as a double. A robot is ACTIVE in a call of sai2b_sim_step when
+ * steps > 0 || steps < 0 on entry (a NaN: inactive); after the call the kernel stores back steps > 0 ? max(steps - 1, 0) :
+ * steps, so a negative value means "until changed" and 0 means off. For an active robot, from the state at the START of
+ * each substep, with R_l, p_l the link's frame, z_i, p_i the axis and origin of joint i:
+ *     x   = p_l + R_l c
+ *     F_w = F  or  R_l F          M_w = M  or  R_l M           (SAI2B_WRENCH_WORLD / SAI2B_WRENCH_LINK)
+ *     tx_i = z_i . ((x - p_i) x F_w + M_w)     revolute joint i <= link
+ *     tx_i = z_i . F_w                          prismatic joint i <= link
+ *     tx_i = 0                                  i > link, and every i of an inactive robot (an exact zero)
+ * tx enters the substep beside the contact torque tc: the plain step is dq += h M^-1 (((tau + tc) + tx) - b), and with joint
+ * dynamics the bracket of that section becomes h (ts + sl - su + tc + tx - b). The torque limit saturates tau only, never
+ * tx. This law is this library's definition. sai2b_get_bias, every tick kernel, the trajectory generators and the
+ * singularity handling never see the wrench.
+ * Sensor: with sensor_task >= 0, after the last substep and from the final state, the kernel writes that task's
+ * SAI2B_BUF_SENSED rows with the wrench the robot applies to the environment in that task's sensor frame, as the contact
+ * sensor does: o_s = x_c + R_c sensor_pos, R_s = R_c sensor_rot, f_s = R_s^T (-F_w), m_s = R_s^T (-(M_w + (x - o_s) x F_w));
+ * zeros for a robot that was inactive in this call, so a reading does not outlive its push. When the contact's sensor is
+ * the same task the sum of the two readings is stored once; on different tasks each stores its own rows. The sensor is
+ * ideal; whether the point lies outboard of the sensor is the caller's business, as for contact. */
+enum sai2b_wrench_frame { SAI2B_WRENCH_WORLD = 0, SAI2B_WRENCH_LINK = 1 };
+typedef struct sai2b_external_wrench_config {
+	int link;		 /* moving link the wrench acts on (0-based, as sai2b_contact_config.link) */
+	int frame;		 /* SAI2B_WRENCH_WORLD: the rows are world components; SAI2B_WRENCH_LINK: components in the link's frame */
+	double point[3]; /* application point in the link's frame, metres */
+	int sensor_task; /* index of a MotionForceTask, or -1 */
+} sai2b_external_wrench_config;
+/* host only: point 0, world frame, no sensor */
+int sai2b_default_external_wrench(sai2b_external_wrench_config* cfg, int link);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (link outside [0, robot_dof), an unknown frame, a
+ * non-finite point, sensor_task neither -1 nor a MotionForceTask of `tasks`) */
+int sai2b_validate_external_wrench(const sai2b_external_wrench_config* cfg, const sai2b_task_config* tasks, int n_tasks,
+								   int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_external_wrench_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_external_wrench_config(void);
+/* force [3][B], moment [3][B] (NULL: 0), steps [B] doubles (NULL: -1, until changed). Host arrays are validated
+ * (SAI2B_INVALID_ARGUMENT: what sai2b_validate_external_wrench rejects, a non-finite force or moment, a NaN in steps);
+ * DEVICE arrays (on_device != 0) are copied under the stream contract and NOT inspected. Ordered on the ctx stream; takes
+ * effect at the next sai2b_sim_step. sai2b_reinitialize, sai2b_reset_robots and sai2b_reinitialize_robots keep the rows and
+ * `steps` of every robot (environment, as the contact rows are): to end a push at a reset, write the selected columns of
+ * SAI2B_BUF_EXTERNAL_WRENCH. A call that fails on its arguments leaves the wrench as it was; one that fails while copying
+ * (SAI2B_RUNTIME_ERROR) leaves the plant without a wrench. A context that never sets an external wrench, or has cleared it,
+ * launches the simulation kernel it would without this feature. */
+int sai2b_set_external_wrench(sai2b_ctx* ctx, const sai2b_external_wrench_config* cfg, const double* force, const double* moment,
+							  const double* steps, int on_device);
+/* back to the plant without an external wrench (the rows are kept for a later set, the two buffer ids give NULL, no sensor
+ * writes) */
+int sai2b_clear_external_wrench(sai2b_ctx* ctx);
+/* the configuration and the [7][B] rows to the host (either may be NULL); link = -1 and zeros without an external wrench */
+int sai2b_get_external_wrench(sai2b_ctx* ctx, sai2b_external_wrench_config* cfg, double* rows);
+/* what the last sai2b_sim_step left, from the state after its last substep, host arrays, any NULL: wrench_world [6][B] = F_w
+ * and M_w about x (zeros for a robot that was inactive), torque [dof][B] = tx, *robots_pushed = robots that were active on
+ * entry with some non-zero component of F or M (counted on the device). Zeros before the first step with an external wrench
+ * and after a clear. */
+int sai2b_get_external_wrench_state(sai2b_ctx* ctx, double* wrench_world, double* torque, int* robots_pushed);
 
 /* ------------------------------------------------------------------ observations and episode-end flags
  * The missing link of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe(out, done), sai2b_reset_robots(done, ..):

@@ -29,6 +29,10 @@ MAX_CONTACT_POINTS = 4
 BUF_JOINT_DYNAMICS = 11  # [6][dof][B] rows of the plant's joint dynamics (sai2b_set_joint_dynamics)
 BUF_JOINT_DYNAMICS_STATE = 12  # [3][dof][B]: applied, stop and dissipative torque of the last sim step
 JOINT_DYNAMICS_ROWS = ("armature", "damping", "friction", "torque_limit", "q_lower", "q_upper")
+BUF_EXTERNAL_WRENCH = 13  # [7][B] external-wrench rows of the plant: force 3, moment 3, remaining periods (sai2b_set_external_wrench)
+BUF_EXTERNAL_WRENCH_STATE = 14  # [6 + dof][B]: F_w, M_w and the joint torques tx of the last sim step
+WRENCH_WORLD, WRENCH_LINK = 0, 1  # enum sai2b_wrench_frame
+WRENCH_FRAMES = {"world": WRENCH_WORLD, "link": WRENCH_LINK}
 PAYLOAD_CONTROLLER, PAYLOAD_PLANT, PAYLOAD_BOTH = 1, 2, 3  # enum sai2b_payload_target
 PAYLOAD_TARGETS = {"controller": PAYLOAD_CONTROLLER, "plant": PAYLOAD_PLANT, "both": PAYLOAD_BOTH}
 
@@ -237,6 +241,17 @@ class JointDynamicsConfig(C.Structure):
     ]
 
 
+class ExternalWrenchConfig(C.Structure):
+    """sai2b_external_wrench_config; load_library() checks the size against sai2b_sizeof_external_wrench_config()"""
+
+    _fields_ = [
+        ("link", _i),
+        ("frame", _i),
+        ("point", _d * 3),
+        ("sensor_task", _i),
+    ]
+
+
 # enum sai2b_action_mode / sai2b_action_block (sai2b.h "actions"); name -> value, blocks in row order
 ACT_NONE, ACT_DELTA_GOAL, ACT_DELTA_CURRENT, ACT_ABSOLUTE = 0, 1, 2, 3
 ACT_POSITION, ACT_ORIENTATION, ACT_FORCE, ACT_MOMENT = 1, 2, 4, 8
@@ -364,6 +379,13 @@ EXPORTS = [
     "sai2b_clear_joint_dynamics",
     "sai2b_get_joint_dynamics",
     "sai2b_get_joint_dynamics_state",
+    "sai2b_default_external_wrench",
+    "sai2b_validate_external_wrench",
+    "sai2b_sizeof_external_wrench_config",
+    "sai2b_set_external_wrench",
+    "sai2b_clear_external_wrench",
+    "sai2b_get_external_wrench",
+    "sai2b_get_external_wrench_state",
     "sai2b_default_action",
     "sai2b_validate_action",
     "sai2b_sizeof_action_config",
@@ -512,5 +534,15 @@ def load_library():
     if lib.sai2b_sizeof_action_config() != C.sizeof(ActionConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_action_config is {lib.sai2b_sizeof_action_config()} bytes in the library, "
                            f"{C.sizeof(ActionConfig)} in the ctypes mirror")
+    lib.sai2b_default_external_wrench.argtypes = [P(ExternalWrenchConfig), _i]
+    lib.sai2b_validate_external_wrench.argtypes = [P(ExternalWrenchConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_external_wrench_config.argtypes = []
+    lib.sai2b_set_external_wrench.argtypes = [vp, P(ExternalWrenchConfig), vp, vp, vp, _i]
+    lib.sai2b_clear_external_wrench.argtypes = [vp]
+    lib.sai2b_get_external_wrench.argtypes = [vp, P(ExternalWrenchConfig), vp]
+    lib.sai2b_get_external_wrench_state.argtypes = [vp, vp, vp, P(_i)]
+    if lib.sai2b_sizeof_external_wrench_config() != C.sizeof(ExternalWrenchConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_external_wrench_config is {lib.sai2b_sizeof_external_wrench_config()} bytes in the library, "
+                           f"{C.sizeof(ExternalWrenchConfig)} in the ctypes mirror")
     _lib = lib
     return lib

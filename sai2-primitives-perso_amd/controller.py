@@ -393,6 +393,85 @@ class Controller:
         self._rc(self.lib.sai2b_get_joint_dynamics_state(self.h, None, None, None, None, C.byref(n)))
         return n.value
 
+    # -- external wrench on a link of the simulated plant (sai2b.h "external wrench on a link of the simulated plant")
+    def external_wrench_config(self, link, point=(0.0, 0.0, 0.0), frame="world", sensor_task=-1):
+        """-> ExternalWrenchConfig: application `point` in the frame of moving link `link`; frame 'world' or 'link'"""
+        cfg = _abi.ExternalWrenchConfig()
+        if self.lib.sai2b_default_external_wrench(C.byref(cfg), int(link)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        try:
+            cfg.frame = _abi.WRENCH_FRAMES[frame] if isinstance(frame, str) else int(frame)
+        except KeyError:
+            raise ValueError("frame must be 'world' or 'link'") from None
+        p = np.asarray(point, dtype=np.float64)
+        if p.shape != (3,):
+            raise ValueError("point: expected 3 values")
+        cfg.point[:] = [float(x) for x in p]
+        cfg.sensor_task = int(sensor_task)
+        msg = C.create_string_buffer(256)
+        tasks = (_abi.TaskConfig * len(self.tasks))(*self.tasks)
+        if self.lib.sai2b_validate_external_wrench(C.byref(cfg), tasks, len(self.tasks), self.dof, msg, 256):
+            raise ValueError(msg.value.decode())
+        return cfg
+
+    def set_external_wrench(self, link, force, moment=None, steps=None, point=(0.0, 0.0, 0.0), frame="world", sensor_task=-1):
+        """every robot's own push for sim_step: force [3][B] (N) and moment [3][B] (a pure couple, N m; None: 0) on moving link
+        `link` at `point` (link frame), world components or, with frame='link', components that turn with the link; steps [B]:
+        the robot's remaining pushed periods (> 0 counted down by every sim_step, < 0 until changed, 0 off; None: -1). numpy
+        arrays ([3] broadcasts over the batch, a scalar `steps` too) or torch CUDA tensors [3][B] / [B]. sensor_task: the
+        MotionForceTask whose sensed rows read the wrench after every step (-1: none). An ExternalWrenchConfig as `link`
+        carries its own point, frame and sensor_task"""
+        if isinstance(link, _abi.ExternalWrenchConfig):
+            if tuple(point) != (0.0, 0.0, 0.0) or frame != "world" or sensor_task != -1:
+                raise ValueError("set_external_wrench: an ExternalWrenchConfig carries its own point, frame and sensor_task")
+            cfg = link
+        else:
+            cfg = self.external_wrench_config(link, point, frame, sensor_task)
+
+        def rows3(a, name):
+            if a is None or hasattr(a, "data_ptr"):
+                return a
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (3,):
+                a = a[:, None]
+            elif a.shape != (3, self.B):
+                raise ValueError(f"{name}: expected 3 values or an array of shape (3, {self.B})")
+            return np.ascontiguousarray(np.broadcast_to(a, (3, self.B)))
+
+        f, m = rows3(force, "force"), rows3(moment, "moment")
+        if steps is not None and hasattr(steps, "data_ptr"):
+            s = steps if steps.dim() == 2 else steps.view(1, -1)
+        elif steps is not None:
+            s = np.asarray(steps, dtype=np.float64)
+            if s.ndim > 1 and s.shape != (1, self.B) or s.ndim == 1 and s.shape != (self.B,):
+                raise ValueError(f"steps: expected a scalar or {self.B} values")
+            s = np.ascontiguousarray(np.broadcast_to(s.reshape(1, -1) if s.ndim else s, (1, self.B)))
+        else:
+            s = None
+        ins = [self._in(o, r) for o, r in zip((f, m, s), (3, 3, 1))]
+        self._rc(self.lib.sai2b_set_external_wrench(self.h, C.byref(cfg), *[p for p, _ in ins], self._dev(f, m, s)))
+
+    def clear_external_wrench(self):
+        self._rc(self.lib.sai2b_clear_external_wrench(self.h))
+
+    def get_external_wrench(self):
+        """-> (ExternalWrenchConfig, rows [7][B]: force 3, moment 3, steps); link -1 and zeros when the plant has no wrench"""
+        cfg, rows = _abi.ExternalWrenchConfig(), np.empty((7, self.B))
+        self._rc(self.lib.sai2b_get_external_wrench(self.h, C.byref(cfg), C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def get_external_wrench_state(self):
+        """what the last sim_step left: dict wrench_world [6][B] (F_w, M_w about the point), torque [dof][B], robots_pushed"""
+        n = C.c_int()
+        w, t = np.empty((6, self.B)), np.empty((self.dof, self.B))
+        self._rc(self.lib.sai2b_get_external_wrench_state(self.h, C.c_void_p(w.ctypes.data), C.c_void_p(t.ctypes.data), C.byref(n)))
+        return dict(wrench_world=w, torque=t, robots_pushed=n.value)
+
+    def robots_pushed(self):
+        n = C.c_int()
+        self._rc(self.lib.sai2b_get_external_wrench_state(self.h, None, None, C.byref(n)))
+        return n.value
+
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod
     def _flags(names, table, what):
@@ -1869,6 +1948,19 @@ class BatchedSimulation:
 
     def getJointDynamicsState(self):
         return self._c._ctrl.get_joint_dynamics_state()
+
+    # -- external wrench on a link of the plant (Controller.set_external_wrench)
+    def setExternalWrench(self, *args, **kwargs):
+        self._c._ctrl.set_external_wrench(*args, **kwargs)
+
+    def clearExternalWrench(self):
+        self._c._ctrl.clear_external_wrench()
+
+    def getExternalWrenchState(self):
+        return self._c._ctrl.get_external_wrench_state()
+
+    def robotsPushed(self):
+        return self._c._ctrl.robots_pushed()
 
     # -- contact of the plant (Controller.set_contact); the force sensor writes the sensed rows of one MotionForceTask
     def setContactPlanes(self, *args, **kwargs):

@@ -107,6 +107,13 @@ struct sai2b_ctx {
 	sai2b::JointParams joint;
 	double *joint_rows = nullptr, *joint_status = nullptr;
 	int* joint_counts = nullptr;
+	// external wrench on a link of the plant (sai2b_set_external_wrench): the [7][B] rows, the [6 + dof][B] status rows and the device
+	// counter of robots pushed, created on first use; wrench_on: sai2b_sim_step launches the wrench forms with `wrench` as their argument
+	bool wrench_on = false;
+	sai2b_external_wrench_config wrench_cfg = {};
+	sai2b::WrenchParams wrench;
+	double *wrench_rows = nullptr, *wrench_status = nullptr;
+	int* wrench_count = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -1527,6 +1534,8 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_CONTACT: return (void*)ctx->h_params.contact;
 		case SAI2B_BUF_JOINT_DYNAMICS: return ctx->joint_on ? (void*)ctx->joint_rows : nullptr;
 		case SAI2B_BUF_JOINT_DYNAMICS_STATE: return ctx->joint_on ? (void*)ctx->joint_status : nullptr;
+		case SAI2B_BUF_EXTERNAL_WRENCH: return ctx->wrench_on ? (void*)ctx->wrench_rows : nullptr;
+		case SAI2B_BUF_EXTERNAL_WRENCH_STATE: return ctx->wrench_on ? (void*)ctx->wrench_status : nullptr;
 	}
 	return nullptr;
 }
@@ -1968,6 +1977,132 @@ extern "C" int sai2b_get_joint_dynamics_state(sai2b_ctx* ctx, double* applied_to
 	return SAI2B_OK;
 }
 
+// ---- external wrench on a link of the simulated plant ----
+extern "C" int sai2b_default_external_wrench(sai2b_external_wrench_config* cfg, int link) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_external_wrench: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->link = link;
+	cfg->frame = SAI2B_WRENCH_WORLD;
+	cfg->sensor_task = -1;
+	return SAI2B_OK;
+}
+static std::string external_wrench_config_error(const sai2b_external_wrench_config* c, const sai2b_task_config* tasks, int n_tasks, int robot_dof) {
+	if (!c) return "external wrench: null config";
+	if (c->link < 0 || c->link >= robot_dof) return "external wrench: link must be in [0, dof)";
+	if (c->frame != SAI2B_WRENCH_WORLD && c->frame != SAI2B_WRENCH_LINK) return "external wrench: frame must be SAI2B_WRENCH_WORLD or SAI2B_WRENCH_LINK";
+	for (int a = 0; a < 3; a++)
+		if (!std::isfinite(c->point[a])) return "external wrench: point must be finite";
+	if (c->sensor_task != -1 && (!tasks || c->sensor_task < 0 || c->sensor_task >= n_tasks || tasks[c->sensor_task].type != SAI2B_MOTION_FORCE_TASK))
+		return "external wrench: sensor_task must be -1 or the index of a MotionForceTask";
+	return "";
+}
+extern "C" int sai2b_validate_external_wrench(const sai2b_external_wrench_config* cfg, const sai2b_task_config* tasks, int n_tasks,
+											  int robot_dof, char* msg, int msg_len) {
+	const std::string err =
+		robot_dof == N ? external_wrench_config_error(cfg, tasks, n_tasks, robot_dof) : "external wrench: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_external_wrench_config(void) { return (int)sizeof(sai2b_external_wrench_config); }
+extern "C" int sai2b_set_external_wrench(sai2b_ctx* ctx, const sai2b_external_wrench_config* cfg, const double* force, const double* moment,
+										 const double* steps, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_external_wrench: null ctx");
+	const std::string err = external_wrench_config_error(cfg, ctx->cfg, ctx->T, N);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_external_wrench: " + err);
+	if (!force) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_external_wrench: force is required");
+	const size_t B = ctx->B;
+	if (!on_device) {
+		for (size_t i = 0; i < 3 * B; i++)
+			if (!std::isfinite(force[i]) || (moment && !std::isfinite(moment[i])))
+				return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_external_wrench: force and moment must be finite");
+		for (size_t b = 0; steps && b < B; b++)
+			if (std::isnan(steps[b])) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_external_wrench: steps must not be NaN");
+	}
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// three buffers, each created once: a failed allocation leaves the others for the next call, and the context as it was
+	if (!ctx->wrench_rows && (rc = dev_alloc(ctx, &ctx->wrench_rows, (size_t)sai2b::WRENCH_ROWS * B))) return rc;
+	if (!ctx->wrench_status) {
+		if ((rc = dev_alloc(ctx, &ctx->wrench_status, (size_t)sai2b::WRENCH_STATUS_ROWS * B))) return rc;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_status, 0, (size_t)sai2b::WRENCH_STATUS_ROWS * B * sizeof(double), ctx->stream));
+	}
+	if (!ctx->wrench_count) {
+		if ((rc = dev_alloc(ctx, &ctx->wrench_count, 1))) return rc;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_count, 0, sizeof(int), ctx->stream));
+	}
+	// the rows of a wrench already in force are rewritten in place: it is taken out of force first, so that a copy that fails
+	// leaves the plant without a wrench, never with rows that are half the old ones and half the new
+	ctx->wrench_on = false;
+	double* rows = ctx->wrench_rows;
+	if ((rc = copy_rows(ctx, rows, force, 3, on_device))) return rc;
+	if (moment) {
+		if ((rc = copy_rows(ctx, rows + 3 * B, moment, 3, on_device))) return rc;
+	} else
+		HIP_TRY(ctx, hipMemsetAsync(rows + 3 * B, 0, 3 * B * sizeof(double), ctx->stream));
+	if (steps) {
+		if ((rc = copy_rows(ctx, rows + 6 * B, steps, 1, on_device))) return rc;
+	} else {
+		const std::vector<double> until_changed(B, -1.0);
+		if ((rc = copy_rows(ctx, rows + 6 * B, until_changed.data(), 1, 0))) return rc;
+	}
+	// everything is written: only now does the wrench become the one in force (again)
+	ctx->wrench_cfg = *cfg;
+	sai2b::WrenchParams& W = ctx->wrench;
+	W.rows = rows, W.status = ctx->wrench_status, W.count = ctx->wrench_count;
+	W.link = cfg->link, W.frame = cfg->frame, W.sensor_task = cfg->sensor_task;
+	for (int a = 0; a < 3; a++) W.point[a] = cfg->point[a];
+	ctx->wrench_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_external_wrench(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_external_wrench: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	// the status of the last step with a wrench does not outlive it: sai2b_get_external_wrench_state gives zeros from here on
+	if (ctx->wrench_status) {
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_status, 0, (size_t)sai2b::WRENCH_STATUS_ROWS * ctx->B * sizeof(double), ctx->stream));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_count, 0, sizeof(int), ctx->stream));
+	}
+	ctx->wrench_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_external_wrench(sai2b_ctx* ctx, sai2b_external_wrench_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_external_wrench: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) {
+		if (ctx->wrench_on)
+			*cfg = ctx->wrench_cfg;
+		else
+			sai2b_default_external_wrench(cfg, -1);
+	}
+	if (!ctx->wrench_on) {
+		if (rows) std::fill(rows, rows + (size_t)sai2b::WRENCH_ROWS * ctx->B, 0.0);
+		return SAI2B_OK;
+	}
+	return fetch_rows(ctx, ctx->wrench_rows, 0, sai2b::WRENCH_ROWS, rows);
+}
+extern "C" int sai2b_get_external_wrench_state(sai2b_ctx* ctx, double* wrench_world, double* torque, int* robots_pushed) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_external_wrench_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	if (!ctx->wrench_status || !ctx->wrench_count) {  // never had an external wrench
+		if (wrench_world) std::fill(wrench_world, wrench_world + 6 * B, 0.0);
+		if (torque) std::fill(torque, torque + (size_t)N * B, 0.0);
+		if (robots_pushed) *robots_pushed = 0;
+		return SAI2B_OK;
+	}
+	int rc;
+	if ((rc = fetch_rows(ctx, ctx->wrench_status, 0, 6, wrench_world))) return rc;
+	if ((rc = fetch_rows(ctx, ctx->wrench_status, 6, N, torque))) return rc;
+	if (robots_pushed) {
+		HIP_TRY(ctx, hipMemcpyAsync(robots_pushed, ctx->wrench_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	return SAI2B_OK;
+}
+
 // ---- observations and episode-end flags ----
 namespace {
 constexpr int OBS_ALL_BLOCKS = SAI2B_OBS_Q | SAI2B_OBS_DQ | SAI2B_OBS_TAU | SAI2B_OBS_LIMIT_MARGIN | SAI2B_OBS_EPISODE_STEP | SAI2B_OBS_CONTACT;
@@ -2367,8 +2502,10 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	if (hp.contact) HIP_TRY(ctx, hipMemsetAsync(hp.contact_count, 0, sizeof(int), ctx->stream));
 	// joint dynamics: sim_joint_kernel, its two counters zeroed alike
 	if (ctx->joint_on) HIP_TRY(ctx, hipMemsetAsync(ctx->joint_counts, 0, sai2b::JOINT_COUNTS * sizeof(int), ctx->stream));
+	// external wrench: the wrench forms of either kernel, the counter of robots pushed zeroed alike
+	if (ctx->wrench_on) HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_count, 0, sizeof(int), ctx->stream));
 	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr,
-						  ctx->joint_on ? &ctx->joint : nullptr, nullptr, q_keep, ctx->stream))
+						  ctx->joint_on ? &ctx->joint : nullptr, ctx->wrench_on ? &ctx->wrench : nullptr, nullptr, q_keep, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
 	ctx->models_fresh = false;
@@ -2390,7 +2527,7 @@ extern "C" int sai2b_get_bias(sai2b_ctx* ctx, int with_gravity, double* bias) {
 	if (rc) return rc;
 	if (!ctx->sim_tau && (rc = dev_alloc(ctx, &ctx->sim_tau, (size_t)N * ctx->B))) return rc;
 	// a zero-length step leaves the state as it is and writes the bias vector of the current state
-	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, nullptr, ctx->sim_tau, nullptr, ctx->stream))
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, nullptr, nullptr, ctx->sim_tau, nullptr, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	return fetch_rows(ctx, ctx->sim_tau, 0, N, bias);
 }

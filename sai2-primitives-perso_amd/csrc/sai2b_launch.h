@@ -87,11 +87,22 @@ struct JointParams {
 	int* counts = nullptr;		   // [JOINT_COUNTS]: robots saturated, robots at a stop; zeroed by the caller ahead of the launch
 	double stop_k[N] = {}, stop_c[N] = {}, v_eps[N] = {};
 };
+// external wrench on a link of the plant (sai2b_set_external_wrench, sai2b_sim.hip: sim_wrench_kernel / sim_joint_wrench_kernel):
+// the kernels' own parameter block, passed by value as a kernel argument like JointParams; DevParams is not touched by the feature.
+constexpr int WRENCH_ROWS = 7, WRENCH_STATUS_ROWS = 6 + N;
+struct WrenchParams {
+	double* rows = nullptr;	   // [WRENCH_ROWS][B]: force 3, moment 3, remaining pushed periods (counted down by the kernel)
+	double* status = nullptr;  // [WRENCH_STATUS_ROWS][B]: F_w, M_w about x, tx at the final state
+	int* count = nullptr;	   // robots pushed; zeroed by the caller ahead of the launch
+	int link = 0, frame = 0, sensor_task = -1;
+	double point[3] = {};
+};
 // simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.
 // payload / contact select the instantiation: the plant's payload rows, the contact rows, status and counter of DevParams;
-// joint != NULL: sim_joint_kernel (the same two selectors) instead of sim_kernel, dbg_bias must be NULL then
+// joint != NULL: sim_joint_kernel (the same two selectors) instead of sim_kernel, dbg_bias must be NULL then;
+// wrench != NULL: the forms of either with an external wrench, dbg_bias must be NULL then
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   const JointParams* joint, double* dbg_bias, double* q_keep, hipStream_t stream);
+			   const JointParams* joint, const WrenchParams* wrench, double* dbg_bias, double* q_keep, hipStream_t stream);
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
 int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream);
 

@@ -197,14 +197,52 @@ DI void contact_torques(const MD& md, const DevParams& P, const Contact& ct, con
 		}
 	}
 }
+// A second wrench ON the robot for the same ideal sensor (the external wrench of sai2b_set_external_wrench): F, M about x, world
+// frame. NoReading: contact_report compiles to what it is without one. add (batch-uniform): the sensor task is the contact's
+// own, the sum of the two readings is stored once.
+struct NoReading {
+	static constexpr bool on = false;
+};
+struct WrenchReading {
+	static constexpr bool on = true;
+	bool add;
+	real x[3], F[3], M[3];
+};
+// the reading of the ideal sensor of task t from the wrench ON the robot, Ft and Mt about the control point x_c (Rc: the
+// control frame): f_s = R_s^T (-Ft), m_s = R_s^T (-(Mt - (o_s - x_c) x Ft)), stored into the task's sensed rows. For the
+// external wrench's own sensor; contact_report holds the same statements in line (behind a call its kernels compile differently)
+DI void sensor_store(const DevTask& t, const real* Rc, const real* Ft, const real* Mt, int B, int b) {
+	real Rs[9], os[3], ms_w[3], t1[3], fs[3], ms[3];
+	mm<3, 3, 3>(Rc, t.sensor_rot, Rs);
+	mv3(Rc, t.sensor_pos, os);	// o_s - x_c
+	cross3(os, Ft, t1);
+	// -sum (x_k - o_s) x F_k = -(sum (x_k - x_c) x F_k - (o_s - x_c) x sum F_k)
+	UNROLL for (int a = 0; a < 3; a++) {
+		ms_w[a] = t1[a] - Mt[a];
+		t1[a] = -Ft[a];
+	}
+	mv_t<3, 3>(Rs, t1, fs);
+	mv_t<3, 3>(Rs, ms_w, ms);
+	UNROLL for (int a = 0; a < 3; a++) {
+		st(t.sensed, a, B, b, fs[a]);
+		st(t.sensed, 3 + a, B, b, ms[a]);
+	}
+}
 // After the last substep: the status rows [2 * 4 + 6][B] (per point delta and f_n, then sum F_k and sum (x_k - x_c) x F_k in
 // the world frame; x_c: the control point of the sensor task, the contact link's origin without one), the count of robots
 // in contact, and the reading of the ideal force / moment sensor: the wrench the robot applies to the environment in the
 // sensor frame of the sensor task (MotionForceTask.cpp:793-828 read backwards), stored into that task's sensed rows.
-template <class MD>
-DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, const real* q, const real* dq, int B, int b) {
+// rd: a second wrench for the sensor, or NoReading; given (with a reading only): the frames of the final state, computed by
+// the caller for its own report; without a reading they are computed here
+template <class MD, class RD>
+DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, const real* q, const real* dq, int B, int b, const RD& rd,
+					   const Frames* given) {
 	Frames Fr;
-	fk(md, q, Fr);
+	if constexpr (RD::on) {
+		Fr = *given;
+	} else {
+		fk(md, q, Fr);
+	}
 	real Rl[9], pl[3], xc[3], Rc[9];
 	link_frame(P.contact_link, Fr, Rl, pl);
 	const bool sensor = P.contact_sensor_task >= 0;
@@ -238,6 +276,15 @@ DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, cons
 	const unsigned long long in_contact = __ballot(touching);
 	if (threadIdx.x == 0 && in_contact) atomicAdd(P.contact_count, __popcll(in_contact));  // lane 0 always has a robot
 	if (sensor) {
+		if constexpr (RD::on) if (rd.add) {  // the external wrench on the same sensor: its moment about x_c joins the sum
+			const real r[3] = {rd.x[0] - xc[0], rd.x[1] - xc[1], rd.x[2] - xc[2]};
+			real m[3];
+			cross3(r, rd.F, m);
+			UNROLL for (int a = 0; a < 3; a++) {
+				Ft[a] += rd.F[a];
+				Mt[a] += rd.M[a] + m[a];
+			}
+		}
 		const DevTask& t = P.task[P.contact_sensor_task];
 		real Rs[9], os[3], ms_w[3], t1[3], fs[3], ms[3];
 		mm<3, 3, 3>(Rc, t.sensor_rot, Rs);
@@ -254,6 +301,87 @@ DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, cons
 			st(t.sensed, a, B, b, fs[a]);
 			st(t.sensed, 3 + a, B, b, ms[a]);
 		}
+	}
+}
+
+// ---- external wrench on a link of the plant (sai2b_set_external_wrench): a force F and a couple M per robot at point c of
+// one link, for the robot's remaining `steps` periods.
+// The law (DESIGN "External wrench on a link"), from the frames at the start of a substep:
+//   x = p_l + R_l c,  F_w = F or R_l F,  M_w = M or R_l M,
+//   tx_i = z_i . ((x - p_i) x F_w + M_w) revolute, z_i . F_w prismatic, for i <= link; 0 outboard and for an inactive robot
+struct Wrench {
+	real F[3], M[3], steps;	 // the robot's own rows of the [7][B] buffer
+	bool active;			 // steps > 0 || steps < 0 on entry (a NaN: inactive)
+};
+DI void wrench_load(const WrenchParams& W, int B, int b, Wrench& wr) {
+	UNROLL for (int k = 0; k < 3; k++) {
+		wr.F[k] = ld(W.rows, k, B, b);
+		wr.M[k] = ld(W.rows, 3 + k, B, b);
+	}
+	wr.steps = ld(W.rows, 6, B, b);
+	wr.active = wr.steps > 0 || wr.steps < 0;
+}
+// x, F_w, M_w (zeros by select for an inactive robot) and tx in one pass over the joints; J is never formed
+template <class MD>
+DI void wrench_torques(const MD& md, const WrenchParams& W, const Wrench& wr, const Frames& Fr, real* x, real* Fw, real* Mw, real* tx) {
+	real Rl[9], pl[3];
+	link_frame(W.link, Fr, Rl, pl);
+	const bool turn = W.frame != 0;	 // batch-uniform
+	UNROLL for (int a = 0; a < 3; a++) {
+		x[a] = fma(Rl[3 * a], W.point[0], fma(Rl[3 * a + 1], W.point[1], fma(Rl[3 * a + 2], W.point[2], pl[a])));
+		const real f = turn ? fma(Rl[3 * a], wr.F[0], fma(Rl[3 * a + 1], wr.F[1], Rl[3 * a + 2] * wr.F[2])) : wr.F[a];
+		const real m = turn ? fma(Rl[3 * a], wr.M[0], fma(Rl[3 * a + 1], wr.M[1], Rl[3 * a + 2] * wr.M[2])) : wr.M[a];
+		Fw[a] = wr.active ? f : 0.0;
+		Mw[a] = wr.active ? m : 0.0;
+	}
+	UNROLL for (int i = 0; i < N; i++) {
+		const real z[3] = {Fr.R[i][2], Fr.R[i][5], Fr.R[i][8]};
+		const real r[3] = {x[0] - Fr.p[i][0], x[1] - Fr.p[i][1], x[2] - Fr.p[i][2]};
+		real m[3];
+		cross3(r, Fw, m);
+		UNROLL for (int a = 0; a < 3; a++) m[a] += Mw[a];
+		const real* pr = (md.jtype[i] != 0) ? Fw : m;
+		const real t = z[0] * pr[0] + z[1] * pr[1] + z[2] * pr[2];
+		tx[i] = (i <= W.link && wr.active) ? t : 0.0;
+	}
+}
+// After the last substep, from the frames of the final state: the status rows [6 + N][B] (F_w, M_w about x, tx), the count of
+// robots pushed (one ballot, one atomic) and the countdown of `steps`; rd: what the sensor is to read
+template <class MD>
+DI void wrench_report(const MD& md, const WrenchParams& W, const Wrench& wr, const Frames& Fr, int B, int b, WrenchReading& rd) {
+	real tx[N];
+	wrench_torques(md, W, wr, Fr, rd.x, rd.F, rd.M, tx);
+	UNROLL for (int a = 0; a < 3; a++) {
+		st(W.status, a, B, b, rd.F[a]);
+		st(W.status, 3 + a, B, b, rd.M[a]);
+	}
+	UNROLL for (int i = 0; i < N; i++) st(W.status, 6 + i, B, b, tx[i]);
+	bool loaded = false;
+	UNROLL for (int a = 0; a < 3; a++) loaded = loaded || wr.F[a] != 0.0 || wr.M[a] != 0.0;
+	const unsigned long long pushed = __ballot(wr.active && loaded);
+	if (threadIdx.x == 0 && pushed) atomicAdd(W.count, __popcll(pushed));  // lane 0 always has a robot
+	st(W.rows, 6, B, b, wr.steps > 0 ? fmax(wr.steps - 1.0, 0.0) : wr.steps);
+}
+// what follows the last substep of a step with an external wrench: one fk for the wrench's report, the contact's and the sensor
+template <class MD, class CT>
+DI void wrench_finish(const MD& md, const DevParams& P, const WrenchParams& W, const Wrench& wr, const CT& ct, const real* q,
+					  const real* dq, int B, int b) {
+	Frames Fr;
+	fk(md, q, Fr);
+	WrenchReading rd;
+	wrench_report(md, W, wr, Fr, B, b, rd);
+	rd.add = false;
+	if constexpr (CT::on) {
+		rd.add = W.sensor_task >= 0 && W.sensor_task == P.contact_sensor_task;
+		contact_report(md, P, ct, q, dq, B, b, rd, &Fr);
+	}
+	if (W.sensor_task >= 0 && !rd.add) {
+		real xc[3], Rc[9], m[3];
+		frame_pose(P.task[W.sensor_task], Fr, xc, Rc);
+		const real r[3] = {rd.x[0] - xc[0], rd.x[1] - xc[1], rd.x[2] - xc[2]};
+		cross3(r, rd.F, m);
+		UNROLL for (int a = 0; a < 3; a++) m[a] += rd.M[a];	 // about x_c
+		sensor_store(P.task[W.sensor_task], Rc, rd.F, m, B, b);
 	}
 }
 
@@ -311,7 +439,62 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 		st((real*)P.q, i, B, b, q[i]);
 		st((real*)P.dq, i, B, b, dq[i]);
 	}
-	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b);
+	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b, NoReading{}, nullptr);
+}
+// sim_kernel's step with the external wrench beside the contact torque: W by value as a kernel argument (batch-uniform, read
+// with scalar loads). The step is written out a second time and sim_kernel is NOT an instantiation of a body shared with this
+// one: behind one more level of inlining the compiler allocates and schedules the very same statements differently, and a
+// context without a wrench must run the kernels it ran before the feature. A change to the step goes into both.
+template <class PL, class CT>
+__global__ __launch_bounds__(64) void sim_wrench_kernel(const DevParams* __restrict__ Pp, const real* __restrict__ tau, real dt, int substeps,
+														int with_gravity, real* __restrict__ q_keep, const WrenchParams W) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b >= B) return;
+	real q[N], dq[N], tq[N];
+	UNROLL for (int i = 0; i < N; i++) {
+		q[i] = ld(P.q, i, B, b);
+		dq[i] = ld(P.dq, i, B, b);
+		tq[i] = tau ? ld(tau, i, B, b) : 0.0;
+		if (q_keep) st(q_keep, i, B, b, q[i]);
+	}
+	[[maybe_unused]] PL pl;
+	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] CT ct;
+	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	Wrench wr;
+	wrench_load(W, B, b, wr);
+	const real h = dt / substeps;
+#pragma unroll 1
+	for (int s = 0; s < substeps; s++) {
+		Frames F;
+		fk(P.model, q, F);
+		real M[N * N], L[N * N], dinv[N], bias[N], x[N];
+		bias_forces(P.model, F, dq, with_gravity != 0, bias, pl);
+		mass_matrix(P.model, F, M, pl);
+		chol<N>(M, L, dinv);
+		real tx[N], xw[3], Fw[3], Mw[3];
+		wrench_torques(P.model, W, wr, F, xw, Fw, Mw, tx);
+		if constexpr (CT::on) {
+			real tc[N];
+			contact_torques(P.model, P, ct, F, dq, tc);
+			UNROLL for (int i = 0; i < N; i++) x[i] = ((tq[i] + tc[i]) + tx[i]) - bias[i];
+		} else {
+			UNROLL for (int i = 0; i < N; i++) x[i] = (tq[i] + tx[i]) - bias[i];
+		}
+		solve_lower<N>(L, dinv, x);
+		solve_lower_t<N>(L, dinv, x);
+		UNROLL for (int i = 0; i < N; i++) {
+			dq[i] = fma(h, x[i], dq[i]);
+			q[i] = fma(h, dq[i], q[i]);
+		}
+	}
+	UNROLL for (int i = 0; i < N; i++) {
+		st((real*)P.q, i, B, b, q[i]);
+		st((real*)P.dq, i, B, b, dq[i]);
+	}
+	wrench_finish(P.model, P, W, wr, ct, q, dq, B, b);
 }
 
 // ---- joint dynamics of the plant (sai2b_set_joint_dynamics): armature, damping, Coulomb friction, actuator saturation and
@@ -414,7 +597,77 @@ __global__ __launch_bounds__(64) void sim_joint_kernel(const DevParams* __restri
 		st((real*)P.q, i, B, b, q[i]);
 		st((real*)P.dq, i, B, b, dq[i]);
 	}
-	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b);
+	if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b, NoReading{}, nullptr);
+	joint_report(J, jr, ts, saturated, q, dq, B, b);
+}
+// sim_joint_kernel's step with the external wrench, written out a second time for the reason given at sim_wrench_kernel
+template <class PL, class CT>
+__global__ __launch_bounds__(64) void sim_joint_wrench_kernel(const DevParams* __restrict__ Pp, const real* __restrict__ tau, real dt,
+															  int substeps, int with_gravity, real* __restrict__ q_keep, const JointParams J,
+															  const WrenchParams W) {
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b >= B) return;
+	real q[N], dq[N], ts[N];
+	JointRows jr;
+	bool saturated = false;
+	UNROLL for (int i = 0; i < N; i++) {
+		q[i] = ld(P.q, i, B, b);
+		dq[i] = ld(P.dq, i, B, b);
+		const real tq = tau ? ld(tau, i, B, b) : 0.0;
+		if (q_keep) st(q_keep, i, B, b, q[i]);
+		jr.a[i] = ld(J.rows, JOINT_ARMATURE * N + i, B, b);
+		jr.d[i] = ld(J.rows, JOINT_DAMPING * N + i, B, b);
+		jr.f[i] = ld(J.rows, JOINT_FRICTION * N + i, B, b);
+		jr.lo[i] = ld(J.rows, JOINT_LOWER * N + i, B, b);
+		jr.hi[i] = ld(J.rows, JOINT_UPPER * N + i, B, b);
+		const real lim = ld(J.rows, JOINT_TORQUE_LIMIT * N + i, B, b);
+		saturated = saturated || fabs(tq) > lim;
+		ts[i] = fmin(fmax(tq, -lim), lim);
+	}
+	[[maybe_unused]] PL pl;
+	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] CT ct;
+	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	Wrench wr;
+	wrench_load(W, B, b, wr);
+	const real h = dt / substeps;
+#pragma unroll 1
+	for (int s = 0; s < substeps; s++) {
+		Frames F;
+		fk(P.model, q, F);
+		real M[N * N], L[N * N], dinv[N], x[N];
+		bias_forces(P.model, F, dq, with_gravity != 0, x, pl);
+		real tx[N], xw[3], Fw[3], Mw[3];
+		wrench_torques(P.model, W, wr, F, xw, Fw, Mw, tx);
+		if constexpr (CT::on) {
+			real tc[N];
+			contact_torques(P.model, P, ct, F, dq, tc);
+			UNROLL for (int i = 0; i < N; i++) x[i] = (((ts[i] + joint_stop_torque(J, jr, i, q[i], dq[i])) + tc[i]) + tx[i]) - x[i];
+		} else {
+			UNROLL for (int i = 0; i < N; i++) x[i] = ((ts[i] + joint_stop_torque(J, jr, i, q[i], dq[i])) + tx[i]) - x[i];
+		}
+		mass_matrix(P.model, F, M, pl);
+		UNROLL for (int i = 0; i < N; i++) {
+			real m = jr.a[i] * dq[i];
+			UNROLL for (int j = 0; j < N; j++) m = fma(M[i * N + j], dq[j], m);
+			x[i] = fma(h, x[i], m);
+		}
+		UNROLL for (int i = 0; i < N; i++) M[i * N + i] += fma(h, joint_dissipation(J, jr, i, dq[i]), jr.a[i]);
+		chol<N>(M, L, dinv);
+		solve_lower<N>(L, dinv, x);
+		solve_lower_t<N>(L, dinv, x);
+		UNROLL for (int i = 0; i < N; i++) {
+			dq[i] = x[i];
+			q[i] = fma(h, dq[i], q[i]);
+		}
+	}
+	UNROLL for (int i = 0; i < N; i++) {
+		st((real*)P.q, i, B, b, q[i]);
+		st((real*)P.dq, i, B, b, dq[i]);
+	}
+	wrench_finish(P.model, P, W, wr, ct, q, dq, B, b);
 	joint_report(J, jr, ts, saturated, q, dq, B, b);
 }
 
@@ -487,7 +740,24 @@ int launch_mft_status(const DevParams* d_params, int B, int task, double* out, h
 }
 
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   const JointParams* joint, double* dbg_bias, double* q_keep, hipStream_t stream) {
+			   const JointParams* joint, const WrenchParams* wrench, double* dbg_bias, double* q_keep, hipStream_t stream) {
+	const dim3 grid((B + 63) / 64), block(64);
+	if (wrench) {  // the forms with an external wrench (dbg_bias: sai2b_get_bias never sees one)
+		if (dbg_bias) return 1;
+		if (joint) {
+			static constexpr decltype(&sim_joint_wrench_kernel<NoPayload, NoContact>) joint_wrench_kernel[2][2] = {
+				{sim_joint_wrench_kernel<NoPayload, NoContact>, sim_joint_wrench_kernel<Payload, NoContact>},
+				{sim_joint_wrench_kernel<NoPayload, Contact>, sim_joint_wrench_kernel<Payload, Contact>}};
+			hipLaunchKernelGGL(joint_wrench_kernel[contact][payload], grid, block, 0, stream, d_params, tau, dt, substeps, with_gravity, q_keep,
+							   *joint, *wrench);
+			return launch_result();
+		}
+		static constexpr decltype(&sim_wrench_kernel<NoPayload, NoContact>) wrench_kernel[2][2] = {
+			{sim_wrench_kernel<NoPayload, NoContact>, sim_wrench_kernel<Payload, NoContact>},
+			{sim_wrench_kernel<NoPayload, Contact>, sim_wrench_kernel<Payload, Contact>}};
+		hipLaunchKernelGGL(wrench_kernel[contact][payload], grid, block, 0, stream, d_params, tau, dt, substeps, with_gravity, q_keep, *wrench);
+		return launch_result();
+	}
 	if (joint) {
 		static constexpr decltype(&sim_joint_kernel<NoPayload, NoContact>) joint_kernel[2][2] = {
 			{sim_joint_kernel<NoPayload, NoContact>, sim_joint_kernel<Payload, NoContact>},

@@ -60,6 +60,16 @@ def set_link_payload(ctrl, world, rank, link, mass, com=None, inertia=None, targ
     ctrl.set_link_payload(link, *[shard_rows(a, world, rank) for a in (mass, com, inertia)], target=target)
 
 
+def set_external_wrench(ctrl, world, rank, link, force, moment=None, steps=None, **kwargs):
+    """Controller.set_external_wrench on this rank's shard of per-robot force / moment rows [3][global_batch] and steps
+    [global_batch] given for the whole batch (a [3] force or moment, or a scalar steps, is batch-uniform and passes as it is)"""
+
+    def part(a, ndim):
+        return shard_rows(a, world, rank) if a is not None and getattr(a, "ndim", 0) == ndim else a
+
+    ctrl.set_external_wrench(link, part(force, 2), part(moment, 2), part(steps, 1), **kwargs)
+
+
 def reinitialize_robots(ctrl, world, rank, mask, task=-1):
     """Controller.reinitialize_robots on this rank's shard of a mask given for the whole batch"""
     ctrl.reinitialize_robots(shard_rows(mask, world, rank), task)
