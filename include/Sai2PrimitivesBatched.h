@@ -73,6 +73,58 @@ inline void checkResetArguments(const int dof, const size_t B, const std::vector
 }
 }  // namespace detail
 
+// Snapshot banks (sai2b.h "snapshot banks"): `capacity` slots of whole robot states in device memory, from
+// RobotController::createSnapshotBank / BatchedSimulation::createSnapshotBank. save / load move robot b with mask[b] != 0 (empty
+// mask: every robot) to / from slot slots[b] (empty: slot b, which needs capacity >= B); a robot whose slot is out of range, or
+// on load was never saved, is left alone and counted. A load that names one slot for many robots clones it. exportBlob /
+// importBlob: the bank as host bytes, for checkpoint and resume. std::invalid_argument for what the library rejects: a layout
+// that has changed since the bank was made, a blob of another layout (the message names the first differing block).
+// Destroy the bank before the controller it came from.
+struct SnapshotCounts {
+	int moved = 0, out_of_range = 0, never_saved = 0;
+};
+class SnapshotBank {
+public:
+	SnapshotBank(sai2b_ctx* ctx, const int capacity, const int what) : _ctx(ctx) {
+		detail::check(ctx, sai2b_snapshot_bank_create(ctx, capacity, what, &_bank));
+	}
+	~SnapshotBank() { sai2b_snapshot_bank_destroy(_bank); }
+	SnapshotBank(const SnapshotBank&) = delete;
+	SnapshotBank& operator=(const SnapshotBank&) = delete;
+	void save(const std::vector<int>& slots = {}, const std::vector<unsigned char>& mask = {}) {
+		checkArguments(slots, mask, "save");
+		detail::check(_ctx, sai2b_snapshot_save(_ctx, _bank, slots.empty() ? nullptr : slots.data(), mask.empty() ? nullptr : mask.data(), 0));
+	}
+	void load(const std::vector<int>& slots = {}, const std::vector<unsigned char>& mask = {}) {
+		checkArguments(slots, mask, "load");
+		detail::check(_ctx, sai2b_snapshot_load(_ctx, _bank, slots.empty() ? nullptr : slots.data(), mask.empty() ? nullptr : mask.data(), 0));
+	}
+	// of the context's last save / load
+	SnapshotCounts counts() const {
+		int c[3];
+		detail::check(_ctx, sai2b_get_snapshot_counts(_ctx, c));
+		SnapshotCounts out;
+		out.moved = c[0], out.out_of_range = c[1], out.never_saved = c[2];
+		return out;
+	}
+	std::vector<unsigned char> exportBlob() {
+		std::vector<unsigned char> blob(sai2b_snapshot_export_size(_bank));
+		detail::check(nullptr, sai2b_snapshot_export(_bank, blob.data(), blob.size()));
+		return blob;
+	}
+	void importBlob(const std::vector<unsigned char>& blob) { detail::check(nullptr, sai2b_snapshot_import(_bank, blob.data(), blob.size())); }
+	sai2b_snapshot_bank* handle() { return _bank; }
+
+private:
+	void checkArguments(const std::vector<int>& slots, const std::vector<unsigned char>& mask, const char* fn) const {
+		const size_t B = (size_t)sai2b_batch(_ctx);
+		if ((!slots.empty() && slots.size() != B) || (!mask.empty() && mask.size() != B))
+			throw std::invalid_argument(std::string("SnapshotBank::") + fn + ": slots and mask must have one entry per robot (or be empty)");
+	}
+	sai2b_ctx* _ctx = nullptr;
+	sai2b_snapshot_bank* _bank = nullptr;
+};
+
 // Observations and episode-end flags (sai2b.h "observations and episode-end flags"): what observe() returns, and the counts
 // of the last observe per reason bit and of robots with a non-zero done byte
 struct Observation {
@@ -1130,6 +1182,10 @@ public:
 			}
 		throw std::invalid_argument("Task " + task_name + " not found in RobotController::GetTaskByName");
 	}
+	// whole robot states saved to and restored from device memory (SnapshotBank above); what: SAI2B_SNAP_* groups
+	std::unique_ptr<SnapshotBank> createSnapshotBank(const int capacity, const int what = SAI2B_SNAP_EPISODE) {
+		return std::make_unique<SnapshotBank>(_ctx, capacity, what);
+	}
 	const std::vector<std::string>& getTaskNames() const { return _task_names; }
 	sai2b_ctx* ctx() { return _ctx; }
 
@@ -1505,6 +1561,11 @@ public:
 	void enableGravity(const bool on = true) { _gravity = on; }
 	void setJointTorques(const Batch& tau) { _tau = tau; }
 	inline void integrate();
+	// SnapshotBank of the context the plant runs in; by default with the plant's per-robot environment (payloads, planes, joint rows,
+	// pushes) next to the episode state
+	std::unique_ptr<SnapshotBank> createSnapshotBank(const int capacity, const int what = SAI2B_SNAP_EPISODE | SAI2B_SNAP_ENVIRONMENT) {
+		return std::make_unique<SnapshotBank>(_c, capacity, what);
+	}
 	inline Batch getJointPositions() const;
 	inline Batch getJointVelocities() const;
 

@@ -21,6 +21,7 @@
 #ifndef SAI2B_H_
 #define SAI2B_H_
 
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -788,6 +789,62 @@ int sai2b_apply_action(sai2b_ctx* ctx, const double* action, const unsigned char
  * whose goal was limited by a box, the lead or a joint clamp (a rejected robot counts as rejected only). Zeros before the
  * first apply; SAI2B_INVALID_ARGUMENT without a configured action. Waits for the ctx stream. */
 int sai2b_get_action_counts(sai2b_ctx* ctx, int counts[3]);
+
+/* ------------------------------------------------------------------ snapshot banks
+ * Whole robot states, saved to and restored from device memory: branching (copy one robot into K siblings, roll them out, come
+ * back), reset to a bank of stored states, checkpoint and resume. A bank holds `capacity` slots of one robot's state each,
+ * structure-of-arrays [word][capacity] like the context, and one valid byte per slot.
+ *
+ * What a robot's state is. SAI2B_SNAP_EPISODE: everything a later tick, sim_step, observe, apply_action or task-level call of
+ * that robot can read and that sai2b_reset_robots would have replaced or that advances with time: q, dq, the stored torques,
+ * the cached pose; per task the goals, the sensed wrench, the integrators and singularity histories (state, istate), the
+ * trajectory generator (desired rows, state, the jerk-limited profile), the passivity observer and the task-level N_prec where
+ * these exist; the episode step; the remaining periods of a timed push; the contact, joint-dynamics and wrench status rows that
+ * sai2b_observe and the sensor path read. SAI2B_SNAP_ENVIRONMENT: what sai2b_reset_robots documents as kept: both payload
+ * buffers, the contact rows, the joint-dynamics rows and the force and moment rows of the external wrench.
+ * NOT state, never restored: batch-level counts, work lists, route-switch probes, introspection outputs and the N, N_total
+ * and tau outputs of task-level calls; batch-uniform configuration (gains, limits, which features are in force).
+ * A load invalidates the cached models exactly as sai2b_reset_robots does: the next tick or task-level call updates them, the
+ * generators compare their goals again.
+ *
+ * Layout. Fixed when the bank is created, from the joint count, every task's type, size, generator mode and observer and
+ * which optional buffers exist (csrc/sai2b_snapshot_layout.h); its fingerprint is kept in the bank and in an exported blob.
+ * save / load on a context whose layout has changed since (a contact set after a bank with SAI2B_SNAP_ENVIRONMENT was made, a
+ * generator switched to jerk-limited), or on another context than the bank's, and import of a blob with another fingerprint
+ * or capacity, return SAI2B_INVALID_ARGUMENT; the message names the first differing block; nothing is written.
+ *
+ * Slots. Robot b with mask[b] != 0 (mask NULL: every robot) <-> slot[b] (slot NULL: slot b). A robot whose slot is outside
+ * [0, capacity), or on load was never saved, is left untouched and counted, as sai2b_apply_action leaves a robot with a
+ * non-finite action; the host does not reject such a call. Two robots saving to one slot in one call: one of them wins, and
+ * which words come from which is UNDEFINED. A load may name one slot for many robots: that is the clone.
+ *
+ * Ordering. Both calls flush a deferred sai2b_update_task_models first, are ONE launch whatever the mask selects, and follow
+ * the stream contract below for on_device != 0 (slot and mask are then device pointers, read before anything the caller
+ * enqueues on its stream after the call). Host slot / mask arrays are staged as sai2b_reset_robots stages its mask.
+ * The cached pose is one flag for the batch (q itself until the state moves on, a column of its own afterwards): a save
+ * stores the pose from wherever it lives; a load always leaves it in the column of its own, for the robots it does not select
+ * too (copied in the same launch). Destroy a bank before its context. */
+enum { SAI2B_SNAP_EPISODE = 1, SAI2B_SNAP_ENVIRONMENT = 2 };
+#define SAI2B_SNAPSHOT_HEADER_BYTES 256 /* of an exported blob: header, then words * 4 * capacity, then capacity valid bytes */
+typedef struct sai2b_snapshot_bank sai2b_snapshot_bank;
+/* 4-byte words per robot for this context as configured now; -1 for a bad argument */
+int sai2b_snapshot_words(sai2b_ctx* ctx, int what);
+/* the row table behind sai2b_snapshot_words: up to max_rows entries of {block id, task or -1, rows, element bytes, first word}
+ * (block ids: enum SnapBlock of csrc/sai2b_snapshot_layout.h); returns the number of entries of the table, -1 for a bad argument */
+int sai2b_snapshot_layout(sai2b_ctx* ctx, int what, int* table5, int max_rows);
+int sai2b_snapshot_bank_create(sai2b_ctx* ctx, int capacity, int what, sai2b_snapshot_bank** out);
+void sai2b_snapshot_bank_destroy(sai2b_snapshot_bank* bank);
+int sai2b_snapshot_save(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* slot, const unsigned char* mask, int on_device);
+int sai2b_snapshot_load(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* slot, const unsigned char* mask, int on_device);
+/* of the last save / load of this context, counted on the device: robots moved, slot out of range, slot never saved. Zeros
+ * before the first. Waits for the ctx stream; the counts arrive through mapped host words, no copy is enqueued. */
+int sai2b_get_snapshot_counts(sai2b_ctx* ctx, int counts[3]);
+/* A bank as a host blob: SAI2B_SNAPSHOT_HEADER_BYTES of header (fingerprint, layout description, capacity), the words, the
+ * valid bytes. export / import wait for the last save / load of the bank. import into a bank of a fresh context built from
+ * the same configuration, then load: the context continues bit-equal. */
+size_t sai2b_snapshot_export_size(const sai2b_snapshot_bank* bank);
+int sai2b_snapshot_export(sai2b_snapshot_bank* bank, void* host_blob, size_t size);
+int sai2b_snapshot_import(sai2b_snapshot_bank* bank, const void* host_blob, size_t size);
 
 /* ------------------------------------------------------------------ simulation harness
  * What the reference's examples obtain from the external sai2-simulation (examples/05-...cpp:215-236:

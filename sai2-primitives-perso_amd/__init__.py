@@ -12,6 +12,8 @@ from ._abi import (  # noqa: F401
     JOINT_TASK,
     MOTION_FORCE_TASK,
     RobotModel,
+    SNAP_ENVIRONMENT,
+    SNAP_EPISODE,
     SV_SIGN_BOTH,
     SV_SIGN_EITHER,
     SV_SIGN_V_MAX_NEGATIVE,
@@ -25,6 +27,7 @@ from .controller import (  # noqa: F401,E402
     JointTask,
     MotionForceTask,
     RobotController,
+    SnapshotBank,
     joint_task_config,
     model_from_urdf,
     resolve_link_frame,

@@ -396,7 +396,24 @@ EXPORTS = [
     "sai2b_action_layout",
     "sai2b_apply_action",
     "sai2b_get_action_counts",
+    "sai2b_snapshot_words",
+    "sai2b_snapshot_layout",
+    "sai2b_snapshot_bank_create",
+    "sai2b_snapshot_bank_destroy",
+    "sai2b_snapshot_save",
+    "sai2b_snapshot_load",
+    "sai2b_get_snapshot_counts",
+    "sai2b_snapshot_export_size",
+    "sai2b_snapshot_export",
+    "sai2b_snapshot_import",
 ]
+# snapshot banks (sai2b.h "snapshot banks"): the groups, the blob's header and the block names of csrc/sai2b_snapshot_layout.h
+SNAP_EPISODE, SNAP_ENVIRONMENT = 1, 2
+SNAPSHOT_HEADER_BYTES = 256
+SNAP_COUNTS = ("moved", "out_of_range", "never_saved")
+SNAP_BLOCKS = ("q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i",
+               "popc_q", "N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status", "payload",
+               "plant_payload", "contact", "joint_dynamics", "external_wrench")
 
 _lib = None
 
@@ -544,5 +561,17 @@ def load_library():
     if lib.sai2b_sizeof_external_wrench_config() != C.sizeof(ExternalWrenchConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_external_wrench_config is {lib.sai2b_sizeof_external_wrench_config()} bytes in the library, "
                            f"{C.sizeof(ExternalWrenchConfig)} in the ctypes mirror")
+    lib.sai2b_snapshot_words.argtypes = [vp, _i]
+    lib.sai2b_snapshot_layout.argtypes = [vp, _i, P(_i), _i]
+    lib.sai2b_snapshot_bank_create.argtypes = [vp, _i, _i, P(vp)]
+    lib.sai2b_snapshot_bank_destroy.argtypes = [vp]
+    lib.sai2b_snapshot_bank_destroy.restype = None
+    lib.sai2b_snapshot_save.argtypes = [vp, vp, vp, vp, _i]
+    lib.sai2b_snapshot_load.argtypes = [vp, vp, vp, vp, _i]
+    lib.sai2b_get_snapshot_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_snapshot_export_size.argtypes = [vp]
+    lib.sai2b_snapshot_export_size.restype = C.c_size_t
+    lib.sai2b_snapshot_export.argtypes = [vp, vp, C.c_size_t]
+    lib.sai2b_snapshot_import.argtypes = [vp, vp, C.c_size_t]
     _lib = lib
     return lib

@@ -738,6 +738,47 @@ class Controller:
         pd, kd = self._in(dq, self.dof)
         self._rc(self.lib.sai2b_reset_robots(self.h, pm, pq, pd, self._dev(mask, q, dq)))
 
+    # -- snapshot banks (sai2b.h "snapshot banks")
+    def snapshot_words(self, what=_abi.SNAP_EPISODE):
+        """4-byte words of one robot's state for this controller as configured now"""
+        n = self.lib.sai2b_snapshot_words(self.h, int(what))
+        if n < 0:
+            self._rc(_abi.INVALID_ARGUMENT)
+        return n
+
+    def snapshot_layout(self, what=_abi.SNAP_EPISODE):
+        """the row table behind snapshot_words(): list of dicts block (name), task (-1: none), rows, elem_bytes, first_word"""
+        tab = (C.c_int * (5 * 64))()
+        n = self.lib.sai2b_snapshot_layout(self.h, int(what), tab, 64)
+        if n < 0:
+            self._rc(_abi.INVALID_ARGUMENT)
+        return [dict(block=_abi.SNAP_BLOCKS[tab[5 * i]], task=tab[5 * i + 1], rows=tab[5 * i + 2], elem_bytes=tab[5 * i + 3],
+                     first_word=tab[5 * i + 4]) for i in range(n)]
+
+    def snapshot_bank(self, capacity, what=_abi.SNAP_EPISODE):
+        """a SnapshotBank of `capacity` slots for the state groups `what` (SNAP_EPISODE | SNAP_ENVIRONMENT)"""
+        return SnapshotBank(self, capacity, what)
+
+    def _slots(self, slots):
+        """-> (pointer, keepalive) for [B] slot indices: numpy integer array or contiguous torch CUDA int32 tensor"""
+        if hasattr(slots, "data_ptr"):  # torch tensor
+            if not slots.is_cuda or not slots.is_contiguous() or tuple(slots.shape) != (self.B,) or str(slots.dtype) != "torch.int32":
+                raise ValueError(f"expected a contiguous int32 CUDA tensor of shape ({self.B},)")
+            import torch
+
+            s = torch.cuda.current_stream(slots.device).cuda_stream
+            if s != self._caller_stream:
+                self._rc(self.lib.sai2b_set_caller_stream(self.h, C.c_void_p(s)))
+                self._caller_stream = s
+            return C.c_void_p(slots.data_ptr()), slots
+        arr = np.asarray(slots)
+        if arr.dtype.kind not in "iu":
+            raise ValueError(f"expected integer slots, got dtype {arr.dtype}")
+        if arr.shape != (self.B,):
+            raise ValueError(f"expected slots of shape ({self.B},), got {arr.shape}")
+        arr = np.ascontiguousarray(np.clip(arr, -1, 2**31 - 1), dtype=np.int32)  # (anything out of range stays out of range)
+        return C.c_void_p(arr.ctypes.data), arr
+
     def update_task_models(self):
         self._rc(self.lib.sai2b_update_task_models(self.h))
 
@@ -954,6 +995,64 @@ class Controller:
 # --------------------------------------------------------------------------------------------------
 # reference-named, batch-aware facade
 # --------------------------------------------------------------------------------------------------
+class SnapshotBank:
+    """sai2b_snapshot_bank: `capacity` slots of whole robot states on the device (sai2b.h "snapshot banks"). save / load move
+    robot b with mask[b] != 0 (None: every robot) to / from slot slots[b] (None: slot b); slots and mask are numpy arrays or
+    torch CUDA tensors (int32 / bool or uint8; then nothing leaves the device and nothing synchronises). A robot whose slot
+    is out of range, or on load was never saved, is left alone and counted. Close the bank before its controller."""
+
+    def __init__(self, ctrl, capacity, what=_abi.SNAP_EPISODE):
+        self._ctrl, self.lib = ctrl, ctrl.lib
+        self.capacity, self.what = int(capacity), int(what)
+        h = C.c_void_p()
+        ctrl._rc(self.lib.sai2b_snapshot_bank_create(ctrl.h, self.capacity, self.what, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sai2b_snapshot_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _move(self, fn, slots, mask):
+        c = self._ctrl
+        dev = c._dev(slots, mask)
+        ps, ks = c._slots(slots) if slots is not None else (None, None)
+        pm, km = c._mask(mask) if mask is not None else (None, None)
+        c._rc(fn(c.h, self.h, ps, pm, dev))
+
+    def save(self, slots=None, mask=None):
+        self._move(self.lib.sai2b_snapshot_save, slots, mask)
+
+    def load(self, slots=None, mask=None):
+        self._move(self.lib.sai2b_snapshot_load, slots, mask)
+
+    def counts(self):
+        """of the controller's last save() / load(): dict 'moved', 'out_of_range', 'never_saved' -> robots"""
+        c = (C.c_int * 3)()
+        self._ctrl._rc(self.lib.sai2b_get_snapshot_counts(self._ctrl.h, c))
+        return dict(zip(_abi.SNAP_COUNTS, list(c)))
+
+    def export_size(self):
+        return int(self.lib.sai2b_snapshot_export_size(self.h))
+
+    def export(self):
+        """the bank as a numpy uint8 blob: header, words, valid bytes"""
+        blob = np.empty(self.export_size(), dtype=np.uint8)
+        _check(self.lib, None, self.lib.sai2b_snapshot_export(self.h, C.c_void_p(blob.ctypes.data), blob.size))
+        return blob
+
+    def import_(self, blob):
+        """a blob of export() into this bank; ValueError (naming the first differing block) when its layout is not the bank's"""
+        arr = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        _check(self.lib, None, self.lib.sai2b_snapshot_import(self.h, C.c_void_p(arr.ctypes.data), arr.size))
+
+
 class BatchedRobotModel:
     """Stands where the reference takes ``std::shared_ptr<Sai2Model::Sai2Model>``: the constant
     model plus the batch size and the device; q/dq are set on it as on the reference's model
@@ -1890,6 +1989,10 @@ class RobotController:
                     cur[:, sel] = np.asarray(new, dtype=np.float64)[:, sel]
                     setattr(self._robot, name, cur)
 
+    def createSnapshotBank(self, capacity, what=_abi.SNAP_EPISODE):
+        """Controller.snapshot_bank: whole robot states saved to and restored from device memory"""
+        return self._ctrl.snapshot_bank(capacity, what)
+
     def getTaskNames(self):
         return [t.getTaskName() for t in self._tasks]
 
@@ -1938,6 +2041,10 @@ class BatchedSimulation:
 
     def getJointVelocities(self):
         return self._c._ctrl.get_state()[1]
+
+    def createSnapshotBank(self, capacity, what=_abi.SNAP_EPISODE | _abi.SNAP_ENVIRONMENT):
+        """Controller.snapshot_bank; by default with the plant's per-robot environment (payloads, planes, joint rows, pushes)"""
+        return self._c._ctrl.snapshot_bank(capacity, what)
 
     # -- joint dynamics of the plant (Controller.set_joint_dynamics)
     def setJointDynamics(self, *args, **kwargs):

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sai2b_launch.h"
+#include "sai2b_snapshot_layout.h"
 #include "sai2b_model_host.h"
 #include "sai2b_baked_panda.h"
 
@@ -139,6 +140,13 @@ struct sai2b_ctx {
 	// staged here, created on first use
 	unsigned char* reset_mask = nullptr;
 	double* reset_rows = nullptr;
+	// snapshot banks (sai2b_snapshot_save / _load), created with the first bank: the four device words the kernel counts in, the
+	// three mapped host words the counts of a call arrive in (tagged with snap_stamp; snap_report_dev is their device address)
+	// and the staging of a host slot array (a host mask goes through reset_mask)
+	int* snap_counts = nullptr;
+	unsigned long long *snap_report = nullptr, *snap_report_dev = nullptr;
+	unsigned snap_stamp = 0;
+	int* snap_slot = nullptr;
 	// task-level calls (TemplateTask.h:42-88): per task the caller's N_prec, the task's N and N * N_prec of the
 	// last sai2b_task_update_model, its torques and a staging copy of a host tau_prec; created on first use
 	int last_call_task = 0;	  // the last launch sequence was a task-level call: 1 = task_cert_kernel + work list, 2 = the generic task kernel alone
@@ -831,6 +839,7 @@ extern "C" void sai2b_destroy(sai2b_ctx* ctx) {
 	if (ctx->otg_busy_seen) (void)hipHostFree(ctx->otg_busy_seen);
 	if (ctx->fb_seen) (void)hipHostFree(ctx->fb_seen);
 	if (ctx->fb_report) (void)hipHostFree(ctx->fb_report);
+	if (ctx->snap_report) (void)hipHostFree(ctx->snap_report);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -2778,5 +2787,299 @@ extern "C" int sai2b_counters(const sai2b_ctx* ctx, long long* launches, long lo
 	if (!ctx) return SAI2B_INVALID_ARGUMENT;
 	if (launches) *launches = ctx->launches;
 	if (ticks) *ticks = ctx->ticks;
+	return SAI2B_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// snapshot banks (include/sai2b.h "snapshot banks"; layout: sai2b_snapshot_layout.h; kernels: sai2b_snapshot.hip)
+// ------------------------------------------------------------------------------------------------
+static_assert(sai2b::SNAP_JOINT_ROWS == sai2b::JOINT_ROWS && sai2b::SNAP_JOINT_STATUS_ROWS == sai2b::JOINT_STATUS_ROWS &&
+				  sai2b::SNAP_WRENCH_MOTION_ROWS + 1 == sai2b::WRENCH_ROWS && 6 + N == sai2b::WRENCH_STATUS_ROWS &&
+				  sai2b::MFT_STATE_ROWS == 12 + 3 * N,
+			  "sai2b_snapshot_layout.h and the kernels disagree about a buffer's rows");
+
+namespace {
+struct SnapBlobHeader {
+	char magic[8];	// "SAI2BSNP"
+	int version, capacity, words, rows;
+	unsigned long long fingerprint;
+	sai2b::SnapDesc desc;
+	char pad[SAI2B_SNAPSHOT_HEADER_BYTES - 8 - 16 - 8 - sizeof(sai2b::SnapDesc)];
+};
+static_assert(sizeof(SnapBlobHeader) == SAI2B_SNAPSHOT_HEADER_BYTES, "blob header");
+}  // namespace
+
+struct sai2b_snapshot_bank {
+	int dof_tag = N;  // FIRST member, as in sai2b_ctx: sai2b_dispatch.cpp routes by it
+	sai2b_ctx* owner = nullptr;
+	int device = 0, capacity = 0;
+	sai2b::SnapDesc desc;
+	sai2b::SnapLayout layout;
+	char* data = nullptr;			 // [words][capacity] 4-byte words
+	unsigned char* valid = nullptr;	 // [capacity]
+	sai2b::SnapDevBlock* table = nullptr;
+	hipEvent_t last = nullptr;	// behind the last save / load
+	size_t data_bytes() const { return (size_t)layout.words * 4 * (size_t)capacity; }
+};
+
+// the context as sai2b_snapshot_layout.h sees it; what the chosen groups do not read stays zero
+static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
+	sai2b::SnapDesc d;
+	std::memset(&d, 0, sizeof(d));
+	d.dof = N, d.n_tasks = ctx->T, d.what = what;
+	const bool epi = what & SAI2B_SNAP_EPISODE, env = what & SAI2B_SNAP_ENVIRONMENT;
+	for (int t = 0; t < ctx->T && epi; t++) {
+		const DevTask& k = ctx->h_params.task[t];
+		d.task[t].kind = k.type, d.task[t].k0 = k.k0;
+		d.task[t].otg_mode = k.otg_on ? (k.otg_jerk ? 2 : 1) : 0;
+		d.task[t].otg3 = k.otg3_traj != nullptr, d.task[t].popc = k.popc_f != nullptr, d.task[t].nprec = ctx->tio[t].Nprec != nullptr;
+	}
+	d.steps = epi && ctx->obs_steps != nullptr;
+	d.contact = ctx->contact_rows != nullptr && ctx->h_params.contact_status != nullptr;
+	d.joint = ctx->joint_rows != nullptr && ctx->joint_status != nullptr;
+	d.wrench = ctx->wrench_rows != nullptr && ctx->wrench_status != nullptr;
+	d.payload = env && ctx->payload_rows[0] != nullptr, d.plant_payload = env && ctx->payload_rows[1] != nullptr;
+	return d;
+}
+
+// where a block of the table lives in the context
+static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
+	using namespace sai2b;
+	const size_t B = ctx->B;
+	DevTask* k = r.task >= 0 ? &ctx->h_params.task[r.task] : nullptr;
+	switch (r.block) {
+		case SNAP_Q: return ctx->q;
+		case SNAP_DQ: return ctx->dq;
+		case SNAP_TAU: return ctx->tau;
+		case SNAP_Q_POSE: return ctx->q_pose;
+		case SNAP_GOALS: return k->goals;
+		case SNAP_SENSED: return k->sensed;
+		case SNAP_STATE: return k->state;
+		case SNAP_ISTATE: return k->istate;
+		case SNAP_OTG_DESIRED: return k->otg_desired;
+		case SNAP_OTG_STATE: return k->otg_state;
+		case SNAP_OTG3_TRAJ: return k->otg3_traj;
+		case SNAP_POPC_F: return k->popc_f;
+		case SNAP_POPC_I: return k->popc_i;
+		case SNAP_POPC_Q: return k->popc_q;
+		case SNAP_NPREC: return ctx->tio[r.task].Nprec;
+		case SNAP_EPISODE_STEP: return ctx->obs_steps;
+		case SNAP_WRENCH_REMAINING: return ctx->wrench_rows + (size_t)SNAP_WRENCH_MOTION_ROWS * B;
+		case SNAP_CONTACT_STATUS: return ctx->h_params.contact_status;
+		case SNAP_JOINT_STATUS: return ctx->joint_status;
+		case SNAP_WRENCH_STATUS: return ctx->wrench_status;
+		case SNAP_PAYLOAD: return ctx->payload_rows[0];
+		case SNAP_PLANT_PAYLOAD: return ctx->payload_rows[1];
+		case SNAP_CONTACT: return ctx->contact_rows;
+		case SNAP_JOINT: return ctx->joint_rows;
+		case SNAP_WRENCH: return ctx->wrench_rows;
+		default: return nullptr;
+	}
+}
+
+static bool snapshot_what_ok(int what) { return what > 0 && (what & ~(SAI2B_SNAP_EPISODE | SAI2B_SNAP_ENVIRONMENT)) == 0; }
+
+extern "C" int sai2b_snapshot_words(sai2b_ctx* ctx, int what) {
+	if (!ctx || !snapshot_what_ok(what)) {
+		set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_words: bad arguments");
+		return -1;
+	}
+	return sai2b::snapshot_layout(snapshot_describe(ctx, what)).words;
+}
+
+extern "C" int sai2b_snapshot_layout(sai2b_ctx* ctx, int what, int* table5, int max_rows) {
+	if (!ctx || !snapshot_what_ok(what) || (max_rows > 0 && !table5)) {
+		set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_layout: bad arguments");
+		return -1;
+	}
+	const sai2b::SnapLayout L = sai2b::snapshot_layout(snapshot_describe(ctx, what));
+	for (int i = 0; i < L.n && i < max_rows; i++) {
+		const sai2b::SnapRow& r = L.row[i];
+		const int v[5] = {r.block, r.task, r.rows, r.elem_bytes, r.first_word};
+		std::memcpy(table5 + 5 * i, v, sizeof(v));
+	}
+	return L.n;
+}
+
+extern "C" void sai2b_snapshot_bank_destroy(sai2b_snapshot_bank* bank) {
+	if (!bank) return;
+	(void)hipSetDevice(bank->device);
+	if (bank->last) {
+		(void)hipEventSynchronize(bank->last);
+		(void)hipEventDestroy(bank->last);
+	}
+	if (bank->data) (void)hipFree(bank->data);
+	if (bank->valid) (void)hipFree(bank->valid);
+	if (bank->table) (void)hipFree(bank->table);
+	delete bank;
+}
+
+extern "C" int sai2b_snapshot_bank_create(sai2b_ctx* ctx, int capacity, int what, sai2b_snapshot_bank** out) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_bank_create: null ctx");
+	if (!out || capacity < 1 || !snapshot_what_ok(what))
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_bank_create: capacity must be >= 1 and what a combination of SAI2B_SNAP_*");
+	*out = nullptr;
+	int rc = flush_update(ctx);
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (!ctx->snap_counts) {
+		if ((rc = dev_alloc(ctx, &ctx->snap_counts, 4))) return rc;
+		HIP_TRY(ctx, hipHostMalloc((void**)&ctx->snap_report, 3 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+		ctx->snap_report[0] = ctx->snap_report[1] = ctx->snap_report[2] = 0;
+		HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->snap_report_dev, ctx->snap_report, 0));
+	}
+	sai2b_snapshot_bank* bank = new sai2b_snapshot_bank();
+	bank->owner = ctx, bank->device = ctx->device, bank->capacity = capacity;
+	bank->desc = snapshot_describe(ctx, what);
+	bank->layout = sai2b::snapshot_layout(bank->desc);
+	std::vector<sai2b::SnapDevBlock> table(bank->layout.n);
+	for (int i = 0; i < bank->layout.n; i++) {
+		const sai2b::SnapRow& r = bank->layout.row[i];
+		table[i] = sai2b::SnapDevBlock{snapshot_block_base(ctx, r), r.rows, r.elem_bytes, r.first_word, r.first_row, r.block == sai2b::SNAP_Q_POSE, 0};
+	}
+	auto fail = [&](hipError_t e, const char* what_failed) {
+		sai2b_snapshot_bank_destroy(bank);
+		return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string("sai2b_snapshot_bank_create: ") + what_failed + ": " + hipGetErrorString(e));
+	};
+	hipError_t e;
+	if ((e = hipMalloc((void**)&bank->data, std::max<size_t>(bank->data_bytes(), 8))) != hipSuccess) return fail(e, "hipMalloc of the bank");
+	if ((e = hipMalloc((void**)&bank->valid, (size_t)capacity)) != hipSuccess) return fail(e, "hipMalloc of the valid bytes");
+	if ((e = hipMalloc((void**)&bank->table, std::max<size_t>(table.size(), 1) * sizeof(sai2b::SnapDevBlock))) != hipSuccess)
+		return fail(e, "hipMalloc of the row table");
+	if ((e = hipEventCreateWithFlags(&bank->last, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+	if ((e = hipMemsetAsync(bank->data, 0, std::max<size_t>(bank->data_bytes(), 8), ctx->stream)) != hipSuccess) return fail(e, "hipMemset");
+	if ((e = hipMemsetAsync(bank->valid, 0, (size_t)capacity, ctx->stream)) != hipSuccess) return fail(e, "hipMemset");
+	if (!table.empty() &&
+		(e = hipMemcpyAsync(bank->table, table.data(), table.size() * sizeof(sai2b::SnapDevBlock), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+		return fail(e, "upload of the row table");
+	if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e, "hipStreamSynchronize");
+	*out = bank;
+	return SAI2B_OK;
+}
+
+// save (true) / load (false): one launch of snapshot_kernel
+static int snapshot_move(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* slot, const unsigned char* mask, int on_device, bool save) {
+	const std::string fn = save ? "sai2b_snapshot_save" : "sai2b_snapshot_load";
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, fn + ": null ctx");
+	if (!bank) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": null bank");
+	if (bank->owner != ctx) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": the bank was created for another context");
+	int rc = flush_update(ctx);
+	if (rc) return rc;
+	const sai2b::SnapDesc now = snapshot_describe(ctx, bank->desc.what);
+	char diff[160] = "";
+	if (sai2b::snapshot_first_difference(bank->desc, now, diff, sizeof(diff)))
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": the context's layout has changed since the bank was created, first at " + diff);
+	if (!slot && bank->capacity < ctx->B) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": slot NULL (slot b for robot b) needs capacity >= batch");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	const int* d_slot = slot;
+	const unsigned char* d_mask = mask;
+	if (on_device) {
+		if ((slot || mask) && (rc = caller_before_read(ctx))) return rc;
+	} else if (slot || mask) {
+		if (mask) {
+			if (!ctx->reset_mask && (rc = dev_alloc(ctx, &ctx->reset_mask, B))) return rc;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->reset_mask, mask, B, hipMemcpyHostToDevice, ctx->stream));
+			d_mask = ctx->reset_mask;
+		}
+		if (slot) {
+			if (!ctx->snap_slot && (rc = dev_alloc(ctx, &ctx->snap_slot, B))) return rc;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->snap_slot, slot, B * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+			d_slot = ctx->snap_slot;
+		}
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
+	}
+	sai2b::SnapArgs a;
+	a.table = bank->table, a.n_blocks = bank->layout.n, a.total_rows = bank->layout.rows;
+	a.B = ctx->B, a.capacity = bank->capacity, a.dof = N;
+	if (++ctx->snap_stamp == 0) ctx->snap_stamp = 1;
+	a.stamp = ctx->snap_stamp;
+	a.bank = bank->data, a.valid = bank->valid, a.slot = d_slot, a.mask = d_mask;
+	a.counts = ctx->snap_counts, a.report = ctx->snap_report_dev;
+	const bool episode = bank->desc.what & SAI2B_SNAP_EPISODE;
+	// q_is_pose is one flag for the batch. A save stores the cached pose from wherever it lives. A load puts a loaded robot's pose
+	// into q_pose, so the flag ends for the batch: the robots the call leaves alone get q_pose := q in the same launch.
+	if (save && ctx->q_is_pose) a.pose_src = ctx->q;
+	if (!save && episode && ctx->q_is_pose) a.keep_pose_q = ctx->q, a.keep_pose_dst = ctx->q_pose;
+	if (sai2b::launch_snapshot(a, save, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, fn + ": launch failed");
+	ctx->launches++;
+	HIP_TRY(ctx, hipEventRecord(bank->last, ctx->stream));
+	if (!save) {
+		if (episode) ctx->q_is_pose = false;
+		// as reset_subset: batch-wide and conservative
+		ctx->goals_dirty = ~0u;
+		ctx->goals_epoch++, ctx->otg_all_idle = false;
+		ctx->models_fresh = false;
+		for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
+	}
+	return (on_device && (slot || mask)) ? caller_after_read(ctx) : SAI2B_OK;
+}
+
+extern "C" int sai2b_snapshot_save(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* slot, const unsigned char* mask, int on_device) {
+	return snapshot_move(ctx, bank, slot, mask, on_device, true);
+}
+extern "C" int sai2b_snapshot_load(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* slot, const unsigned char* mask, int on_device) {
+	return snapshot_move(ctx, bank, slot, mask, on_device, false);
+}
+
+extern "C" int sai2b_get_snapshot_counts(sai2b_ctx* ctx, int counts[3]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_snapshot_counts: bad arguments");
+	counts[0] = counts[1] = counts[2] = 0;
+	if (!ctx->snap_stamp) return SAI2B_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	for (int k = 0; k < 3; k++) {
+		const unsigned long long w = __atomic_load_n(ctx->snap_report + k, __ATOMIC_ACQUIRE);
+		if ((unsigned)(w >> 32) != ctx->snap_stamp)
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_get_snapshot_counts: the counts of the last call have not arrived");
+		counts[k] = (int)(unsigned)w;
+	}
+	return SAI2B_OK;
+}
+
+extern "C" size_t sai2b_snapshot_export_size(const sai2b_snapshot_bank* bank) {
+	return bank ? SAI2B_SNAPSHOT_HEADER_BYTES + bank->data_bytes() + (size_t)bank->capacity : 0;
+}
+
+extern "C" int sai2b_snapshot_export(sai2b_snapshot_bank* bank, void* host_blob, size_t size) {
+	if (!bank) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_export: null bank");
+	sai2b_ctx* ctx = nullptr;  // (the bank may outlive nothing, but it never dereferences its context here)
+	if (!host_blob || size < sai2b_snapshot_export_size(bank))
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_export: the blob is smaller than sai2b_snapshot_export_size");
+	HIP_TRY(ctx, hipSetDevice(bank->device));
+	HIP_TRY(ctx, hipEventSynchronize(bank->last));
+	SnapBlobHeader h;
+	std::memset(&h, 0, sizeof(h));
+	std::memcpy(h.magic, "SAI2BSNP", 8);
+	h.version = 1, h.capacity = bank->capacity, h.words = bank->layout.words, h.rows = bank->layout.rows;
+	h.fingerprint = bank->layout.fingerprint, h.desc = bank->desc;
+	char* blob = (char*)host_blob;
+	std::memcpy(blob, &h, sizeof(h));
+	if (bank->data_bytes()) HIP_TRY(ctx, hipMemcpy(blob + sizeof(h), bank->data, bank->data_bytes(), hipMemcpyDeviceToHost));
+	HIP_TRY(ctx, hipMemcpy(blob + sizeof(h) + bank->data_bytes(), bank->valid, (size_t)bank->capacity, hipMemcpyDeviceToHost));
+	return SAI2B_OK;
+}
+
+extern "C" int sai2b_snapshot_import(sai2b_snapshot_bank* bank, const void* host_blob, size_t size) {
+	if (!bank) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_import: null bank");
+	sai2b_ctx* ctx = nullptr;
+	if (!host_blob || size < sizeof(SnapBlobHeader)) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_import: the blob is shorter than its header");
+	SnapBlobHeader h;
+	std::memcpy(&h, host_blob, sizeof(h));
+	if (std::memcmp(h.magic, "SAI2BSNP", 8) != 0 || h.version != 1)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_import: not a snapshot blob of this library version");
+	char diff[160] = "";
+	if (sai2b::snapshot_first_difference(h.desc, bank->desc, diff, sizeof(diff)) || h.fingerprint != bank->layout.fingerprint)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string("sai2b_snapshot_import: the blob's layout is not the bank's, first at ") +
+														  (h.fingerprint != bank->layout.fingerprint && !diff[0] ? "block q: fingerprint" : diff));
+	if (h.capacity != bank->capacity || h.words != bank->layout.words)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_import: the blob's capacity is not the bank's");
+	if (size < sai2b_snapshot_export_size(bank)) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_snapshot_import: the blob is truncated");
+	HIP_TRY(ctx, hipSetDevice(bank->device));
+	HIP_TRY(ctx, hipEventSynchronize(bank->last));
+	const char* blob = (const char*)host_blob;
+	if (bank->data_bytes()) HIP_TRY(ctx, hipMemcpy(bank->data, blob + sizeof(h), bank->data_bytes(), hipMemcpyHostToDevice));
+	HIP_TRY(ctx, hipMemcpy(bank->valid, blob + sizeof(h) + bank->data_bytes(), (size_t)bank->capacity, hipMemcpyHostToDevice));
+	HIP_TRY(ctx, hipDeviceSynchronize());
 	return SAI2B_OK;
 }

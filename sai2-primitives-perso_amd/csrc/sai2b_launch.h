@@ -142,4 +142,30 @@ struct ActParams {
 int launch_action(const DevParams* d_params, int B, const ActParams& act, const double* action, const unsigned char* mask, int* counts,
 				  hipStream_t stream);
 
+// snapshot banks (sai2b_snapshot_save / sai2b_snapshot_load, sai2b_snapshot.hip: snapshot_kernel): the kernel's own argument
+// block, passed by value; DevParams is not read. table: the bank's row table on the device (sai2b_snapshot_layout.h), each block
+// with its base pointer in the context.
+constexpr int SNAP_CHUNK_ROWS = 32;	 // rows of the table one workgroup moves (the grid's second dimension counts the chunks)
+struct SnapDevBlock {
+	void* base;	 // [rows][B] elements of elem_bytes in the context
+	int rows, elem_bytes, first_word, first_row;
+	int pose, reserved;	 // pose: the q_pose block (a save reads SnapArgs::pose_src instead when that is set)
+};
+struct SnapArgs {
+	const SnapDevBlock* table = nullptr;
+	int n_blocks = 0, total_rows = 0;
+	int B = 0, capacity = 0, dof = 0;
+	unsigned stamp = 0;
+	char* bank = nullptr;			  // [words][capacity] 4-byte words
+	unsigned char* valid = nullptr;	  // [capacity]
+	const int* slot = nullptr;		  // [B] or NULL: slot b
+	const unsigned char* mask = nullptr;  // [B] or NULL: every robot
+	int* counts = nullptr;			  // [4]: moved, out of range, never saved, ticket; zero between launches
+	unsigned long long* report = nullptr;  // three mapped host words (device address): stamp << 32 | count
+	const double* pose_src = nullptr;	   // save: where the cached pose lives now when that is not q_pose (q while q_is_pose holds)
+	const double* keep_pose_q = nullptr;   // load while q_is_pose holds: robots left alone get q_pose := q ...
+	double* keep_pose_dst = nullptr;	   // ... here
+};
+int launch_snapshot(const SnapArgs& args, bool save, hipStream_t stream);
+
 }  // namespace sai2b
