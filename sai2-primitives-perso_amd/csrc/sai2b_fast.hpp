@@ -5,8 +5,10 @@
 // non-singular" (SingularityHandler.cpp:100-141). In that
 // branch the reference's result does not depend on the singular vectors at all:
 //     tau_mft = J^T ( (J Mb^-1 J^T)^-1 F_unit + F_force )            (U_ns cancels, :307-309)
-//     N       = I - M^-1 J^T (J M^-1 J^T)^-1 J  =  L^-T (w w^T) L^T   with M = L L^T, w ⟂ range(L^-1 J^T)
-// so with a = L^-T w, b = L w the nullspace projector is the rank-one matrix a b^T, and the whole
+//     N       = I - M^-1 J^T (J M^-1 J^T)^-1 J  =  nv (M nv)^T / (nv^T M nv)   for any nv in null(J)
+// (N projects onto null(J), one-dimensional for 7 joints, along range(M^-1 J^T): N = nv c^T with c^T nv = 1 and
+// M^-1 c in null(J), so c = M nv / (nv^T M nv)). With a = nv / sqrt(nv^T M nv), b = M a the nullspace projector is the
+// rank-one matrix a b^T, a^T M a = 1, and the whole
 // second-level JointTask (JointTask.cpp:218-356) collapses to a handful of dot products:
 //     Jp = N,  range(Jp) = span(a),  R M_partial R^T = a a^T / |a|^4,
 //     R (R^T Jp Mb^-1 Jp^T R)^-1 R^T = a a^T / (beta |a|^4),   beta = b^T Mb^-1 b.
@@ -91,6 +93,12 @@ DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEa
 // Scheduling fence between phases (and a marker in the ISA for per-phase inspection): the kernel is
 // one huge basic block, and without fences the scheduler interleaves phases and inflates the live set.
 #define SAI2B_PHASE() do { __builtin_amdgcn_sched_barrier(0); asm volatile("; SAI2B_PHASE_MARK"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SAI2B_CHAIN_PHASE() SAI2B_PHASE()
+#endif
+}  // namespace sai2b
+#include "sai2b_chain.h"
+namespace sai2b {
 
 // ---- Input staging of tick_fast_kernel (used by FAST = 2; FAST = 1 keeps its loads in registers). Every per-robot
 // row the fast tick reads before its Cholesky part, besides q, goes global -> LDS by DMA (global_load_lds) at kernel
@@ -104,7 +112,7 @@ DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEa
 // 37 632 bytes for FAST = 2. The force-space rows (MotionForceTask goals 24-29, sensed, state 6-11) are not staged: they
 // stay plain loads after the barrier (StagedRows). Nor are the JointTask's law_goals (3N) and state (N): its law is only
 // ever needed as two dot products with the nullspace vector a, so it is evaluated behind a, from plain loads issued
-// before the Gram / Cholesky / nullspace work that hides them (JtLate). That is what makes room for M and g within
+// ahead of the whole factor chain, which hides them (JtLate). That is what makes room for M and g within
 // 40 KiB (4 workgroups per CU).
 // PAY: the payload form of the kernel. Its CRBA needs the robot's payload, which arrives by the DMA, so its model phase
 // stays behind the barrier and nothing is parked: the image is dq | JointTask law_goals and state (FAST == 2) |
@@ -194,7 +202,8 @@ struct LdsSym {
 // Where fast_tick gets the second-level JointTask law from. JtGiven: evaluated by the caller (fast_jt_early).
 struct JtGiven {
 	const JtEarly& e;
-	DI void prefetch(const real*) {}
+	DI void prefetch() {}
+	DI void prefetch_q() {}
 	DI void project(const real* a, real& af, real& aacc) {
 		UNROLL for (int i = 0; i < N; i++) {
 			af = fma(a[i], e.f[i], af);
@@ -202,23 +211,28 @@ struct JtGiven {
 		}
 	}
 };
-// JtLate: nothing of the law exists until the nullspace vector does. prefetch() issues the plain loads of its 4N rows
-// and of q; project() evaluates the same fast_jt_early from them (dq from the image), stores the advanced integrators
-// (the caller is past worklist_append: this lane is committed to the fast path) and forms the two dot products.
+// JtLate: nothing of the law exists until the nullspace vector does. prefetch() issues the plain loads of its 4N rows,
+// ahead of the chain; prefetch_q() those of q (an L2 hit: the wavefront loaded these rows at entry), behind the QR, so
+// that q is not live across it; project() evaluates the same fast_jt_early from them (dq from the image), stores the
+// advanced integrators (the caller is past worklist_append: this lane is committed to the fast path) and forms the two
+// dot products.
 struct JtLate {
 	const DevTask& t1;
 	int B, b;
 	const real* dq;	 // image row of dq[0], at this lane's column
+	const real* qrows;
 	real lg[3 * N], s[N], q[N];
 	struct Rows {
 		const real *lg, *s;
 		DI real law_goal(int k) const { return lg[k]; }
 		DI real state(int k) const { return s[k]; }
 	};
-	DI void prefetch(const real* qrows) {
-		UNROLL for (int i = 0; i < N; i++) q[i] = ld(qrows, i, B, b);
+	DI void prefetch() {
 		UNROLL for (int k = 0; k < 3 * N; k++) lg[k] = ld(t1.law_goals, k, B, b);
 		UNROLL for (int i = 0; i < N; i++) s[i] = ld(t1.state, i, B, b);
+	}
+	DI void prefetch_q() {
+		UNROLL for (int i = 0; i < N; i++) q[i] = ld(qrows, i, B, b);
 	}
 	DI void project(const real* a, real& af, real& aacc) {
 		// Nothing in the law depends on a, and arithmetic without a dependency is free to move up to the loads, taking
@@ -236,24 +250,17 @@ struct JtLate {
 	}
 };
 
-// The Cholesky part of the fast tick. J and M are the Jacobian and mass matrix at rc.q (M an array or LdsSym: it is
-// read twice, for the bounded-inertia factor and for its own), Fu/Ff the task forces of the MotionForceTask law, jt
-// the JointTask law (JtGiven or JtLate); HAS_JT selects the 2-level form. Ordered to
-// keep few matrices alive at once: bounded-inertia side -> Y = L^-1 J^T -> nullspace vectors -> torques.
-template <bool HAS_JT, class Mat, class JT>
-DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* Fu, const real* Ff, int B, int b,
-				  bool with_comp, JT& jt, real* tau) {
+// The Cholesky part of the one-level fast tick, [full MotionForceTask]. J and M are the Jacobian and mass matrix at
+// rc.q, Fu/Ff the task forces of the MotionForceTask law. No nullspace is needed, so the operational-space matrix is
+// factored as a Gram matrix: bounded-inertia side -> Y = L^-1 J^T -> (Lambda for FULL decoupling) -> torques.
+template <class Mat>
+DI void fast_tick_mft(const DevParams& P, const real* J, const Mat& M, const real* Fu, const real* Ff, real* tau) {
 	const DevTask& t0 = P.task[0];
 
-	// bounded inertia estimate shared by the tasks that ask for it (host checks thresholds agree)
 	const bool mft_bie = t0.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES;
 	const bool mft_full = t0.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING;
-	bool any_bie = mft_bie;
-	real thr = t0.bie_threshold;
-	if (HAS_JT && P.task[1].decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES) {
-		any_bie = true;
-		thr = P.task[1].bie_threshold;
-	}
+	const bool any_bie = mft_bie;
+	const real thr = t0.bie_threshold;
 	// Phase A: bounded-inertia side (LB, YB = LB^-1 J^T, AB = YB^T YB, z = AB^-1 F_unit); YB dies here
 	real LB[N * N], dB[N], z[6];
 	UNROLL for (int i = 0; i < 6; i++) z[i] = Fu[i];
@@ -292,13 +299,8 @@ DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* F
 		UNROLL for (int i = 0; i < N; i++) Y[i * 6 + c] = col[i];
 	}
 	SAI2B_PHASE();
-	if constexpr (HAS_JT) {
-		jt.prefetch(P.q);
-		SAI2B_PHASE();
-	}
-	// ---- A = J M^-1 J^T = Y^T Y and its factor: Lambda for FULL decoupling, nullspace for the JT
-	real a[N], bb[N], na2 = 0;
-	if (HAS_JT || mft_full) {
+	// ---- A = J M^-1 J^T = Y^T Y and its factor: Lambda for FULL decoupling
+	if (mft_full) {
 		real A[36], LA[36], dA[6];
 		UNROLL for (int i = 0; i < 6; i++) UNROLL for (int j = 0; j <= i; j++) {
 			real s = 0;
@@ -307,63 +309,8 @@ DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* F
 			A[j * 6 + i] = s;
 		}
 		chol<6>(A, LA, dA);
-		if (mft_full) {	 // Lambda_mod = Lambda = A^-1
-			solve_lower<6>(LA, dA, z);
-			solve_lower_t<6>(LA, dA, z);
-		}
-		if (HAS_JT) {
-			// w = unit vector orthogonal to range(Y): the row k of the complementary projector
-			// I - Y A^-1 Y^T with the largest diagonal, normalised
-			real tk[6], best = -1;
-			int ks = 0;
-			UNROLL for (int c = 0; c < 6; c++) tk[c] = 0;
-			UNROLL for (int i = 0; i < N; i++) {
-				real t[6];
-				UNROLL for (int c = 0; c < 6; c++) t[c] = Y[i * 6 + c];
-				solve_lower<6>(LA, dA, t);
-				real pd = 1.0;
-				UNROLL for (int c = 0; c < 6; c++) pd = fma(-t[c], t[c], pd);
-				const bool take = pd > best;
-				best = take ? pd : best;
-				ks = take ? i : ks;
-				UNROLL for (int c = 0; c < 6; c++) tk[c] = take ? t[c] : tk[c];
-			}
-			solve_lower_t<6>(LA, dA, tk);  // A^-1 y_k
-			real w[N];
-			const real wn = rsqrt(best);
-			UNROLL for (int i = 0; i < N; i++) {
-				real s = (ks == i) ? 1.0 : 0.0;
-				UNROLL for (int c = 0; c < 6; c++) s = fma(-Y[i * 6 + c], tk[c], s);
-				w[i] = s * wn;
-			}
-			{  // one re-orthogonalisation pass: w <- w - Y A^-1 Y^T w, renormalise
-				real cw[6];
-				UNROLL for (int c = 0; c < 6; c++) {
-					real s = 0;
-					UNROLL for (int i = 0; i < N; i++) s = fma(Y[i * 6 + c], w[i], s);
-					cw[c] = s;
-				}
-				solve_lower<6>(LA, dA, cw);
-				solve_lower_t<6>(LA, dA, cw);
-				real nn = 0;
-				UNROLL for (int i = 0; i < N; i++) {
-					real s = w[i];
-					UNROLL for (int c = 0; c < 6; c++) s = fma(-Y[i * 6 + c], cw[c], s);
-					w[i] = s;
-					nn = fma(s, s, nn);
-				}
-				const real rn = rsqrt(nn);
-				UNROLL for (int i = 0; i < N; i++) w[i] *= rn;
-			}
-			UNROLL for (int i = 0; i < N; i++) a[i] = w[i];
-			solve_lower_t<N>(L, dL, a);	 // a = L^-T w
-			UNROLL for (int i = 0; i < N; i++) {
-				real s = 0;
-				UNROLL for (int k = 0; k <= i; k++) s = fma(L[i * N + k], w[k], s);
-				bb[i] = s;	// b = L w
-			}
-			UNROLL for (int i = 0; i < N; i++) na2 = fma(a[i], a[i], na2);
-		}
+		solve_lower<6>(LA, dA, z);	// Lambda_mod = Lambda = A^-1
+		solve_lower_t<6>(LA, dA, z);
 	}
 	SAI2B_PHASE();
 	// ---- MotionForceTask torques J^T (Lambda_mod F_unit + F_force) = L (Y z)   (SingularityHandler.cpp:307-309)
@@ -375,33 +322,29 @@ DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* F
 		UNROLL for (int k = 0; k <= i; k++) s = fma(L[i * N + k], yz[k], s);
 		tau_mft[i] = s;
 	}
+	// (the copy stays: with it the one-level kernels compile to the instructions they had, profiles/one_chain_isa.txt)
 	UNROLL for (int i = 0; i < N; i++) tau[i] = tau_mft[i];
-	if (!HAS_JT) return;
+}
 
-	// ---- JointTask: its law enters only as a . f and a . ddq
-	const DevTask& t1 = P.task[1];
-	real af = 0, aacc = 0;
-	jt.project(a, af, aacc);
-	if (with_comp) {  // JointTask.cpp:285-292: - Jp^T R M_partial R^T S M^-1 tau_prec;  M^-1 tau_mft = L^-T (Y z)
-		real u[N];
-		UNROLL for (int i = 0; i < N; i++) u[i] = yz[i];
-		solve_lower_t<N>(L, dL, u);
-		UNROLL for (int i = 0; i < N; i++) aacc = fma(-a[i], u[i], aacc);
-	}
-	real coef = aacc / na2;	 // a^T (a a^T / |a|^4) v = (a.v) / |a|^2
-	if (t1.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING) {
-		coef += af / na2;
-	} else if (t1.decoupling == SAI2B_IMPEDANCE) {
-		coef += af;	 // a^T (a a^T / |a|^2) f
+// The two-level fast tick, [full MotionForceTask, full JointTask]: chain::tick2 (sai2b_chain.h) on this lane's J and M
+// (M an array or LdsSym: it is read for the chain's factor, for M nv, and for the other factor where one is needed).
+// One whitened chain Lx, Yx = Lx^-1 J^T on Mb (bounded-inertia MotionForceTask) or on M; Householder QR of Yx gives
+// the factor R of J Mx^-1 J^T for the MotionForceTask solves and the nullspace direction w = Q e_6 in one pass; the
+// projector is N = a bb^T with a, bb from nv = Lx^-T w and M nv. jt is the JointTask law (JtGiven or JtLate): its loads
+// are issued ahead of the whole chain, which is what hides them.
+template <bool HAS_JT, class Mat, class JT>
+DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* Fu, const real* Ff, int B, int b,
+				  bool with_comp, JT& jt, real* tau) {
+	if constexpr (!HAS_JT) {
+		fast_tick_mft(P, J, M, Fu, Ff, tau);
 	} else {
-		real y[N];
-		UNROLL for (int i = 0; i < N; i++) y[i] = bb[i];
-		solve_lower<N>(LB, dB, y);
-		real beta = 0;
-		UNROLL for (int i = 0; i < N; i++) beta = fma(y[i], y[i], beta);
-		coef += af / (beta * na2);
+		const DevTask &t0 = P.task[0], &t1 = P.task[1];
+		// one bounded inertia estimate for the tasks that ask for it (host checks thresholds agree)
+		const bool jt_bie = t1.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES;
+		chain::tick2<N>(J, M, Fu, Ff, t0.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES,
+						t0.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING, t1.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING,
+						t1.decoupling == SAI2B_IMPEDANCE, jt_bie ? t1.bie_threshold : t0.bie_threshold, with_comp, jt, tau);
 	}
-	UNROLL for (int i = 0; i < N; i++) tau[i] = fma(bb[i], coef, tau[i]);  // Jp^T x = b (a^T x)
 }
 
 }  // namespace sai2b

@@ -218,7 +218,7 @@ DI bool tick_fast_body(const DevParams* __restrict__ Pp, int with_comp, int* __r
 		SAI2B_PHASE();
 		// the JointTask law and its integrator store are fast_tick's, behind the nullspace vector (JtLate)
 		const real* park = col + S::IMAGE;
-		JtLate jt{P.task[1], B, b, col + S::DQ * 64};
+		JtLate jt{P.task[1], B, b, col + S::DQ * 64, P.q};
 		fast_tick<FAST == 2>(P, J, LdsSym{park}, Fu, Ff, B, b, with_comp != 0, jt, tau);
 		UNROLL for (int i = 0; i < N; i++) st(P.tau, i, B, b, tau[i] + park[(S::MROWS + i) * 64]);
 	} else {
