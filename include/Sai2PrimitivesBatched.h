@@ -1739,6 +1739,38 @@ public:
 		return n;
 	}
 
+	// Actuator and force-sensor models (sai2b.h "actuator and force-sensor models"): per robot the signal path between controller
+	// and plant. actuator_rows [1 + 3 dof][B] = delay in periods, then dof rows each of lag coefficient, gain and noise deviation
+	// (empty: ideal); sensor_rows [13][B] = bias 6, noise deviation 6, filter coefficient (empty: ideal); max_delay: depth of the
+	// torque history (0..SAI2B_MAX_ACTUATION_DELAY); sensor: the MotionForceTask whose sensed rows become the measured wrench
+	// (nullptr: none); first_robot: the global index of this simulation's robot 0 when the batch is a shard. Takes effect at the
+	// next integrate() and restarts every robot's period and episode counters. std::invalid_argument on rows of another shape
+	// and on what sai2b_set_hardware rejects (its message).
+	void setHardware(const Batch& actuator_rows, const Batch& sensor_rows, const int max_delay = 0, const MotionForceTask* sensor = nullptr,
+					 const unsigned long long seed = 0, const unsigned first_robot = 0) {
+		const size_t B = (size_t)sai2b_batch(_c), n = (size_t)_dof;  // the shapes are all the C ABI cannot see; it judges the rest
+		if ((!actuator_rows.empty() && actuator_rows.size() != (1 + 3 * n) * B) || (!sensor_rows.empty() && sensor_rows.size() != 13 * B))
+			throw std::invalid_argument("setHardware: actuator_rows must be [1 + 3 dof][B], sensor_rows [13][B]");
+		if (sensor && sensor->context() != _c) throw std::invalid_argument("setHardware: the sensor task does not belong to this simulation's controller");
+		sai2b_hardware_config cfg;
+		detail::check(nullptr, sai2b_default_hardware(&cfg));
+		cfg.max_delay = max_delay, cfg.sensor_task = sensor ? sensor->index() : -1, cfg.seed = seed, cfg.first_robot = first_robot;
+		detail::check(_c, sai2b_set_hardware(_c, &cfg, actuator_rows.empty() ? nullptr : actuator_rows.data(),
+											 sensor_rows.empty() ? nullptr : sensor_rows.data(), 0));
+	}
+	void clearHardware() { detail::check(_c, sai2b_clear_hardware(_c)); }
+	struct HardwareState {
+		Batch applied_torque;			  // [dof][B]: what the plant received in the last integrate()
+		std::vector<int> period, episode;  // [B] each
+	};
+	HardwareState getHardwareState() const {
+		const size_t B = (size_t)sai2b_batch(_c);
+		HardwareState s;
+		s.applied_torque.resize((size_t)_dof * B), s.period.resize(B), s.episode.resize(B);
+		detail::check(_c, sai2b_get_hardware_state(_c, s.applied_torque.data(), s.period.data(), s.episode.data()));
+		return s;
+	}
+
 	// Joint dynamics of the plant (sai2b.h "joint dynamics of the simulated plant"): per robot and joint, [dof][B] each, empty =
 	// that effect off: armature (>= 0), viscous damping (>= 0), Coulomb friction level (>= 0), torque limit (> 0, +inf: none),
 	// lower and upper joint limit (q_lower < q_upper, -inf / +inf: none). Batch-uniform per joint, one value for all joints or

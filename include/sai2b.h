@@ -403,7 +403,14 @@ enum sai2b_buffer {
 	 * (and after it is cleared). A device-resident producer may rewrite the rows between steps, ordered with sai2b_stream();
 	 * the next sai2b_sim_step reads them. Such rows are not inspected. */
 	SAI2B_BUF_EXTERNAL_WRENCH = 13,
-	SAI2B_BUF_EXTERNAL_WRENCH_STATE = 14
+	SAI2B_BUF_EXTERNAL_WRENCH_STATE = 14,
+	/* the actuator rows [1 + 3 dof][B] and the sensor rows [13][B] of sai2b_set_hardware, and the torques the plant received in
+	 * the last sai2b_sim_step, [dof][B]. NULL until hardware has been set (and after it is cleared). A device-resident producer
+	 * may rewrite the two row buffers between steps, ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows
+	 * are not inspected. */
+	SAI2B_BUF_HARDWARE_ACTUATOR = 15,
+	SAI2B_BUF_HARDWARE_SENSOR = 16,
+	SAI2B_BUF_TAU_APPLIED = 17
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -615,6 +622,83 @@ int sai2b_get_external_wrench(sai2b_ctx* ctx, sai2b_external_wrench_config* cfg,
  * entry with some non-zero component of F or M (counted on the device). Zeros before the first step with an external wrench
  * and after a clear. */
 int sai2b_get_external_wrench_state(sai2b_ctx* ctx, double* wrench_world, double* torque, int* robots_pushed);
+
+/* ------------------------------------------------------------------ actuator and force-sensor models ("hardware")
+ * The signal path between controller and plant, different for every robot: the commanded torque reaches the joints late,
+ * through a current loop of finite bandwidth, with a gain error and ripple; the wrist sensor has a bias, noise and an
+ * anti-aliasing filter. Both act once per call of sai2b_sim_step (one call is one control period) as stages of their own
+ * around the simulation kernel; a context that never sets hardware, or has cleared it, launches what it would without it.
+ * Batch-uniform (sai2b_hardware_config): the depth D of the torque history, the MotionForceTask whose sensed rows the sensor
+ * model rewrites (-1: none), the random generator's seed and the global index of this context's robot 0. Per robot, doubles,
+ * rows [row][B]:
+ *   actuator_rows [1 + 3 dof][B]: row 0 the delay d in periods, then dof rows each of the lag coefficient alpha_i, the gain
+ *       k_i and the noise standard deviation sigma_i (N m). NULL: ideal (d 0, alpha 1, k 1, sigma 0).
+ *   sensor_rows [13][B]: rows 0-5 the bias beta (force 3, moment 3, sensor frame), rows 6-11 the noise standard deviation s
+ *       per component, row 12 the filter coefficient alpha_s. NULL: ideal (beta 0, s 0, alpha_s 1).
+ * State per robot: a period counter n and an episode index e, the history of commanded torques [(D + 1)][dof], the lag state
+ * f [dof], the sensor filter state g [6]. With n, e as they are on entry, c the commanded torque (the tau argument of
+ * sai2b_sim_step, or the stored torques when that is NULL):
+ *   ACTUATION, ahead of the simulation kernel, for joint i:
+ *     hist[n mod (D + 1)][i] = c_i
+ *     u_i = hist[max(n - d, 0) mod (D + 1)][i]       the command of d periods ago; the first command until d have passed
+ *     f_i = (n == 0 || alpha_i == 1) ? u_i : f_i + alpha_i (u_i - f_i)
+ *     a_i = k_i f_i + sigma_i z_i
+ *   a is stored in SAI2B_BUF_TAU_APPLIED and is what the simulation kernel receives as its tau: the torque limit of the joint
+ *   dynamics saturates a, and their status row "applied torque" reports the saturated a. SAI2B_BUF_TAU and SAI2B_OBS_TAU stay
+ *   the command. The delay is read as (int) fmin(fmax(row, 0), D), so a NaN in a device-written row gives 0. With the ideal
+ *   rows a is c bit for bit.
+ *   SENSOR, behind the simulation kernel, only in a call in which that kernel wrote the ideal reading into sensor_task's
+ *   SAI2B_BUF_SENSED rows (the contact's or the external wrench's sensor_task equals this one); otherwise the stage is not
+ *   launched and the rows are left alone, so a reading set by hand is never compounded. With r the six rows as left:
+ *     y_k = (r_k + beta_k) + s_k z'_k
+ *     g_k = (n == 0 || alpha_s == 1) ? y_k : g_k + alpha_s (y_k - g_k)
+ *     sensed row k = g_k
+ *   The tick's force law, SAI2B_OBS_SENSED and SAI2B_DONE_FORCE therefore see the measured wrench.
+ *   After the call n = n + 1; both stages of a call use the same n.
+ * Random numbers: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (n, e, 256 stream + call, first_robot + b),
+ * stream 0 the actuator, 1 the sensor. The words x0..x3 of call j give four unit normals by Box-Muller on u = (x + 0.5) 2^-32:
+ * (x0, x1) -> z_4j = r cos(2 pi u1), z_4j+1 = r sin(2 pi u1) with r = sqrt(-2 ln u0); (x2, x3) -> z_4j+2, z_4j+3 likewise.
+ * Joint i takes z_i, sensor component k takes z'_k. |z| <= 6.77. A robot whose deviation is 0 gets a = k f exactly.
+ * The noise of a robot depends on the seed, its global index, its episode and its period alone: a batch run as shards with
+ * first_robot set to each shard's first global index is bit-equal to the one-context run.
+ * sai2b_reset_robots: a selected robot gets n = 0, e += 1; at n = 0 the law re-initialises the history, f and g, and no older
+ * entry is read again. The per-robot rows are kept (environment). sai2b_reinitialize and sai2b_reinitialize_robots do not
+ * touch the hardware state. Snapshot banks: SAI2B_SNAP_EPISODE holds the history, f, g, the applied torque and the two
+ * counters, SAI2B_SNAP_ENVIRONMENT the two row buffers. The seed and first_robot are configuration, not state: they are neither
+ * stored in a bank nor part of its fingerprint, so a bank loaded into a context set up with another seed or first_robot
+ * continues with that context's noise. n and e are 32-bit ints: a robot that is never reset must not run past 2^31 - 1
+ * periods (24 days at 1 kHz); beyond that the history slot and the counter word are undefined. This law is this library's
+ * definition. */
+#define SAI2B_MAX_ACTUATION_DELAY 8
+typedef struct sai2b_hardware_config {
+	int max_delay;		  /* D: depth of the torque history in periods, 0..SAI2B_MAX_ACTUATION_DELAY */
+	int sensor_task;	  /* MotionForceTask whose sensed rows the sensor model rewrites, or -1 */
+	unsigned first_robot; /* global index of robot 0 of this context (0 unless the batch is a shard) */
+	int reserved;
+	unsigned long long seed;
+} sai2b_hardware_config;
+/* host only: D 0, no sensor, first_robot 0, seed 0 */
+int sai2b_default_hardware(sai2b_hardware_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (max_delay outside [0, SAI2B_MAX_ACTUATION_DELAY],
+ * sensor_task neither -1 nor a MotionForceTask of `tasks`) */
+int sai2b_validate_hardware(const sai2b_hardware_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+							int msg_len);
+/* sizeof(sai2b_hardware_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_hardware_config(void);
+/* Host arrays are validated (SAI2B_INVALID_ARGUMENT with the reason: what sai2b_validate_hardware rejects; d not an integer in
+ * [0, D]; alpha, alpha_s outside (0, 1]; k, sigma, s negative or not finite; beta not finite); DEVICE arrays (on_device != 0)
+ * are copied under the stream contract and NOT inspected. Zeroes n and e of every robot. Ordered on the ctx stream; takes
+ * effect at the next sai2b_sim_step. A call that fails on its arguments leaves the context as it was; one that fails while
+ * copying (SAI2B_RUNTIME_ERROR) leaves the context without hardware. */
+int sai2b_set_hardware(sai2b_ctx* ctx, const sai2b_hardware_config* cfg, const double* actuator_rows, const double* sensor_rows,
+					   int on_device);
+/* back to the ideal signal path (the three buffer ids give NULL, no stage is launched) */
+int sai2b_clear_hardware(sai2b_ctx* ctx);
+/* the configuration and the rows to the host (any may be NULL); the default configuration and the ideal rows without hardware */
+int sai2b_get_hardware(sai2b_ctx* ctx, sai2b_hardware_config* cfg, double* actuator_rows, double* sensor_rows);
+/* host arrays, any NULL: applied_torque [dof][B] of the last sai2b_sim_step, period [B] = n, episode [B] = e. Zeros without
+ * hardware. */
+int sai2b_get_hardware_state(sai2b_ctx* ctx, double* applied_torque, int* period, int* episode);
 
 /* ------------------------------------------------------------------ observations and episode-end flags
  * The missing link of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe(out, done), sai2b_reset_robots(done, ..):

@@ -31,6 +31,11 @@ BUF_JOINT_DYNAMICS_STATE = 12  # [3][dof][B]: applied, stop and dissipative torq
 JOINT_DYNAMICS_ROWS = ("armature", "damping", "friction", "torque_limit", "q_lower", "q_upper")
 BUF_EXTERNAL_WRENCH = 13  # [7][B] external-wrench rows of the plant: force 3, moment 3, remaining periods (sai2b_set_external_wrench)
 BUF_EXTERNAL_WRENCH_STATE = 14  # [6 + dof][B]: F_w, M_w and the joint torques tx of the last sim step
+BUF_HARDWARE_ACTUATOR = 15  # [1 + 3 dof][B] actuator rows: delay, lag coefficient, gain, noise deviation (sai2b_set_hardware)
+BUF_HARDWARE_SENSOR = 16  # [13][B] sensor rows: bias 6, noise deviation 6, filter coefficient
+BUF_TAU_APPLIED = 17  # [dof][B]: the torques the plant received in the last sim step
+MAX_ACTUATION_DELAY = 8  # SAI2B_MAX_ACTUATION_DELAY
+HARDWARE_SENSOR_ROWS = 13
 WRENCH_WORLD, WRENCH_LINK = 0, 1  # enum sai2b_wrench_frame
 WRENCH_FRAMES = {"world": WRENCH_WORLD, "link": WRENCH_LINK}
 PAYLOAD_CONTROLLER, PAYLOAD_PLANT, PAYLOAD_BOTH = 1, 2, 3  # enum sai2b_payload_target
@@ -252,6 +257,18 @@ class ExternalWrenchConfig(C.Structure):
     ]
 
 
+class HardwareConfig(C.Structure):
+    """sai2b_hardware_config; load_library() checks the size against sai2b_sizeof_hardware_config()"""
+
+    _fields_ = [
+        ("max_delay", _i),
+        ("sensor_task", _i),
+        ("first_robot", C.c_uint),
+        ("reserved", _i),
+        ("seed", C.c_ulonglong),
+    ]
+
+
 # enum sai2b_action_mode / sai2b_action_block (sai2b.h "actions"); name -> value, blocks in row order
 ACT_NONE, ACT_DELTA_GOAL, ACT_DELTA_CURRENT, ACT_ABSOLUTE = 0, 1, 2, 3
 ACT_POSITION, ACT_ORIENTATION, ACT_FORCE, ACT_MOMENT = 1, 2, 4, 8
@@ -386,6 +403,13 @@ EXPORTS = [
     "sai2b_clear_external_wrench",
     "sai2b_get_external_wrench",
     "sai2b_get_external_wrench_state",
+    "sai2b_default_hardware",
+    "sai2b_validate_hardware",
+    "sai2b_sizeof_hardware_config",
+    "sai2b_set_hardware",
+    "sai2b_clear_hardware",
+    "sai2b_get_hardware",
+    "sai2b_get_hardware_state",
     "sai2b_default_action",
     "sai2b_validate_action",
     "sai2b_sizeof_action_config",
@@ -413,7 +437,8 @@ SNAPSHOT_HEADER_BYTES = 256
 SNAP_COUNTS = ("moved", "out_of_range", "never_saved")
 SNAP_BLOCKS = ("q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i",
                "popc_q", "N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status", "payload",
-               "plant_payload", "contact", "joint_dynamics", "external_wrench")
+               "plant_payload", "contact", "joint_dynamics", "external_wrench", "hw_history", "hw_filter", "hw_applied", "hw_clock",
+               "hw_actuator", "hw_sensor")
 
 _lib = None
 
@@ -573,5 +598,15 @@ def load_library():
     lib.sai2b_snapshot_export_size.restype = C.c_size_t
     lib.sai2b_snapshot_export.argtypes = [vp, vp, C.c_size_t]
     lib.sai2b_snapshot_import.argtypes = [vp, vp, C.c_size_t]
+    lib.sai2b_default_hardware.argtypes = [P(HardwareConfig)]
+    lib.sai2b_validate_hardware.argtypes = [P(HardwareConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_hardware_config.argtypes = []
+    lib.sai2b_set_hardware.argtypes = [vp, P(HardwareConfig), vp, vp, _i]
+    lib.sai2b_clear_hardware.argtypes = [vp]
+    lib.sai2b_get_hardware.argtypes = [vp, P(HardwareConfig), vp, vp]
+    lib.sai2b_get_hardware_state.argtypes = [vp, vp, vp, vp]
+    if lib.sai2b_sizeof_hardware_config() != C.sizeof(HardwareConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_hardware_config is {lib.sai2b_sizeof_hardware_config()} bytes in the library, "
+                           f"{C.sizeof(HardwareConfig)} in the ctypes mirror")
     _lib = lib
     return lib

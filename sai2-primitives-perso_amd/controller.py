@@ -472,6 +472,80 @@ class Controller:
         self._rc(self.lib.sai2b_get_external_wrench_state(self.h, None, None, C.byref(n)))
         return n.value
 
+    # -- actuator and force-sensor models (sai2b.h "actuator and force-sensor models")
+    def hardware_config(self, max_delay=0, sensor_task=-1, seed=0, first_robot=0):
+        """-> HardwareConfig, validated against this controller's tasks"""
+        cfg = _abi.HardwareConfig()
+        if self.lib.sai2b_default_hardware(C.byref(cfg)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        cfg.max_delay, cfg.sensor_task = int(max_delay), int(sensor_task)
+        cfg.seed, cfg.first_robot = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_robot) & 0xFFFFFFFF
+        msg = C.create_string_buffer(256)
+        tasks = (_abi.TaskConfig * len(self.tasks))(*self.tasks)
+        if self.lib.sai2b_validate_hardware(C.byref(cfg), tasks, len(self.tasks), self.dof, msg, 256):
+            raise ValueError(msg.value.decode())
+        return cfg
+
+    def hardware_rows(self, delay=0, lag=1.0, gain=1.0, noise=0.0, bias=0.0, sensor_noise=0.0, sensor_filter=1.0):
+        """-> (actuator_rows [1 + 3 dof][B], sensor_rows [13][B]) as numpy arrays: delay [B] in periods; lag, gain and noise
+        [dof][B] (the lag coefficient alpha, the gain k, the noise deviation sigma); bias and sensor_noise [6][B];
+        sensor_filter [B]. A scalar, or a [dof] / [6] column, is the same for every robot. The defaults are the ideal path."""
+        n, B = self.dof, self.B
+
+        def block(a, rows, name):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 1 and a.shape[0] == rows and rows != B:
+                a = a[:, None]
+            try:
+                return np.broadcast_to(a, (rows, B))
+            except ValueError:
+                raise ValueError(f"{name}: expected a scalar, {rows} values or an array of shape ({rows}, {B})") from None
+
+        act = np.empty((1 + 3 * n, B))
+        act[0] = np.broadcast_to(np.asarray(delay, dtype=np.float64), (B,))
+        act[1 : 1 + n], act[1 + n : 1 + 2 * n], act[1 + 2 * n :] = block(lag, n, "lag"), block(gain, n, "gain"), block(noise, n, "noise")
+        sen = np.empty((_abi.HARDWARE_SENSOR_ROWS, B))
+        sen[0:6], sen[6:12] = block(bias, 6, "bias"), block(sensor_noise, 6, "sensor_noise")
+        sen[12] = np.broadcast_to(np.asarray(sensor_filter, dtype=np.float64), (B,))
+        return act, sen
+
+    def set_hardware(self, actuator_rows=None, sensor_rows=None, max_delay=0, sensor_task=-1, seed=0, first_robot=0, config=None):
+        """the signal path of every robot for sim_step: actuator_rows [1 + 3 dof][B] (delay, lag coefficient, gain, noise
+        deviation) and sensor_rows [13][B] (bias 6, noise deviation 6, filter coefficient), numpy or torch CUDA, None = ideal
+        (hardware_rows() builds them); max_delay: depth D of the torque history; sensor_task: the MotionForceTask whose sensed
+        rows become the measured wrench (-1: none); seed, first_robot: the random generator's key and the global index of this
+        controller's robot 0. A HardwareConfig as `config` carries max_delay, sensor_task, seed and first_robot. Restarts every
+        robot's period and episode counters."""
+        cfg = config if config is not None else self.hardware_config(max_delay, sensor_task, seed, first_robot)
+        rows = (1 + 3 * self.dof, _abi.HARDWARE_SENSOR_ROWS)
+        objs = []
+        for a, r, name in zip((actuator_rows, sensor_rows), rows, ("actuator_rows", "sensor_rows")):
+            if a is not None and not hasattr(a, "data_ptr"):
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (r, self.B):
+                    raise ValueError(f"{name}: expected an array of shape ({r}, {self.B})")
+            objs.append(a)
+        ins = [self._in(o, r) for o, r in zip(objs, rows)]
+        self._rc(self.lib.sai2b_set_hardware(self.h, C.byref(cfg), ins[0][0], ins[1][0], self._dev(*objs)))
+
+    def clear_hardware(self):
+        self._rc(self.lib.sai2b_clear_hardware(self.h))
+
+    def get_hardware(self):
+        """-> (HardwareConfig, actuator_rows [1 + 3 dof][B], sensor_rows [13][B]); the default configuration and the ideal rows
+        when no hardware is set"""
+        cfg = _abi.HardwareConfig()
+        act, sen = np.empty((1 + 3 * self.dof, self.B)), np.empty((_abi.HARDWARE_SENSOR_ROWS, self.B))
+        self._rc(self.lib.sai2b_get_hardware(self.h, C.byref(cfg), C.c_void_p(act.ctypes.data), C.c_void_p(sen.ctypes.data)))
+        return cfg, act, sen
+
+    def get_hardware_state(self):
+        """what the last sim_step left: dict applied_torque [dof][B], period [B], episode [B] (int32)"""
+        a = np.empty((self.dof, self.B))
+        n, e = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        self._rc(self.lib.sai2b_get_hardware_state(self.h, C.c_void_p(a.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(e.ctypes.data)))
+        return dict(applied_torque=a, period=n, episode=e)
+
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod
     def _flags(names, table, what):
@@ -2068,6 +2142,16 @@ class BatchedSimulation:
 
     def robotsPushed(self):
         return self._c._ctrl.robots_pushed()
+
+    # -- actuator and force-sensor models (Controller.set_hardware)
+    def setHardware(self, *args, **kwargs):
+        self._c._ctrl.set_hardware(*args, **kwargs)
+
+    def clearHardware(self):
+        self._c._ctrl.clear_hardware()
+
+    def getHardwareState(self):
+        return self._c._ctrl.get_hardware_state()
 
     # -- contact of the plant (Controller.set_contact); the force sensor writes the sensed rows of one MotionForceTask
     def setContactPlanes(self, *args, **kwargs):

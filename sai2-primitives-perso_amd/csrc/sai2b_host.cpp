@@ -115,6 +115,14 @@ struct sai2b_ctx {
 	sai2b::WrenchParams wrench;
 	double *wrench_rows = nullptr, *wrench_status = nullptr;
 	int* wrench_count = nullptr;
+	// actuator and force-sensor models (sai2b_set_hardware), created on first use: the [1 + 3 dof][B] actuator rows, the [13][B]
+	// sensor rows, the torque history (room for the deepest, [SAI2B_MAX_ACTUATION_DELAY + 1][dof][B]; hw_cfg.max_delay + 1 slots
+	// are in use), the filter states f, g [dof + 6][B], the applied torques [dof][B] and the clocks (period, episode) [2][B].
+	// hw_on: sai2b_sim_step launches actuate_kernel ahead of the simulation kernel and, when due, sense_kernel behind it
+	bool hw_on = false;
+	sai2b_hardware_config hw_cfg = {};
+	double *hw_act = nullptr, *hw_sensor = nullptr, *hw_history = nullptr, *hw_filter = nullptr, *hw_applied = nullptr;
+	int* hw_clock = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -1112,6 +1120,12 @@ static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned
 	if (!ctx->q_is_pose && (task < 0 || ctx->T == 1)) flags |= sai2b::RESET_KEEP_POSE;
 	if (sai2b::launch_reset_subset(ctx->d_params, ctx->B, d_mask, d_q, d_dq, ctx->q, ctx->dq, ctx->q_pose, task, flags, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
+	// hardware: a reset robot starts a new episode at period 0 (a re-initialisation alone leaves its clocks as they are)
+	if (episode && ctx->hw_on) {
+		if (sai2b::launch_hardware_reset(ctx->B, d_mask, ctx->hw_clock, ctx->stream))
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": hardware reset launch failed");
+		ctx->launches++;
+	}
 	// batch-wide and conservative: a dirty flag makes the generator kernel compare goals, and an untouched robot's compare equal
 	ctx->goals_dirty = task < 0 ? ~0u : (ctx->goals_dirty | 1u << task);
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1545,6 +1559,9 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_JOINT_DYNAMICS_STATE: return ctx->joint_on ? (void*)ctx->joint_status : nullptr;
 		case SAI2B_BUF_EXTERNAL_WRENCH: return ctx->wrench_on ? (void*)ctx->wrench_rows : nullptr;
 		case SAI2B_BUF_EXTERNAL_WRENCH_STATE: return ctx->wrench_on ? (void*)ctx->wrench_status : nullptr;
+		case SAI2B_BUF_HARDWARE_ACTUATOR: return ctx->hw_on ? (void*)ctx->hw_act : nullptr;
+		case SAI2B_BUF_HARDWARE_SENSOR: return ctx->hw_on ? (void*)ctx->hw_sensor : nullptr;
+		case SAI2B_BUF_TAU_APPLIED: return ctx->hw_on ? (void*)ctx->hw_applied : nullptr;
 	}
 	return nullptr;
 }
@@ -2112,6 +2129,150 @@ extern "C" int sai2b_get_external_wrench_state(sai2b_ctx* ctx, double* wrench_wo
 	return SAI2B_OK;
 }
 
+// ---- actuator and force-sensor models ----
+static_assert(sai2b::HW_MAX_DELAY == SAI2B_MAX_ACTUATION_DELAY, "sai2b_launch.h and sai2b.h disagree about the deepest torque history");
+extern "C" int sai2b_default_hardware(sai2b_hardware_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_hardware: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->sensor_task = -1;
+	return SAI2B_OK;
+}
+static std::string hardware_config_error(const sai2b_hardware_config* c, const sai2b_task_config* tasks, int n_tasks) {
+	if (!c) return "hardware: null config";
+	if (c->max_delay < 0 || c->max_delay > SAI2B_MAX_ACTUATION_DELAY) return "hardware: max_delay must be in [0, SAI2B_MAX_ACTUATION_DELAY]";
+	if (c->sensor_task != -1 && (!tasks || c->sensor_task < 0 || c->sensor_task >= n_tasks || tasks[c->sensor_task].type != SAI2B_MOTION_FORCE_TASK))
+		return "hardware: sensor_task must be -1 or the index of a MotionForceTask";
+	return "";
+}
+// the per-robot rows given as host arrays (either may be NULL)
+static std::string hardware_rows_error(const sai2b_hardware_config* c, const double* act, const double* sen, size_t B) {
+	if (act) {
+		for (size_t b = 0; b < B; b++) {
+			const double d = act[b];
+			if (!(d >= 0 && d <= c->max_delay) || d != std::floor(d)) return "hardware: the delay must be an integer in [0, max_delay]";
+		}
+		for (size_t i = 0; i < (size_t)N * B; i++) {
+			const double alpha = act[B + i], k = act[(1 + (size_t)N) * B + i], sigma = act[(1 + 2 * (size_t)N) * B + i];
+			if (!(alpha > 0 && alpha <= 1)) return "hardware: the lag coefficient alpha must be in (0, 1]";
+			if (!std::isfinite(k) || k < 0) return "hardware: the gain k must be finite and not negative";
+			if (!std::isfinite(sigma) || sigma < 0) return "hardware: the actuator noise sigma must be finite and not negative";
+		}
+	}
+	if (sen) {
+		for (size_t i = 0; i < 6 * B; i++) {
+			if (!std::isfinite(sen[i])) return "hardware: the sensor bias must be finite";
+			if (!std::isfinite(sen[6 * B + i]) || sen[6 * B + i] < 0) return "hardware: the sensor noise s must be finite and not negative";
+		}
+		for (size_t b = 0; b < B; b++)
+			if (!(sen[12 * B + b] > 0 && sen[12 * B + b] <= 1)) return "hardware: the sensor filter coefficient alpha_s must be in (0, 1]";
+	}
+	return "";
+}
+extern "C" int sai2b_validate_hardware(const sai2b_hardware_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+									   int msg_len) {
+	const std::string err = robot_dof == N ? hardware_config_error(cfg, tasks, n_tasks) : "hardware: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_hardware_config(void) { return (int)sizeof(sai2b_hardware_config); }
+// the rows of the ideal signal path: d 0, alpha 1, k 1, sigma 0; beta 0, s 0, alpha_s 1
+static void hardware_ideal_rows(size_t B, std::vector<double>* act, std::vector<double>* sen) {
+	if (act) {
+		act->assign((size_t)sai2b::HW_ACT_ROWS * B, 0.0);
+		std::fill(act->begin() + B, act->begin() + (1 + 2 * (size_t)N) * B, 1.0);
+	}
+	if (sen) {
+		sen->assign((size_t)sai2b::HW_SENSOR_ROWS * B, 0.0);
+		std::fill(sen->begin() + 12 * B, sen->end(), 1.0);
+	}
+}
+extern "C" int sai2b_set_hardware(sai2b_ctx* ctx, const sai2b_hardware_config* cfg, const double* actuator_rows, const double* sensor_rows,
+								  int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_hardware: null ctx");
+	std::string err = hardware_config_error(cfg, ctx->cfg, ctx->T);
+	const size_t B = ctx->B;
+	if (err.empty() && !on_device) err = hardware_rows_error(cfg, actuator_rows, sensor_rows, B);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_hardware: " + err);
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// six buffers, each created once: a failed allocation leaves the others for the next call, and the context as it was
+	const size_t hist = (size_t)(SAI2B_MAX_ACTUATION_DELAY + 1) * N * B;
+	if (!ctx->hw_act && (rc = dev_alloc(ctx, &ctx->hw_act, (size_t)sai2b::HW_ACT_ROWS * B))) return rc;
+	if (!ctx->hw_sensor && (rc = dev_alloc(ctx, &ctx->hw_sensor, (size_t)sai2b::HW_SENSOR_ROWS * B))) return rc;
+	if (!ctx->hw_history && (rc = dev_alloc(ctx, &ctx->hw_history, hist))) return rc;
+	if (!ctx->hw_filter && (rc = dev_alloc(ctx, &ctx->hw_filter, (size_t)sai2b::HW_FILTER_ROWS * B))) return rc;
+	if (!ctx->hw_applied && (rc = dev_alloc(ctx, &ctx->hw_applied, (size_t)N * B))) return rc;
+	if (!ctx->hw_clock && (rc = dev_alloc(ctx, &ctx->hw_clock, 2 * B))) return rc;
+	// rows already in force are rewritten in place: the hardware is taken out of force first, so that a copy that fails leaves
+	// the context without hardware, never with rows that are half the old ones and half the new
+	ctx->hw_on = false;
+	// every robot starts at period 0 of episode 0; the law re-initialises the history and the filters there, zeros until then
+	HIP_TRY(ctx, hipMemsetAsync(ctx->hw_clock, 0, 2 * B * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->hw_history, 0, hist * sizeof(double), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->hw_filter, 0, (size_t)sai2b::HW_FILTER_ROWS * B * sizeof(double), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->hw_applied, 0, (size_t)N * B * sizeof(double), ctx->stream));
+	std::vector<double> ideal_act, ideal_sen;
+	hardware_ideal_rows(B, actuator_rows ? nullptr : &ideal_act, sensor_rows ? nullptr : &ideal_sen);
+	if ((rc = copy_rows(ctx, ctx->hw_act, actuator_rows ? actuator_rows : ideal_act.data(), sai2b::HW_ACT_ROWS, actuator_rows ? on_device : 0)))
+		return rc;
+	if ((rc = copy_rows(ctx, ctx->hw_sensor, sensor_rows ? sensor_rows : ideal_sen.data(), sai2b::HW_SENSOR_ROWS, sensor_rows ? on_device : 0)))
+		return rc;
+	// everything is written: only now does the hardware become the one in force (again)
+	ctx->hw_cfg = *cfg;
+	ctx->hw_cfg.reserved = 0;
+	ctx->hw_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_hardware(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_hardware: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	ctx->hw_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_hardware(sai2b_ctx* ctx, sai2b_hardware_config* cfg, double* actuator_rows, double* sensor_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_hardware: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) {
+		if (ctx->hw_on)
+			*cfg = ctx->hw_cfg;
+		else
+			sai2b_default_hardware(cfg);
+	}
+	if (!ctx->hw_on) {
+		std::vector<double> act, sen;
+		hardware_ideal_rows(ctx->B, actuator_rows ? &act : nullptr, sensor_rows ? &sen : nullptr);
+		if (actuator_rows) std::copy(act.begin(), act.end(), actuator_rows);
+		if (sensor_rows) std::copy(sen.begin(), sen.end(), sensor_rows);
+		return SAI2B_OK;
+	}
+	if (int rc = fetch_rows(ctx, ctx->hw_act, 0, sai2b::HW_ACT_ROWS, actuator_rows)) return rc;
+	return fetch_rows(ctx, ctx->hw_sensor, 0, sai2b::HW_SENSOR_ROWS, sensor_rows);
+}
+extern "C" int sai2b_get_hardware_state(sai2b_ctx* ctx, double* applied_torque, int* period, int* episode) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_hardware_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	if (!ctx->hw_on) {
+		if (applied_torque) std::fill(applied_torque, applied_torque + (size_t)N * B, 0.0);
+		if (period) std::fill(period, period + B, 0);
+		if (episode) std::fill(episode, episode + B, 0);
+		return SAI2B_OK;
+	}
+	if (int rc = fetch_rows(ctx, ctx->hw_applied, 0, N, applied_torque)) return rc;
+	if (period) HIP_TRY(ctx, hipMemcpyAsync(period, ctx->hw_clock, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (episode) HIP_TRY(ctx, hipMemcpyAsync(episode, ctx->hw_clock + B, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (period || episode) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+// what the two stages take from the context
+static sai2b::HwStream hardware_stream(const sai2b_ctx* ctx) {
+	sai2b::HwStream s;
+	s.key0 = (unsigned)(ctx->hw_cfg.seed & 0xffffffffull), s.key1 = (unsigned)(ctx->hw_cfg.seed >> 32), s.first_robot = ctx->hw_cfg.first_robot;
+	return s;
+}
+
 // ---- observations and episode-end flags ----
 namespace {
 constexpr int OBS_ALL_BLOCKS = SAI2B_OBS_Q | SAI2B_OBS_DQ | SAI2B_OBS_TAU | SAI2B_OBS_LIMIT_MARGIN | SAI2B_OBS_EPISODE_STEP | SAI2B_OBS_CONTACT;
@@ -2513,10 +2674,27 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	if (ctx->joint_on) HIP_TRY(ctx, hipMemsetAsync(ctx->joint_counts, 0, sai2b::JOINT_COUNTS * sizeof(int), ctx->stream));
 	// external wrench: the wrench forms of either kernel, the counter of robots pushed zeroed alike
 	if (ctx->wrench_on) HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_count, 0, sizeof(int), ctx->stream));
+	// hardware: actuate_kernel turns the command into the applied torques, which the simulation kernel receives as its tau
+	if (ctx->hw_on) {
+		sai2b::ActuateParams a;
+		a.rows = ctx->hw_act, a.command = t, a.history = ctx->hw_history, a.filter = ctx->hw_filter, a.applied = ctx->hw_applied;
+		a.clock = ctx->hw_clock, a.depth = ctx->hw_cfg.max_delay, a.rng = hardware_stream(ctx);
+		if (sai2b::launch_actuate(ctx->B, a, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "actuation launch failed");
+		ctx->launches++;
+		t = ctx->hw_applied;
+	}
 	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr,
 						  ctx->joint_on ? &ctx->joint : nullptr, ctx->wrench_on ? &ctx->wrench : nullptr, nullptr, q_keep, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
+	// hardware: sense_kernel, only when the simulation kernel has just written the ideal reading into the sensor's task
+	const int hw_task = ctx->hw_on ? ctx->hw_cfg.sensor_task : -1;
+	if (hw_task >= 0 && ((hp.contact && hp.contact_sensor_task == hw_task) || (ctx->wrench_on && ctx->wrench_cfg.sensor_task == hw_task))) {
+		sai2b::SenseParams s;
+		s.rows = ctx->hw_sensor, s.sensed = hp.task[hw_task].sensed, s.filter = ctx->hw_filter, s.clock = ctx->hw_clock, s.rng = hardware_stream(ctx);
+		if (sai2b::launch_sense(ctx->B, s, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "sensor launch failed");
+		ctx->launches++;
+	}
 	ctx->models_fresh = false;
 	for (int k = 0; k < ctx->T; k++) ctx->tio[k].model_fresh = false;
 	if (caller_tau) return caller_after_read(ctx);
@@ -2795,7 +2973,8 @@ extern "C" int sai2b_counters(const sai2b_ctx* ctx, long long* launches, long lo
 // ------------------------------------------------------------------------------------------------
 static_assert(sai2b::SNAP_JOINT_ROWS == sai2b::JOINT_ROWS && sai2b::SNAP_JOINT_STATUS_ROWS == sai2b::JOINT_STATUS_ROWS &&
 				  sai2b::SNAP_WRENCH_MOTION_ROWS + 1 == sai2b::WRENCH_ROWS && 6 + N == sai2b::WRENCH_STATUS_ROWS &&
-				  sai2b::MFT_STATE_ROWS == 12 + 3 * N,
+				  sai2b::MFT_STATE_ROWS == 12 + 3 * N && sai2b::SNAP_HW_SENSOR_ROWS == sai2b::HW_SENSOR_ROWS &&
+				  sai2b::SNAP_HW_MAX_DEPTH == sai2b::HW_MAX_DELAY && sai2b::HW_FILTER_ROWS == N + 6 && sai2b::HW_ACT_ROWS == 1 + 3 * N,
 			  "sai2b_snapshot_layout.h and the kernels disagree about a buffer's rows");
 
 namespace {
@@ -2839,6 +3018,9 @@ static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
 	d.joint = ctx->joint_rows != nullptr && ctx->joint_status != nullptr;
 	d.wrench = ctx->wrench_rows != nullptr && ctx->wrench_status != nullptr;
 	d.payload = env && ctx->payload_rows[0] != nullptr, d.plant_payload = env && ctx->payload_rows[1] != nullptr;
+	// the hardware's buffers exist from the first sai2b_set_hardware on; the history's depth is that of the last one
+	d.hardware = ctx->hw_clock != nullptr;
+	d.hardware_depth = d.hardware && epi ? ctx->hw_cfg.max_delay : 0;
 	return d;
 }
 
@@ -2873,6 +3055,12 @@ static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
 		case SNAP_CONTACT: return ctx->contact_rows;
 		case SNAP_JOINT: return ctx->joint_rows;
 		case SNAP_WRENCH: return ctx->wrench_rows;
+		case SNAP_HW_HISTORY: return ctx->hw_history;
+		case SNAP_HW_FILTER: return ctx->hw_filter;
+		case SNAP_HW_APPLIED: return ctx->hw_applied;
+		case SNAP_HW_CLOCK: return ctx->hw_clock;
+		case SNAP_HW_ACTUATOR: return ctx->hw_act;
+		case SNAP_HW_SENSOR: return ctx->hw_sensor;
 		default: return nullptr;
 	}
 }

@@ -168,4 +168,36 @@ struct SnapArgs {
 };
 int launch_snapshot(const SnapArgs& args, bool save, hipStream_t stream);
 
+// actuator and force-sensor models around the simulation kernel (sai2b_set_hardware, sai2b_hardware.hip): each kernel has its
+// own parameter block, passed by value as a kernel argument like WrenchParams; DevParams is not touched by the feature.
+constexpr int HW_MAX_DELAY = 8;					  // SAI2B_MAX_ACTUATION_DELAY
+constexpr int HW_ACT_ROWS = 1 + 3 * N;			  // delay, lag coefficient [N], gain [N], noise deviation [N]
+constexpr int HW_SENSOR_ROWS = 13;				  // bias 6, noise deviation 6, filter coefficient
+constexpr int HW_FILTER_ROWS = N + 6;			  // the lag state f [N], the sensor filter state g [6]
+enum { HW_STREAM_ACTUATOR = 0, HW_STREAM_SENSOR = 1 };
+struct HwStream {
+	unsigned key0 = 0, key1 = 0, first_robot = 0;  // the generator's key (seed low, high) and the global index of robot 0
+};
+struct ActuateParams {
+	const double* rows = nullptr;  // [HW_ACT_ROWS][B]
+	const double* command = nullptr;  // [N][B]: the torques the caller commands in this call
+	double* history = nullptr;		  // [depth + 1][N][B]
+	double* filter = nullptr;		  // [HW_FILTER_ROWS][B]; the kernel touches the first N rows
+	double* applied = nullptr;		  // [N][B]: what the simulation kernel receives
+	int* clock = nullptr;			  // [2][B]: period n, episode e; the kernel leaves n + 1
+	int depth = 0;
+	HwStream rng;
+};
+struct SenseParams {
+	const double* rows = nullptr;  // [HW_SENSOR_ROWS][B]
+	double* sensed = nullptr;	   // [6][B]: the task's sensed rows, the ideal reading on entry
+	double* filter = nullptr;	   // [HW_FILTER_ROWS][B]; the kernel touches the last 6 rows
+	const int* clock = nullptr;	   // [2][B] as actuate_kernel left it in this call: the period is clock - 1
+	HwStream rng;
+};
+int launch_actuate(int B, const ActuateParams& p, hipStream_t stream);
+int launch_sense(int B, const SenseParams& p, hipStream_t stream);
+// the selected robots' period := 0, episode += 1; mask [B] device bytes
+int launch_hardware_reset(int B, const unsigned char* mask, int* clock, hipStream_t stream);
+
 }  // namespace sai2b

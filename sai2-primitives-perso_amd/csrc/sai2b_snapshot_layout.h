@@ -23,16 +23,28 @@ enum SnapBlock {
 	SNAP_CONTACT_STATUS, SNAP_JOINT_STATUS, SNAP_WRENCH_STATUS,
 	// ---- SAI2B_SNAP_ENVIRONMENT
 	SNAP_PAYLOAD, SNAP_PLANT_PAYLOAD, SNAP_CONTACT, SNAP_JOINT, SNAP_WRENCH,
+	// ---- appended for the actuator and sensor models (sai2b_set_hardware): ids stay what exported blobs hold. Episode: the torque
+	// history, the filter states f and g, the applied torques, the clocks (period, episode; int); environment: the two row buffers.
+	// In a description they stand with their group: snap_block_order()
+	SNAP_HW_HISTORY, SNAP_HW_FILTER, SNAP_HW_APPLIED, SNAP_HW_CLOCK, SNAP_HW_ACTUATOR, SNAP_HW_SENSOR,
 	SNAP_BLOCKS
 };
 static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS] = {
 	"q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i", "popc_q",
 	"N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status",
-	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench"};
+	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench",
+	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor"};
+// where a block stands in the sequence snapshot_blocks() draws from: the hardware's episode blocks ahead of the environment group
+static inline int snap_block_order(int block) {
+	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + (SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1);
+	if (block >= SNAP_HW_HISTORY && block <= SNAP_HW_CLOCK) return block - (SNAP_WRENCH - SNAP_PAYLOAD + 1);
+	return block;
+}
 
 constexpr int SNAP_EPISODE_BIT = 1, SNAP_ENVIRONMENT_BIT = 2;  // SAI2B_SNAP_EPISODE, SAI2B_SNAP_ENVIRONMENT
 // rows of the plant's optional buffers (sai2b_launch.h has the same numbers for the kernels; sai2b_host.cpp asserts they agree)
 constexpr int SNAP_JOINT_ROWS = 6, SNAP_JOINT_STATUS_ROWS = 3, SNAP_WRENCH_MOTION_ROWS = 6, SNAP_POPC_F_ROWS = 4, SNAP_POPC_I_ROWS = 3;
+constexpr int SNAP_HW_SENSOR_ROWS = 13, SNAP_HW_MAX_DEPTH = 8;
 
 // one task as the layout sees it
 struct SnapTaskDesc {
@@ -50,6 +62,8 @@ struct SnapDesc {
 	int steps;						 // observation step counters exist
 	int contact, joint, wrench;		 // the plant's optional buffers exist
 	int payload, plant_payload;
+	int hardware;		 // the buffers of the actuator and sensor models exist (0: none, and hardware_depth is 0)
+	int hardware_depth;	 // D: the torque history holds D + 1 periods
 };
 
 struct SnapRow {
@@ -59,7 +73,7 @@ struct SnapRow {
 	int first_word;	  // first 4-byte word of the block in a robot's bank column
 	int first_row;	  // rows of all blocks before this one
 };
-constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5;
+constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6;
 
 struct SnapLayout {
 	int n = 0;
@@ -98,6 +112,10 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_CONTACT_STATUS, -1, d.contact ? CONTACT_STATUS_ROWS : 0, 8);
 		add(SNAP_JOINT_STATUS, -1, d.joint ? SNAP_JOINT_STATUS_ROWS * d.dof : 0, 8);
 		add(SNAP_WRENCH_STATUS, -1, d.wrench ? 6 + d.dof : 0, 8);
+		add(SNAP_HW_HISTORY, -1, d.hardware ? (d.hardware_depth + 1) * d.dof : 0, 8);
+		add(SNAP_HW_FILTER, -1, d.hardware ? d.dof + 6 : 0, 8);
+		add(SNAP_HW_APPLIED, -1, d.hardware ? d.dof : 0, 8);
+		add(SNAP_HW_CLOCK, -1, d.hardware ? 2 : 0, 4);
 	}
 	if (d.what & SNAP_ENVIRONMENT_BIT) {
 		add(SNAP_PAYLOAD, -1, d.payload ? PAYLOAD_ROWS : 0, 8);
@@ -105,6 +123,8 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_CONTACT, -1, d.contact ? CONTACT_ROWS : 0, 8);
 		add(SNAP_JOINT, -1, d.joint ? SNAP_JOINT_ROWS * d.dof : 0, 8);
 		add(SNAP_WRENCH, -1, d.wrench ? SNAP_WRENCH_MOTION_ROWS : 0, 8);
+		add(SNAP_HW_ACTUATOR, -1, d.hardware ? 1 + 3 * d.dof : 0, 8);
+		add(SNAP_HW_SENSOR, -1, d.hardware ? SNAP_HW_SENSOR_ROWS : 0, 8);
 	}
 	return n;
 }
@@ -121,6 +141,8 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 		mix(k.kind), mix(k.k0), mix(k.otg_mode), mix(k.otg3), mix(k.popc), mix(k.nprec);
 	}
 	mix(d.steps), mix(d.contact), mix(d.joint), mix(d.wrench), mix(d.payload), mix(d.plant_payload);
+	// only with the feature: a description without it keeps the fingerprint it had before the fields existed
+	if (d.hardware != 0) mix(d.hardware), mix(d.hardware_depth);
 	return h;
 }
 
@@ -160,7 +182,7 @@ static inline bool snapshot_first_difference(const SnapDesc& a, const SnapDesc& 
 		// both lists are drawn from one sequence (globals, then task by task, then the optional features): the earlier entry is missing in the other
 		auto key = [](const SnapRow& r) {
 			const int grp = r.block < SNAP_GOALS ? 0 : r.block <= SNAP_NPREC ? 1 : 2;
-			return (grp * 16 + (r.task < 0 ? 0 : r.task)) * 64 + r.block;
+			return (grp * 16 + (r.task < 0 ? 0 : r.task)) * 64 + snap_block_order(r.block);
 		};
 		const SnapRow& first = key(x) <= key(y) ? x : y;
 		if (first.task >= 0) return std::snprintf(msg, len, "block %s of task %d", SNAP_BLOCK_NAME[first.block], first.task), true;

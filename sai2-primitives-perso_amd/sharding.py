@@ -70,6 +70,13 @@ def set_external_wrench(ctrl, world, rank, link, force, moment=None, steps=None,
     ctrl.set_external_wrench(link, part(force, 2), part(moment, 2), part(steps, 1), **kwargs)
 
 
+def set_hardware(ctrl, world, rank, global_batch, actuator_rows=None, sensor_rows=None, **kwargs):
+    """Controller.set_hardware on this rank's shard of the per-robot rows [..][global_batch] given for the whole batch, with
+    first_robot set to the shard's first global index: every robot draws the noise it draws in the one-context run"""
+    lo, _ = shard_bounds(global_batch, world, rank)
+    ctrl.set_hardware(shard_rows(actuator_rows, world, rank), shard_rows(sensor_rows, world, rank), first_robot=lo, **kwargs)
+
+
 def reinitialize_robots(ctrl, world, rank, mask, task=-1):
     """Controller.reinitialize_robots on this rank's shard of a mask given for the whole batch"""
     ctrl.reinitialize_robots(shard_rows(mask, world, rank), task)

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
 """compare_kernel_isa.py <dir A> <dir B>: is the device code of two states of csrc/ the same? Each directory holds
-<unit>_n<N>.s for the eight device translation units of the Makefile and N = 4, 6, 7, 8, made in csrc/ of either state with
+<unit>_n<N>.s for the device translation units of the Makefile and N = 4, 6, 7, 8, made in csrc/ of either state with
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSAI2B_N=<N> -include sai2b_dof_rename.h --cuda-device-only -S <unit>.hip
   (sai2b_otg.hip: with -ffp-contract=off, as the Makefile builds it)
 
 Compared per kernel: the .amdhsa_* descriptor block and the instruction lines (directives and comments dropped, as
 tests/test_fast_kernel_isa.py filters them). Exit status 0 when every kernel of every unit is the same."""
+import os
 import re
 import sys
 
-UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action"]
+UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action", "sai2b_snapshot", "sai2b_hardware"]
 
 
 def kernels(path):
@@ -38,6 +39,11 @@ print(f"{'translation unit':<16} {'N':>2} {'kernels':>8} {'same set':>9} {'descr
 bad = 0
 for u in UNITS:
     for n in (4, 6, 7, 8):
+        # a unit the second state adds (no size of it in the first directory) has nothing to be compared with; one missing
+        # file of a unit the first state has is an error (kernels() fails on it)
+        if not any(os.path.exists(f"{a_dir}/{u}_n{m}.s") for m in (4, 6, 7, 8)):
+            print(f"{u:<16} {n:>2} {len(kernels(f'{b_dir}/{u}_n{n}.s')):>8} {'new unit':>9}")
+            continue
         a, b = kernels(f"{a_dir}/{u}_n{n}.s"), kernels(f"{b_dir}/{u}_n{n}.s")
         same_set = set(a) == set(b)
         common = set(a) & set(b)
