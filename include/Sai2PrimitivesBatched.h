@@ -136,6 +136,15 @@ struct DoneCounts {
 	int reason[SAI2B_DONE_REASONS] = {};
 	int any = 0;
 };
+// Rewards and episode returns (sai2b.h "rewards and episode returns"): the counts of the last observeReward, and the per-robot
+// accumulators as they are now
+struct RewardCounts {
+	int closed = 0, replaced = 0;  // robots whose episode was closed; robots whose reward was not finite and was replaced
+};
+struct EpisodeStats {
+	std::vector<double> ret, discount, last_return;	 // [B]: running return, running discount, return of the last closed episode
+	std::vector<int> last_length;					 // [B]: its length
+};
 namespace detail {
 // the host-only validation of an observation configuration against a hierarchy (sai2b_validate_observation)
 inline void checkObservationConfig(const sai2b_observation_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof) {
@@ -147,6 +156,18 @@ inline void checkObserveArguments(const int rows, const size_t B, const Batch* o
 	if (rows < 0) throw std::invalid_argument("observe: no observation is configured (setObservation)");
 	if (out && out->size() != (size_t)rows * B) throw std::invalid_argument("observe: out must be [rows][B]");
 	if (done && done->size() != B) throw std::invalid_argument("observe: done must have one entry per robot");
+}
+// the host-only validation of a reward configuration against a hierarchy (sai2b_validate_reward)
+inline void checkRewardConfig(const sai2b_reward_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof) {
+	char msg[256];
+	if (sai2b_validate_reward(&cfg, tasks.data(), (int)tasks.size(), dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(msg);
+}
+// what observeReward checks ahead of the device beyond checkObserveArguments: a configured reward, reward [B] and terms
+// [reward rows][B] where given
+inline void checkRewardArguments(const int reward_rows, const size_t B, const std::vector<double>* reward, const Batch* terms) {
+	if (reward_rows < 0) throw std::invalid_argument("observeReward: no reward is configured (setReward)");
+	if (reward && reward->size() != B) throw std::invalid_argument("observeReward: reward must have one entry per robot");
+	if (terms && terms->size() != (size_t)reward_rows * B) throw std::invalid_argument("observeReward: terms must be [reward rows][B]");
 }
 // the members RobotController and BatchedSimulation share: they act on the controller's context
 class ObservationMembers {
@@ -182,6 +203,41 @@ public:
 		for (int r = 0; r < SAI2B_DONE_REASONS; r++) d.reason[r] = c[r];
 		d.any = c[SAI2B_DONE_REASONS];
 		return d;
+	}
+
+	// rewards and episode returns. setReward validates against the controller's tasks, needs an observation (the done criteria
+	// live there) and restarts every robot's accumulators
+	void setReward(const sai2b_reward_config& cfg) { check(_obs_ctx, sai2b_set_reward(_obs_ctx, &cfg)); }
+	void clearReward() { check(_obs_ctx, sai2b_clear_reward(_obs_ctx)); }
+	int rewardRows() const { return sai2b_reward_rows(_obs_ctx); }	// -1 without a reward
+	// the row of a global term (task = -1: enum sai2b_reward_term) or of a task's term; -1: not selected
+	int rewardLayout(const int term, const int task = -1) const {
+		int first = -1, n = 0;
+		check(_obs_ctx, sai2b_reward_layout(_obs_ctx, term, task, &first, &n));
+		return first;
+	}
+	// observe() and the reward in one launch; out [rows][B], done [B], reward [B] and terms [reward rows][B] are filled where
+	// given (any may be NULL) and must have those sizes; the accumulators advance whatever is given
+	void observeReward(Batch* out, std::vector<unsigned char>* done, std::vector<double>* reward, Batch* terms) {
+		const size_t B = (size_t)sai2b_batch(_obs_ctx);
+		checkObserveArguments(observationRows(), B, out, done);
+		checkRewardArguments(rewardRows(), B, reward, terms);
+		check(_obs_ctx, sai2b_observe_reward(_obs_ctx, out ? out->data() : nullptr, done ? done->data() : nullptr, reward ? reward->data() : nullptr,
+											 terms ? terms->data() : nullptr, 0));
+	}
+	RewardCounts rewardCounts() const {
+		int c[2];
+		check(_obs_ctx, sai2b_get_reward_counts(_obs_ctx, c));
+		RewardCounts r;
+		r.closed = c[0], r.replaced = c[1];
+		return r;
+	}
+	EpisodeStats episodeStats() const {
+		const size_t B = (size_t)sai2b_batch(_obs_ctx);
+		EpisodeStats e;
+		e.ret.resize(B), e.discount.resize(B), e.last_return.resize(B), e.last_length.resize(B);
+		check(_obs_ctx, sai2b_get_episode_stats(_obs_ctx, e.ret.data(), e.discount.data(), e.last_return.data(), e.last_length.data()));
+		return e;
 	}
 
 protected:

@@ -410,7 +410,12 @@ enum sai2b_buffer {
 	 * are not inspected. */
 	SAI2B_BUF_HARDWARE_ACTUATOR = 15,
 	SAI2B_BUF_HARDWARE_SENSOR = 16,
-	SAI2B_BUF_TAU_APPLIED = 17
+	SAI2B_BUF_TAU_APPLIED = 17,
+	/* the reward's per-robot accumulators (sai2b_set_reward): [3 + dof][B] doubles = running discounted return, running discount,
+	 * return of the episode that ended last, tau_prev [dof]; and [2][B] ints = length of the episode that ended last, tau_prev is
+	 * valid. NULL until a reward has been set (and after it is cleared). */
+	SAI2B_BUF_REWARD_STATE = 18,
+	SAI2B_BUF_REWARD_EPISODE = 19
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -873,6 +878,102 @@ int sai2b_apply_action(sai2b_ctx* ctx, const double* action, const unsigned char
  * whose goal was limited by a box, the lead or a joint clamp (a rejected robot counts as rejected only). Zeros before the
  * first apply; SAI2B_INVALID_ARGUMENT without a configured action. Waits for the ctx stream. */
 int sai2b_get_action_counts(sai2b_ctx* ctx, int counts[3]);
+
+/* ------------------------------------------------------------------ rewards and episode returns
+ * The reward (for sampling MPC: the stage cost) of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe_reward, policy,
+ * sai2b_apply_action, sai2b_reset_robots: sai2b_observe_reward is sai2b_observe plus, in the SAME launch, one reward per robot
+ * and the per-robot episode bookkeeping that goes with it (discounted return, return and length of the episode that just
+ * ended). Everything in the configuration is batch-uniform. A context that never configures a reward launches exactly the
+ * kernels it launches without this feature.
+ *
+ * Term rows [reward_rows][B]: the selected global terms in the order of their flags, then for every task of task_mask (in
+ * ascending task index) the selected task terms in the order of their flags; one row each, unweighted (DONE: its done_value
+ * sum). */
+enum sai2b_reward_term {
+	SAI2B_REW_ALIVE = 1,	   /* 1 */
+	SAI2B_REW_JOINT_SPEED = 2, /* sum_i dq_i^2 */
+	SAI2B_REW_TORQUE = 4,	   /* sum_i tau_i^2, tau = SAI2B_BUF_TAU as SAI2B_OBS_TAU reads it */
+	SAI2B_REW_TORQUE_RATE = 8, /* sum_i (tau_i - tau_prev_i)^2; 0 while the robot has no valid tau_prev (below) */
+	SAI2B_REW_LIMIT = 16,	   /* max(0, limit_soft_margin - margin), margin = the SAI2B_OBS_LIMIT_MARGIN observation */
+	SAI2B_REW_DONE = 32		   /* sum_r done_value[r] * bit r of this call's done byte */
+};
+enum sai2b_reward_task_term {
+	SAI2B_REW_POS = 1,		 /* d_p: row 6 of the SAI2B_OBS_ERROR block, sqrt(max(e^T sigma_p e, 0)) */
+	SAI2B_REW_POS_SQ = 2,	 /* d_p * d_p */
+	SAI2B_REW_POS_TANH = 4,	 /* 1 - tanh(d_p / pos_scale[t]) */
+	SAI2B_REW_ORI = 8,		 /* d_o: row 7 of the SAI2B_OBS_ERROR block */
+	SAI2B_REW_ORI_SQ = 16,	 /* d_o * d_o */
+	SAI2B_REW_ORI_TANH = 32, /* 1 - tanh(d_o / ori_scale[t]) */
+	SAI2B_REW_LIN_VEL_SQ = 64,	/* |v|^2, (v, w) = J dq, the SAI2B_OBS_TWIST block */
+	SAI2B_REW_ANG_VEL_SQ = 128, /* |w|^2 */
+	SAI2B_REW_FORCE_ERR_SQ = 256, /* |sigma_f (f_sensed_world - f_goal)|^2: the difference the force law's kp_force multiplies
+								   * (MotionForceTask.cpp:330-336), f_goal = goal rows 24..26 */
+	SAI2B_REW_FORCE_EXCESS = 512  /* max(0, |f_sensed_world| - force_soft_limit[t]) */
+};
+#define SAI2B_REWARD_TERMS 6
+#define SAI2B_REWARD_TASK_TERMS 10
+typedef struct sai2b_reward_config {
+	int terms;		/* SAI2B_REW_ALIVE | ... : the global terms */
+	int task_mask;	/* bit t: MotionForceTask t takes part */
+	int task_terms; /* SAI2B_REW_POS | ... : the terms evaluated for every task of task_mask */
+	int reserved;
+	double weight[SAI2B_REWARD_TERMS];							  /* by flag bit */
+	double task_weight[SAI2B_MAX_TASKS][SAI2B_REWARD_TASK_TERMS]; /* by task, by flag bit */
+	double done_value[SAI2B_DONE_REASONS];						  /* by reason bit */
+	double limit_soft_margin;
+	double pos_scale[SAI2B_MAX_TASKS], ori_scale[SAI2B_MAX_TASKS], force_soft_limit[SAI2B_MAX_TASKS];
+	double gamma;			 /* discount of the running return, in [0, 1] */
+	double nonfinite_reward; /* finite; what a robot gets whose reward came out not finite */
+} sai2b_reward_config;
+/* host only: no term, weights and values 0, scales 1, soft margin and soft limits 0, gamma 1, nonfinite_reward 0 */
+int sai2b_default_reward(sai2b_reward_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: unknown bits in terms / task_terms, a task of task_mask
+ * that is not a MotionForceTask of `tasks`, task terms without a task or a task without task terms, a weight, done value or
+ * scale that is not finite, pos_scale / ori_scale not > 0 for a task whose TANH term is selected, a negative or non-finite
+ * limit_soft_margin or force_soft_limit, gamma outside [0, 1], a nonfinite_reward that is not finite, no term at all */
+int sai2b_validate_reward(const sai2b_reward_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+						  int msg_len);
+/* sizeof(sai2b_reward_config) as the library was compiled: a binding that mirrors the struct checks its layout with it */
+int sai2b_sizeof_reward_config(void);
+/* host only, the layout arithmetic: the row of `term`. task = -1: a global term (enum sai2b_reward_term), else a term of that
+ * task (enum sai2b_reward_task_term). *n_rows = 0 and *first_row = -1 when the configuration does not select it; *total_rows:
+ * rows of all terms. Any output may be NULL. SAI2B_INVALID_ARGUMENT when `term` is not exactly one known flag or task is
+ * outside [-1, SAI2B_MAX_TASKS). */
+int sai2b_reward_config_layout(const sai2b_reward_config* cfg, int term, int task, int* first_row, int* n_rows, int* total_rows);
+/* validates against the context's tasks; needs a configured observation (the done criteria live there); allocates the
+ * accumulators and sets every robot's to their start values (return 0, discount 1, last return 0, last length 0, no tau_prev),
+ * also when called again */
+int sai2b_set_reward(sai2b_ctx* ctx, const sai2b_reward_config* cfg);
+/* back to a context without a reward: sai2b_observe_reward fails from here on, sai2b_reset_robots makes no extra launch */
+int sai2b_clear_reward(sai2b_ctx* ctx);
+/* rows of the configured reward's terms; -1 without one */
+int sai2b_reward_rows(sai2b_ctx* ctx);
+/* sai2b_reward_config_layout for the context's configuration; SAI2B_INVALID_ARGUMENT without one */
+int sai2b_reward_layout(sai2b_ctx* ctx, int term, int task, int* first_row, int* n_rows);
+/* One launch. Per robot:
+ *  1. everything sai2b_observe does, unchanged: out and done (either may be NULL; the byte is computed either way), the episode
+ *     counter, the done counts, the NaN and non-finite-state rules;
+ *  2. the selected terms, and r = sum weight * term in layout order starting from 0.0, every step a separate multiply and a
+ *     separate add (no fused multiply-add here or in 4.);
+ *  3. r not finite: r = nonfinite_reward and the robot is counted; the term rows keep what was computed;
+ *  4. ret = ret + disc * r, then disc = disc * gamma;
+ *  5. done byte non-zero: last_return = ret, last_length = the episode step this call reported, then ret = 0, disc = 1, tau_prev
+ *     invalid; otherwise tau_prev = tau, valid;
+ *  6. reward [B] and terms [reward_rows][B] are written where given (either may be NULL).
+ * All pointers host, or all device when on_device != 0; the stream contract and the staging of host outputs are those of
+ * sai2b_observe. SAI2B_INVALID_ARGUMENT without a configured observation or without a configured reward (nothing is launched
+ * then). A plain sai2b_observe on a context with a reward stays what it is and does not touch the reward's state: a done it
+ * reports does NOT close the reward's episode (the episode counter restarts, the return goes on). sai2b_reset_robots sets the
+ * selected robots' ret = 0, disc = 1, tau_prev invalid in one more small launch and keeps last_return and last_length;
+ * sai2b_reinitialize_robots does not touch the reward's state. The accumulators are part of SAI2B_SNAP_EPISODE.
+ * There is no batch sum of returns on the device: a float atomic sum depends on arrival order. */
+int sai2b_observe_reward(sai2b_ctx* ctx, double* out, unsigned char* done, double* reward, double* terms, int on_device);
+/* of the last sai2b_observe_reward, counted on the device: robots whose episode was closed, robots whose reward was replaced by
+ * nonfinite_reward. Zeros before the first; SAI2B_INVALID_ARGUMENT without a configured reward. Waits for the ctx stream. */
+int sai2b_get_reward_counts(sai2b_ctx* ctx, int counts[2]);
+/* the accumulators as they are now, host arrays [B] each, any may be NULL: running return, running discount, return and length
+ * of the episode that ended last. Waits for the ctx stream. */
+int sai2b_get_episode_stats(sai2b_ctx* ctx, double* ret, double* discount, double* last_return, int* last_length);
 
 /* ------------------------------------------------------------------ snapshot banks
  * Whole robot states, saved to and restored from device memory: branching (copy one robot into K siblings, roll them out, come

@@ -34,6 +34,8 @@ BUF_EXTERNAL_WRENCH_STATE = 14  # [6 + dof][B]: F_w, M_w and the joint torques t
 BUF_HARDWARE_ACTUATOR = 15  # [1 + 3 dof][B] actuator rows: delay, lag coefficient, gain, noise deviation (sai2b_set_hardware)
 BUF_HARDWARE_SENSOR = 16  # [13][B] sensor rows: bias 6, noise deviation 6, filter coefficient
 BUF_TAU_APPLIED = 17  # [dof][B]: the torques the plant received in the last sim step
+BUF_REWARD_STATE = 18  # [3 + dof][B]: running return, running discount, last return, tau_prev
+BUF_REWARD_EPISODE = 19  # [2][B] int32: last length, tau_prev is valid
 MAX_ACTUATION_DELAY = 8  # SAI2B_MAX_ACTUATION_DELAY
 HARDWARE_SENSOR_ROWS = 13
 WRENCH_WORLD, WRENCH_LINK = 0, 1  # enum sai2b_wrench_frame
@@ -236,6 +238,34 @@ class ObservationConfig(C.Structure):
     ]
 
 
+# enum sai2b_reward_term / sai2b_reward_task_term (sai2b.h "rewards and episode returns"); name -> flag, in storage order
+REW_TERMS = {"alive": 1, "joint_speed": 2, "torque": 4, "torque_rate": 8, "limit": 16, "done": 32}
+REW_TASK_TERMS = {"pos": 1, "pos_sq": 2, "pos_tanh": 4, "ori": 8, "ori_sq": 16, "ori_tanh": 32, "lin_vel_sq": 64, "ang_vel_sq": 128,
+                  "force_err_sq": 256, "force_excess": 512}
+REWARD_TERMS, REWARD_TASK_TERMS = 6, 10
+REW_COUNTS = ("closed", "replaced")
+
+
+class RewardConfig(C.Structure):
+    """sai2b_reward_config; load_library() checks the size against sai2b_sizeof_reward_config()"""
+
+    _fields_ = [
+        ("terms", _i),
+        ("task_mask", _i),
+        ("task_terms", _i),
+        ("reserved", _i),
+        ("weight", _d * REWARD_TERMS),
+        ("task_weight", (_d * REWARD_TASK_TERMS) * MAX_TASKS),
+        ("done_value", _d * DONE_REASONS),
+        ("limit_soft_margin", _d),
+        ("pos_scale", _d * MAX_TASKS),
+        ("ori_scale", _d * MAX_TASKS),
+        ("force_soft_limit", _d * MAX_TASKS),
+        ("gamma", _d),
+        ("nonfinite_reward", _d),
+    ]
+
+
 class JointDynamicsConfig(C.Structure):
     """sai2b_joint_dynamics_config; load_library() checks the size against sai2b_sizeof_joint_dynamics_config()"""
 
@@ -420,6 +450,17 @@ EXPORTS = [
     "sai2b_action_layout",
     "sai2b_apply_action",
     "sai2b_get_action_counts",
+    "sai2b_default_reward",
+    "sai2b_validate_reward",
+    "sai2b_sizeof_reward_config",
+    "sai2b_reward_config_layout",
+    "sai2b_set_reward",
+    "sai2b_clear_reward",
+    "sai2b_reward_rows",
+    "sai2b_reward_layout",
+    "sai2b_observe_reward",
+    "sai2b_get_reward_counts",
+    "sai2b_get_episode_stats",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -576,6 +617,20 @@ def load_library():
     if lib.sai2b_sizeof_action_config() != C.sizeof(ActionConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_action_config is {lib.sai2b_sizeof_action_config()} bytes in the library, "
                            f"{C.sizeof(ActionConfig)} in the ctypes mirror")
+    lib.sai2b_default_reward.argtypes = [P(RewardConfig)]
+    lib.sai2b_validate_reward.argtypes = [P(RewardConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_reward_config.argtypes = []
+    lib.sai2b_reward_config_layout.argtypes = [P(RewardConfig), _i, _i, P(_i), P(_i), P(_i)]
+    lib.sai2b_set_reward.argtypes = [vp, P(RewardConfig)]
+    lib.sai2b_clear_reward.argtypes = [vp]
+    lib.sai2b_reward_rows.argtypes = [vp]
+    lib.sai2b_reward_layout.argtypes = [vp, _i, _i, P(_i), P(_i)]
+    lib.sai2b_observe_reward.argtypes = [vp, vp, vp, vp, vp, _i]
+    lib.sai2b_get_reward_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_get_episode_stats.argtypes = [vp, vp, vp, vp, vp]
+    if lib.sai2b_sizeof_reward_config() != C.sizeof(RewardConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_reward_config is {lib.sai2b_sizeof_reward_config()} bytes in the library, "
+                           f"{C.sizeof(RewardConfig)} in the ctypes mirror")
     lib.sai2b_default_external_wrench.argtypes = [P(ExternalWrenchConfig), _i]
     lib.sai2b_validate_external_wrench.argtypes = [P(ExternalWrenchConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
     lib.sai2b_sizeof_external_wrench_config.argtypes = []

@@ -143,6 +143,7 @@ class Controller:
                 raise RuntimeError(msg)
             raise ValueError(msg)
         self._caller_stream = 0  # the legacy default stream
+        self._device = int(device)
         if introspection:
             self.enable_introspection(True)
 
@@ -680,6 +681,159 @@ class Controller:
         c = (C.c_int * 7)()
         self._rc(self.lib.sai2b_get_done_counts(self.h, c))
         return dict(zip(list(_abi.DONE_BITS) + ["any"], list(c)))
+
+    # -- rewards and episode returns (sai2b.h "rewards and episode returns")
+    def reward_config(self, terms=None, tasks=None, done_value=None, limit_soft_margin=0.0, gamma=1.0, nonfinite_reward=0.0):
+        """-> RewardConfig. terms: dict name of _abi.REW_TERMS ('alive', 'joint_speed', 'torque', 'torque_rate', 'limit', 'done')
+        -> weight. tasks: dict MotionForceTask index -> dict of that task's settings: 'terms': dict name of _abi.REW_TASK_TERMS
+        ('pos', 'pos_sq', 'pos_tanh', 'ori', 'ori_sq', 'ori_tanh', 'lin_vel_sq', 'ang_vel_sq', 'force_err_sq', 'force_excess') ->
+        weight, and pos_scale, ori_scale, force_soft_limit. The configuration is batch-uniform and every task evaluates the same
+        set of terms: the union over the tasks, with weight 0 where a task does not name one. done_value: dict reason name of
+        _abi.DONE_BITS -> value of the 'done' term."""
+        cfg = _abi.RewardConfig()
+        rc = self.lib.sai2b_default_reward(C.byref(cfg))
+        if rc:
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        names = list(_abi.REW_TERMS)
+        for name, w in (terms or {}).items():
+            cfg.terms |= self._flags((name,), _abi.REW_TERMS, "reward term")
+            cfg.weight[names.index(name)] = float(w)
+        tnames = list(_abi.REW_TASK_TERMS)
+        for t, spec in (tasks or {}).items():
+            t = int(t)
+            if not 0 <= t < _abi.MAX_TASKS:
+                raise ValueError(f"task index {t} out of range")
+            spec = dict(spec)
+            cfg.task_mask |= 1 << t
+            for name, w in spec.pop("terms", {}).items():
+                cfg.task_terms |= self._flags((name,), _abi.REW_TASK_TERMS, "reward task term")
+                cfg.task_weight[t][tnames.index(name)] = float(w)
+            for key in ("pos_scale", "ori_scale", "force_soft_limit"):
+                if key in spec:
+                    getattr(cfg, key)[t] = float(spec.pop(key))
+            if spec:
+                raise ValueError(f"reward_config: unknown task setting(s) {sorted(spec)}")
+        reasons = list(_abi.DONE_BITS)
+        for name, v in (done_value or {}).items():
+            if name not in _abi.DONE_BITS:
+                raise ValueError(f"unknown done reason {name!r}: one of {reasons}")
+            cfg.done_value[reasons.index(name)] = float(v)
+        cfg.limit_soft_margin, cfg.gamma, cfg.nonfinite_reward = float(limit_soft_margin), float(gamma), float(nonfinite_reward)
+        return cfg
+
+    def set_reward(self, cfg=None, **kwargs):
+        """configure what observe_reward() evaluates (a RewardConfig, or the arguments of reward_config); needs a configured
+        observation; every robot's accumulators restart (return 0, discount 1, no last episode, no tau_prev)"""
+        if cfg is None:
+            cfg = self.reward_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_reward: a RewardConfig or keyword arguments, not both")
+        self._rc(self.lib.sai2b_set_reward(self.h, C.byref(cfg)))
+
+    def clear_reward(self):
+        self._rc(self.lib.sai2b_clear_reward(self.h))
+
+    def reward_rows(self):
+        """rows of the configured reward's terms; -1 without one"""
+        return self.lib.sai2b_reward_rows(self.h)
+
+    def reward_layout(self):
+        """dict name -> row of observe_reward()'s terms: the global terms by their names, the task terms as 'pos0',
+        'force_err_sq1', ... with the task index; only what the configuration selects"""
+        first, n = C.c_int(), C.c_int()
+        out = {}
+        for name, flag in _abi.REW_TERMS.items():
+            self._rc(self.lib.sai2b_reward_layout(self.h, flag, -1, C.byref(first), C.byref(n)))
+            if n.value:
+                out[name] = first.value
+        for t in range(len(self.tasks)):
+            for name, flag in _abi.REW_TASK_TERMS.items():
+                self._rc(self.lib.sai2b_reward_layout(self.h, flag, t, C.byref(first), C.byref(n)))
+                if n.value:
+                    out[f"{name}{t}"] = first.value
+        return out
+
+    def observe_reward(self, out=None, done=None, reward=None, terms=False):
+        """observe() and the reward in one launch -> (rows, done, reward [B] float64, terms [reward_rows()][B] float64). Every
+        argument: a numpy array or a torch CUDA tensor to fill (all of one kind; torch arguments never leave the device and
+        nothing synchronises), None: a new numpy array, False: not wanted (None is returned in its place). The accumulators
+        advance whatever is wanted."""
+        rows, rrows = self.observation_rows(), self.reward_rows()
+        if rows < 0:
+            raise ValueError("sai2b_observe_reward: no observation is configured (sai2b_set_observation)")
+        if rrows < 0:
+            raise ValueError("sai2b_observe_reward: no reward is configured (sai2b_set_reward)")
+        args = (out, done, reward, terms)
+        dev = self._dev(*[o for o in args if o is not None and o is not False])
+        if dev and any(o is None for o in args):
+            raise ValueError("observe_reward: with a device tensor pass every other argument as a tensor too, or False")
+        if out is None:
+            out = np.empty((rows, self.B))
+        if done is None:
+            done = np.zeros(self.B, dtype=np.uint8)
+        if reward is None:
+            reward = np.empty(self.B)
+        if terms is None:
+            terms = np.empty((rrows, self.B))
+
+        def rows_ptr(a, n, name, flat=False):
+            if a is False:
+                return None
+            shape = (self.B,) if flat else (n, self.B)
+            if hasattr(a, "data_ptr"):
+                if tuple(a.shape) != shape:
+                    raise ValueError(f"{name} must be a tensor of shape {shape}")
+                return self._in(a.view(n, self.B), n)[0]
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shape):
+                raise ValueError(f"{name} must be a C-contiguous float64 array of shape {shape}")
+            return C.c_void_p(a.ctypes.data)
+
+        po = rows_ptr(out, rows, "out")
+        pr = rows_ptr(reward, 1, "reward", flat=True)
+        pt = rows_ptr(terms, rrows, "terms")
+        pd = None
+        if done is not False:
+            if hasattr(done, "data_ptr"):
+                if str(done.dtype) != "torch.uint8":
+                    raise ValueError("done must be a uint8 tensor (it receives the reason bits)")
+                pd, _ = self._mask(done)
+            else:
+                if not (isinstance(done, np.ndarray) and done.dtype == np.uint8 and done.flags.c_contiguous and done.shape == (self.B,)):
+                    raise ValueError(f"done must be a C-contiguous uint8 array of shape ({self.B},)")
+                pd = C.c_void_p(done.ctypes.data)
+        self._rc(self.lib.sai2b_observe_reward(self.h, po, pd, pr, pt, dev))
+        return tuple(None if o is False else o for o in (out, done, reward, terms))
+
+    def reward_counts(self):
+        """of the last observe_reward(): dict 'closed' -> robots whose episode was closed, 'replaced' -> robots whose reward was
+        not finite and became nonfinite_reward"""
+        c = (C.c_int * 2)()
+        self._rc(self.lib.sai2b_get_reward_counts(self.h, c))
+        return dict(zip(_abi.REW_COUNTS, list(c)))
+
+    def episode_stats(self):
+        """the accumulators as they are now: dict of [B] arrays ret, discount, last_return (float64) and last_length (int32)"""
+        r, d, l = np.empty(self.B), np.empty(self.B), np.empty(self.B)
+        n = np.empty(self.B, dtype=np.int32)
+        self._rc(self.lib.sai2b_get_episode_stats(self.h, *[C.c_void_p(a.ctypes.data) for a in (r, d, l, n)]))
+        return dict(ret=r, discount=d, last_return=l, last_length=n)
+
+    def reward_state(self):
+        """the two device buffers as torch views (no copy): state [3 + dof][B] float64 = ret, disc, last_return, tau_prev and
+        episode [2][B] int32 = last_length, tau_prev_valid. Order reads and writes with stream()."""
+        import torch
+
+        ps, pe = self.device_buffer(_abi.BUF_REWARD_STATE), self.device_buffer(_abi.BUF_REWARD_EPISODE)
+        if not ps or not pe:
+            raise ValueError("reward_state: no reward is configured (sai2b_set_reward)")
+
+        def view(ptr, rows, typestr, dtype):
+            class _Buf:
+                __cuda_array_interface__ = dict(shape=(rows, self.B), typestr=typestr, data=(int(ptr), False), version=2)
+
+            return torch.as_tensor(_Buf(), device=f"cuda:{self._device}").view(dtype)
+
+        return view(ps, 3 + self.dof, "<f8", torch.float64), view(pe, 2, "<i4", torch.int32)
 
     # -- actions (sai2b.h "actions")
     def action_config(self, tasks=None, clip_actions=False):

@@ -134,6 +134,15 @@ struct sai2b_ctx {
 	int *obs_steps = nullptr, *obs_counts = nullptr;
 	double* obs_out = nullptr;
 	unsigned char* obs_done = nullptr;
+	// rewards and episode returns (sai2b_set_reward): the configuration in force and what observe_reward_kernel takes from it, the
+	// per-robot accumulators (SAI2B_BUF_REWARD_STATE / _EPISODE) and the device counters of the last call, created on first use;
+	// rew_out stages reward [B] and terms [rew_rows][B] of a call with host arguments
+	bool rew_on = false;
+	sai2b_reward_config rew_cfg = {};
+	sai2b::RewParams rew;
+	int rew_rows = 0;
+	double *rew_state = nullptr, *rew_out = nullptr;
+	int *rew_episode = nullptr, *rew_counts = nullptr;	// rew_counts: obs_counts + OBS_COUNTS
 	// actions (sai2b_set_action): the configuration in force and what action_kernel takes from it, the device counters of the
 	// last apply, created on first use; act_in / act_mask stage the inputs of a call with host arguments (act_in_rows: rows
 	// act_in has room for)
@@ -1126,6 +1135,12 @@ static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": hardware reset launch failed");
 		ctx->launches++;
 	}
+	// reward: a reset robot starts a new return (a re-initialisation alone leaves its accumulators as they are)
+	if (episode && ctx->rew_on) {
+		if (sai2b::launch_reward_reset(ctx->B, d_mask, ctx->rew_state, ctx->rew_episode, ctx->stream))
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": reward reset launch failed");
+		ctx->launches++;
+	}
 	// batch-wide and conservative: a dirty flag makes the generator kernel compare goals, and an untouched robot's compare equal
 	ctx->goals_dirty = task < 0 ? ~0u : (ctx->goals_dirty | 1u << task);
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1562,6 +1577,8 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_HARDWARE_ACTUATOR: return ctx->hw_on ? (void*)ctx->hw_act : nullptr;
 		case SAI2B_BUF_HARDWARE_SENSOR: return ctx->hw_on ? (void*)ctx->hw_sensor : nullptr;
 		case SAI2B_BUF_TAU_APPLIED: return ctx->hw_on ? (void*)ctx->hw_applied : nullptr;
+		case SAI2B_BUF_REWARD_STATE: return ctx->rew_on ? (void*)ctx->rew_state : nullptr;
+		case SAI2B_BUF_REWARD_EPISODE: return ctx->rew_on ? (void*)ctx->rew_episode : nullptr;
 	}
 	return nullptr;
 }
@@ -2369,10 +2386,11 @@ extern "C" int sai2b_set_observation(sai2b_ctx* ctx, const sai2b_observation_con
 	int rc;
 	const size_t B = ctx->B;
 	if (!ctx->obs_steps && (rc = dev_alloc(ctx, &ctx->obs_steps, B))) return rc;
-	if (!ctx->obs_counts && (rc = dev_alloc(ctx, &ctx->obs_counts, (size_t)sai2b::OBS_COUNTS))) return rc;
+	// (the reward's two counters stand behind the seven of the observation, so that sai2b_observe_reward zeroes all with one memset)
+	if (!ctx->obs_counts && (rc = dev_alloc(ctx, &ctx->obs_counts, (size_t)sai2b::OBS_COUNTS + sai2b::REW_COUNTS))) return rc;
 	// a new configuration starts every robot's episode (stream-ordered behind observes already enqueued)
 	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_steps, 0, B * sizeof(int), ctx->stream));
-	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, sai2b::OBS_COUNTS * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, (sai2b::OBS_COUNTS + sai2b::REW_COUNTS) * sizeof(int), ctx->stream));
 	sai2b::ObsParams o;
 	o.blocks = cfg->blocks, o.task_mask = cfg->task_mask, o.task_blocks = cfg->task_blocks;
 	o.criteria = cfg->criteria, o.success_mask = cfg->success_task_mask, o.force_mask = cfg->force_task_mask;
@@ -2446,6 +2464,218 @@ extern "C" int sai2b_get_done_counts(sai2b_ctx* ctx, int counts[7]) {
 	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_done_counts: no observation is configured (sai2b_set_observation)");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->obs_counts, sai2b::OBS_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
+// ---- rewards and episode returns ----
+namespace {
+constexpr int REW_ALL_TERMS = (1 << SAI2B_REWARD_TERMS) - 1, REW_ALL_TASK_TERMS = (1 << SAI2B_REWARD_TASK_TERMS) - 1;
+// rows of the global terms and of every task's terms; returns the rows of all terms
+int reward_rows(const sai2b_reward_config& c, int row_global[SAI2B_REWARD_TERMS], int row_task[SAI2B_MAX_TASKS], int off_task[SAI2B_REWARD_TASK_TERMS]) {
+	int rows = 0;
+	for (int k = 0; k < SAI2B_REWARD_TERMS; k++) row_global[k] = (c.terms >> k) & 1 ? rows++ : -1;
+	int per_task = 0;
+	for (int k = 0; k < SAI2B_REWARD_TASK_TERMS; k++) off_task[k] = (c.task_terms >> k) & 1 ? per_task++ : -1;
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		const bool on = ((c.task_mask >> t) & 1) && per_task > 0;
+		row_task[t] = on ? rows : -1;
+		if (on) rows += per_task;
+	}
+	return rows;
+}
+std::string reward_config_error(const sai2b_reward_config* c, const sai2b_task_config* tasks, int n_tasks) {
+	if (!c) return "reward: null config";
+	if (c->terms & ~REW_ALL_TERMS) return "reward: unknown bits in terms";
+	if (c->task_terms & ~REW_ALL_TASK_TERMS) return "reward: unknown bits in task_terms";
+	for (int t = 0; t < 32; t++)
+		if (((unsigned)c->task_mask >> t) & 1u)
+			if (!tasks || t >= n_tasks || t >= SAI2B_MAX_TASKS || tasks[t].type != SAI2B_MOTION_FORCE_TASK)
+				return "reward: task_mask selects a task that is not a MotionForceTask";
+	if (c->task_terms && !c->task_mask) return "reward: task_terms needs a task in task_mask";
+	if (c->task_mask && !c->task_terms) return "reward: task_mask needs a term in task_terms";
+	for (double v : c->weight)
+		if (!std::isfinite(v)) return "reward: weights must be finite";
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++)
+		for (double v : c->task_weight[t])
+			if (!std::isfinite(v)) return "reward: weights must be finite";
+	for (double v : c->done_value)
+		if (!std::isfinite(v)) return "reward: done_value must be finite";
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		if (!std::isfinite(c->pos_scale[t]) || !std::isfinite(c->ori_scale[t])) return "reward: scales must be finite";
+		const bool on = (c->task_mask >> t) & 1;
+		if (on && (c->task_terms & SAI2B_REW_POS_TANH) && !(c->pos_scale[t] > 0)) return "reward: POS_TANH needs pos_scale > 0";
+		if (on && (c->task_terms & SAI2B_REW_ORI_TANH) && !(c->ori_scale[t] > 0)) return "reward: ORI_TANH needs ori_scale > 0";
+		if (!std::isfinite(c->force_soft_limit[t]) || c->force_soft_limit[t] < 0) return "reward: force_soft_limit must be finite and >= 0";
+	}
+	if (!std::isfinite(c->limit_soft_margin) || c->limit_soft_margin < 0) return "reward: limit_soft_margin must be finite and >= 0";
+	if (!(c->gamma >= 0 && c->gamma <= 1)) return "reward: gamma must be in [0, 1]";
+	if (!std::isfinite(c->nonfinite_reward)) return "reward: nonfinite_reward must be finite";
+	if (!c->terms && !c->task_terms) return "reward: no term is selected";
+	return "";
+}
+}  // namespace
+extern "C" int sai2b_default_reward(sai2b_reward_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_reward: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) cfg->pos_scale[t] = cfg->ori_scale[t] = 1.0;
+	cfg->gamma = 1.0;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_reward_config(void) { return (int)sizeof(sai2b_reward_config); }
+extern "C" int sai2b_validate_reward(const sai2b_reward_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof, char* msg,
+									 int msg_len) {
+	const std::string err = robot_dof == N ? reward_config_error(cfg, tasks, n_tasks) : "reward: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_reward_config_layout(const sai2b_reward_config* cfg, int term, int task, int* first_row, int* n_rows, int* total_rows) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_reward_config_layout: bad arguments");
+	const int k = single_bit_index(term, task < 0 ? SAI2B_REWARD_TERMS : SAI2B_REWARD_TASK_TERMS);
+	if (k < 0 || task < -1 || task >= SAI2B_MAX_TASKS)
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_reward_config_layout: term must be one known flag and task -1 or a task index");
+	int row_global[SAI2B_REWARD_TERMS], row_task[SAI2B_MAX_TASKS], off_task[SAI2B_REWARD_TASK_TERMS];
+	const int rows = reward_rows(*cfg, row_global, row_task, off_task);
+	int first = -1;
+	if (task < 0)
+		first = row_global[k];
+	else if (row_task[task] >= 0 && off_task[k] >= 0)
+		first = row_task[task] + off_task[k];
+	if (first_row) *first_row = first;
+	if (n_rows) *n_rows = first >= 0 ? 1 : 0;
+	if (total_rows) *total_rows = rows;
+	return SAI2B_OK;
+}
+// every robot's accumulators at their start values, stream-ordered
+static int reward_state_start(sai2b_ctx* ctx) {
+	const size_t B = ctx->B;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->rew_state, 0, (size_t)sai2b::REW_STATE_ROWS * B * sizeof(double), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->rew_episode, 0, (size_t)sai2b::REW_EPISODE_ROWS * B * sizeof(int), ctx->stream));
+	const std::vector<double> ones(B, 1.0);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->rew_state + (size_t)sai2b::REW_DISC * B, ones.data(), B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `ones` goes out of scope
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_reward(sai2b_ctx* ctx, const sai2b_reward_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_reward: null ctx");
+	const std::string err = reward_config_error(cfg, ctx->cfg, ctx->T);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	if (!ctx->obs_on)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_reward: no observation is configured (sai2b_set_observation): the done criteria live there");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	const size_t B = ctx->B;
+	if (!ctx->rew_state && (rc = dev_alloc(ctx, &ctx->rew_state, (size_t)sai2b::REW_STATE_ROWS * B))) return rc;
+	if (!ctx->rew_episode && (rc = dev_alloc(ctx, &ctx->rew_episode, (size_t)sai2b::REW_EPISODE_ROWS * B))) return rc;
+	ctx->rew_counts = ctx->obs_counts + sai2b::OBS_COUNTS;	// allocated with the observation's counters (sai2b_set_observation)
+	if ((rc = reward_state_start(ctx))) return rc;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->rew_counts, 0, sai2b::REW_COUNTS * sizeof(int), ctx->stream));
+	sai2b::RewParams w;
+	w.terms = cfg->terms, w.task_mask = cfg->task_terms ? cfg->task_mask : 0, w.task_terms = cfg->task_terms;
+	ctx->rew_rows = reward_rows(*cfg, w.row_global, w.row_task, w.off_task);
+	for (int k = 0; k < SAI2B_REWARD_TERMS; k++) w.global_rows += (cfg->terms >> k) & 1;
+	w.task_rows = ctx->rew_rows - w.global_rows;
+	for (int k = 0; k < SAI2B_REWARD_TERMS; k++) w.weight[k] = cfg->weight[k];
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) {
+		w.pos_scale[t] = cfg->pos_scale[t], w.ori_scale[t] = cfg->ori_scale[t], w.force_soft_limit[t] = cfg->force_soft_limit[t];
+		if (w.row_task[t] < 0) continue;
+		for (int k = 0; k < SAI2B_REWARD_TASK_TERMS; k++)
+			if (w.off_task[k] >= 0) w.row_weight[w.row_task[t] - w.global_rows + w.off_task[k]] = cfg->task_weight[t][k];
+	}
+	for (int r = 0; r < SAI2B_DONE_REASONS; r++) w.done_value[r] = cfg->done_value[r];
+	w.limit_soft_margin = cfg->limit_soft_margin, w.gamma = cfg->gamma, w.nonfinite_reward = cfg->nonfinite_reward;
+	w.state = ctx->rew_state, w.episode = ctx->rew_episode, w.counts = ctx->rew_counts;
+	ctx->rew = w;
+	ctx->rew_cfg = *cfg;
+	ctx->rew_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_reward(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_reward: null ctx");
+	ctx->rew_on = false;
+	ctx->rew_rows = 0;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_reward_rows(sai2b_ctx* ctx) { return ctx && ctx->rew_on ? ctx->rew_rows : -1; }
+extern "C" int sai2b_reward_layout(sai2b_ctx* ctx, int term, int task, int* first_row, int* n_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_reward_layout: null ctx");
+	if (!ctx->rew_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_reward_layout: no reward is configured (sai2b_set_reward)");
+	const int rc = sai2b_reward_config_layout(&ctx->rew_cfg, term, task, first_row, n_rows, nullptr);
+	return rc ? set_error(ctx, rc, g_error) : SAI2B_OK;
+}
+extern "C" int sai2b_observe_reward(sai2b_ctx* ctx, double* out, unsigned char* done, double* reward, double* terms, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_observe_reward: null ctx");
+	if (!ctx->obs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_observe_reward: no observation is configured (sai2b_set_observation)");
+	if (!ctx->rew_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_observe_reward: no reward is configured (sai2b_set_reward)");
+	int rc = flush_update(ctx);	 // a deferred model update happens before anything is observed
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if ((rc = upload_params(ctx))) return rc;
+	const size_t B = ctx->B;
+	const bool want_out = out && ctx->obs_rows > 0;
+	const bool any = want_out || done || reward || terms;
+	double* d_out = want_out ? out : nullptr;
+	unsigned char* d_done = done;
+	sai2b::RewParams w = ctx->rew;
+	w.reward = reward, w.rows = terms;
+	if (on_device) {
+		// device results are written on the ctx stream: what the caller's stream still does with those buffers comes first
+		if (any && (rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (want_out) {
+			if (ctx->obs_out_rows < ctx->obs_rows) {  // a configuration with more rows: the smaller staging buffer goes
+				if (ctx->obs_out) {
+					HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)ctx->obs_out), ctx->allocs.end());
+					HIP_TRY(ctx, hipFree(ctx->obs_out));
+					ctx->obs_out = nullptr, ctx->obs_out_rows = 0;
+				}
+				if ((rc = dev_alloc(ctx, &ctx->obs_out, (size_t)ctx->obs_rows * B))) return rc;
+				ctx->obs_out_rows = ctx->obs_rows;
+			}
+			d_out = ctx->obs_out;
+		}
+		if (done) {
+			if (!ctx->obs_done && (rc = dev_alloc(ctx, &ctx->obs_done, B))) return rc;
+			d_done = ctx->obs_done;
+		}
+		if (reward || terms) {	// one staging buffer for both, sized for every term of any configuration
+			const size_t max_rows = 1 + SAI2B_REWARD_TERMS + SAI2B_MAX_TASKS * SAI2B_REWARD_TASK_TERMS;
+			if (!ctx->rew_out && (rc = dev_alloc(ctx, &ctx->rew_out, max_rows * B))) return rc;
+			if (reward) w.reward = ctx->rew_out;
+			if (terms) w.rows = ctx->rew_out + B;
+		}
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, (sai2b::OBS_COUNTS + sai2b::REW_COUNTS) * sizeof(int), ctx->stream));
+	if (sai2b::launch_observe_reward(ctx->d_params, ctx->B, ctx->obs, w, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
+		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_observe_reward: launch failed");
+	ctx->launches++;
+	if (on_device) return any ? caller_after_read(ctx) : SAI2B_OK;
+	if (want_out) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)ctx->obs_rows * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (done) HIP_TRY(ctx, hipMemcpyAsync(done, d_done, B, hipMemcpyDeviceToHost, ctx->stream));
+	if (reward) HIP_TRY(ctx, hipMemcpyAsync(reward, w.reward, B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (terms) HIP_TRY(ctx, hipMemcpyAsync(terms, w.rows, (size_t)ctx->rew_rows * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (any) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_reward_counts(sai2b_ctx* ctx, int counts[2]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_reward_counts: bad arguments");
+	if (!ctx->rew_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_reward_counts: no reward is configured (sai2b_set_reward)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->rew_counts, sai2b::REW_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_episode_stats(sai2b_ctx* ctx, double* ret, double* discount, double* last_return, int* last_length) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_episode_stats: null ctx");
+	if (!ctx->rew_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_episode_stats: no reward is configured (sai2b_set_reward)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	double* dst[3] = {ret, discount, last_return};
+	for (int k = 0; k < 3; k++)
+		if (dst[k]) HIP_TRY(ctx, hipMemcpyAsync(dst[k], ctx->rew_state + k * B, B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (last_length) HIP_TRY(ctx, hipMemcpyAsync(last_length, ctx->rew_episode, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }
@@ -3021,6 +3251,8 @@ static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
 	// the hardware's buffers exist from the first sai2b_set_hardware on; the history's depth is that of the last one
 	d.hardware = ctx->hw_clock != nullptr;
 	d.hardware_depth = d.hardware && epi ? ctx->hw_cfg.max_delay : 0;
+	// the reward's accumulators exist from the first sai2b_set_reward on
+	d.reward = epi && ctx->rew_state != nullptr;
 	return d;
 }
 
@@ -3061,6 +3293,8 @@ static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
 		case SNAP_HW_CLOCK: return ctx->hw_clock;
 		case SNAP_HW_ACTUATOR: return ctx->hw_act;
 		case SNAP_HW_SENSOR: return ctx->hw_sensor;
+		case SNAP_REWARD_STATE: return ctx->rew_state;
+		case SNAP_REWARD_EPISODE: return ctx->rew_episode;
 		default: return nullptr;
 	}
 }

@@ -123,6 +123,36 @@ struct ObsParams {
 int launch_observe(const DevParams* d_params, int B, const ObsParams& obs, double* out, unsigned char* done, int* steps, int* counts,
 				   hipStream_t stream);
 
+// sai2b_observe_reward (sai2b_observe.hip: observe_reward_kernel, the REWARD instantiation of observe_kernel's body): the reward's
+// own parameter block, passed by value beside ObsParams. Rows are rows of the [rows][B] terms output, -1 = term not selected;
+// a task's terms stand at row_task[t] + off_task[bit]. row_weight: the weight of every task-term row, by its distance from the
+// first task-term row (the order the reward is summed in).
+constexpr int REW_TERMS = SAI2B_REWARD_TERMS, REW_TASK_TERMS = SAI2B_REWARD_TASK_TERMS, REW_COUNTS = 2;	 // counts: closed, replaced
+constexpr int REW_STATE_ROWS = 3 + N, REW_EPISODE_ROWS = 2;
+enum { REW_RET = 0, REW_DISC = 1, REW_LAST_RETURN = 2, REW_TAU_PREV = 3 };	// rows of state; episode: last_length, tau_prev_valid
+struct RewParams {
+	int terms = 0, task_mask = 0, task_terms = 0;
+	int global_rows = 0, task_rows = 0;	 // rows of the global terms, rows of all task terms
+	int row_global[REW_TERMS] = {-1, -1, -1, -1, -1, -1};
+	int row_task[SAI2B_MAX_TASKS] = {-1, -1, -1, -1};
+	int off_task[REW_TASK_TERMS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+	double weight[REW_TERMS] = {};
+	double row_weight[SAI2B_MAX_TASKS * REW_TASK_TERMS] = {};
+	double done_value[SAI2B_DONE_REASONS] = {};
+	double limit_soft_margin = 0, gamma = 1, nonfinite_reward = 0;
+	double pos_scale[SAI2B_MAX_TASKS] = {}, ori_scale[SAI2B_MAX_TASKS] = {}, force_soft_limit[SAI2B_MAX_TASKS] = {};
+	double* reward = nullptr;  // [B] or NULL
+	double* rows = nullptr;	   // [global_rows + task_rows][B] or NULL
+	double* state = nullptr;   // [REW_STATE_ROWS][B]
+	int* episode = nullptr;	   // [REW_EPISODE_ROWS][B]
+	int* counts = nullptr;	   // [REW_COUNTS], zeroed by the caller on the stream ahead of the launch
+};
+// as launch_observe, with the reward evaluated in the same launch
+int launch_observe_reward(const DevParams* d_params, int B, const ObsParams& obs, const RewParams& rew, double* out, unsigned char* done,
+						  int* steps, int* counts, hipStream_t stream);
+// the selected robots' ret := 0, disc := 1, tau_prev invalid; mask [B] device bytes
+int launch_reward_reset(int B, const unsigned char* mask, double* state, int* episode, hipStream_t stream);
+
 // sai2b_apply_action (sai2b_action.hip: action_kernel): its own parameter block, passed by value as a kernel argument like
 // ObsParams; DevParams is not touched by the feature. Per task what sai2b_action_task holds, with the task's first action row.
 constexpr int ACT_BLOCKS = 4, ACT_COUNTS = 3;  // counts: rejected, clipped, limited

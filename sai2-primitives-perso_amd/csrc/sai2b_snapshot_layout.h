@@ -27,17 +27,25 @@ enum SnapBlock {
 	// history, the filter states f and g, the applied torques, the clocks (period, episode; int); environment: the two row buffers.
 	// In a description they stand with their group: snap_block_order()
 	SNAP_HW_HISTORY, SNAP_HW_FILTER, SNAP_HW_APPLIED, SNAP_HW_CLOCK, SNAP_HW_ACTUATOR, SNAP_HW_SENSOR,
+	// ---- appended for the reward's accumulators (sai2b_set_reward), both episode: return, discount, last return, tau_prev; last
+	// length and tau_prev's valid flag (int)
+	SNAP_REWARD_STATE, SNAP_REWARD_EPISODE,
 	SNAP_BLOCKS
 };
 static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS] = {
 	"q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i", "popc_q",
 	"N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status",
 	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench",
-	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor"};
-// where a block stands in the sequence snapshot_blocks() draws from: the hardware's episode blocks ahead of the environment group
+	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor", "reward_state", "reward_episode"};
+// where a block stands in the sequence snapshot_blocks() draws from: the hardware's and the reward's episode blocks ahead of the
+// environment group
 static inline int snap_block_order(int block) {
-	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + (SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1);
-	if (block >= SNAP_HW_HISTORY && block <= SNAP_HW_CLOCK) return block - (SNAP_WRENCH - SNAP_PAYLOAD + 1);
+	constexpr int hw_episode = SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1, reward = SNAP_REWARD_EPISODE - SNAP_REWARD_STATE + 1;
+	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1;
+	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + hw_episode + reward;
+	if (block >= SNAP_HW_HISTORY && block <= SNAP_HW_CLOCK) return block - environment;
+	if (block >= SNAP_REWARD_STATE && block <= SNAP_REWARD_EPISODE) return block - environment - hw_environment;
+	if (block >= SNAP_HW_ACTUATOR && block <= SNAP_HW_SENSOR) return block + reward;
 	return block;
 }
 
@@ -64,6 +72,7 @@ struct SnapDesc {
 	int payload, plant_payload;
 	int hardware;		 // the buffers of the actuator and sensor models exist (0: none, and hardware_depth is 0)
 	int hardware_depth;	 // D: the torque history holds D + 1 periods
+	int reward;			 // the reward's accumulators exist. Last: code that zeroes a description and fills the fields above stays valid
 };
 
 struct SnapRow {
@@ -73,7 +82,7 @@ struct SnapRow {
 	int first_word;	  // first 4-byte word of the block in a robot's bank column
 	int first_row;	  // rows of all blocks before this one
 };
-constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6;
+constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6 + 2;
 
 struct SnapLayout {
 	int n = 0;
@@ -116,6 +125,8 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_HW_FILTER, -1, d.hardware ? d.dof + 6 : 0, 8);
 		add(SNAP_HW_APPLIED, -1, d.hardware ? d.dof : 0, 8);
 		add(SNAP_HW_CLOCK, -1, d.hardware ? 2 : 0, 4);
+		add(SNAP_REWARD_STATE, -1, d.reward ? 3 + d.dof : 0, 8);
+		add(SNAP_REWARD_EPISODE, -1, d.reward ? 2 : 0, 4);
 	}
 	if (d.what & SNAP_ENVIRONMENT_BIT) {
 		add(SNAP_PAYLOAD, -1, d.payload ? PAYLOAD_ROWS : 0, 8);
@@ -143,6 +154,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 	mix(d.steps), mix(d.contact), mix(d.joint), mix(d.wrench), mix(d.payload), mix(d.plant_payload);
 	// only with the feature: a description without it keeps the fingerprint it had before the fields existed
 	if (d.hardware != 0) mix(d.hardware), mix(d.hardware_depth);
+	if (d.reward != 0) mix(d.reward);
 	return h;
 }
 
