@@ -145,7 +145,30 @@ struct EpisodeStats {
 	std::vector<double> ret, discount, last_return;	 // [B]: running return, running discount, return of the last closed episode
 	std::vector<int> last_length;					 // [B]: its length
 };
+// Episode starts (sai2b.h "episode starts"): the counts of the last resetRobotsSampled
+struct ResetSamplerCounts {
+	int reset = 0, rejected = 0, exhausted = 0;	 // robots reset; candidates rejected; robots that got q_nominal
+};
 namespace detail {
+// what setResetSampler checks ahead of the device: the configuration against the hierarchy (sai2b_validate_reset_sampler) and
+// rows [total rows][B] (or empty: the defaults); returns the total rows
+inline int checkResetSampler(const sai2b_reset_sampler_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof, const size_t B,
+							 const Batch& rows) {
+	char msg[256];
+	if (sai2b_validate_reset_sampler(&cfg, tasks.data(), (int)tasks.size(), dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(msg);
+	int total = 0;
+	if (sai2b_reset_sampler_config_layout(&cfg, tasks.data(), (int)tasks.size(), dof, 0, 0, nullptr, nullptr, &total) != SAI2B_OK)
+		throw std::invalid_argument("setResetSampler: no row layout for this configuration");
+	if (!rows.empty() && rows.size() != (size_t)total * B) throw std::invalid_argument("setResetSampler: rows must be [total rows][B] (or empty)");
+	return total;
+}
+inline ResetSamplerCounts resetSamplerCounts(sai2b_ctx* ctx) {
+	int c[3];
+	check(ctx, sai2b_get_reset_sampler_counts(ctx, c));
+	ResetSamplerCounts out;
+	out.reset = c[0], out.rejected = c[1], out.exhausted = c[2];
+	return out;
+}
 // the host-only validation of an observation configuration against a hierarchy (sai2b_validate_observation)
 inline void checkObservationConfig(const sai2b_observation_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof) {
 	char msg[256];
@@ -1220,6 +1243,20 @@ public:
 		detail::checkResetArguments(_robot->dof(), (size_t)_robot->batch(), mask, q, dq, "resetRobots");
 		detail::check(_ctx, sai2b_reset_robots(_ctx, mask.data(), q.empty() ? nullptr : q.data(), dq.empty() ? nullptr : dq.data(), 0));
 	}
+	// Episode starts drawn on the device (sai2b.h "episode starts"): the sampler's configuration and its per-robot rows
+	// [total rows][B] (empty: the defaults), and resetRobots with the state and the goals of the selected robots drawn
+	void setResetSampler(const sai2b_reset_sampler_config& cfg, const Batch& rows = {}) {
+		std::vector<sai2b_task_config> cfgs;
+		for (auto& task : _tasks) cfgs.push_back(task->config());
+		detail::checkResetSampler(cfg, cfgs, _robot->dof(), (size_t)_robot->batch(), rows);
+		detail::check(_ctx, sai2b_set_reset_sampler(_ctx, &cfg, rows.empty() ? nullptr : rows.data(), 0));
+	}
+	void clearResetSampler() { detail::check(_ctx, sai2b_clear_reset_sampler(_ctx)); }
+	void resetRobotsSampled(const std::vector<unsigned char>& mask) {
+		detail::checkResetArguments(_robot->dof(), (size_t)_robot->batch(), mask, {}, {}, "resetRobotsSampled");
+		detail::check(_ctx, sai2b_reset_robots_sampled(_ctx, mask.data(), 0));
+	}
+	ResetSamplerCounts resetSamplerCounts() const { return detail::resetSamplerCounts(_ctx); }
 	std::shared_ptr<JointTask> getJointTaskByName(const std::string& task_name) {
 		for (auto& task : _tasks)
 			if (task->getTaskName() == task_name) {
@@ -1380,6 +1417,31 @@ public:
 			const Batch qs = slice(q, _dof, sh), dqs = slice(dq, _dof, sh);
 			detail::check(sh.ctx, sai2b_reset_robots(sh.ctx, mask.data() + sh.lo, ptr(qs), ptr(dqs), 0));
 		});
+	}
+	// Episode starts drawn on the device for the whole sharded batch: rows [total rows][B_total] (empty: the defaults); every shard
+	// gets its columns and first_robot = cfg.first_robot + its first global index, so the draws are those of one context
+	void setResetSampler(const sai2b_reset_sampler_config& cfg, const Batch& rows = {}) {
+		const int total = detail::checkResetSampler(cfg, _cfgs, _dof, (size_t)_total, rows);
+		forAll([&](Shard& sh) {
+			sai2b_reset_sampler_config c = cfg;
+			c.first_robot = cfg.first_robot + (unsigned)sh.lo;
+			const Batch part = slice(rows, total, sh);
+			detail::check(sh.ctx, sai2b_set_reset_sampler(sh.ctx, &c, ptr(part), 0));
+		});
+	}
+	void clearResetSampler() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_reset_sampler(sh.ctx)); }); }
+	void resetRobotsSampled(const std::vector<unsigned char>& mask) {
+		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "resetRobotsSampled");
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_reset_robots_sampled(sh.ctx, mask.data() + sh.lo, 0)); });
+	}
+	// summed over the shards
+	ResetSamplerCounts resetSamplerCounts() {
+		ResetSamplerCounts out;
+		for (auto& sh : _shards) {
+			const ResetSamplerCounts c = detail::resetSamplerCounts(sh.ctx);
+			out.reset += c.reset, out.rejected += c.rejected, out.exhausted += c.exhausted;
+		}
+		return out;
 	}
 	void enableGravityCompensation(const bool on) {
 		forAll([on](Shard& sh) { detail::check(sh.ctx, sai2b_enable_gravity_compensation(sh.ctx, on)); });

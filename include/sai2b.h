@@ -975,6 +975,105 @@ int sai2b_get_reward_counts(sai2b_ctx* ctx, int counts[2]);
  * of the episode that ended last. Waits for the ctx stream. */
 int sai2b_get_episode_stats(sai2b_ctx* ctx, double* ret, double* discount, double* last_return, int* last_length);
 
+/* ------------------------------------------------------------------ episode starts
+ * Where a reset robot starts and what it is asked to do, drawn on the device: sai2b_reset_robots_sampled is sai2b_reset_robots
+ * with q, dq and the goals of the new episode drawn per robot, in ONE launch (plus the follow-up launches sai2b_reset_robots makes
+ * for the hardware's clocks and the reward's accumulators), for the robots a [B] byte mask selects. The resident loop  tick,
+ * sai2b_sim_step(NULL), sai2b_observe_reward, policy, sai2b_apply_action, sai2b_reset_robots_sampled(done)  then leaves the device
+ * for nothing but the policy. A context that never configures the sampler launches exactly what it launches without the feature.
+ * Batch-uniform (sai2b_reset_sampler_config): the generator's seed and the global index of this context's robot 0 (as the
+ * hardware's), the number of candidates a robot may try, which tasks get a drawn goal, and the three acceptance criteria with
+ * their thresholds. Per robot, doubles, rows [row][B], in this order:
+ *   q_lower [dof], q_upper [dof]   the box candidates are drawn from. Default: the middle 80 % of the model's joint range,
+ *                                  mid -+ 0.8 half with mid = (lower + upper) / 2, half = (upper - lower) / 2
+ *   dq_sigma [dof]                 standard deviation of the start velocity. Default 0
+ *   q_nominal [dof]                the posture of a robot whose candidates were all rejected. Default mid
+ *   for every MotionForceTask of goal_tasks, in task order: pos_lower [3], pos_upper [3], theta_max [1]. Default 0
+ *   then for every JointTask of goal_tasks, in task order: half_width [task_dof]. Default 0
+ * State per robot: an episode counter e (int, 0 after sai2b_set_reset_sampler) and the candidates the last call used.
+ *
+ * THE LAW, per selected robot b with e as on entry. Random numbers: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), as the
+ * hardware's; word x gives u = (x + 0.5) 2^-32; "call j" of a stream has the counter (n, e, 256 stream + j, first_robot + b).
+ *  1. CANDIDATES, tries n = 0 .. max_tries - 1, stream 2: joint i takes u_i = word i mod 4 of call i / 4 and
+ *       q_i = q_lower_i + (q_upper_i - q_lower_i) u_i        one product and one sum, never fused: lower == upper gives lower
+ *  2. CRITERIA on the candidate; the first n whose candidate passes every configured criterion wins, tries = n + 1:
+ *     (a) ratio_task >= 0: with J the 6 x dof world-frame Jacobian of that MotionForceTask's control point (linear rows first)
+ *         and P its 6 x 6 partial projection (the task stands at level 1: N_prec = I), s_0 >= s_1 >= .. >= s_5 the singular values
+ *         of P J (those beyond dof are 0) and r the rank of P: accept iff s_(r-1) / s_0 >= min_ratio;
+ *     (b) box_task >= 0: accept iff box_lower_k <= x_k <= box_upper_k, k = 0..2, x that task's control point in the world frame;
+ *     (c) use_clearance: with the contact's link, its points c_k (link frame) and this robot's plane rows (point p0, unit normal
+ *         n): accept iff n . (p0 - x_k) <= -clearance for every point x_k = p_link + R_link c_k;
+ *     a comparison with a NaN is false: a candidate that is not finite is rejected. Without any criterion candidate 0 wins.
+ *  3. EXHAUSTED, no candidate accepted: q = q_nominal, dq = 0 exactly, tries = max_tries + 1, the robot is counted; it still
+ *     gets its goals drawn.
+ *  4. VELOCITY (accepted robots), stream 3 with n = 0: dq_i = dq_sigma_i z_i, z_i the unit normal i mod 4 of call i / 4 as the
+ *     hardware law derives it; dq_sigma_i == 0 gives exactly 0.
+ *  5. RESET: everything sai2b_reset_robots(mask, q, dq) does for the robot: state columns, tasks, generators and passivity
+ *     observers re-initialised at the new pose, torque columns zeroed, the hardware's clocks and the reward's accumulators.
+ *     Every goal now is the start pose: x, R of a MotionForceTask, S q of a JointTask.
+ *  6. GOALS of every task t of goal_tasks, stream 4 with n = t:
+ *     MotionForceTask: call 0 words 0..2 give p_k = pos_lower_k + (pos_upper_k - pos_lower_k) u_k and the goal position x + p,
+ *       or p itself when bit t of absolute_position is set; theta = theta_max u with u word 3 of call 0; call 1 words 0, 1 give
+ *       c = 2 u0 - 1, phi = 2 pi u1, the axis a = (sqrt(1 - c^2) cos phi, sqrt(1 - c^2) sin phi, c) (uniform on the sphere) and
+ *       the goal rotation R (I + sin(theta) K + (1 - cos(theta)) K^2), K = [a]x; theta_max == 0 keeps R bit for bit.
+ *     JointTask: goal_j = (S q)_j + half_width_j (2 u_j - 1), u_j word j mod 4 of call j / 4.
+ *     Velocity, acceleration and wrench goals stay zero. An internal generator plans to the drawn goal at the next tick, exactly
+ *     as after a goal setter.
+ *  7. e = e + 1. Robots the mask does not select are neither read nor written.
+ * The draws of a robot depend on the seed, its global index and its episode alone: shards with first_robot set reproduce the
+ * one-context run bit for bit. The episode counter is a block of SAI2B_SNAP_EPISODE; seed and first_robot are configuration and
+ * are neither stored in a bank nor part of its fingerprint. sai2b_reset_robots and sai2b_reinitialize_robots do not touch e.
+ * This law is this library's definition. */
+#define SAI2B_MAX_RESET_TRIES 64
+typedef struct sai2b_reset_sampler_config {
+	unsigned long long seed;
+	unsigned first_robot;		/* global index of robot 0 of this context (0 unless the batch is a shard) */
+	int max_tries;				/* 1 .. SAI2B_MAX_RESET_TRIES candidates per robot and call */
+	unsigned goal_tasks;		/* bit t: draw task t's goal (MotionForceTask or JointTask) */
+	unsigned absolute_position; /* bit t: MotionForceTask t's position box is in the world frame, else relative to the start pose */
+	int ratio_task;				/* MotionForceTask of the singularity criterion, or -1 */
+	double min_ratio;			/* accept iff s_(rank-1) / s_0 >= min_ratio; in [0, 1] */
+	int box_task;				/* MotionForceTask whose control point must start inside the box, or -1 */
+	double box_lower[3], box_upper[3]; /* world frame */
+	int use_clearance;			/* 0 / 1; needs sai2b_set_contact: every contact point at least `clearance` outside the robot's plane */
+	double clearance;			/* metres */
+} sai2b_reset_sampler_config;
+/* host only: seed 0, first_robot 0, max_tries 8, no goal, no criterion */
+int sai2b_default_reset_sampler(sai2b_reset_sampler_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (max_tries outside [1, SAI2B_MAX_RESET_TRIES]; a bit of
+ * goal_tasks beyond the task list; a bit of absolute_position that is not a MotionForceTask of goal_tasks; ratio_task or box_task
+ * neither -1 nor a MotionForceTask of `tasks`; min_ratio outside [0, 1]; a box or clearance that is not finite; use_clearance not
+ * 0 or 1). That use_clearance needs a contact is checked against a context only (sai2b_set_reset_sampler and every call). */
+int sai2b_validate_reset_sampler(const sai2b_reset_sampler_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+								 char* msg, int msg_len);
+/* sizeof(sai2b_reset_sampler_config) as the library was compiled: a binding that mirrors the struct checks its layout with it */
+int sai2b_sizeof_reset_sampler_config(void);
+/* host only, the layout arithmetic of the per-robot rows. block: 0 q_lower, 1 q_upper, 2 dq_sigma, 3 q_nominal (task ignored),
+ * 4 the goal rows of `task` (7 for a MotionForceTask, task_dof for a JointTask). *n_rows = 0 and *first_row = -1 when the
+ * configuration draws no goal for that task; *total_rows: rows of the whole buffer. Any output may be NULL. */
+int sai2b_reset_sampler_config_layout(const sai2b_reset_sampler_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+									  int block, int task, int* first_row, int* n_rows, int* total_rows);
+/* rows [total_rows][B], NULL: the defaults above. Host rows are validated (SAI2B_INVALID_ARGUMENT with the reason: what
+ * sai2b_validate_reset_sampler rejects; use_clearance without a contact in force; anything not finite; q_lower > q_upper;
+ * q_nominal outside the model's joint limits; a negative dq_sigma, theta_max or half_width; theta_max > pi); DEVICE rows
+ * (on_device != 0) are copied under the stream contract and NOT inspected. Zeroes every robot's episode counter. A call that
+ * fails on its arguments leaves the context as it was; one that fails while copying leaves it without a sampler. */
+int sai2b_set_reset_sampler(sai2b_ctx* ctx, const sai2b_reset_sampler_config* cfg, const double* rows, int on_device);
+/* back to a context without a sampler: sai2b_reset_robots_sampled fails from here on */
+int sai2b_clear_reset_sampler(sai2b_ctx* ctx);
+/* the configuration and the rows [total_rows][B] to the host (either may be NULL); SAI2B_INVALID_ARGUMENT without a sampler */
+int sai2b_get_reset_sampler(sai2b_ctx* ctx, sai2b_reset_sampler_config* cfg, double* rows);
+/* The law above for the robots with mask[b] != 0; mask [B] bytes, host or (on_device != 0) device under the stream contract, as
+ * sai2b_reset_robots takes it. SAI2B_INVALID_ARGUMENT (nothing is launched): no sampler configured, mask NULL, use_clearance while
+ * no contact is in force (it was cleared since). */
+int sai2b_reset_robots_sampled(sai2b_ctx* ctx, const unsigned char* mask, int on_device);
+/* of the last sai2b_reset_robots_sampled, counted on the device: robots reset, candidates rejected, robots exhausted. Zeros before
+ * the first; SAI2B_INVALID_ARGUMENT without a sampler. Waits for the ctx stream. */
+int sai2b_get_reset_sampler_counts(sai2b_ctx* ctx, int counts[3]);
+/* host arrays [B] each, any NULL: the episode counter e, and the candidates the robot used in the call that reset it last
+ * (max_tries + 1: exhausted; 0: never reset). SAI2B_INVALID_ARGUMENT without a sampler. Waits for the ctx stream. */
+int sai2b_get_reset_sampler_state(sai2b_ctx* ctx, int* episode, int* tries);
+
 /* ------------------------------------------------------------------ snapshot banks
  * Whole robot states, saved to and restored from device memory: branching (copy one robot into K siblings, roll them out, come
  * back), reset to a bank of stored states, checkpoint and resume. A bank holds `capacity` slots of one robot's state each,

@@ -299,6 +299,30 @@ class HardwareConfig(C.Structure):
     ]
 
 
+MAX_RESET_TRIES = 64  # SAI2B_MAX_RESET_TRIES
+RESET_SAMPLER_COUNTS = ("reset", "rejected", "exhausted")
+RESET_SAMPLER_BLOCKS = {"q_lower": 0, "q_upper": 1, "dq_sigma": 2, "q_nominal": 3, "goal": 4}  # sai2b_reset_sampler_config_layout
+
+
+class ResetSamplerConfig(C.Structure):
+    """sai2b_reset_sampler_config; load_library() checks the size against sai2b_sizeof_reset_sampler_config()"""
+
+    _fields_ = [
+        ("seed", C.c_ulonglong),
+        ("first_robot", C.c_uint),
+        ("max_tries", _i),
+        ("goal_tasks", C.c_uint),
+        ("absolute_position", C.c_uint),
+        ("ratio_task", _i),
+        ("min_ratio", _d),
+        ("box_task", _i),
+        ("box_lower", _d * 3),
+        ("box_upper", _d * 3),
+        ("use_clearance", _i),
+        ("clearance", _d),
+    ]
+
+
 # enum sai2b_action_mode / sai2b_action_block (sai2b.h "actions"); name -> value, blocks in row order
 ACT_NONE, ACT_DELTA_GOAL, ACT_DELTA_CURRENT, ACT_ABSOLUTE = 0, 1, 2, 3
 ACT_POSITION, ACT_ORIENTATION, ACT_FORCE, ACT_MOMENT = 1, 2, 4, 8
@@ -461,6 +485,16 @@ EXPORTS = [
     "sai2b_observe_reward",
     "sai2b_get_reward_counts",
     "sai2b_get_episode_stats",
+    "sai2b_default_reset_sampler",
+    "sai2b_validate_reset_sampler",
+    "sai2b_sizeof_reset_sampler_config",
+    "sai2b_reset_sampler_config_layout",
+    "sai2b_set_reset_sampler",
+    "sai2b_clear_reset_sampler",
+    "sai2b_get_reset_sampler",
+    "sai2b_reset_robots_sampled",
+    "sai2b_get_reset_sampler_counts",
+    "sai2b_get_reset_sampler_state",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -479,7 +513,7 @@ SNAP_COUNTS = ("moved", "out_of_range", "never_saved")
 SNAP_BLOCKS = ("q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i",
                "popc_q", "N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status", "payload",
                "plant_payload", "contact", "joint_dynamics", "external_wrench", "hw_history", "hw_filter", "hw_applied", "hw_clock",
-               "hw_actuator", "hw_sensor")
+               "hw_actuator", "hw_sensor", "reward_state", "reward_episode", "reset_sampler_episode")
 
 _lib = None
 
@@ -663,5 +697,18 @@ def load_library():
     if lib.sai2b_sizeof_hardware_config() != C.sizeof(HardwareConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_hardware_config is {lib.sai2b_sizeof_hardware_config()} bytes in the library, "
                            f"{C.sizeof(HardwareConfig)} in the ctypes mirror")
+    lib.sai2b_default_reset_sampler.argtypes = [P(ResetSamplerConfig)]
+    lib.sai2b_validate_reset_sampler.argtypes = [P(ResetSamplerConfig), P(TaskConfig), _i, _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_reset_sampler_config.argtypes = []
+    lib.sai2b_reset_sampler_config_layout.argtypes = [P(ResetSamplerConfig), P(TaskConfig), _i, _i, _i, _i, P(_i), P(_i), P(_i)]
+    lib.sai2b_set_reset_sampler.argtypes = [vp, P(ResetSamplerConfig), vp, _i]
+    lib.sai2b_clear_reset_sampler.argtypes = [vp]
+    lib.sai2b_get_reset_sampler.argtypes = [vp, P(ResetSamplerConfig), vp]
+    lib.sai2b_reset_robots_sampled.argtypes = [vp, vp, _i]
+    lib.sai2b_get_reset_sampler_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_get_reset_sampler_state.argtypes = [vp, vp, vp]
+    if lib.sai2b_sizeof_reset_sampler_config() != C.sizeof(ResetSamplerConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_reset_sampler_config is {lib.sai2b_sizeof_reset_sampler_config()} bytes in the library, "
+                           f"{C.sizeof(ResetSamplerConfig)} in the ctypes mirror")
     _lib = lib
     return lib

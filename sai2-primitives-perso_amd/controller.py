@@ -966,6 +966,144 @@ class Controller:
         pd, kd = self._in(dq, self.dof)
         self._rc(self.lib.sai2b_reset_robots(self.h, pm, pq, pd, self._dev(mask, q, dq)))
 
+    # -- episode starts (sai2b.h "episode starts")
+    def reset_sampler_config(self, seed=0, first_robot=0, max_tries=8, goal_tasks=(), absolute_position=(), ratio_task=-1, min_ratio=0.0,
+                             box_task=-1, box_lower=(0.0, 0.0, 0.0), box_upper=(0.0, 0.0, 0.0), clearance=None):
+        """-> ResetSamplerConfig, validated against this controller's tasks. goal_tasks / absolute_position: task indices (or an
+        int of bits); ratio_task, min_ratio: the singularity criterion; box_task, box_lower, box_upper: the workspace box;
+        clearance: metres over the contact plane (None: no clearance criterion)"""
+        cfg = _abi.ResetSamplerConfig()
+        if self.lib.sai2b_default_reset_sampler(C.byref(cfg)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+
+        def bits(v):
+            if isinstance(v, (int, np.integer)):
+                return int(v) & 0xFFFFFFFF
+            out = 0
+            for t in v:
+                if not 0 <= int(t) < 32:
+                    raise ValueError(f"reset sampler: task index {t} out of range")
+                out |= 1 << int(t)
+            return out
+
+        cfg.seed, cfg.first_robot, cfg.max_tries = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_robot) & 0xFFFFFFFF, int(max_tries)
+        cfg.goal_tasks, cfg.absolute_position = bits(goal_tasks), bits(absolute_position)
+        cfg.ratio_task, cfg.min_ratio, cfg.box_task = int(ratio_task), float(min_ratio), int(box_task)
+        lo, hi = np.asarray(box_lower, dtype=np.float64), np.asarray(box_upper, dtype=np.float64)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("box_lower, box_upper: expected 3 values each")
+        cfg.box_lower[:], cfg.box_upper[:] = [float(x) for x in lo], [float(x) for x in hi]
+        cfg.use_clearance, cfg.clearance = (0, 0.0) if clearance is None else (1, float(clearance))
+        msg = C.create_string_buffer(256)
+        tasks = (_abi.TaskConfig * len(self.tasks))(*self.tasks)
+        if self.lib.sai2b_validate_reset_sampler(C.byref(cfg), tasks, len(self.tasks), self.dof, msg, 256):
+            # (for a robot size without a build the dispatcher answers and leaves msg empty: its text is the shared error's)
+            raise ValueError(msg.value.decode() or self.lib.sai2b_last_error(None).decode())
+        return cfg
+
+    def reset_sampler_layout(self, cfg):
+        """dict name -> (first_row, n_rows) of the per-robot rows of `cfg`: 'q_lower', 'q_upper', 'dq_sigma', 'q_nominal' and
+        'goal<t>' for every task of goal_tasks; 'total' -> rows of the whole buffer"""
+        tasks = (_abi.TaskConfig * len(self.tasks))(*self.tasks)
+        first, n, total = C.c_int(), C.c_int(), C.c_int()
+        out = {}
+        for name, block in _abi.RESET_SAMPLER_BLOCKS.items():
+            for t in range(len(self.tasks)) if name == "goal" else (0,):
+                rc = self.lib.sai2b_reset_sampler_config_layout(C.byref(cfg), tasks, len(self.tasks), self.dof, block, t, C.byref(first),
+                                                                C.byref(n), C.byref(total))
+                if rc:
+                    raise ValueError(self.lib.sai2b_last_error(None).decode())
+                if n.value:
+                    out[f"goal{t}" if name == "goal" else name] = (first.value, n.value)
+        out["total"] = total.value
+        return out
+
+    def reset_sampler_rows(self, cfg, q_lower=None, q_upper=None, dq_sigma=0.0, q_nominal=None, goals=None):
+        """-> rows [total][B] (numpy) for `cfg`. q_lower, q_upper, q_nominal (None: the defaults: the middle 80 % of the joint range
+        and its middle), dq_sigma: a scalar, [dof] values or [dof][B]. goals: dict task -> dict(pos_lower=, pos_upper=, theta_max=)
+        for a MotionForceTask ([3] / scalar or [..][B]) or dict(half_width=) for a JointTask; what is left out is 0"""
+        n, B = self.dof, self.B
+        lay = self.reset_sampler_layout(cfg)
+        lo_m = np.array([self.model.q_lower[i] for i in range(n)])
+        hi_m = np.array([self.model.q_upper[i] for i in range(n)])
+        mid, half = 0.5 * (lo_m + hi_m), 0.5 * (hi_m - lo_m)
+
+        def block(a, rows, name):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 1 and a.shape[0] == rows and rows != B:
+                a = a[:, None]
+            try:
+                return np.broadcast_to(a, (rows, B))
+            except ValueError:
+                raise ValueError(f"{name}: expected a scalar, {rows} values or an array of shape ({rows}, {B})") from None
+
+        rows = np.zeros((lay["total"], B))
+        rows[0:n] = block(mid - 0.8 * half if q_lower is None else q_lower, n, "q_lower")
+        rows[n : 2 * n] = block(mid + 0.8 * half if q_upper is None else q_upper, n, "q_upper")
+        rows[2 * n : 3 * n] = block(dq_sigma, n, "dq_sigma")
+        rows[3 * n : 4 * n] = block(mid if q_nominal is None else q_nominal, n, "q_nominal")
+        for t, spec in (goals or {}).items():
+            key = f"goal{int(t)}"
+            if key not in lay:
+                raise ValueError(f"reset_sampler_rows: task {t} is not in goal_tasks")
+            first, cnt = lay[key]
+            spec = dict(spec)
+            if self.tasks[int(t)].type == _abi.MOTION_FORCE_TASK:
+                rows[first : first + 3] = block(spec.pop("pos_lower", 0.0), 3, "pos_lower")
+                rows[first + 3 : first + 6] = block(spec.pop("pos_upper", 0.0), 3, "pos_upper")
+                rows[first + 6] = np.broadcast_to(np.asarray(spec.pop("theta_max", 0.0), dtype=np.float64), (B,))
+            else:
+                rows[first : first + cnt] = block(spec.pop("half_width", 0.0), cnt, "half_width")
+            if spec:
+                raise ValueError(f"reset_sampler_rows: unknown setting(s) {sorted(spec)} for task {t}")
+        return rows
+
+    def set_reset_sampler(self, cfg=None, rows=None, **kwargs):
+        """configure what reset_robots_sampled() draws: a ResetSamplerConfig (or the arguments of reset_sampler_config) and the
+        per-robot rows [total][B], numpy (validated) or torch CUDA (not inspected), None = the defaults. Zeroes the episode
+        counters."""
+        if cfg is None:
+            cfg = self.reset_sampler_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_reset_sampler: a ResetSamplerConfig or keyword arguments, not both")
+        total = self.reset_sampler_layout(cfg)["total"]
+        if rows is not None and not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.shape != (total, self.B):
+                raise ValueError(f"rows: expected an array of shape ({total}, {self.B})")
+        pr, keep = self._in(rows, total)
+        self._rc(self.lib.sai2b_set_reset_sampler(self.h, C.byref(cfg), pr, self._dev(rows)))
+
+    def clear_reset_sampler(self):
+        self._rc(self.lib.sai2b_clear_reset_sampler(self.h))
+
+    def get_reset_sampler(self):
+        """-> (ResetSamplerConfig, rows [total][B])"""
+        cfg = _abi.ResetSamplerConfig()
+        self._rc(self.lib.sai2b_get_reset_sampler(self.h, C.byref(cfg), None))
+        rows = np.empty((self.reset_sampler_layout(cfg)["total"], self.B))
+        self._rc(self.lib.sai2b_get_reset_sampler(self.h, None, C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def reset_robots_sampled(self, mask):
+        """reset_robots() for the robots the mask selects with their start state and goals drawn on the device (sai2b.h "episode
+        starts"); mask numpy or torch CUDA (then nothing synchronises)"""
+        pm, km = self._mask(mask)  # (None: ValueError)
+        self._rc(self.lib.sai2b_reset_robots_sampled(self.h, pm, self._dev(mask)))
+
+    def reset_sampler_counts(self):
+        """of the last reset_robots_sampled(): dict 'reset' -> robots reset, 'rejected' -> candidates rejected, 'exhausted' ->
+        robots that got q_nominal"""
+        c = (C.c_int * 3)()
+        self._rc(self.lib.sai2b_get_reset_sampler_counts(self.h, c))
+        return dict(zip(_abi.RESET_SAMPLER_COUNTS, (int(x) for x in c)))
+
+    def reset_sampler_state(self):
+        """-> dict episode [B], tries [B] (int32): the episode counter, the candidates used by the call that reset the robot last"""
+        e, t = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        self._rc(self.lib.sai2b_get_reset_sampler_state(self.h, C.c_void_p(e.ctypes.data), C.c_void_p(t.ctypes.data)))
+        return dict(episode=e, tries=t)
+
     # -- snapshot banks (sai2b.h "snapshot banks")
     def snapshot_words(self, what=_abi.SNAP_EPISODE):
         """4-byte words of one robot's state for this controller as configured now"""

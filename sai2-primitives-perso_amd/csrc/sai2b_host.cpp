@@ -14,6 +14,7 @@
 
 #include "sai2b_launch.h"
 #include "sai2b_snapshot_layout.h"
+#include "sai2b_reset_sampler_layout.h"
 #include "sai2b_model_host.h"
 #include "sai2b_baked_panda.h"
 
@@ -153,6 +154,15 @@ struct sai2b_ctx {
 	int* act_counts = nullptr;
 	double* act_in = nullptr;
 	unsigned char* act_mask = nullptr;
+	// episode sampler (sai2b_set_reset_sampler): the configuration in force and its row layout, the per-robot rows (room for
+	// rs_rows_cap rows), the episode counters and the tries of the last reset [2][B] and the device counters of the last call,
+	// created on first use
+	bool rs_on = false;
+	sai2b_reset_sampler_config rs_cfg = {};
+	sai2b::RsLayout rs_lay;
+	double* rs_rows = nullptr;
+	int rs_rows_cap = 0;
+	int *rs_state = nullptr, *rs_counts = nullptr;
 	// sai2b_reinitialize_robots / sai2b_reset_robots with host arguments: the [B]-byte mask and the [2 * dof][B] q, dq rows are
 	// staged here, created on first use
 	unsigned char* reset_mask = nullptr;
@@ -1092,10 +1102,15 @@ extern "C" int sai2b_reinitialize(sai2b_ctx* ctx) {
 }
 
 // sai2b_reinitialize_robots (episode = false) and sai2b_reset_robots (episode = true): one launch of reset_subset_kernel
+// and sai2b_reset_robots_sampled (episode and sampled = true, q and dq NULL): one launch of reset_sampled_kernel in its place
+static sai2b::RsParams reset_sampler_params(const sai2b_ctx* ctx);
 static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned char* mask, const double* q, const double* dq, int on_device,
-						bool episode) {
+						bool episode, bool sampled = false) {
 	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": null ctx");
+	if (sampled && !ctx->rs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": no reset sampler is configured (sai2b_set_reset_sampler)");
 	if (!mask) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": mask is NULL");
+	if (sampled && ctx->rs_cfg.use_clearance && !ctx->h_params.contact)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": reset sampler: use_clearance needs a contact (sai2b_set_contact)");
 	if (task < -1 || task >= ctx->T) return set_error(ctx, SAI2B_INVALID_ARGUMENT, std::string(fn) + ": task must be -1 (every task) or a task index");
 	if (int rc_ = flush_update(ctx)) return rc_;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1127,7 +1142,12 @@ static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned
 	// sai2b_task_reinitialize has it).
 	int flags = episode ? sai2b::RESET_EPISODE : 0;
 	if (!ctx->q_is_pose && (task < 0 || ctx->T == 1)) flags |= sai2b::RESET_KEEP_POSE;
-	if (sai2b::launch_reset_subset(ctx->d_params, ctx->B, d_mask, d_q, d_dq, ctx->q, ctx->dq, ctx->q_pose, task, flags, ctx->stream))
+	if (sampled) {
+		HIP_TRY(ctx, hipMemsetAsync(ctx->rs_counts, 0, sai2b::RS_COUNTS * sizeof(int), ctx->stream));
+		if (sai2b::launch_reset_sampled(ctx->d_params, ctx->B, reset_sampler_params(ctx), d_mask, ctx->q, ctx->dq, ctx->q_pose,
+										flags & sai2b::RESET_KEEP_POSE, ctx->stream))
+			return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
+	} else if (sai2b::launch_reset_subset(ctx->d_params, ctx->B, d_mask, d_q, d_dq, ctx->q, ctx->dq, ctx->q_pose, task, flags, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
 	// hardware: a reset robot starts a new episode at period 0 (a re-initialisation alone leaves its clocks as they are)
 	if (episode && ctx->hw_on) {
@@ -1149,6 +1169,10 @@ static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned
 	for (int t = 0; t < ctx->T; t++)
 		if (task < 0 || t == task || d_q || d_dq) ctx->tio[t].model_fresh = false;
 	return on_device ? caller_after_read(ctx) : SAI2B_OK;
+}
+
+extern "C" int sai2b_reset_robots_sampled(sai2b_ctx* ctx, const unsigned char* mask, int on_device) {
+	return reset_subset(ctx, "sai2b_reset_robots_sampled", -1, mask, nullptr, nullptr, on_device, true, true);
 }
 
 extern "C" int sai2b_reinitialize_robots(sai2b_ctx* ctx, int task, const unsigned char* mask, int on_device) {
@@ -2290,6 +2314,119 @@ static sai2b::HwStream hardware_stream(const sai2b_ctx* ctx) {
 	return s;
 }
 
+// ---- episode starts (the sampler of sai2b_reset_robots_sampled) ----
+extern "C" int sai2b_default_reset_sampler(sai2b_reset_sampler_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_reset_sampler: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->max_tries = 8, cfg->ratio_task = -1, cfg->box_task = -1;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_validate_reset_sampler(const sai2b_reset_sampler_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+											char* msg, int msg_len) {
+	// (whether a contact is in force is a context's business: sai2b_set_reset_sampler)
+	const std::string err = robot_dof == N ? sai2b::rs_config_error(cfg, tasks, n_tasks, true) : "reset sampler: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_reset_sampler_config(void) { return (int)sizeof(sai2b_reset_sampler_config); }
+extern "C" int sai2b_reset_sampler_config_layout(const sai2b_reset_sampler_config* cfg, const sai2b_task_config* tasks, int n_tasks, int robot_dof,
+												 int block, int task, int* first_row, int* n_rows, int* total_rows) {
+	if (!cfg || robot_dof != N || n_tasks < 0 || n_tasks > SAI2B_MAX_TASKS || (n_tasks > 0 && !tasks) || block < 0 || block > 4 ||
+		(block == 4 && (task < 0 || task >= n_tasks)))
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_reset_sampler_config_layout: bad arguments");
+	const sai2b::RsLayout L = sai2b::rs_layout(*cfg, tasks, n_tasks, N);
+	int first = -1, rows = 0;
+	if (block < 4)
+		first = L.first[block], rows = N;
+	else if (L.goal_first[task] >= 0)
+		first = L.goal_first[task], rows = L.goal_rows[task];
+	if (first_row) *first_row = first;
+	if (n_rows) *n_rows = rows;
+	if (total_rows) *total_rows = L.total;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_reset_sampler(sai2b_ctx* ctx, const sai2b_reset_sampler_config* cfg, const double* rows, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_reset_sampler: null ctx");
+	std::string err = sai2b::rs_config_error(cfg, ctx->cfg, ctx->T, ctx->h_params.contact != nullptr);
+	const size_t B = ctx->B;
+	sai2b::RsLayout L;
+	if (err.empty()) {
+		L = sai2b::rs_layout(*cfg, ctx->cfg, ctx->T, N);
+		if (rows && !on_device) err = sai2b::rs_rows_error(L, ctx->cfg, ctx->T, N, ctx->model.q_lower, ctx->model.q_upper, rows, B);
+	}
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_reset_sampler: " + err);
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (ctx->rs_rows_cap < L.total) {  // (an earlier, smaller buffer stays with the context until it is destroyed)
+		double* fresh = nullptr;
+		if ((rc = dev_alloc(ctx, &fresh, (size_t)L.total * B))) return rc;
+		ctx->rs_rows = fresh, ctx->rs_rows_cap = L.total;
+	}
+	if (!ctx->rs_state && (rc = dev_alloc(ctx, &ctx->rs_state, 2 * B))) return rc;
+	if (!ctx->rs_counts && (rc = dev_alloc(ctx, &ctx->rs_counts, sai2b::RS_COUNTS))) return rc;
+	// rows in force are rewritten in place: the sampler is taken out of force first, as sai2b_set_hardware does
+	ctx->rs_on = false;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->rs_state, 0, 2 * B * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->rs_counts, 0, sai2b::RS_COUNTS * sizeof(int), ctx->stream));
+	std::vector<double> defaults;
+	if (!rows) {
+		defaults.resize((size_t)L.total * B);
+		sai2b::rs_default_rows(L, N, ctx->model.q_lower, ctx->model.q_upper, B, defaults.data());
+	}
+	if ((rc = copy_rows(ctx, ctx->rs_rows, rows ? rows : defaults.data(), L.total, rows ? on_device : 0))) return rc;
+	ctx->rs_cfg = *cfg;
+	ctx->rs_lay = L;
+	ctx->rs_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_reset_sampler(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_reset_sampler: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	ctx->rs_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_reset_sampler(sai2b_ctx* ctx, sai2b_reset_sampler_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler: null ctx");
+	if (!ctx->rs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler: no reset sampler is configured (sai2b_set_reset_sampler)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) *cfg = ctx->rs_cfg;
+	return fetch_rows(ctx, ctx->rs_rows, 0, ctx->rs_lay.total, rows);
+}
+extern "C" int sai2b_get_reset_sampler_counts(sai2b_ctx* ctx, int counts[3]) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler_counts: null ctx");
+	if (!ctx->rs_on || !counts)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler_counts: no reset sampler is configured (sai2b_set_reset_sampler), or counts is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->rs_counts, sai2b::RS_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_reset_sampler_state(sai2b_ctx* ctx, int* episode, int* tries) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler_state: null ctx");
+	if (!ctx->rs_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_reset_sampler_state: no reset sampler is configured (sai2b_set_reset_sampler)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	if (episode) HIP_TRY(ctx, hipMemcpyAsync(episode, ctx->rs_state, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (tries) HIP_TRY(ctx, hipMemcpyAsync(tries, ctx->rs_state + B, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+// what reset_sampled_kernel takes from the context
+static sai2b::RsParams reset_sampler_params(const sai2b_ctx* ctx) {
+	const sai2b_reset_sampler_config& c = ctx->rs_cfg;
+	sai2b::RsParams p;
+	p.rows = ctx->rs_rows, p.episode = ctx->rs_state, p.tries = ctx->rs_state + ctx->B, p.counts = ctx->rs_counts;
+	p.rng.key0 = (unsigned)(c.seed & 0xffffffffull), p.rng.key1 = (unsigned)(c.seed >> 32), p.rng.first_robot = c.first_robot;
+	p.max_tries = c.max_tries, p.goal_tasks = c.goal_tasks, p.absolute_position = c.absolute_position;
+	p.ratio_task = c.ratio_task, p.box_task = c.box_task, p.use_clearance = c.use_clearance;
+	p.min_ratio = c.min_ratio, p.clearance = c.clearance;
+	for (int k = 0; k < 3; k++) p.box_lower[k] = c.box_lower[k], p.box_upper[k] = c.box_upper[k];
+	for (int t = 0; t < SAI2B_MAX_TASKS; t++) p.goal_row[t] = ctx->rs_lay.goal_first[t];
+	return p;
+}
+
 // ---- observations and episode-end flags ----
 namespace {
 constexpr int OBS_ALL_BLOCKS = SAI2B_OBS_Q | SAI2B_OBS_DQ | SAI2B_OBS_TAU | SAI2B_OBS_LIMIT_MARGIN | SAI2B_OBS_EPISODE_STEP | SAI2B_OBS_CONTACT;
@@ -3253,6 +3390,8 @@ static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
 	d.hardware_depth = d.hardware && epi ? ctx->hw_cfg.max_delay : 0;
 	// the reward's accumulators exist from the first sai2b_set_reward on
 	d.reward = epi && ctx->rew_state != nullptr;
+	// the sampler's episode counters exist from the first sai2b_set_reset_sampler on
+	d.reset_sampler = epi && ctx->rs_state != nullptr;
 	return d;
 }
 
@@ -3295,6 +3434,7 @@ static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
 		case SNAP_HW_SENSOR: return ctx->hw_sensor;
 		case SNAP_REWARD_STATE: return ctx->rew_state;
 		case SNAP_REWARD_EPISODE: return ctx->rew_episode;
+		case SNAP_RS_EPISODE: return ctx->rs_state;
 		default: return nullptr;
 	}
 }

@@ -230,4 +230,25 @@ int launch_sense(int B, const SenseParams& p, hipStream_t stream);
 // the selected robots' period := 0, episode += 1; mask [B] device bytes
 int launch_hardware_reset(int B, const unsigned char* mask, int* clock, hipStream_t stream);
 
+// sai2b_reset_robots_sampled (sai2b_otg.hip: reset_sampled_kernel): launch_reset_subset with RESET_EPISODE for the masked robots,
+// their q, dq and goals drawn in the same launch. The sampler's own parameter block, passed by value as a kernel argument like
+// ObsParams; DevParams is not touched by the feature. Rows are rows of the [rows][B] per-robot buffer (sai2b_reset_sampler_layout.h).
+constexpr int RS_COUNTS = 3;  // robots reset, candidates rejected, robots exhausted
+struct RsParams {
+	const double* rows = nullptr;  // q_lower, q_upper, dq_sigma, q_nominal [N] each, then the goal rows
+	int* episode = nullptr;		   // [B]
+	int* tries = nullptr;		   // [B]
+	int* counts = nullptr;		   // [RS_COUNTS], zeroed by the caller on the stream ahead of the launch
+	HwStream rng;
+	int max_tries = 1;
+	unsigned goal_tasks = 0, absolute_position = 0;
+	int ratio_task = -1, box_task = -1, use_clearance = 0;
+	int goal_row[SAI2B_MAX_TASKS] = {-1, -1, -1, -1};  // first goal row of task t, -1: none
+	double min_ratio = 0, clearance = 0;
+	double box_lower[3] = {}, box_upper[3] = {};
+};
+// mask [B] device bytes; q_state / dq_state / q_pose: the ctx buffers; flags: RESET_KEEP_POSE or 0 (RESET_EPISODE is implied)
+int launch_reset_sampled(const DevParams* d_params, int B, const RsParams& rs, const unsigned char* mask, double* q_state, double* dq_state,
+						 double* q_pose, int flags, hipStream_t stream);
+
 }  // namespace sai2b

@@ -27,6 +27,7 @@
 #include "sai2b_otg_core.hpp"
 #include "sai2b_otg_group.hpp"
 #include "sai2b_otg3_core.hpp"
+#include "sai2b_reset_draw.h"
 
 namespace sai2b {
 namespace {
@@ -858,6 +859,15 @@ int launch_reset_subset(const DevParams* d_params, int B, const unsigned char* m
 						double* dq_state, double* q_pose, int only_task, int flags, hipStream_t stream) {
 	hipLaunchKernelGGL(reset_subset_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, mask, q_new, dq_new, q_state, dq_state, q_pose,
 					   only_task, flags);
+	return launch_result();
+}
+
+// sai2b_reset_robots_sampled: reset_subset_kernel's episode reset with the state and the goals drawn in the same launch
+#include "sai2b_reset_sampled.inc"
+
+int launch_reset_sampled(const DevParams* d_params, int B, const RsParams& rs, const unsigned char* mask, double* q_state, double* dq_state,
+						 double* q_pose, int flags, hipStream_t stream) {
+	hipLaunchKernelGGL(reset_sampled_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_params, rs, mask, q_state, dq_state, q_pose, flags);
 	return launch_result();
 }
 

@@ -30,22 +30,26 @@ enum SnapBlock {
 	// ---- appended for the reward's accumulators (sai2b_set_reward), both episode: return, discount, last return, tau_prev; last
 	// length and tau_prev's valid flag (int)
 	SNAP_REWARD_STATE, SNAP_REWARD_EPISODE,
+	// ---- appended for the episode sampler (sai2b_set_reset_sampler), episode: the per-robot episode counter its draws are keyed by (int)
+	SNAP_RS_EPISODE,
 	SNAP_BLOCKS
 };
 static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS] = {
 	"q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i", "popc_q",
 	"N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status",
 	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench",
-	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor", "reward_state", "reward_episode"};
-// where a block stands in the sequence snapshot_blocks() draws from: the hardware's and the reward's episode blocks ahead of the
-// environment group
+	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor", "reward_state", "reward_episode",
+	"reset_sampler_episode"};
+// where a block stands in the sequence snapshot_blocks() draws from: the hardware's, the reward's and the sampler's episode blocks
+// ahead of the environment group
 static inline int snap_block_order(int block) {
 	constexpr int hw_episode = SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1, reward = SNAP_REWARD_EPISODE - SNAP_REWARD_STATE + 1;
-	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1;
-	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + hw_episode + reward;
+	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1, sampler = 1;
+	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + hw_episode + reward + sampler;
 	if (block >= SNAP_HW_HISTORY && block <= SNAP_HW_CLOCK) return block - environment;
 	if (block >= SNAP_REWARD_STATE && block <= SNAP_REWARD_EPISODE) return block - environment - hw_environment;
-	if (block >= SNAP_HW_ACTUATOR && block <= SNAP_HW_SENSOR) return block + reward;
+	if (block == SNAP_RS_EPISODE) return block - environment - hw_environment;
+	if (block >= SNAP_HW_ACTUATOR && block <= SNAP_HW_SENSOR) return block + reward + sampler;
 	return block;
 }
 
@@ -72,7 +76,8 @@ struct SnapDesc {
 	int payload, plant_payload;
 	int hardware;		 // the buffers of the actuator and sensor models exist (0: none, and hardware_depth is 0)
 	int hardware_depth;	 // D: the torque history holds D + 1 periods
-	int reward;			 // the reward's accumulators exist. Last: code that zeroes a description and fills the fields above stays valid
+	int reward;			 // the reward's accumulators exist
+	int reset_sampler;	 // the episode sampler's counter exists. Last: code that zeroes a description and fills the fields above stays valid
 };
 
 struct SnapRow {
@@ -82,13 +87,14 @@ struct SnapRow {
 	int first_word;	  // first 4-byte word of the block in a robot's bank column
 	int first_row;	  // rows of all blocks before this one
 };
-constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6 + 2;
+constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6 + 2;	 // the blocks up to the reward's (a description without the sampler)
+constexpr int SNAP_TABLE_CAPACITY = SNAP_MAX_ROWS_TABLE + 1;			 // and the sampler's: what every table below has room for
 
 struct SnapLayout {
 	int n = 0;
 	int words = 0, rows = 0;  // per robot
 	unsigned long long fingerprint = 0;
-	SnapRow row[SNAP_MAX_ROWS_TABLE];
+	SnapRow row[SNAP_TABLE_CAPACITY];
 };
 
 static inline int snap_goal_rows(const SnapTaskDesc& t) { return t.kind == SAI2B_MOTION_FORCE_TASK ? MFT_GOAL_ROWS : 3 * t.k0; }
@@ -127,6 +133,7 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_HW_CLOCK, -1, d.hardware ? 2 : 0, 4);
 		add(SNAP_REWARD_STATE, -1, d.reward ? 3 + d.dof : 0, 8);
 		add(SNAP_REWARD_EPISODE, -1, d.reward ? 2 : 0, 4);
+		add(SNAP_RS_EPISODE, -1, d.reset_sampler ? 1 : 0, 4);
 	}
 	if (d.what & SNAP_ENVIRONMENT_BIT) {
 		add(SNAP_PAYLOAD, -1, d.payload ? PAYLOAD_ROWS : 0, 8);
@@ -155,6 +162,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 	// only with the feature: a description without it keeps the fingerprint it had before the fields existed
 	if (d.hardware != 0) mix(d.hardware), mix(d.hardware_depth);
 	if (d.reward != 0) mix(d.reward);
+	if (d.reset_sampler != 0) mix(d.reset_sampler);
 	return h;
 }
 
@@ -162,7 +170,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 // and stays 8-byte aligned in a [word][capacity] bank of any capacity. Words are contiguous.
 static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 	SnapLayout L;
-	SnapRow all[SNAP_MAX_ROWS_TABLE];
+	SnapRow all[SNAP_TABLE_CAPACITY];
 	const int n = snapshot_blocks(d, all);
 	for (int bytes = 8; bytes >= 4; bytes -= 4)
 		for (int i = 0; i < n; i++) {
@@ -180,7 +188,7 @@ static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 static inline bool snapshot_first_difference(const SnapDesc& a, const SnapDesc& b, char* msg, int len) {
 	if (a.dof != b.dof) return std::snprintf(msg, len, "block q: %d joints against %d", a.dof, b.dof), true;
 	if (a.what != b.what) return std::snprintf(msg, len, "block q: groups %d against %d", a.what, b.what), true;
-	SnapRow ra[SNAP_MAX_ROWS_TABLE], rb[SNAP_MAX_ROWS_TABLE];
+	SnapRow ra[SNAP_TABLE_CAPACITY], rb[SNAP_TABLE_CAPACITY];
 	const int na = snapshot_blocks(a, ra), nb = snapshot_blocks(b, rb);
 	for (int i = 0; i < (na < nb ? na : nb); i++) {
 		const SnapRow &x = ra[i], &y = rb[i];

@@ -87,6 +87,19 @@ def reset_robots(ctrl, world, rank, mask, q=None, dq=None):
     ctrl.reset_robots(*[shard_rows(a, world, rank) for a in (mask, q, dq)])
 
 
+def set_reset_sampler(ctrl, world, rank, global_batch, rows=None, first_robot=0, **kwargs):
+    """Controller.set_reset_sampler on this rank's shard of the per-robot rows [total][global_batch] given for the whole batch
+    (None: the defaults), with first_robot (the whole batch's: its robot 0) moved on by the shard's first global index: every
+    robot draws the start state and the goals it draws in the one-context run"""
+    lo, _ = shard_bounds(global_batch, world, rank)
+    ctrl.set_reset_sampler(rows=shard_rows(rows, world, rank), first_robot=int(first_robot) + lo, **kwargs)
+
+
+def reset_robots_sampled(ctrl, world, rank, mask):
+    """Controller.reset_robots_sampled on this rank's shard of a mask given for the whole batch"""
+    ctrl.reset_robots_sampled(shard_rows(mask, world, rank))
+
+
 def observe(ctrl, world, rank, out=None, done=None):
     """Controller.observe on this rank's shard, written into this rank's columns [lo, hi) of host arrays given for the whole
     batch: out [rows][global_batch] float64, done [global_batch] uint8 (one of the two may be None: not wanted). -> (lo, hi)"""
