@@ -149,7 +149,23 @@ struct EpisodeStats {
 struct ResetSamplerCounts {
 	int reset = 0, rejected = 0, exhausted = 0;	 // robots reset; candidates rejected; robots that got q_nominal
 };
+// of the last randomizeRobots, counted on the device (sai2b_get_env_sampler_counts)
+struct EnvSamplerCounts {
+	int drawn = 0, lag_clipped = 0;	 // robots drawn; robots with a lag clipped at 1
+};
 namespace detail {
+// what setEnvSampler checks ahead of the device: the configuration alone (sai2b_validate_env_sampler)
+inline void checkEnvSampler(const sai2b_env_sampler_config& cfg, const int dof) {
+	char msg[256];
+	if (sai2b_validate_env_sampler(&cfg, dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(msg);
+}
+inline EnvSamplerCounts envSamplerCounts(sai2b_ctx* ctx) {
+	int c[2];
+	check(ctx, sai2b_get_env_sampler_counts(ctx, c));
+	EnvSamplerCounts out;
+	out.drawn = c[0], out.lag_clipped = c[1];
+	return out;
+}
 // what setResetSampler checks ahead of the device: the configuration against the hierarchy (sai2b_validate_reset_sampler) and
 // rows [total rows][B] (or empty: the defaults); returns the total rows
 inline int checkResetSampler(const sai2b_reset_sampler_config& cfg, const std::vector<sai2b_task_config>& tasks, const int dof, const size_t B,
@@ -1257,6 +1273,18 @@ public:
 		detail::check(_ctx, sai2b_reset_robots_sampled(_ctx, mask.data(), 0));
 	}
 	ResetSamplerCounts resetSamplerCounts() const { return detail::resetSamplerCounts(_ctx); }
+	// The plant drawn on the device (sai2b.h "environment sampler"): the rows of the features of cfg.groups as they are now become
+	// the nominal; randomizeRobots redraws the selected robots' plant, groups = 0: every configured group
+	void setEnvSampler(const sai2b_env_sampler_config& cfg) {
+		detail::checkEnvSampler(cfg, _robot->dof());
+		detail::check(_ctx, sai2b_set_env_sampler(_ctx, &cfg));
+	}
+	void clearEnvSampler() { detail::check(_ctx, sai2b_clear_env_sampler(_ctx)); }
+	void randomizeRobots(const std::vector<unsigned char>& mask, const unsigned groups = 0) {
+		detail::checkResetArguments(_robot->dof(), (size_t)_robot->batch(), mask, {}, {}, "randomizeRobots");
+		detail::check(_ctx, sai2b_randomize_robots(_ctx, mask.data(), groups, 0));
+	}
+	EnvSamplerCounts envSamplerCounts() const { return detail::envSamplerCounts(_ctx); }
 	std::shared_ptr<JointTask> getJointTaskByName(const std::string& task_name) {
 		for (auto& task : _tasks)
 			if (task->getTaskName() == task_name) {
@@ -1440,6 +1468,30 @@ public:
 		for (auto& sh : _shards) {
 			const ResetSamplerCounts c = detail::resetSamplerCounts(sh.ctx);
 			out.reset += c.reset, out.rejected += c.rejected, out.exhausted += c.exhausted;
+		}
+		return out;
+	}
+	// The plant drawn on the device for the whole sharded batch: every shard gets first_robot = cfg.first_robot + its first global
+	// index, so the draws are those of one context
+	void setEnvSampler(const sai2b_env_sampler_config& cfg) {
+		detail::checkEnvSampler(cfg, _dof);
+		forAll([&](Shard& sh) {
+			sai2b_env_sampler_config c = cfg;
+			c.first_robot = cfg.first_robot + (unsigned)sh.lo;
+			detail::check(sh.ctx, sai2b_set_env_sampler(sh.ctx, &c));
+		});
+	}
+	void clearEnvSampler() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_env_sampler(sh.ctx)); }); }
+	void randomizeRobots(const std::vector<unsigned char>& mask, const unsigned groups = 0) {
+		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "randomizeRobots");
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_randomize_robots(sh.ctx, mask.data() + sh.lo, groups, 0)); });
+	}
+	// summed over the shards
+	EnvSamplerCounts envSamplerCounts() {
+		EnvSamplerCounts out;
+		for (auto& sh : _shards) {
+			const EnvSamplerCounts c = detail::envSamplerCounts(sh.ctx);
+			out.drawn += c.drawn, out.lag_clipped += c.lag_clipped;
 		}
 		return out;
 	}

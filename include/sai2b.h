@@ -415,7 +415,12 @@ enum sai2b_buffer {
 	 * return of the episode that ended last, tau_prev [dof]; and [2][B] ints = length of the episode that ended last, tau_prev is
 	 * valid. NULL until a reward has been set (and after it is cleared). */
 	SAI2B_BUF_REWARD_STATE = 18,
-	SAI2B_BUF_REWARD_EPISODE = 19
+	SAI2B_BUF_REWARD_EPISODE = 19,
+	/* what the environment sampler (sai2b_set_env_sampler) drew for every robot, [total_rows][B] doubles in the layout of
+	 * sai2b_env_sampler_config_layout: the scales, offsets, height, tilt angle and axis, delay and push themselves, privileged
+	 * information for a critic or an identification network. Zero for a robot that has not been drawn yet. NULL until a sampler has
+	 * been set (and after it is cleared). */
+	SAI2B_BUF_ENV_SAMPLE = 20
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -1073,6 +1078,115 @@ int sai2b_get_reset_sampler_counts(sai2b_ctx* ctx, int counts[3]);
 /* host arrays [B] each, any NULL: the episode counter e, and the candidates the robot used in the call that reset it last
  * (max_tries + 1: exhausted; 0: never reset). SAI2B_INVALID_ARGUMENT without a sampler. Waits for the ctx stream. */
 int sai2b_get_reset_sampler_state(sai2b_ctx* ctx, int* episode, int* tries);
+
+/* ------------------------------------------------------------------ environment sampler
+ * Domain randomisation on the device: sai2b_randomize_robots redraws the plant of the robots a [B] byte mask selects, in ONE
+ * launch: the payload, the contact plane and its material, the joint dynamics, the actuator and sensor models and a timed push,
+ * each a GROUP (enum sai2b_env_group) that can be drawn alone. In the resident loop it stands ahead of the reset:  tick,
+ * sai2b_sim_step(NULL), sai2b_observe_reward, policy, sai2b_apply_action, sai2b_randomize_robots(done),
+ * sai2b_reset_robots_sampled(done)  so that the reset's clearance criterion sees the new plane. A context that never configures
+ * the sampler launches and allocates exactly what it does without the feature. Everything in sai2b_env_sampler_config is
+ * batch-uniform; per-robot variety comes from the NOMINAL rows and the draws.
+ *
+ * SET AND NOMINAL. sai2b_set_env_sampler needs every feature named in `groups` in force: a plant payload (and, with payload_target
+ * SAI2B_PAYLOAD_BOTH, a controller payload on the same link), a contact, joint dynamics, hardware (with delay_upper <= its
+ * max_delay), an external wrench. It copies, device to device, the per-robot rows of those features as they are now into nominal
+ * buffers; every later draw is `nominal op draw`, so draws never compound. A feature setter called afterwards does NOT refresh the
+ * nominal: call sai2b_set_env_sampler again. The call zeroes every robot's draw counter c and the sample rows.
+ *
+ * THE LAW, per selected robot b with c as on entry. Random numbers: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32), as the
+ * hardware's; word x gives u = (x + 0.5) 2^-32; "call j" of a stream has the counter (0, c, 256 stream + j, first_robot + b).
+ * Streams: 5 payload, 6 contact, 7 joint dynamics, 8 hardware, 9 push.
+ *   A range (sai2b_env_range) gives s = lower + (upper - lower) u, one product and one sum, never fused: lower == upper gives lower;
+ *   with log_uniform s = exp(ln lower + (ln upper - ln lower) u), the two logarithms taken on the host. A symmetric offset is
+ *   half (2 u - 1). An integer draw is lo + min((int) floor((hi - lo + 1) u), hi - lo), stored as a double.
+ *   A direction is a = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), z = 2 u0 - 1, phi = 2 pi u1: uniform on the sphere.
+ *  PAYLOAD, call 0: word 0 the mass scale s, words 1..3 the centre-of-mass offsets o_k = payload_com_half_k (2 u - 1). The plant's
+ *     rows become mass s, com_k + o_k, inertia_j s; with SAI2B_PAYLOAD_BOTH the controller's rows get the same s and o, each from
+ *     its own nominal.
+ *  CONTACT, call 0: word 0 the height h (contact_height), word 1 theta = contact_tilt_max u, words 2, 3 the axis a; call 1: words
+ *     0..2 the stiffness, damping and friction scales. p' = p + h n with the nominal n; n' = D n, D = I + sin(theta) K +
+ *     (1 - cos(theta)) K^2, K = [a]x, each component a sum of three products from the left; theta == 0 keeps n bit for bit.
+ *  JOINT DYNAMICS, parameter p = 0 armature, 1 damping, 2 friction, 3 torque limit: joint i takes word i mod 4 of call 2 p + i / 4;
+ *     row = nominal s, so a torque limit of +inf stays +inf. The two limit rows are not touched.
+ *  HARDWARE, call 0 word 0: the delay, an integer draw in [delay_lower, delay_upper] (absolute, no nominal). Parameter p = 0 lag,
+ *     1 gain, 2 torque noise: joint i takes word i mod 4 of call 1 + 2 p + i / 4; row = nominal s, the lag min(nominal s, 1), and a
+ *     robot with some lag clipped is counted. Call 7 words 0..3 and call 8 words 0, 1: the six offsets sensor_bias_half_k (2 u - 1)
+ *     added to the nominal bias; call 8 word 2: one scale for the six sensor-noise rows. The filter row and the clocks n, e are not
+ *     touched.
+ *  PUSH, absolute values, no nominal. Call 0: word 0 the force magnitude (push_force), words 1, 2 its direction, word 3 `steps`,
+ *     an integer draw in [push_steps_lower, push_steps_upper]; call 1: word 0 the moment magnitude (push_moment), words 1, 2 its
+ *     direction. Rows 0..6 of SAI2B_BUF_EXTERNAL_WRENCH become magnitude times direction, and steps. With a sparse mask and
+ *     groups = SAI2B_ENV_PUSH mid-episode this is a random shove.
+ *  Then c = c + 1, whatever the groups. Robots the mask does not select are neither read nor written.
+ * SAMPLE ROWS (SAI2B_BUF_ENV_SAMPLE, sai2b_get_env_sampler_state), the groups of the configuration in the order of their bits:
+ *   payload 4: s, o 3.  contact 8: h, theta, a 3, the three scales.  joint dynamics 4 dof: the scales of p = 0..3, dof rows each.
+ *   hardware 8 + 3 dof: delay, the scales of p = 0..2 (dof rows each), the six bias offsets, the sensor-noise scale.
+ *   push 9: force magnitude, its direction 3, steps, moment magnitude, its direction 3.
+ * A call writes the rows of the groups it draws; the others keep what an earlier call left.
+ * The draws of a robot depend on the seed, its global index and its counter alone: shards with first_robot set reproduce the
+ * one-context run bit for bit. Snapshot banks: c is a block of SAI2B_SNAP_EPISODE, the sample rows one of SAI2B_SNAP_ENVIRONMENT
+ * (they travel with the plant rows they describe); the nominal buffers, seed and first_robot are configuration and never go into
+ * a bank. This law is this library's definition. */
+enum sai2b_env_group { SAI2B_ENV_PAYLOAD = 1, SAI2B_ENV_CONTACT = 2, SAI2B_ENV_JOINT_DYNAMICS = 4, SAI2B_ENV_HARDWARE = 8, SAI2B_ENV_PUSH = 16 };
+typedef struct sai2b_env_range {
+	double lower, upper;
+	int log_uniform; /* 0 / 1 */
+	int reserved;
+} sai2b_env_range;
+typedef struct sai2b_env_sampler_config {
+	unsigned long long seed;
+	unsigned first_robot; /* global index of robot 0 of this context (0 unless the batch is a shard) */
+	unsigned groups;	  /* bits of sai2b_env_group: what the sampler may draw */
+	int payload_target;	  /* SAI2B_PAYLOAD_PLANT or SAI2B_PAYLOAD_BOTH */
+	sai2b_env_range payload_mass_scale;
+	double payload_com_half[3];		/* metres, link frame */
+	sai2b_env_range contact_height; /* metres along the nominal normal */
+	double contact_tilt_max;		/* rad, [0, pi] */
+	sai2b_env_range contact_stiffness_scale, contact_damping_scale, contact_friction_scale;
+	sai2b_env_range armature_scale, damping_scale, friction_scale, torque_limit_scale; /* one draw per joint */
+	int delay_lower, delay_upper; /* periods, within [0, max_delay of the hardware in force] */
+	sai2b_env_range lag_scale, gain_scale, torque_noise_scale; /* one draw per joint */
+	double sensor_bias_half[6];
+	sai2b_env_range sensor_noise_scale;
+	sai2b_env_range push_force, push_moment; /* N, N m */
+	int push_steps_lower, push_steps_upper;	 /* periods >= 0 */
+} sai2b_env_sampler_config;
+/* host only: every scale [1, 1], every offset, height, tilt, delay and push 0, SAI2B_PAYLOAD_PLANT, groups 0 */
+int sai2b_default_env_sampler(sai2b_env_sampler_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg, each with its own text: unknown group bits; a
+ * payload_target other than the two named; a range with lower > upper or a bound that is not finite; a scale range with
+ * lower < 0, or lower <= 0 under log_uniform; log_uniform not 0 or 1; lag_scale.lower not > 0; a negative or non-finite half;
+ * contact_tilt_max outside [0, pi]; a delay outside [0, SAI2B_MAX_ACTUATION_DELAY] or delay_lower > delay_upper; negative push
+ * steps or push_steps_lower > push_steps_upper. (contact_height may be negative; push magnitudes are scale ranges.) Every field is
+ * checked whatever `groups` says. That delay_upper <= max_delay of the hardware in force is checked against a context only. */
+int sai2b_validate_env_sampler(const sai2b_env_sampler_config* cfg, int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_env_sampler_config) as the library was compiled: a binding that mirrors the struct checks its layout with it */
+int sai2b_sizeof_env_sampler_config(void);
+/* host only, the layout arithmetic of the sample rows. group: ONE bit of sai2b_env_group. *n_rows = 0 and *first_row = -1 when
+ * cfg->groups does not hold that group; *total_rows: rows of the whole buffer. Any output may be NULL. */
+int sai2b_env_sampler_config_layout(const sai2b_env_sampler_config* cfg, int robot_dof, int group, int* first_row, int* n_rows,
+									int* total_rows);
+/* SAI2B_INVALID_ARGUMENT with the reason: what sai2b_validate_env_sampler rejects; a group whose feature is not in force;
+ * delay_upper above the hardware's max_delay. Copies the nominal rows on the ctx stream, zeroes the counters and the sample rows.
+ * A call that fails on its arguments leaves the context as it was; one that fails while copying (SAI2B_RUNTIME_ERROR) leaves it
+ * without a sampler. */
+int sai2b_set_env_sampler(sai2b_ctx* ctx, const sai2b_env_sampler_config* cfg);
+/* back to a context without a sampler: sai2b_randomize_robots fails from here on (the feature rows stay as last drawn) */
+int sai2b_clear_env_sampler(sai2b_ctx* ctx);
+/* the configuration in force; SAI2B_INVALID_ARGUMENT without a sampler */
+int sai2b_get_env_sampler(sai2b_ctx* ctx, sai2b_env_sampler_config* cfg);
+/* The law above for the robots with mask[b] != 0 and the groups of `groups` (0: every configured group); mask [B] bytes, host or
+ * (on_device != 0) device under the stream contract, staged and ordered as sai2b_reset_robots does it. One launch.
+ * SAI2B_INVALID_ARGUMENT (nothing is launched): no sampler configured; mask NULL; a bit of `groups` that was not configured; a
+ * group to be drawn whose feature has been cleared since (or whose hardware now has max_delay < delay_upper). */
+int sai2b_randomize_robots(sai2b_ctx* ctx, const unsigned char* mask, unsigned groups, int on_device);
+/* of the last sai2b_randomize_robots, counted on the device: robots drawn; robots with a lag clipped at 1. Zeros before the first;
+ * SAI2B_INVALID_ARGUMENT without a sampler. Waits for the ctx stream. */
+int sai2b_get_env_sampler_counts(sai2b_ctx* ctx, int counts[2]);
+/* host arrays, any NULL: draw_counter [B] ints = c, sample_rows [total_rows][B]. SAI2B_INVALID_ARGUMENT without a sampler. Waits
+ * for the ctx stream. */
+int sai2b_get_env_sampler_state(sai2b_ctx* ctx, int* draw_counter, double* sample_rows);
 
 /* ------------------------------------------------------------------ snapshot banks
  * Whole robot states, saved to and restored from device memory: branching (copy one robot into K siblings, roll them out, come

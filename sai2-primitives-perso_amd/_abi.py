@@ -323,6 +323,54 @@ class ResetSamplerConfig(C.Structure):
     ]
 
 
+# enum sai2b_env_group (sai2b.h "environment sampler"), in the order of the sample rows
+ENV_PAYLOAD, ENV_CONTACT, ENV_JOINT_DYNAMICS, ENV_HARDWARE, ENV_PUSH = 1, 2, 4, 8, 16
+ENV_GROUPS = {"payload": ENV_PAYLOAD, "contact": ENV_CONTACT, "joint_dynamics": ENV_JOINT_DYNAMICS, "hardware": ENV_HARDWARE, "push": ENV_PUSH}
+ENV_SAMPLER_COUNTS = ("drawn", "lag_clipped")
+BUF_ENV_SAMPLE = 20  # SAI2B_BUF_ENV_SAMPLE
+
+
+class EnvRange(C.Structure):
+    """sai2b_env_range"""
+
+    _fields_ = [("lower", _d), ("upper", _d), ("log_uniform", _i), ("reserved", _i)]
+
+
+class EnvSamplerConfig(C.Structure):
+    """sai2b_env_sampler_config; load_library() checks the size against sai2b_sizeof_env_sampler_config()"""
+
+    _fields_ = [
+        ("seed", C.c_ulonglong),
+        ("first_robot", C.c_uint),
+        ("groups", C.c_uint),
+        ("payload_target", _i),
+        ("payload_mass_scale", EnvRange),
+        ("payload_com_half", _d * 3),
+        ("contact_height", EnvRange),
+        ("contact_tilt_max", _d),
+        ("contact_stiffness_scale", EnvRange),
+        ("contact_damping_scale", EnvRange),
+        ("contact_friction_scale", EnvRange),
+        ("armature_scale", EnvRange),
+        ("damping_scale", EnvRange),
+        ("friction_scale", EnvRange),
+        ("torque_limit_scale", EnvRange),
+        ("delay_lower", _i),
+        ("delay_upper", _i),
+        ("lag_scale", EnvRange),
+        ("gain_scale", EnvRange),
+        ("torque_noise_scale", EnvRange),
+        ("sensor_bias_half", _d * 6),
+        ("sensor_noise_scale", EnvRange),
+        ("push_force", EnvRange),
+        ("push_moment", EnvRange),
+        ("push_steps_lower", _i),
+        ("push_steps_upper", _i),
+    ]
+
+
+ENV_RANGE_FIELDS = tuple(n for n, t in EnvSamplerConfig._fields_ if t is EnvRange)
+
 # enum sai2b_action_mode / sai2b_action_block (sai2b.h "actions"); name -> value, blocks in row order
 ACT_NONE, ACT_DELTA_GOAL, ACT_DELTA_CURRENT, ACT_ABSOLUTE = 0, 1, 2, 3
 ACT_POSITION, ACT_ORIENTATION, ACT_FORCE, ACT_MOMENT = 1, 2, 4, 8
@@ -495,6 +543,16 @@ EXPORTS = [
     "sai2b_reset_robots_sampled",
     "sai2b_get_reset_sampler_counts",
     "sai2b_get_reset_sampler_state",
+    "sai2b_default_env_sampler",
+    "sai2b_validate_env_sampler",
+    "sai2b_sizeof_env_sampler_config",
+    "sai2b_env_sampler_config_layout",
+    "sai2b_set_env_sampler",
+    "sai2b_clear_env_sampler",
+    "sai2b_get_env_sampler",
+    "sai2b_randomize_robots",
+    "sai2b_get_env_sampler_counts",
+    "sai2b_get_env_sampler_state",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -514,6 +572,9 @@ SNAP_BLOCKS = ("q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate",
                "popc_q", "N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status", "payload",
                "plant_payload", "contact", "joint_dynamics", "external_wrench", "hw_history", "hw_filter", "hw_applied", "hw_clock",
                "hw_actuator", "hw_sensor", "reward_state", "reward_episode", "reset_sampler_episode")
+# the blocks appended for the environment sampler, and every block id's name (enum SnapBlock of csrc/sai2b_snapshot_layout.h)
+SNAP_ENV_SAMPLER_BLOCKS = ("env_sampler_counter", "env_sampler_sample")
+SNAP_BLOCK_NAMES = SNAP_BLOCKS + SNAP_ENV_SAMPLER_BLOCKS
 
 _lib = None
 
@@ -710,5 +771,18 @@ def load_library():
     if lib.sai2b_sizeof_reset_sampler_config() != C.sizeof(ResetSamplerConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_reset_sampler_config is {lib.sai2b_sizeof_reset_sampler_config()} bytes in the library, "
                            f"{C.sizeof(ResetSamplerConfig)} in the ctypes mirror")
+    lib.sai2b_default_env_sampler.argtypes = [P(EnvSamplerConfig)]
+    lib.sai2b_validate_env_sampler.argtypes = [P(EnvSamplerConfig), _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_env_sampler_config.argtypes = []
+    lib.sai2b_env_sampler_config_layout.argtypes = [P(EnvSamplerConfig), _i, _i, P(_i), P(_i), P(_i)]
+    lib.sai2b_set_env_sampler.argtypes = [vp, P(EnvSamplerConfig)]
+    lib.sai2b_clear_env_sampler.argtypes = [vp]
+    lib.sai2b_get_env_sampler.argtypes = [vp, P(EnvSamplerConfig)]
+    lib.sai2b_randomize_robots.argtypes = [vp, vp, C.c_uint, _i]
+    lib.sai2b_get_env_sampler_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_get_env_sampler_state.argtypes = [vp, vp, vp]
+    if lib.sai2b_sizeof_env_sampler_config() != C.sizeof(EnvSamplerConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_env_sampler_config is {lib.sai2b_sizeof_env_sampler_config()} bytes in the library, "
+                           f"{C.sizeof(EnvSamplerConfig)} in the ctypes mirror")
     _lib = lib
     return lib

@@ -1104,6 +1104,96 @@ class Controller:
         self._rc(self.lib.sai2b_get_reset_sampler_state(self.h, C.c_void_p(e.ctypes.data), C.c_void_p(t.ctypes.data)))
         return dict(episode=e, tries=t)
 
+    # -- environment sampler (sai2b.h "environment sampler")
+    def env_sampler_config(self, seed=0, first_robot=0, groups=(), payload_target="plant", **kw):
+        """-> EnvSamplerConfig, validated. groups: names of _abi.ENV_GROUPS (or an int of bits). Every other field of
+        sai2b_env_sampler_config by its name: a range as (lower, upper), (lower, upper, log_uniform) or one number for both
+        bounds; payload_com_half [3], sensor_bias_half [6] as sequences or one number; the rest as numbers"""
+        cfg = _abi.EnvSamplerConfig()
+        if self.lib.sai2b_default_env_sampler(C.byref(cfg)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        cfg.seed, cfg.first_robot = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_robot) & 0xFFFFFFFF
+        if isinstance(groups, (int, np.integer)):
+            cfg.groups = int(groups) & 0xFFFFFFFF
+        else:
+            for g in [groups] if isinstance(groups, str) else groups:
+                if g not in _abi.ENV_GROUPS:
+                    raise ValueError(f"env sampler: unknown group {g!r} (one of {sorted(_abi.ENV_GROUPS)})")
+                cfg.groups |= _abi.ENV_GROUPS[g]
+        cfg.payload_target = _abi.PAYLOAD_TARGETS[payload_target] if isinstance(payload_target, str) else int(payload_target)
+        for name, v in kw.items():
+            if name in _abi.ENV_RANGE_FIELDS:
+                v = (v, v) if np.isscalar(v) else tuple(v)
+                if len(v) not in (2, 3):
+                    raise ValueError(f"{name}: expected (lower, upper) or (lower, upper, log_uniform)")
+                r = getattr(cfg, name)
+                r.lower, r.upper, r.log_uniform = float(v[0]), float(v[1]), int(bool(v[2])) if len(v) == 3 else 0
+            elif name in ("payload_com_half", "sensor_bias_half"):
+                n = 3 if name == "payload_com_half" else 6
+                a = np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))
+                getattr(cfg, name)[:] = [float(x) for x in a]
+            elif name == "contact_tilt_max":
+                cfg.contact_tilt_max = float(v)
+            elif name in ("delay_lower", "delay_upper", "push_steps_lower", "push_steps_upper"):
+                setattr(cfg, name, int(v))
+            else:
+                raise ValueError(f"env sampler: unknown setting {name!r}")
+        msg = C.create_string_buffer(256)
+        if self.lib.sai2b_validate_env_sampler(C.byref(cfg), self.dof, msg, 256):
+            raise ValueError(msg.value.decode() or self.lib.sai2b_last_error(None).decode())
+        return cfg
+
+    def env_sampler_layout(self, cfg):
+        """dict group name -> (first_row, n_rows) of the sample rows of `cfg` (its configured groups); 'total' -> rows of the buffer"""
+        first, n, total = C.c_int(), C.c_int(), C.c_int()
+        out = {}
+        for name, bit in _abi.ENV_GROUPS.items():
+            if self.lib.sai2b_env_sampler_config_layout(C.byref(cfg), self.dof, bit, C.byref(first), C.byref(n), C.byref(total)):
+                raise ValueError(self.lib.sai2b_last_error(None).decode())
+            if n.value:
+                out[name] = (first.value, n.value)
+        out["total"] = total.value
+        return out
+
+    def set_env_sampler(self, cfg=None, **kwargs):
+        """configure what randomize_robots() draws: an EnvSamplerConfig (or the arguments of env_sampler_config). The rows of
+        the features of its groups as they are now become the nominal every draw starts from; zeroes the draw counters"""
+        if cfg is None:
+            cfg = self.env_sampler_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_env_sampler: an EnvSamplerConfig or keyword arguments, not both")
+        self._rc(self.lib.sai2b_set_env_sampler(self.h, C.byref(cfg)))
+
+    def clear_env_sampler(self):
+        self._rc(self.lib.sai2b_clear_env_sampler(self.h))
+
+    def get_env_sampler(self):
+        """-> the EnvSamplerConfig in force"""
+        cfg = _abi.EnvSamplerConfig()
+        self._rc(self.lib.sai2b_get_env_sampler(self.h, C.byref(cfg)))
+        return cfg
+
+    def randomize_robots(self, mask, groups=0):
+        """redraw the plant of the robots the mask selects (sai2b.h "environment sampler"); groups: names of _abi.ENV_GROUPS or
+        an int of bits, 0 = every configured group; mask numpy or torch CUDA (then nothing synchronises)"""
+        if not isinstance(groups, (int, np.integer)):
+            groups = sum({_abi.ENV_GROUPS[g] for g in ([groups] if isinstance(groups, str) else groups)})
+        pm, km = self._mask(mask)  # (None: ValueError)
+        self._rc(self.lib.sai2b_randomize_robots(self.h, pm, int(groups) & 0xFFFFFFFF, self._dev(mask)))
+
+    def env_sampler_counts(self):
+        """of the last randomize_robots(): dict 'drawn' -> robots drawn, 'lag_clipped' -> robots with a lag clipped at 1"""
+        c = (C.c_int * 2)()
+        self._rc(self.lib.sai2b_get_env_sampler_counts(self.h, c))
+        return dict(zip(_abi.ENV_SAMPLER_COUNTS, (int(x) for x in c)))
+
+    def env_sampler_state(self):
+        """-> dict counter [B] (int32): the draw counter, sample [total][B]: what the last draws were"""
+        total = self.env_sampler_layout(self.get_env_sampler())["total"]
+        c, s = np.empty(self.B, dtype=np.int32), np.zeros((total, self.B))
+        self._rc(self.lib.sai2b_get_env_sampler_state(self.h, C.c_void_p(c.ctypes.data), C.c_void_p(s.ctypes.data) if total else None))
+        return dict(counter=c, sample=s)
+
     # -- snapshot banks (sai2b.h "snapshot banks")
     def snapshot_words(self, what=_abi.SNAP_EPISODE):
         """4-byte words of one robot's state for this controller as configured now"""
@@ -1114,11 +1204,11 @@ class Controller:
 
     def snapshot_layout(self, what=_abi.SNAP_EPISODE):
         """the row table behind snapshot_words(): list of dicts block (name), task (-1: none), rows, elem_bytes, first_word"""
-        tab = (C.c_int * (5 * 64))()
-        n = self.lib.sai2b_snapshot_layout(self.h, int(what), tab, 64)
+        tab = (C.c_int * (5 * 80))()
+        n = self.lib.sai2b_snapshot_layout(self.h, int(what), tab, 80)
         if n < 0:
             self._rc(_abi.INVALID_ARGUMENT)
-        return [dict(block=_abi.SNAP_BLOCKS[tab[5 * i]], task=tab[5 * i + 1], rows=tab[5 * i + 2], elem_bytes=tab[5 * i + 3],
+        return [dict(block=_abi.SNAP_BLOCK_NAMES[tab[5 * i]], task=tab[5 * i + 1], rows=tab[5 * i + 2], elem_bytes=tab[5 * i + 3],
                      first_word=tab[5 * i + 4]) for i in range(n)]
 
     def snapshot_bank(self, capacity, what=_abi.SNAP_EPISODE):

@@ -15,6 +15,7 @@
 #include "sai2b_launch.h"
 #include "sai2b_snapshot_layout.h"
 #include "sai2b_reset_sampler_layout.h"
+#include "sai2b_env_sampler_layout.h"
 #include "sai2b_model_host.h"
 #include "sai2b_baked_panda.h"
 
@@ -163,6 +164,15 @@ struct sai2b_ctx {
 	double* rs_rows = nullptr;
 	int rs_rows_cap = 0;
 	int *rs_state = nullptr, *rs_counts = nullptr;
+	// environment sampler (sai2b_set_env_sampler): the configuration in force and its sample-row layout (es_lay stays that of the
+	// last set after a clear: the snapshot layout reads it), the nominal rows (sai2b::EnvNominal), the sample rows (room for
+	// es_sample_cap rows), the draw counters [B] and the device counters of the last call, created on first use
+	bool es_on = false;
+	sai2b_env_sampler_config es_cfg = {};
+	sai2b::EnvLayout es_lay;
+	double *es_nominal = nullptr, *es_sample = nullptr;
+	int es_sample_cap = 0;
+	int *es_counter = nullptr, *es_counts = nullptr;
 	// sai2b_reinitialize_robots / sai2b_reset_robots with host arguments: the [B]-byte mask and the [2 * dof][B] q, dq rows are
 	// staged here, created on first use
 	unsigned char* reset_mask = nullptr;
@@ -1603,6 +1613,7 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_TAU_APPLIED: return ctx->hw_on ? (void*)ctx->hw_applied : nullptr;
 		case SAI2B_BUF_REWARD_STATE: return ctx->rew_on ? (void*)ctx->rew_state : nullptr;
 		case SAI2B_BUF_REWARD_EPISODE: return ctx->rew_on ? (void*)ctx->rew_episode : nullptr;
+		case SAI2B_BUF_ENV_SAMPLE: return ctx->es_on ? (void*)ctx->es_sample : nullptr;
 	}
 	return nullptr;
 }
@@ -2425,6 +2436,170 @@ static sai2b::RsParams reset_sampler_params(const sai2b_ctx* ctx) {
 	for (int k = 0; k < 3; k++) p.box_lower[k] = c.box_lower[k], p.box_upper[k] = c.box_upper[k];
 	for (int t = 0; t < SAI2B_MAX_TASKS; t++) p.goal_row[t] = ctx->rs_lay.goal_first[t];
 	return p;
+}
+
+// ---- environment sampler (sai2b_randomize_robots) ----
+extern "C" int sai2b_default_env_sampler(sai2b_env_sampler_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_env_sampler: null config");
+	sai2b::env_default_config(cfg);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_validate_env_sampler(const sai2b_env_sampler_config* cfg, int robot_dof, char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? sai2b::env_config_error(cfg) : "env sampler: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, err);
+	return SAI2B_OK;
+}
+extern "C" int sai2b_sizeof_env_sampler_config(void) { return (int)sizeof(sai2b_env_sampler_config); }
+extern "C" int sai2b_env_sampler_config_layout(const sai2b_env_sampler_config* cfg, int robot_dof, int group, int* first_row, int* n_rows,
+											   int* total_rows) {
+	int g = -1;
+	for (int k = 0; k < sai2b::ENV_GROUPS; k++)
+		if (group == 1 << k) g = k;
+	if (!cfg || robot_dof != N || g < 0) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_env_sampler_config_layout: bad arguments");
+	const sai2b::EnvLayout L = sai2b::env_layout(cfg->groups & sai2b::ENV_ALL_GROUPS, N);
+	if (first_row) *first_row = L.first[g];
+	if (n_rows) *n_rows = L.rows[g];
+	if (total_rows) *total_rows = L.total;
+	return SAI2B_OK;
+}
+// "" or the first group of `groups` whose feature is not in force as the configuration needs it
+static std::string env_feature_error(const sai2b_ctx* ctx, const sai2b_env_sampler_config& c, unsigned groups) {
+	const DevParams& hp = ctx->h_params;
+	if (groups & SAI2B_ENV_PAYLOAD) {
+		if (!hp.plant_payload) return "SAI2B_ENV_PAYLOAD needs a plant payload (sai2b_set_link_payload)";
+		if (c.payload_target == SAI2B_PAYLOAD_BOTH && (!hp.payload || hp.payload_link != hp.plant_payload_link))
+			return "SAI2B_ENV_PAYLOAD with SAI2B_PAYLOAD_BOTH needs a controller payload on the plant payload's link";
+	}
+	if ((groups & SAI2B_ENV_CONTACT) && !hp.contact) return "SAI2B_ENV_CONTACT needs a contact (sai2b_set_contact)";
+	if ((groups & SAI2B_ENV_JOINT_DYNAMICS) && !ctx->joint_on) return "SAI2B_ENV_JOINT_DYNAMICS needs joint dynamics (sai2b_set_joint_dynamics)";
+	if (groups & SAI2B_ENV_HARDWARE) {
+		if (!ctx->hw_on) return "SAI2B_ENV_HARDWARE needs hardware (sai2b_set_hardware)";
+		if (c.delay_upper > ctx->hw_cfg.max_delay) return "delay_upper exceeds max_delay of the hardware in force";
+	}
+	if ((groups & SAI2B_ENV_PUSH) && !ctx->wrench_on) return "SAI2B_ENV_PUSH needs an external wrench (sai2b_set_external_wrench)";
+	return "";
+}
+extern "C" int sai2b_set_env_sampler(sai2b_ctx* ctx, const sai2b_env_sampler_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_env_sampler: null ctx");
+	std::string err = sai2b::env_config_error(cfg);
+	if (err.empty()) err = env_feature_error(ctx, *cfg, cfg->groups);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_env_sampler: " + err);
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	const sai2b::EnvLayout L = sai2b::env_layout(cfg->groups, N);
+	const sai2b::EnvNominal M = sai2b::env_nominal(N);
+	if (!ctx->es_nominal && (rc = dev_alloc(ctx, &ctx->es_nominal, (size_t)M.total * B))) return rc;
+	if (!ctx->es_sample || ctx->es_sample_cap < L.total) {	// (an earlier, smaller buffer stays with the context until it is destroyed)
+		double* fresh = nullptr;
+		if ((rc = dev_alloc(ctx, &fresh, (size_t)std::max(L.total, 1) * B))) return rc;
+		ctx->es_sample = fresh, ctx->es_sample_cap = std::max(L.total, 1);
+	}
+	if (!ctx->es_counter && (rc = dev_alloc(ctx, &ctx->es_counter, B))) return rc;
+	if (!ctx->es_counts && (rc = dev_alloc(ctx, &ctx->es_counts, sai2b::ENV_COUNTS))) return rc;
+	// the nominal rows in force are rewritten in place: the sampler is taken out of force first, as sai2b_set_hardware does
+	ctx->es_on = false;
+	ctx->es_lay = L;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->es_counter, 0, B * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->es_counts, 0, sai2b::ENV_COUNTS * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->es_sample, 0, (size_t)ctx->es_sample_cap * B * sizeof(double), ctx->stream));
+	auto keep = [&](int row, const double* src, int rows) {
+		return hipMemcpyAsync(ctx->es_nominal + (size_t)row * B, src, (size_t)rows * B * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
+	};
+	const unsigned g = cfg->groups;
+	if (g & SAI2B_ENV_PAYLOAD) {
+		HIP_TRY(ctx, keep(M.plant_payload, ctx->payload_rows[1], sai2b::PAYLOAD_ROWS));
+		if (cfg->payload_target == SAI2B_PAYLOAD_BOTH) HIP_TRY(ctx, keep(M.payload, ctx->payload_rows[0], sai2b::PAYLOAD_ROWS));
+	}
+	if (g & SAI2B_ENV_CONTACT) HIP_TRY(ctx, keep(M.contact, ctx->contact_rows, sai2b::CONTACT_ROWS));
+	if (g & SAI2B_ENV_JOINT_DYNAMICS) HIP_TRY(ctx, keep(M.joint, ctx->joint_rows, sai2b::ENV_JOINT_PARAMS * N));
+	if (g & SAI2B_ENV_HARDWARE) {
+		HIP_TRY(ctx, keep(M.actuator, ctx->hw_act, sai2b::HW_ACT_ROWS));
+		HIP_TRY(ctx, keep(M.sensor, ctx->hw_sensor, 12));
+	}
+	ctx->es_cfg = *cfg;
+	ctx->es_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_env_sampler(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_env_sampler: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	ctx->es_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_env_sampler(sai2b_ctx* ctx, sai2b_env_sampler_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler: null ctx");
+	if (!ctx->es_on || !cfg)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler: no environment sampler is configured (sai2b_set_env_sampler), or cfg is NULL");
+	*cfg = ctx->es_cfg;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_randomize_robots(sai2b_ctx* ctx, const unsigned char* mask, unsigned groups, int on_device) {
+	const std::string fn = "sai2b_randomize_robots";
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, fn + ": null ctx");
+	if (!ctx->es_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": no environment sampler is configured (sai2b_set_env_sampler)");
+	if (!mask) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": mask is NULL");
+	const sai2b_env_sampler_config& c = ctx->es_cfg;
+	if (groups & ~c.groups) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": groups names a group the sampler was not configured with");
+	if (!groups) groups = c.groups;
+	const std::string err = env_feature_error(ctx, c, groups);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, fn + ": " + err);
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	const unsigned char* d_mask = mask;
+	if (on_device) {
+		if ((rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (!ctx->reset_mask && (rc = dev_alloc(ctx, &ctx->reset_mask, B))) return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->reset_mask, mask, B, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
+		d_mask = ctx->reset_mask;
+	}
+	const sai2b::EnvNominal M = sai2b::env_nominal(N);
+	sai2b::EnvParams p;
+	p.groups = groups, p.both = c.payload_target == SAI2B_PAYLOAD_BOTH;
+	p.counter = ctx->es_counter, p.counts = ctx->es_counts, p.sample = ctx->es_sample;
+	for (int g = 0; g < sai2b::ENV_GROUPS; g++) p.sample_row[g] = ctx->es_lay.first[g];
+	const double* nom = ctx->es_nominal;
+	p.nom_plant_payload = nom + (size_t)M.plant_payload * B, p.nom_payload = nom + (size_t)M.payload * B;
+	p.nom_contact = nom + (size_t)M.contact * B, p.nom_joint = nom + (size_t)M.joint * B;
+	p.nom_actuator = nom + (size_t)M.actuator * B, p.nom_sensor = nom + (size_t)M.sensor * B;
+	p.plant_payload = ctx->payload_rows[1], p.payload = ctx->payload_rows[0], p.contact = ctx->contact_rows, p.joint = ctx->joint_rows;
+	p.actuator = ctx->hw_act, p.sensor = ctx->hw_sensor, p.wrench = ctx->wrench_rows;
+	p.rng.key0 = (unsigned)(c.seed & 0xffffffffull), p.rng.key1 = (unsigned)(c.seed >> 32), p.rng.first_robot = c.first_robot;
+	p.draw = sai2b::env_draw_params(c);
+	HIP_TRY(ctx, hipMemsetAsync(ctx->es_counts, 0, sai2b::ENV_COUNTS * sizeof(int), ctx->stream));
+	if (sai2b::launch_env_randomize(ctx->B, p, d_mask, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, fn + ": launch failed");
+	ctx->launches++;
+	if ((groups & SAI2B_ENV_PAYLOAD) && p.both) {  // the controller's model has changed: nothing computed from the old rows may be reused
+		ctx->models_fresh = false;
+		for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
+	}
+	return on_device ? caller_after_read(ctx) : SAI2B_OK;
+}
+extern "C" int sai2b_get_env_sampler_counts(sai2b_ctx* ctx, int counts[2]) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler_counts: null ctx");
+	if (!ctx->es_on || !counts)
+		return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler_counts: no environment sampler is configured (sai2b_set_env_sampler), or counts is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->es_counts, sai2b::ENV_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_env_sampler_state(sai2b_ctx* ctx, int* draw_counter, double* sample_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler_state: null ctx");
+	if (!ctx->es_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_env_sampler_state: no environment sampler is configured (sai2b_set_env_sampler)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	if (draw_counter) HIP_TRY(ctx, hipMemcpyAsync(draw_counter, ctx->es_counter, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (sample_rows && ctx->es_lay.total)
+		HIP_TRY(ctx, hipMemcpyAsync(sample_rows, ctx->es_sample, (size_t)ctx->es_lay.total * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
 }
 
 // ---- observations and episode-end flags ----
@@ -3392,6 +3567,8 @@ static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
 	d.reward = epi && ctx->rew_state != nullptr;
 	// the sampler's episode counters exist from the first sai2b_set_reset_sampler on
 	d.reset_sampler = epi && ctx->rs_state != nullptr;
+	// the environment sampler's counters and sample rows exist from the first sai2b_set_env_sampler on; the rows are those of the last one
+	d.env_sampler = ctx->es_counter != nullptr ? 1 + ctx->es_lay.total : 0;
 	return d;
 }
 
@@ -3435,6 +3612,8 @@ static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
 		case SNAP_REWARD_STATE: return ctx->rew_state;
 		case SNAP_REWARD_EPISODE: return ctx->rew_episode;
 		case SNAP_RS_EPISODE: return ctx->rs_state;
+		case SNAP_ES_COUNTER: return ctx->es_counter;
+		case SNAP_ES_SAMPLE: return ctx->es_sample;
 		default: return nullptr;
 	}
 }

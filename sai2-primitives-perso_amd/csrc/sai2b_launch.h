@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sai2b_env_draw.h"  // EnvDraw
 #include "sai2b_params.h"
 #include "sai2b_tick_policy.h"  // TickForm, TickCall
 
@@ -250,5 +251,26 @@ struct RsParams {
 // mask [B] device bytes; q_state / dq_state / q_pose: the ctx buffers; flags: RESET_KEEP_POSE or 0 (RESET_EPISODE is implied)
 int launch_reset_sampled(const DevParams* d_params, int B, const RsParams& rs, const unsigned char* mask, double* q_state, double* dq_state,
 						 double* q_pose, int flags, hipStream_t stream);
+
+// sai2b_randomize_robots (sai2b_env_sampler.hip: env_randomize_kernel): the plant rows of the masked robots redrawn from their
+// nominal rows in one launch. Its own parameter block, passed by value as a kernel argument; DevParams is not read. A pointer
+// the groups of the call do not need may be NULL.
+constexpr int ENV_COUNTS = 2;  // robots drawn, robots with a lag clipped at 1
+struct EnvParams {
+	unsigned groups = 0;  // bits of sai2b_env_group this call draws
+	int both = 0;		  // the payload draw goes to the controller's rows too
+	int* counter = nullptr;	 // [B]
+	int* counts = nullptr;	 // [ENV_COUNTS], zeroed by the caller on the stream ahead of the launch
+	double* sample = nullptr;  // [total][B]
+	int sample_row[5] = {-1, -1, -1, -1, -1};  // first sample row of group g
+	const double *nom_plant_payload = nullptr, *nom_payload = nullptr, *nom_contact = nullptr, *nom_joint = nullptr, *nom_actuator = nullptr,
+				 *nom_sensor = nullptr;
+	double *plant_payload = nullptr, *payload = nullptr, *contact = nullptr, *joint = nullptr, *actuator = nullptr, *sensor = nullptr,
+		   *wrench = nullptr;
+	HwStream rng;
+	EnvDraw draw;
+};
+// mask [B] device bytes
+int launch_env_randomize(int B, const EnvParams& p, const unsigned char* mask, hipStream_t stream);
 
 }  // namespace sai2b

@@ -32,23 +32,27 @@ enum SnapBlock {
 	SNAP_REWARD_STATE, SNAP_REWARD_EPISODE,
 	// ---- appended for the episode sampler (sai2b_set_reset_sampler), episode: the per-robot episode counter its draws are keyed by (int)
 	SNAP_RS_EPISODE,
-	SNAP_BLOCKS
+	SNAP_BLOCKS,  // the blocks up to the episode sampler's (a test pins the value)
+	// ---- appended for the environment sampler (sai2b_set_env_sampler): its per-robot draw counter (int), episode; the drawn
+	// quantities (the sample rows), environment: they travel with the plant rows they describe
+	SNAP_ES_COUNTER = SNAP_BLOCKS, SNAP_ES_SAMPLE,
+	SNAP_BLOCKS_ALL
 };
-static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS] = {
+static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS_ALL] = {
 	"q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i", "popc_q",
 	"N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status",
 	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench",
 	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor", "reward_state", "reward_episode",
-	"reset_sampler_episode"};
-// where a block stands in the sequence snapshot_blocks() draws from: the hardware's, the reward's and the sampler's episode blocks
-// ahead of the environment group
+	"reset_sampler_episode", "env_sampler_counter", "env_sampler_sample"};
+// where a block stands in the sequence snapshot_blocks() draws from: the hardware's, the reward's and the two samplers' episode
+// blocks ahead of the environment group, the environment sampler's sample rows at its end
 static inline int snap_block_order(int block) {
 	constexpr int hw_episode = SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1, reward = SNAP_REWARD_EPISODE - SNAP_REWARD_STATE + 1;
-	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1, sampler = 1;
+	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1, sampler = 2;
 	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + hw_episode + reward + sampler;
 	if (block >= SNAP_HW_HISTORY && block <= SNAP_HW_CLOCK) return block - environment;
 	if (block >= SNAP_REWARD_STATE && block <= SNAP_REWARD_EPISODE) return block - environment - hw_environment;
-	if (block == SNAP_RS_EPISODE) return block - environment - hw_environment;
+	if (block == SNAP_RS_EPISODE || block == SNAP_ES_COUNTER) return block - environment - hw_environment;
 	if (block >= SNAP_HW_ACTUATOR && block <= SNAP_HW_SENSOR) return block + reward + sampler;
 	return block;
 }
@@ -77,7 +81,9 @@ struct SnapDesc {
 	int hardware;		 // the buffers of the actuator and sensor models exist (0: none, and hardware_depth is 0)
 	int hardware_depth;	 // D: the torque history holds D + 1 periods
 	int reward;			 // the reward's accumulators exist
-	int reset_sampler;	 // the episode sampler's counter exists. Last: code that zeroes a description and fills the fields above stays valid
+	int reset_sampler;	 // the episode sampler's counter exists
+	int env_sampler;	 // 0: no environment sampler; else 1 + its sample rows. Last: code that zeroes a description and fills the
+						 // fields above stays valid
 };
 
 struct SnapRow {
@@ -88,13 +94,14 @@ struct SnapRow {
 	int first_row;	  // rows of all blocks before this one
 };
 constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6 + 2;	 // the blocks up to the reward's (a description without the sampler)
-constexpr int SNAP_TABLE_CAPACITY = SNAP_MAX_ROWS_TABLE + 1;			 // and the sampler's: what every table below has room for
+constexpr int SNAP_TABLE_CAPACITY = SNAP_MAX_ROWS_TABLE + 1;			 // and the episode sampler's (a test pins this value too)
+constexpr int SNAP_TABLE_ROOM = SNAP_TABLE_CAPACITY + 2;				 // and the environment sampler's two: what every table below has room for
 
 struct SnapLayout {
 	int n = 0;
 	int words = 0, rows = 0;  // per robot
 	unsigned long long fingerprint = 0;
-	SnapRow row[SNAP_TABLE_CAPACITY];
+	SnapRow row[SNAP_TABLE_ROOM];
 };
 
 static inline int snap_goal_rows(const SnapTaskDesc& t) { return t.kind == SAI2B_MOTION_FORCE_TASK ? MFT_GOAL_ROWS : 3 * t.k0; }
@@ -134,6 +141,7 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_REWARD_STATE, -1, d.reward ? 3 + d.dof : 0, 8);
 		add(SNAP_REWARD_EPISODE, -1, d.reward ? 2 : 0, 4);
 		add(SNAP_RS_EPISODE, -1, d.reset_sampler ? 1 : 0, 4);
+		add(SNAP_ES_COUNTER, -1, d.env_sampler ? 1 : 0, 4);
 	}
 	if (d.what & SNAP_ENVIRONMENT_BIT) {
 		add(SNAP_PAYLOAD, -1, d.payload ? PAYLOAD_ROWS : 0, 8);
@@ -143,6 +151,7 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_WRENCH, -1, d.wrench ? SNAP_WRENCH_MOTION_ROWS : 0, 8);
 		add(SNAP_HW_ACTUATOR, -1, d.hardware ? 1 + 3 * d.dof : 0, 8);
 		add(SNAP_HW_SENSOR, -1, d.hardware ? SNAP_HW_SENSOR_ROWS : 0, 8);
+		add(SNAP_ES_SAMPLE, -1, d.env_sampler ? d.env_sampler - 1 : 0, 8);
 	}
 	return n;
 }
@@ -163,6 +172,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 	if (d.hardware != 0) mix(d.hardware), mix(d.hardware_depth);
 	if (d.reward != 0) mix(d.reward);
 	if (d.reset_sampler != 0) mix(d.reset_sampler);
+	if (d.env_sampler != 0) mix(d.env_sampler);
 	return h;
 }
 
@@ -170,7 +180,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 // and stays 8-byte aligned in a [word][capacity] bank of any capacity. Words are contiguous.
 static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 	SnapLayout L;
-	SnapRow all[SNAP_TABLE_CAPACITY];
+	SnapRow all[SNAP_TABLE_ROOM];
 	const int n = snapshot_blocks(d, all);
 	for (int bytes = 8; bytes >= 4; bytes -= 4)
 		for (int i = 0; i < n; i++) {
@@ -188,7 +198,7 @@ static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 static inline bool snapshot_first_difference(const SnapDesc& a, const SnapDesc& b, char* msg, int len) {
 	if (a.dof != b.dof) return std::snprintf(msg, len, "block q: %d joints against %d", a.dof, b.dof), true;
 	if (a.what != b.what) return std::snprintf(msg, len, "block q: groups %d against %d", a.what, b.what), true;
-	SnapRow ra[SNAP_TABLE_CAPACITY], rb[SNAP_TABLE_CAPACITY];
+	SnapRow ra[SNAP_TABLE_ROOM], rb[SNAP_TABLE_ROOM];
 	const int na = snapshot_blocks(a, ra), nb = snapshot_blocks(b, rb);
 	for (int i = 0; i < (na < nb ? na : nb); i++) {
 		const SnapRow &x = ra[i], &y = rb[i];

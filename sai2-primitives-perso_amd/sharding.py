@@ -100,6 +100,18 @@ def reset_robots_sampled(ctrl, world, rank, mask):
     ctrl.reset_robots_sampled(shard_rows(mask, world, rank))
 
 
+def set_env_sampler(ctrl, world, rank, global_batch, first_robot=0, **kwargs):
+    """Controller.set_env_sampler with first_robot (the whole batch's: its robot 0) moved on by the shard's first global index:
+    every robot draws the plant it draws in the one-context run"""
+    lo, _ = shard_bounds(global_batch, world, rank)
+    ctrl.set_env_sampler(first_robot=int(first_robot) + lo, **kwargs)
+
+
+def randomize_robots(ctrl, world, rank, mask, groups=0):
+    """Controller.randomize_robots on this rank's shard of a mask given for the whole batch"""
+    ctrl.randomize_robots(shard_rows(mask, world, rank), groups)
+
+
 def observe(ctrl, world, rank, out=None, done=None):
     """Controller.observe on this rank's shard, written into this rank's columns [lo, hi) of host arrays given for the whole
     batch: out [rows][global_batch] float64, done [global_batch] uint8 (one of the two may be None: not wanted). -> (lo, hi)"""
