@@ -284,6 +284,51 @@ protected:
 };
 }  // namespace detail
 
+// Joint sensors (sai2b.h "joint sensors"): the clocks of the readings, and the measured pair the controller side reads
+struct JointSensorState {
+	std::vector<int> clock, episode;  // [B] each: the index of the next reading, the episode
+};
+struct MeasuredState {
+	Batch q, dq;  // [dof][B] each
+};
+namespace detail {
+// what setJointSensor checks ahead of the device: the shape of the rows is all the C ABI cannot see; it judges the rest
+inline void checkJointSensorRows(const int dof, const size_t B, const Batch& rows) {
+	if (!rows.empty() && rows.size() != (size_t)(1 + 5 * dof) * B) throw std::invalid_argument("setJointSensor: rows must be [1 + 5 dof][B]");
+}
+// the members RobotController and BatchedSimulation share: they act on the controller's context
+class JointSensorMembers {
+public:
+	// The controller's view of every robot's joint state: rows [1 + 5 dof][B] = the delay in periods, then dof rows each of the
+	// offset, the position noise deviation, the quantum, the velocity noise deviation and the velocity filter coefficient (empty:
+	// the ideal sensor). From here on the tick, observe and applyAction read measuredState(); the plant, setQ / the state getters
+	// and the resets keep the truth. Seeds every robot's measurement and zeroes its clocks. std::invalid_argument on rows of
+	// another shape and on what sai2b_set_joint_sensor rejects (its message).
+	void setJointSensor(const sai2b_joint_sensor_config& cfg, const Batch& rows = {}) {
+		checkJointSensorRows(sai2b_num_joints(_js_ctx), (size_t)sai2b_batch(_js_ctx), rows);
+		check(_js_ctx, sai2b_set_joint_sensor(_js_ctx, &cfg, rows.empty() ? nullptr : rows.data(), 0));
+	}
+	void clearJointSensor() { check(_js_ctx, sai2b_clear_joint_sensor(_js_ctx)); }
+	JointSensorState jointSensorState() const {
+		const size_t B = (size_t)sai2b_batch(_js_ctx);
+		JointSensorState s;
+		s.clock.resize(B), s.episode.resize(B);
+		check(_js_ctx, sai2b_get_joint_sensor_state(_js_ctx, s.clock.data(), s.episode.data()));
+		return s;
+	}
+	// the measured q and dq; the truth without a joint sensor
+	MeasuredState measuredState() const {
+		const size_t n = (size_t)sai2b_num_joints(_js_ctx) * (size_t)sai2b_batch(_js_ctx);
+		MeasuredState m;
+		m.q.resize(n), m.dq.resize(n);
+		check(_js_ctx, sai2b_get_measured_state(_js_ctx, m.q.data(), m.dq.data()));
+		return m;
+	}
+
+protected:
+	sai2b_ctx* _js_ctx = nullptr;
+};
+}  // namespace detail
 // Actions (sai2b.h "actions"): the counts of the last applyAction
 struct ActionCounts {
 	int rejected = 0, clipped = 0, limited = 0;
@@ -1191,7 +1236,7 @@ protected:
 };
 
 // reference src/RobotController.{h,cpp}
-class RobotController : public detail::ObservationMembers, public detail::ActionMembers {
+class RobotController : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers {
 public:
 	RobotController(std::shared_ptr<BatchedRobotModel>& robot, std::vector<std::shared_ptr<TemplateTask>>& tasks) : _robot(robot) {
 		if (tasks.size() == 0) throw std::invalid_argument("RobotController must have at least one task");
@@ -1207,7 +1252,7 @@ public:
 			if (msg.find("HIP") != std::string::npos || msg.find("hip") != std::string::npos) throw std::runtime_error(msg);
 			throw std::invalid_argument(msg);
 		}
-		_obs_ctx = _act_ctx = _ctx;
+		_obs_ctx = _act_ctx = _js_ctx = _ctx;
 		_tasks = tasks;
 		robot->_controller = this;
 		robot->applyPayloads(_ctx, SAI2B_PAYLOAD_BOTH);
@@ -1482,6 +1527,38 @@ public:
 		});
 	}
 	void clearEnvSampler() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_env_sampler(sh.ctx)); }); }
+	// Joint sensors for the whole sharded batch: rows [1 + 5 dof][B_total] (empty: ideal); every shard gets its columns and
+	// first_robot = cfg.first_robot + its first global index, so the noise is that of one context
+	void setJointSensor(const sai2b_joint_sensor_config& cfg, const Batch& rows = {}) {
+		detail::checkJointSensorRows(_dof, (size_t)_total, rows);
+		forAll([&](Shard& sh) {
+			sai2b_joint_sensor_config c = cfg;
+			c.first_robot = cfg.first_robot + (unsigned)sh.lo;
+			const Batch part = slice(rows, 1 + 5 * _dof, sh);
+			detail::check(sh.ctx, sai2b_set_joint_sensor(sh.ctx, &c, ptr(part), 0));
+		});
+	}
+	void clearJointSensor() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_joint_sensor(sh.ctx)); }); }
+	JointSensorState jointSensorState() {
+		JointSensorState out;
+		out.clock.resize((size_t)_total), out.episode.resize((size_t)_total);
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_get_joint_sensor_state(sh.ctx, out.clock.data() + sh.lo, out.episode.data() + sh.lo)); });
+		return out;
+	}
+	// the measured q and dq of the whole batch, [dof][B_total] each
+	MeasuredState measuredState() {
+		MeasuredState out;
+		out.q.resize((size_t)_dof * _total), out.dq.resize((size_t)_dof * _total);
+		forAll([&](Shard& sh) {
+			const size_t Bs = (size_t)(sh.hi - sh.lo);
+			Batch q((size_t)_dof * Bs), dq((size_t)_dof * Bs);
+			detail::check(sh.ctx, sai2b_get_measured_state(sh.ctx, q.data(), dq.data()));
+			for (int i = 0; i < _dof; i++)
+				for (size_t b = 0; b < Bs; b++)
+					out.q[(size_t)i * _total + sh.lo + b] = q[(size_t)i * Bs + b], out.dq[(size_t)i * _total + sh.lo + b] = dq[(size_t)i * Bs + b];
+		});
+		return out;
+	}
 	void randomizeRobots(const std::vector<unsigned char>& mask, const unsigned groups = 0) {
 		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "randomizeRobots");
 		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_randomize_robots(sh.ctx, mask.data() + sh.lo, groups, 0)); });
@@ -1711,7 +1788,7 @@ private:
 // integrate, getJointPositions, getJointVelocities): rigid-body dynamics of the whole batch with the
 // state resident on the device (sai2b_sim_step). Without setJointTorques, integrate() consumes the
 // torques of the controller's last computeControlTorques() without a host round trip.
-class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers {
+class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers {
 public:
 	explicit BatchedSimulation(RobotController& controller, const double timestep = 0.001, const int substeps = 1)
 		: BatchedSimulation(controller.ctx(), timestep, substeps) {}
@@ -1722,7 +1799,7 @@ public:
 	BatchedSimulation(sai2b_ctx* ctx, const double timestep, const int substeps) : _c(ctx), _dt(timestep), _substeps(substeps) {
 		if (timestep <= 0 || substeps < 1) throw std::invalid_argument("simulation timestep must be positive");
 		_dof = sai2b_num_joints(ctx);
-		_obs_ctx = _act_ctx = ctx;
+		_obs_ctx = _act_ctx = _js_ctx = ctx;
 	}
 	void setTimestep(const double dt) {
 		if (dt <= 0) throw std::invalid_argument("simulation timestep must be positive");

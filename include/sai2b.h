@@ -420,7 +420,14 @@ enum sai2b_buffer {
 	 * sai2b_env_sampler_config_layout: the scales, offsets, height, tilt angle and axis, delay and push themselves, privileged
 	 * information for a critic or an identification network. Zero for a robot that has not been drawn yet. NULL until a sampler has
 	 * been set (and after it is cleared). */
-	SAI2B_BUF_ENV_SAMPLE = 20
+	SAI2B_BUF_ENV_SAMPLE = 20,
+	/* the controller's view of the joint state (sai2b_set_joint_sensor): the measured q and dq, [dof][B] each, and the per-robot
+	 * rows [1 + 5 dof][B]. NULL until a joint sensor has been set (and after it is cleared). SAI2B_BUF_Q / SAI2B_BUF_DQ stay what
+	 * sai2b_sim_step integrates: the truth, privileged information for a critic. A device-resident producer may rewrite the rows
+	 * between steps, ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
+	SAI2B_BUF_Q_MEASURED = 21,
+	SAI2B_BUF_DQ_MEASURED = 22,
+	SAI2B_BUF_JOINT_SENSOR = 23
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -709,6 +716,79 @@ int sai2b_get_hardware(sai2b_ctx* ctx, sai2b_hardware_config* cfg, double* actua
 /* host arrays, any NULL: applied_torque [dof][B] of the last sai2b_sim_step, period [B] = n, episode [B] = e. Zeros without
  * hardware. */
 int sai2b_get_hardware_state(sai2b_ctx* ctx, double* applied_torque, int* period, int* episode);
+
+/* ------------------------------------------------------------------ joint sensors
+ * The controller's view of the joint state, different for every robot: encoder resolution, calibration offset, position noise,
+ * the velocity estimate (a tachometer, or a finite difference of the quantised positions, with noise, behind a first-order
+ * filter) and the bus latency of the reading. With a joint sensor set the context has TWO views of the state:
+ *   the TRUE view, SAI2B_BUF_Q / SAI2B_BUF_DQ: what sai2b_sim_step integrates (with contact, joint dynamics, wrench and the
+ *     wrist sensor's ideal reading), what sai2b_get_bias, sai2b_set_state, sai2b_get_state, sai2b_reset_robots and
+ *     sai2b_reset_robots_sampled (its criteria and goals included) and the snapshot banks read and write;
+ *   the MEASURED view, SAI2B_BUF_Q_MEASURED / SAI2B_BUF_DQ_MEASURED: what everything on the controller's or the policy's side
+ *     reads: sai2b_tick, the split update / compute calls and a deferred sai2b_update_task_models, the trajectory generators,
+ *     the sai2b_task_* calls, sai2b_reinitialize and sai2b_reinitialize_robots, the MotionForceTask status getters and run-time
+ *     re-parametrisation, sai2b_observe and sai2b_observe_reward (SAI2B_OBS_Q / SAI2B_OBS_DQ, the task blocks and the criteria
+ *     JOINT_LIMIT, SPEED, NONFINITE and SUCCESS, as a real system would evaluate them) and sai2b_apply_action (delta_current and
+ *     the lead bound included).
+ * A context that never sets a joint sensor, or has cleared it, has one view and launches what it launches without the feature.
+ * Batch-uniform (sai2b_joint_sensor_config): the depth D of the reading history, the velocity mode, the generator's seed and the
+ * global index of this context's robot 0. Per robot, doubles, rows [1 + 5 dof][B]: row 0 the delay d in periods, then dof rows
+ * each of the offset o_i (rad or m), the position noise deviation s_i, the quantum Delta_i, the velocity noise deviation r_i
+ * and the velocity filter coefficient alpha_i. NULL: ideal (d 0, o 0, s 0, Delta 0, r 0, alpha 1).
+ * State per robot: a clock (c, e) = the index of the next reading and the episode, the previous position reading pprev [dof],
+ * the filter state v [dof], a history [(D + 1)][2 dof] of (p, v).
+ * READING m of the true q, dq, with dt the dt of the sai2b_sim_step call that produced them. An effect whose parameter is zero
+ * is skipped, not multiplied by zero, so the ideal rows reproduce the truth bit for bit:
+ *     x_i    = q_i (+ o_i if o_i != 0) (+ s_i z_i if s_i != 0)
+ *     p_i    = Delta_i > 0 ? Delta_i * rint(x_i / Delta_i) : x_i                  (round half to even)
+ *     base_i = (velocity_mode == 1 && m > 0) ? (p_i - pprev_i) / dt : dq_i
+ *     w_i    = r_i != 0 ? base_i + r_i z_{dof + i} : base_i
+ *     v_i    = (m == 0 || alpha_i == 1) ? w_i : v_i + alpha_i (w_i - v_i)
+ *     pprev_i = p_i;  hist[m mod (D + 1)] = (p, v)
+ *     (q_measured, dq_measured) = hist[max(m - d, 0) mod (D + 1)]        d = (int) fmin(fmax(row 0, 0), D): a NaN gives 0
+ *   Every sum is one product and one sum (no fused multiply-add).
+ * Random numbers: the hardware's generator (Philox4x32-10, Box-Muller), stream 10, key (seed & 0xffffffff, seed >> 32), counter
+ * (m, e, 256 * 10 + j, first_robot + b); joint i takes z_i and z_{dof + i} of the calls j = 0 .. ceil(2 dof / 4) - 1. The noise
+ * of a robot depends on the seed, its global index, its episode and the reading's index alone, so shards with first_robot set
+ * are bit-equal to the one-context run.
+ * WHEN READINGS ARE TAKEN. Seeding takes reading 0 and leaves c = 1: in sai2b_set_joint_sensor (all robots, e = 0), in
+ * sai2b_set_state (all robots, e kept), and in sai2b_reset_robots / sai2b_reset_robots_sampled for the selected robots with
+ * e += 1, in a launch behind the reset's own. The sense stage runs last in every sai2b_sim_step (behind the wrist sensor's
+ * stage where that runs), takes reading c and leaves c + 1.
+ * A CONSEQUENCE: the reset kernels run on the true view, so the tasks of a reset robot are re-initialised at its TRUE start
+ * state (its goals sit at the true start pose), and its first tick reads the seeded measurement. sai2b_reinitialize and
+ * sai2b_reinitialize_robots read the measured view and do not touch the sensor's state.
+ * Snapshot banks: SAI2B_SNAP_EPISODE holds the measured pair, pprev, v, the history and the clock, SAI2B_SNAP_ENVIRONMENT the
+ * rows; seed and first_robot are configuration, as for the hardware. c and e are 32-bit ints with the hardware's limit. This
+ * law is this library's definition. */
+typedef struct sai2b_joint_sensor_config {
+	int max_delay;		  /* D: depth of the reading history in periods, 0..SAI2B_MAX_ACTUATION_DELAY */
+	int velocity_mode;	  /* 0: tachometer (the true dq), 1: finite difference of the position readings */
+	unsigned first_robot; /* global index of robot 0 of this context (0 unless the batch is a shard) */
+	int reserved;
+	unsigned long long seed;
+} sai2b_joint_sensor_config;
+/* host only: D 0, tachometer, first_robot 0, seed 0 */
+int sai2b_default_joint_sensor(sai2b_joint_sensor_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg (max_delay outside [0, SAI2B_MAX_ACTUATION_DELAY],
+ * velocity_mode not 0 or 1) */
+int sai2b_validate_joint_sensor(const sai2b_joint_sensor_config* cfg, int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_joint_sensor_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_joint_sensor_config(void);
+/* Host rows are validated (SAI2B_INVALID_ARGUMENT with the reason: what sai2b_validate_joint_sensor rejects; d not an integer
+ * in [0, D]; alpha outside (0, 1]; s, Delta, r negative or not finite; o not finite); DEVICE rows (on_device != 0) are copied
+ * under the stream contract and NOT inspected. Zeroes the clocks and seeds every robot's measurement from the state as it is.
+ * Ordered on the ctx stream. A call that fails on its arguments leaves the context as it was; one that fails while copying
+ * (SAI2B_RUNTIME_ERROR) leaves the context without a joint sensor. */
+int sai2b_set_joint_sensor(sai2b_ctx* ctx, const sai2b_joint_sensor_config* cfg, const double* rows, int on_device);
+/* back to one view (the three buffer ids give NULL, no stage is launched); the state buffers keep the truth */
+int sai2b_clear_joint_sensor(sai2b_ctx* ctx);
+/* the configuration and the rows to the host (either may be NULL); the default configuration and the ideal rows without one */
+int sai2b_get_joint_sensor(sai2b_ctx* ctx, sai2b_joint_sensor_config* cfg, double* rows);
+/* host arrays, either NULL: clock [B] = c, episode [B] = e. Zeros without a joint sensor. */
+int sai2b_get_joint_sensor_state(sai2b_ctx* ctx, int* clock, int* episode);
+/* host arrays [dof][B], either NULL: the measured pair; the truth without a joint sensor */
+int sai2b_get_measured_state(sai2b_ctx* ctx, double* q, double* dq);
 
 /* ------------------------------------------------------------------ observations and episode-end flags
  * The missing link of the resident loop  tick, sai2b_sim_step(NULL), sai2b_observe(out, done), sai2b_reset_robots(done, ..):

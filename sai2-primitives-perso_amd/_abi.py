@@ -37,6 +37,9 @@ BUF_TAU_APPLIED = 17  # [dof][B]: the torques the plant received in the last sim
 BUF_REWARD_STATE = 18  # [3 + dof][B]: running return, running discount, last return, tau_prev
 BUF_REWARD_EPISODE = 19  # [2][B] int32: last length, tau_prev is valid
 MAX_ACTUATION_DELAY = 8  # SAI2B_MAX_ACTUATION_DELAY
+BUF_Q_MEASURED, BUF_DQ_MEASURED = 21, 22  # [dof][B] each: the controller's view of the state (sai2b_set_joint_sensor)
+BUF_JOINT_SENSOR = 23  # [1 + 5 dof][B] rows: delay; offset, position noise, quantum, velocity noise, velocity filter coefficient
+JOINT_SENSOR_VELOCITY_MODES = {"tachometer": 0, "finite_difference": 1}
 HARDWARE_SENSOR_ROWS = 13
 WRENCH_WORLD, WRENCH_LINK = 0, 1  # enum sai2b_wrench_frame
 WRENCH_FRAMES = {"world": WRENCH_WORLD, "link": WRENCH_LINK}
@@ -299,6 +302,18 @@ class HardwareConfig(C.Structure):
     ]
 
 
+class JointSensorConfig(C.Structure):
+    """sai2b_joint_sensor_config; load_library() checks the size against sai2b_sizeof_joint_sensor_config()"""
+
+    _fields_ = [
+        ("max_delay", _i),
+        ("velocity_mode", _i),
+        ("first_robot", C.c_uint),
+        ("reserved", _i),
+        ("seed", C.c_ulonglong),
+    ]
+
+
 MAX_RESET_TRIES = 64  # SAI2B_MAX_RESET_TRIES
 RESET_SAMPLER_COUNTS = ("reset", "rejected", "exhausted")
 RESET_SAMPLER_BLOCKS = {"q_lower": 0, "q_upper": 1, "dq_sigma": 2, "q_nominal": 3, "goal": 4}  # sai2b_reset_sampler_config_layout
@@ -553,6 +568,14 @@ EXPORTS = [
     "sai2b_randomize_robots",
     "sai2b_get_env_sampler_counts",
     "sai2b_get_env_sampler_state",
+    "sai2b_default_joint_sensor",
+    "sai2b_validate_joint_sensor",
+    "sai2b_sizeof_joint_sensor_config",
+    "sai2b_set_joint_sensor",
+    "sai2b_clear_joint_sensor",
+    "sai2b_get_joint_sensor",
+    "sai2b_get_joint_sensor_state",
+    "sai2b_get_measured_state",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -575,6 +598,10 @@ SNAP_BLOCKS = ("q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate",
 # the blocks appended for the environment sampler, and every block id's name (enum SnapBlock of csrc/sai2b_snapshot_layout.h)
 SNAP_ENV_SAMPLER_BLOCKS = ("env_sampler_counter", "env_sampler_sample")
 SNAP_BLOCK_NAMES = SNAP_BLOCKS + SNAP_ENV_SAMPLER_BLOCKS
+# the blocks appended for the joint sensors behind those, and the name of every block id there is
+SNAP_JOINT_SENSOR_BLOCKS = ("joint_sensor_q", "joint_sensor_dq", "joint_sensor_previous", "joint_sensor_filter", "joint_sensor_history",
+                            "joint_sensor_clock", "joint_sensor_rows")
+SNAP_BLOCK_NAMES_ALL = SNAP_BLOCK_NAMES + SNAP_JOINT_SENSOR_BLOCKS
 
 _lib = None
 
@@ -755,6 +782,17 @@ def load_library():
     lib.sai2b_clear_hardware.argtypes = [vp]
     lib.sai2b_get_hardware.argtypes = [vp, P(HardwareConfig), vp, vp]
     lib.sai2b_get_hardware_state.argtypes = [vp, vp, vp, vp]
+    lib.sai2b_default_joint_sensor.argtypes = [P(JointSensorConfig)]
+    lib.sai2b_validate_joint_sensor.argtypes = [P(JointSensorConfig), _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_joint_sensor_config.argtypes = []
+    lib.sai2b_set_joint_sensor.argtypes = [vp, P(JointSensorConfig), vp, _i]
+    lib.sai2b_clear_joint_sensor.argtypes = [vp]
+    lib.sai2b_get_joint_sensor.argtypes = [vp, P(JointSensorConfig), vp]
+    lib.sai2b_get_joint_sensor_state.argtypes = [vp, vp, vp]
+    lib.sai2b_get_measured_state.argtypes = [vp, vp, vp]
+    if lib.sai2b_sizeof_joint_sensor_config() != C.sizeof(JointSensorConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_joint_sensor_config is {lib.sai2b_sizeof_joint_sensor_config()} bytes in the library, "
+                           f"{C.sizeof(JointSensorConfig)} in the ctypes mirror")
     if lib.sai2b_sizeof_hardware_config() != C.sizeof(HardwareConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_hardware_config is {lib.sai2b_sizeof_hardware_config()} bytes in the library, "
                            f"{C.sizeof(HardwareConfig)} in the ctypes mirror")

@@ -547,6 +547,115 @@ class Controller:
         self._rc(self.lib.sai2b_get_hardware_state(self.h, C.c_void_p(a.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(e.ctypes.data)))
         return dict(applied_torque=a, period=n, episode=e)
 
+    # -- joint sensors (sai2b.h "joint sensors")
+    def joint_sensor_config(self, max_delay=0, velocity_mode="tachometer", seed=0, first_robot=0):
+        """-> JointSensorConfig, validated. velocity_mode: 'tachometer' or 'finite_difference' (or 0 / 1)"""
+        cfg = _abi.JointSensorConfig()
+        if self.lib.sai2b_default_joint_sensor(C.byref(cfg)):
+            raise ValueError(self.lib.sai2b_last_error(None).decode())
+        if isinstance(velocity_mode, str):
+            if velocity_mode not in _abi.JOINT_SENSOR_VELOCITY_MODES:
+                raise ValueError("velocity_mode must be 'tachometer' or 'finite_difference'")
+            velocity_mode = _abi.JOINT_SENSOR_VELOCITY_MODES[velocity_mode]
+        cfg.max_delay, cfg.velocity_mode = int(max_delay), int(velocity_mode)
+        cfg.seed, cfg.first_robot = int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_robot) & 0xFFFFFFFF
+        msg = C.create_string_buffer(256)
+        if self.lib.sai2b_validate_joint_sensor(C.byref(cfg), self.dof, msg, 256):
+            raise ValueError(msg.value.decode())
+        return cfg
+
+    def joint_sensor_rows(self, delay=0, offset=0.0, noise=0.0, quantum=0.0, velocity_noise=0.0, velocity_alpha=1.0):
+        """-> rows [1 + 5 dof][B]: delay [B] in periods; offset, noise (position noise deviation), quantum, velocity_noise and
+        velocity_alpha (the velocity filter's coefficient) [dof][B]. A scalar, or a [dof] column, is the same for every robot.
+        numpy in, numpy out; when any argument is a torch CUDA tensor the rows are a CUDA tensor on this controller's device.
+        The defaults are the ideal sensor."""
+        n, B = self.dof, self.B
+        args = (delay, offset, noise, quantum, velocity_noise, velocity_alpha)
+        if any(hasattr(a, "data_ptr") for a in args):
+            import torch
+
+            dev = f"cuda:{self._device}"
+            out = torch.empty((1 + 5 * n, B), dtype=torch.float64, device=dev)
+
+            def block(a, rows, name):
+                a = torch.as_tensor(a, dtype=torch.float64, device=dev)
+                if a.dim() == 1 and a.shape[0] == rows and rows != B:
+                    a = a[:, None]
+                try:
+                    return torch.broadcast_to(a, (rows, B))
+                except RuntimeError:
+                    raise ValueError(f"{name}: expected a scalar, {rows} values or an array of shape ({rows}, {B})") from None
+
+        else:
+            out = np.empty((1 + 5 * n, B))
+
+            def block(a, rows, name):
+                a = np.asarray(a, dtype=np.float64)
+                if a.ndim == 1 and a.shape[0] == rows and rows != B:
+                    a = a[:, None]
+                try:
+                    return np.broadcast_to(a, (rows, B))
+                except ValueError:
+                    raise ValueError(f"{name}: expected a scalar, {rows} values or an array of shape ({rows}, {B})") from None
+
+        out[0:1] = block(delay, 1, "delay")
+        for k, (a, name) in enumerate(zip(args[1:], ("offset", "noise", "quantum", "velocity_noise", "velocity_alpha"))):
+            out[1 + k * n : 1 + (k + 1) * n] = block(a, n, name)
+        return out
+
+    def set_joint_sensor(self, rows=None, *, max_delay=0, velocity_mode="tachometer", seed=0, first_robot=0, config=None):
+        """the controller's view of every robot's joint state: rows [1 + 5 dof][B] (joint_sensor_rows() builds them), numpy or
+        torch CUDA, None = ideal; max_delay: depth D of the reading history; velocity_mode: 'tachometer' or
+        'finite_difference'; seed, first_robot: the random generator's key and the global index of this controller's robot 0.
+        A JointSensorConfig as `config` carries the four. From here on tick, observe and apply_action read measured_state(),
+        sim_step, set_state, get_state and the resets the truth. Seeds every robot's measurement and zeroes its clocks."""
+        cfg = config if config is not None else self.joint_sensor_config(max_delay, velocity_mode, seed, first_robot)
+        r = 1 + 5 * self.dof
+        if rows is not None and not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.shape != (r, self.B):
+                raise ValueError(f"rows: expected an array of shape ({r}, {self.B})")
+        ptr, _keep = self._in(rows, r)
+        self._rc(self.lib.sai2b_set_joint_sensor(self.h, C.byref(cfg), ptr, self._dev(rows)))
+
+    def clear_joint_sensor(self):
+        self._rc(self.lib.sai2b_clear_joint_sensor(self.h))
+
+    def joint_sensor(self):
+        """-> (JointSensorConfig, rows [1 + 5 dof][B]); the default configuration and the ideal rows when none is set"""
+        cfg, rows = _abi.JointSensorConfig(), np.empty((1 + 5 * self.dof, self.B))
+        self._rc(self.lib.sai2b_get_joint_sensor(self.h, C.byref(cfg), C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def joint_sensor_state(self):
+        """-> dict clock [B]: the index of the next reading, episode [B] (int32); zeros without a joint sensor"""
+        c, e = np.empty(self.B, dtype=np.int32), np.empty(self.B, dtype=np.int32)
+        self._rc(self.lib.sai2b_get_joint_sensor_state(self.h, C.c_void_p(c.ctypes.data), C.c_void_p(e.ctypes.data)))
+        return dict(clock=c, episode=e)
+
+    def get_measured_state(self):
+        """-> (q, dq) [dof][B] as numpy arrays: the measured pair; the truth without a joint sensor"""
+        q, dq = np.empty((self.dof, self.B)), np.empty((self.dof, self.B))
+        self._rc(self.lib.sai2b_get_measured_state(self.h, C.c_void_p(q.ctypes.data), C.c_void_p(dq.ctypes.data)))
+        return q, dq
+
+    def measured_state(self):
+        """the measured q and dq as torch views of the two device buffers (no copy), [dof][B] float64. Order reads with
+        stream()."""
+        import torch
+
+        pq, pd = self.device_buffer(_abi.BUF_Q_MEASURED), self.device_buffer(_abi.BUF_DQ_MEASURED)
+        if not pq or not pd:
+            raise ValueError("measured_state: no joint sensor is set (sai2b_set_joint_sensor)")
+
+        def view(ptr):
+            class _Buf:
+                __cuda_array_interface__ = dict(shape=(self.dof, self.B), typestr="<f8", data=(int(ptr), False), version=2)
+
+            return torch.as_tensor(_Buf(), device=f"cuda:{self._device}")
+
+        return view(pq), view(pd)
+
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod
     def _flags(names, table, what):
@@ -1208,7 +1317,7 @@ class Controller:
         n = self.lib.sai2b_snapshot_layout(self.h, int(what), tab, 80)
         if n < 0:
             self._rc(_abi.INVALID_ARGUMENT)
-        return [dict(block=_abi.SNAP_BLOCK_NAMES[tab[5 * i]], task=tab[5 * i + 1], rows=tab[5 * i + 2], elem_bytes=tab[5 * i + 3],
+        return [dict(block=_abi.SNAP_BLOCK_NAMES_ALL[tab[5 * i]], task=tab[5 * i + 1], rows=tab[5 * i + 2], elem_bytes=tab[5 * i + 3],
                      first_word=tab[5 * i + 4]) for i in range(n)]
 
     def snapshot_bank(self, capacity, what=_abi.SNAP_EPISODE):
@@ -2534,6 +2643,19 @@ class BatchedSimulation:
 
     def getHardwareState(self):
         return self._c._ctrl.get_hardware_state()
+
+    # -- joint sensors (Controller.set_joint_sensor)
+    def setJointSensor(self, *args, **kwargs):
+        self._c._ctrl.set_joint_sensor(*args, **kwargs)
+
+    def clearJointSensor(self):
+        self._c._ctrl.clear_joint_sensor()
+
+    def jointSensorState(self):
+        return self._c._ctrl.joint_sensor_state()
+
+    def measuredState(self):
+        return self._c._ctrl.get_measured_state()
 
     # -- contact of the plant (Controller.set_contact); the force sensor writes the sensed rows of one MotionForceTask
     def setContactPlanes(self, *args, **kwargs):

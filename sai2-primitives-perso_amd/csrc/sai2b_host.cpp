@@ -125,6 +125,17 @@ struct sai2b_ctx {
 	sai2b_hardware_config hw_cfg = {};
 	double *hw_act = nullptr, *hw_sensor = nullptr, *hw_history = nullptr, *hw_filter = nullptr, *hw_applied = nullptr;
 	int* hw_clock = nullptr;
+	// joint sensors (sai2b_set_joint_sensor), created on first use: the [1 + 5 dof][B] rows, the measured pair, the previous position
+	// reading and the velocity filter's state [dof][B] each, the history of readings (room for the deepest,
+	// [SAI2B_MAX_ACTUATION_DELAY + 1][2 dof][B]; js_cfg.max_delay + 1 slots are in use), the clocks (next reading, episode) [2][B] and
+	// d_params_meas, the device copy of h_params whose q, dq are the measured pair. js_on: the controller-side launches take
+	// d_params_meas (ctrl_params), sai2b_sim_step launches joint_sense_kernel last, and while q_is_pose holds the cached pose
+	// is the measured q (ctrl_q)
+	bool js_on = false;
+	sai2b_joint_sensor_config js_cfg = {};
+	double *js_rows = nullptr, *js_qm = nullptr, *js_dqm = nullptr, *js_prev = nullptr, *js_filter = nullptr, *js_history = nullptr;
+	int* js_clock = nullptr;
+	DevParams* d_params_meas = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -199,6 +210,11 @@ struct sai2b_ctx {
 };
 
 static int flush_update(sai2b_ctx* ctx);  // runs a deferred sai2b_update_task_models() now
+
+// the controller's view of the state (include/sai2b.h "joint sensors"): the measured pair with a joint sensor, else the truth
+static const DevParams* ctrl_params(const sai2b_ctx* ctx) { return ctx->js_on ? ctx->d_params_meas : ctx->d_params; }
+static double* ctrl_q(const sai2b_ctx* ctx) { return ctx->js_on ? ctx->js_qm : ctx->q; }
+static double* ctrl_dq(const sai2b_ctx* ctx) { return ctx->js_on ? ctx->js_dqm : ctx->dq; }
 
 static int set_error(sai2b_ctx* ctx, int code, const std::string& msg) {
 	g_error = msg;
@@ -744,6 +760,12 @@ static int upload_params(sai2b_ctx* ctx) {
 		}
 	// stream-ordered so that kernels already enqueued keep the parameters they were launched with
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_params, &ctx->h_params, sizeof(DevParams), hipMemcpyHostToDevice, ctx->stream));
+	DevParams meas;
+	if (ctx->js_on) {  // the same parameters with the measured pair as their state
+		meas = ctx->h_params;
+		meas.q = ctx->js_qm, meas.dq = ctx->js_dqm;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_params_meas, &meas, sizeof(DevParams), hipMemcpyHostToDevice, ctx->stream));
+	}
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // h_params may be edited again right after
 	ctx->params_dirty = false;
 	return SAI2B_OK;
@@ -831,8 +853,8 @@ static int create_impl(sai2b_ctx* ctx, const sai2b_robot_model* model, const sai
 	ctx->params_dirty = true;
 	if ((rc = upload_params(ctx))) return rc;
 	// the reference constructs tasks from the model's current state (q = 0 until set_state)
-	if (sai2b::launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctrl_params(ctx), ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctrl_params(ctx), ctx->B, -1, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
@@ -967,7 +989,7 @@ extern "C" int sai2b_update_task_config(sai2b_ctx* ctx, int task, const sai2b_ta
 		int rc3 = upload_params(ctx);
 		if (rc3) return rc3;
 		if (reinit_mode >= 0) {
-			if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, task, reinit_mode, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
+			if (sai2b::launch_otg_reinit(ctrl_params(ctx), ctx->B, task, reinit_mode, ctx->q_is_pose ? ctrl_q(ctx) : ctx->q_pose, ctx->stream))
 				return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG enable launch failed");
 			ctx->launches++;
 		}
@@ -975,7 +997,7 @@ extern "C" int sai2b_update_task_config(sai2b_ctx* ctx, int task, const sai2b_ta
 	if (reparam) {
 		int rc4 = upload_params(ctx);
 		if (rc4) return rc4;
-		if (sai2b::launch_mft_reparam(ctx->d_params, ctx->B, task, reparam, ctx->q_is_pose ? ctx->q : ctx->q_pose, ctx->stream))
+		if (sai2b::launch_mft_reparam(ctrl_params(ctx), ctx->B, task, reparam, ctx->q_is_pose ? ctrl_q(ctx) : ctx->q_pose, ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "re-parametrisation launch failed");
 		ctx->launches++;
 	}
@@ -1020,8 +1042,29 @@ static int copy_rows(sai2b_ctx* ctx, double* dst, const double* src, size_t rows
 // called before the state buffers are overwritten
 static int keep_pose(sai2b_ctx* ctx) {
 	if (!ctx->q_is_pose) return SAI2B_OK;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->q_pose, ctx->q, sizeof(double) * N * (size_t)ctx->B, hipMemcpyDeviceToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->q_pose, ctrl_q(ctx), sizeof(double) * N * (size_t)ctx->B, hipMemcpyDeviceToDevice, ctx->stream));
 	ctx->q_is_pose = false;
+	return SAI2B_OK;
+}
+
+// joint sensors: what joint_sense_kernel takes from the context
+static sai2b::JointSenseParams joint_sense_params(const sai2b_ctx* ctx) {
+	sai2b::JointSenseParams p;
+	p.rows = ctx->js_rows, p.q = ctx->q, p.dq = ctx->dq, p.q_meas = ctx->js_qm, p.dq_meas = ctx->js_dqm;
+	p.prev = ctx->js_prev, p.filter = ctx->js_filter, p.history = ctx->js_history, p.clock = ctx->js_clock;
+	p.depth = ctx->js_cfg.max_delay, p.velocity_mode = ctx->js_cfg.velocity_mode;
+	p.rng.key0 = (unsigned)(ctx->js_cfg.seed & 0xffffffffull), p.rng.key1 = (unsigned)(ctx->js_cfg.seed >> 32);
+	p.rng.first_robot = ctx->js_cfg.first_robot;
+	return p;
+}
+// reading 0 of the truth as it is on the stream, for the robots of `mask` (device bytes; NULL: all). The measured q is about to be
+// overwritten: while it is the tasks' cached pose it is saved first.
+static int joint_sensor_seed(sai2b_ctx* ctx, const unsigned char* mask, bool next_episode) {
+	if (int rc = keep_pose(ctx)) return rc;
+	sai2b::JointSenseParams p = joint_sense_params(ctx);
+	p.mask = mask, p.next_episode = next_episode ? 1 : 0;
+	if (sai2b::launch_joint_sense(ctx->B, p, true, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "joint sensor seed launch failed");
+	ctx->launches++;
 	return SAI2B_OK;
 }
 
@@ -1033,6 +1076,8 @@ extern "C" int sai2b_set_state(sai2b_ctx* ctx, const double* q, const double* dq
 	if (q && (rc = keep_pose(ctx))) return rc;
 	if ((rc = copy_rows(ctx, ctx->q, q, N, on_device))) return rc;
 	if ((rc = copy_rows(ctx, ctx->dq, dq, N, on_device))) return rc;
+	// joint sensors: the state was set, not measured: every robot's measurement starts again at reading 0 of its episode
+	if (ctx->js_on && (q || dq) && (rc = joint_sensor_seed(ctx, nullptr, false))) return rc;
 	ctx->models_fresh = false;
 	for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
 	return SAI2B_OK;
@@ -1100,8 +1145,8 @@ extern "C" int sai2b_reinitialize(sai2b_ctx* ctx) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	if (sai2b::launch_reinit(ctx->d_params, ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, -1, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctrl_params(ctx), ctx->B, -1, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctrl_params(ctx), ctx->B, -1, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	ctx->goals_dirty = ~0u;
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1150,15 +1195,25 @@ static int reset_subset(sai2b_ctx* ctx, const char* fn, int task, const unsigned
 	// selected robot's new state is the pose it is re-initialised at. Otherwise the unselected robots' poses live in q_pose
 	// and the kernel moves the selected columns there (one task of several: the other tasks keep theirs, as
 	// sai2b_task_reinitialize has it).
+	// Joint sensors: a reset (episode) runs on the true view, so a selected robot's tasks are re-initialised at its true start
+	// state, and the seeding launch behind it takes its first measurement; a re-initialisation alone reads the measured view.
+	// While q_is_pose holds the cached pose of the robots left alone is the measured q, which is no state a reset robot could be
+	// re-initialised at: the pose moves to q_pose first, and the kernel puts the selected robots' true start there.
+	const bool true_view = ctx->js_on && episode;
+	if (true_view && (rc = keep_pose(ctx))) return rc;
+	const DevParams* view = true_view ? ctx->d_params : ctrl_params(ctx);
+	double *q_state = true_view ? ctx->q : ctrl_q(ctx), *dq_state = true_view ? ctx->dq : ctrl_dq(ctx);
 	int flags = episode ? sai2b::RESET_EPISODE : 0;
 	if (!ctx->q_is_pose && (task < 0 || ctx->T == 1)) flags |= sai2b::RESET_KEEP_POSE;
 	if (sampled) {
 		HIP_TRY(ctx, hipMemsetAsync(ctx->rs_counts, 0, sai2b::RS_COUNTS * sizeof(int), ctx->stream));
-		if (sai2b::launch_reset_sampled(ctx->d_params, ctx->B, reset_sampler_params(ctx), d_mask, ctx->q, ctx->dq, ctx->q_pose,
+		if (sai2b::launch_reset_sampled(view, ctx->B, reset_sampler_params(ctx), d_mask, q_state, dq_state, ctx->q_pose,
 										flags & sai2b::RESET_KEEP_POSE, ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
-	} else if (sai2b::launch_reset_subset(ctx->d_params, ctx->B, d_mask, d_q, d_dq, ctx->q, ctx->dq, ctx->q_pose, task, flags, ctx->stream))
+	} else if (sai2b::launch_reset_subset(view, ctx->B, d_mask, d_q, d_dq, q_state, dq_state, ctx->q_pose, task, flags, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, std::string(fn) + ": launch failed");
+	// joint sensors: reading 0 of the selected robots' next episode, from the truth the reset has just written
+	if (true_view && (rc = joint_sensor_seed(ctx, d_mask, true))) return rc;
 	// hardware: a reset robot starts a new episode at period 0 (a re-initialisation alone leaves its clocks as they are)
 	if (episode && ctx->hw_on) {
 		if (sai2b::launch_hardware_reset(ctx->B, d_mask, ctx->hw_clock, ctx->stream))
@@ -1285,13 +1340,13 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	// which robots' gated tasks are active this tick
 	const sai2b::RangePlan range = sai2b::plan_range(ctx->route, ctx->sw, kinds, ctx->B, ask);
 	if (range.run && range.cert) {
-		if (sai2b::launch_range_cert(ctx->d_params, ctx->B, range.max_rows, range.payload, range.inlane_singular, ctx->rg, ctx->stream) ||
-			sai2b::launch_tick_group(ctx->d_params, ctx->B, 16, true, false, with_comp, false, ctx->rg.count(), ctx->rg.list, ctx->stream))
+		if (sai2b::launch_range_cert(ctrl_params(ctx), ctx->B, range.max_rows, range.payload, range.inlane_singular, ctx->rg, ctx->stream) ||
+			sai2b::launch_tick_group(ctrl_params(ctx), ctx->B, 16, true, false, with_comp, false, ctx->rg.count(), ctx->rg.list, ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
 		ctx->rg.parity ^= 1;
 		ctx->launches += 2;
 	} else if (range.run) {
-		if (sai2b::launch_range_pass(ctx->d_params, ctx->B, ctx->introspection, with_comp, range.lanes, ctx->stream))
+		if (sai2b::launch_range_pass(ctrl_params(ctx), ctx->B, ctx->introspection, with_comp, range.lanes, ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task-range pass launch failed");
 		ctx->launches++;
 	}
@@ -1306,7 +1361,7 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 			// (a gated task keeps reading its goals: a robot skipped while they changed must see them later)
 			const int clean_mask = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & ((1u << SAI2B_MAX_TASKS) - 1u));
 			ctx->goals_dirty = 0;
-			if (sai2b::launch_otg(ctx->d_params, ctx->B, ctx->otg, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
+			if (sai2b::launch_otg(ctrl_params(ctx), ctx->B, ctx->otg, clean_mask, ~0, jerk_mask(ctx), ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
 			if (!gated && !ctx->goals_exposed && !ctx->otg_look.pending) {
 				HIP_TRY(ctx, hipMemcpyAsync(ctx->otg_busy_seen, ctx->otg.counts + 2 * SAI2B_MAX_TASKS + ctx->otg.parity, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 				HIP_TRY(ctx, hipEventRecord(ctx->otg_seen_ev, ctx->stream));
@@ -1325,7 +1380,7 @@ static int launch_tick(sai2b_ctx* ctx, int commit_sh, int with_comp, int do_torq
 	}
 	const sai2b::TickPlan plan = sai2b::plan(ctx->route, ctx->sw, kinds, ctx->B, ask);
 	if (plan.fast_launch) ctx->fb.parity ^= 1;
-	if (sai2b::launch_tick(ctx->d_params, ctx->B, plan.form, plan.call, ctx->fb, ctx->stream))
+	if (sai2b::launch_tick(ctrl_params(ctx), ctx->B, plan.form, plan.call, ctx->fb, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 	ctx->launches++;
 	if (plan.by_copy) {
@@ -1433,9 +1488,9 @@ static int launch_task_generic(sai2b_ctx* ctx, int task, const double* Np, const
 	int lanes = ctx->introspection ? 0 : sai2b::generic_lanes(ctx->sw, ctx->B, count == nullptr);
 	if (!count && ctx->sw.generic_lanes_env == 0) lanes = 0;
 	if (lanes)
-		return sai2b::launch_task_group(ctx->d_params, ctx->B, lanes, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list,
+		return sai2b::launch_task_group(ctrl_params(ctx), ctx->B, lanes, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list,
 										ctx->stream);
-	return sai2b::launch_task(ctx->d_params, ctx->B, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list, ctx->stream);
+	return sai2b::launch_task(ctrl_params(ctx), ctx->B, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, count, list, ctx->stream);
 }
 
 static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const double* tp, double* tau_out, double* N_out, double* Ntot_out,
@@ -1448,7 +1503,7 @@ static int launch_task_call(sai2b_ctx* ctx, int task, const double* Np, const do
 			if ((rc = dev_alloc(ctx, &ctx->tk.list, (size_t)ctx->B))) return rc;
 		}
 		ctx->tk.parity ^= 1;
-		if (sai2b::launch_task_cert(ctx->d_params, ctx->B, task, rows, ctx->h_params.payload != nullptr, !ctx->sw.no_inlane_singular, Np, tp, tau_out, N_out, Ntot_out, commit_sh,
+		if (sai2b::launch_task_cert(ctrl_params(ctx), ctx->B, task, rows, ctx->h_params.payload != nullptr, !ctx->sw.no_inlane_singular, Np, tp, tau_out, N_out, Ntot_out, commit_sh,
 									do_torque, ctx->tk, ctx->stream) ||
 			launch_task_generic(ctx, task, Np, tp, tau_out, N_out, Ntot_out, commit_sh, do_torque, ctx->tk.count(), ctx->tk.list))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "task launch failed");
@@ -1494,7 +1549,7 @@ extern "C" int sai2b_task_compute_torques(sai2b_ctx* ctx, int task, const double
 		}
 		const int clean = ctx->goals_exposed ? 0 : (int)(~ctx->goals_dirty & ~gated & (1u << task));
 		ctx->goals_dirty &= ~(1u << task);
-		if (sai2b::launch_otg(ctx->d_params, ctx->B, ctx->otg, clean, 1 << task, jerk_mask(ctx), ctx->stream))
+		if (sai2b::launch_otg(ctrl_params(ctx), ctx->B, ctx->otg, clean, 1 << task, jerk_mask(ctx), ctx->stream))
 			return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG launch failed");
 		ctx->otg.parity ^= 1;
 		ctx->launches += 2;
@@ -1528,8 +1583,8 @@ extern "C" int sai2b_task_reinitialize(sai2b_ctx* ctx, int task) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = upload_params(ctx);
 	if (rc) return rc;
-	if (sai2b::launch_reinit(ctx->d_params, ctx->B, task, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
-	if (sai2b::launch_otg_reinit(ctx->d_params, ctx->B, task, 0, ctx->q, ctx->stream))
+	if (sai2b::launch_reinit(ctrl_params(ctx), ctx->B, task, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "reinit launch failed");
+	if (sai2b::launch_otg_reinit(ctrl_params(ctx), ctx->B, task, 0, ctx->q, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "OTG reinit launch failed");
 	ctx->goals_dirty |= 1u << task;
 	ctx->goals_epoch++, ctx->otg_all_idle = false;
@@ -1611,6 +1666,9 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_HARDWARE_ACTUATOR: return ctx->hw_on ? (void*)ctx->hw_act : nullptr;
 		case SAI2B_BUF_HARDWARE_SENSOR: return ctx->hw_on ? (void*)ctx->hw_sensor : nullptr;
 		case SAI2B_BUF_TAU_APPLIED: return ctx->hw_on ? (void*)ctx->hw_applied : nullptr;
+		case SAI2B_BUF_Q_MEASURED: return ctx->js_on ? (void*)ctx->js_qm : nullptr;
+		case SAI2B_BUF_DQ_MEASURED: return ctx->js_on ? (void*)ctx->js_dqm : nullptr;
+		case SAI2B_BUF_JOINT_SENSOR: return ctx->js_on ? (void*)ctx->js_rows : nullptr;
 		case SAI2B_BUF_REWARD_STATE: return ctx->rew_on ? (void*)ctx->rew_state : nullptr;
 		case SAI2B_BUF_REWARD_EPISODE: return ctx->rew_on ? (void*)ctx->rew_episode : nullptr;
 		case SAI2B_BUF_ENV_SAMPLE: return ctx->es_on ? (void*)ctx->es_sample : nullptr;
@@ -2319,6 +2377,146 @@ extern "C" int sai2b_get_hardware_state(sai2b_ctx* ctx, double* applied_torque, 
 	return SAI2B_OK;
 }
 // what the two stages take from the context
+// ------------------------------------------------------------------------------------------------
+// joint sensors (include/sai2b.h "joint sensors"; law: sai2b_joint_sensor_law.h; kernel: sai2b_joint_sensor.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int sai2b_default_joint_sensor(sai2b_joint_sensor_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_joint_sensor: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	return SAI2B_OK;
+}
+static std::string joint_sensor_config_error(const sai2b_joint_sensor_config* c) {
+	if (!c) return "joint sensor: null config";
+	if (c->max_delay < 0 || c->max_delay > SAI2B_MAX_ACTUATION_DELAY) return "joint sensor: max_delay must be in [0, SAI2B_MAX_ACTUATION_DELAY]";
+	if (c->velocity_mode != 0 && c->velocity_mode != 1) return "joint sensor: velocity_mode must be 0 (tachometer) or 1 (finite difference)";
+	return "";
+}
+static std::string joint_sensor_rows_error(const sai2b_joint_sensor_config* c, const double* rows, size_t B) {
+	if (!rows) return "";
+	for (size_t b = 0; b < B; b++) {
+		const double d = rows[b];
+		if (!(d >= 0 && d <= c->max_delay) || d != std::floor(d)) return "joint sensor: the delay must be an integer in [0, max_delay]";
+	}
+	for (size_t i = 0; i < (size_t)N * B; i++) {
+		const double o = rows[B + i], s = rows[(1 + (size_t)N) * B + i], q = rows[(1 + 2 * (size_t)N) * B + i];
+		const double r = rows[(1 + 3 * (size_t)N) * B + i], alpha = rows[(1 + 4 * (size_t)N) * B + i];
+		if (!std::isfinite(o)) return "joint sensor: the offset o must be finite";
+		if (!std::isfinite(s) || s < 0) return "joint sensor: the position noise s must be finite and not negative";
+		if (!std::isfinite(q) || q < 0) return "joint sensor: the quantum Delta must be finite and not negative";
+		if (!std::isfinite(r) || r < 0) return "joint sensor: the velocity noise r must be finite and not negative";
+		if (!(alpha > 0 && alpha <= 1)) return "joint sensor: the velocity filter coefficient alpha must be in (0, 1]";
+	}
+	return "";
+}
+extern "C" int sai2b_validate_joint_sensor(const sai2b_joint_sensor_config* cfg, int robot_dof, char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? joint_sensor_config_error(cfg) : "joint sensor: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (err.empty()) return SAI2B_OK;
+	return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_validate_joint_sensor: " + err);
+}
+extern "C" int sai2b_sizeof_joint_sensor_config(void) { return (int)sizeof(sai2b_joint_sensor_config); }
+
+static void joint_sensor_ideal_rows(size_t B, std::vector<double>* rows) {
+	rows->assign((size_t)sai2b::JS_ROWS * B, 0.0);
+	std::fill(rows->begin() + (1 + 4 * (size_t)N) * B, rows->end(), 1.0);
+}
+extern "C" int sai2b_set_joint_sensor(sai2b_ctx* ctx, const sai2b_joint_sensor_config* cfg, const double* rows, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_sensor: null ctx");
+	std::string err = joint_sensor_config_error(cfg);
+	const size_t B = ctx->B;
+	if (err.empty() && !on_device) err = joint_sensor_rows_error(cfg, rows, B);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_joint_sensor: " + err);
+	int rc = flush_update(ctx);
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t hist = (size_t)(SAI2B_MAX_ACTUATION_DELAY + 1) * 2 * N * B;
+	if (!ctx->js_rows && (rc = dev_alloc(ctx, &ctx->js_rows, (size_t)sai2b::JS_ROWS * B))) return rc;
+	if (!ctx->js_qm && (rc = dev_alloc(ctx, &ctx->js_qm, (size_t)N * B))) return rc;
+	if (!ctx->js_dqm && (rc = dev_alloc(ctx, &ctx->js_dqm, (size_t)N * B))) return rc;
+	if (!ctx->js_prev && (rc = dev_alloc(ctx, &ctx->js_prev, (size_t)N * B))) return rc;
+	if (!ctx->js_filter && (rc = dev_alloc(ctx, &ctx->js_filter, (size_t)N * B))) return rc;
+	if (!ctx->js_history && (rc = dev_alloc(ctx, &ctx->js_history, hist))) return rc;
+	if (!ctx->js_clock && (rc = dev_alloc(ctx, &ctx->js_clock, 2 * B))) return rc;
+	if (!ctx->d_params_meas && (rc = dev_alloc(ctx, &ctx->d_params_meas, 1))) return rc;
+	// While q_is_pose holds, the cached pose is the controller's q: it moves to q_pose before the controller's q changes buffers.
+	// A sensor already in force is taken out of force first, as sai2b_set_hardware does: a copy that fails leaves the context
+	// with one view, never with rows that are half the old ones and half the new.
+	if ((rc = keep_pose(ctx))) return rc;
+	ctx->js_on = false;
+	ctx->params_dirty = true;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->js_clock, 0, 2 * B * sizeof(int), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->js_history, 0, hist * sizeof(double), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->js_prev, 0, (size_t)N * B * sizeof(double), ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(ctx->js_filter, 0, (size_t)N * B * sizeof(double), ctx->stream));
+	std::vector<double> ideal;
+	if (!rows) joint_sensor_ideal_rows(B, &ideal);
+	if ((rc = copy_rows(ctx, ctx->js_rows, rows ? rows : ideal.data(), sai2b::JS_ROWS, rows ? on_device : 0))) return rc;
+	ctx->js_cfg = *cfg;
+	ctx->js_cfg.reserved = 0;
+	ctx->js_on = true;
+	// everything is written: reading 0 of every robot, episode 0
+	if ((rc = joint_sensor_seed(ctx, nullptr, false))) {
+		ctx->js_on = false;
+		return rc;
+	}
+	ctx->models_fresh = false;
+	for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_joint_sensor(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_joint_sensor: null ctx");
+	if (!ctx->js_on) return SAI2B_OK;
+	int rc = flush_update(ctx);
+	if (rc) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if ((rc = keep_pose(ctx))) return rc;  // the cached pose was the measured q
+	ctx->js_on = false;
+	ctx->params_dirty = true;
+	ctx->models_fresh = false;
+	for (int t = 0; t < ctx->T; t++) ctx->tio[t].model_fresh = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_joint_sensor(sai2b_ctx* ctx, sai2b_joint_sensor_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_joint_sensor: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) {
+		if (ctx->js_on)
+			*cfg = ctx->js_cfg;
+		else
+			sai2b_default_joint_sensor(cfg);
+	}
+	if (!ctx->js_on) {
+		if (rows) {
+			std::vector<double> ideal;
+			joint_sensor_ideal_rows(ctx->B, &ideal);
+			std::memcpy(rows, ideal.data(), ideal.size() * sizeof(double));
+		}
+		return SAI2B_OK;
+	}
+	return fetch_rows(ctx, ctx->js_rows, 0, sai2b::JS_ROWS, rows);
+}
+extern "C" int sai2b_get_joint_sensor_state(sai2b_ctx* ctx, int* clock, int* episode) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_joint_sensor_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t B = ctx->B;
+	if (!ctx->js_on) {
+		if (clock) std::memset(clock, 0, B * sizeof(int));
+		if (episode) std::memset(episode, 0, B * sizeof(int));
+		return SAI2B_OK;
+	}
+	if (clock) HIP_TRY(ctx, hipMemcpyAsync(clock, ctx->js_clock, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	if (episode) HIP_TRY(ctx, hipMemcpyAsync(episode, ctx->js_clock + B, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_measured_state(sai2b_ctx* ctx, double* q, double* dq) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_measured_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc = fetch_rows(ctx, ctrl_q(ctx), 0, N, q);
+	if (rc) return rc;
+	return fetch_rows(ctx, ctrl_dq(ctx), 0, N, dq);
+}
+
 static sai2b::HwStream hardware_stream(const sai2b_ctx* ctx) {
 	sai2b::HwStream s;
 	s.key0 = (unsigned)(ctx->hw_cfg.seed & 0xffffffffull), s.key1 = (unsigned)(ctx->hw_cfg.seed >> 32), s.first_robot = ctx->hw_cfg.first_robot;
@@ -2762,7 +2960,7 @@ extern "C" int sai2b_observe(sai2b_ctx* ctx, double* out, unsigned char* done, i
 		}
 	}
 	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, sai2b::OBS_COUNTS * sizeof(int), ctx->stream));
-	if (sai2b::launch_observe(ctx->d_params, ctx->B, ctx->obs, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
+	if (sai2b::launch_observe(ctrl_params(ctx), ctx->B, ctx->obs, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_observe: launch failed");
 	ctx->launches++;
 	if (on_device) return (want_out || done) ? caller_after_read(ctx) : SAI2B_OK;
@@ -2960,7 +3158,7 @@ extern "C" int sai2b_observe_reward(sai2b_ctx* ctx, double* out, unsigned char* 
 		}
 	}
 	HIP_TRY(ctx, hipMemsetAsync(ctx->obs_counts, 0, (sai2b::OBS_COUNTS + sai2b::REW_COUNTS) * sizeof(int), ctx->stream));
-	if (sai2b::launch_observe_reward(ctx->d_params, ctx->B, ctx->obs, w, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
+	if (sai2b::launch_observe_reward(ctrl_params(ctx), ctx->B, ctx->obs, w, d_out, d_done, ctx->obs_steps, ctx->obs_counts, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_observe_reward: launch failed");
 	ctx->launches++;
 	if (on_device) return any ? caller_after_read(ctx) : SAI2B_OK;
@@ -3170,7 +3368,7 @@ extern "C" int sai2b_apply_action(sai2b_ctx* ctx, const double* action, const un
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
 	}
 	HIP_TRY(ctx, hipMemsetAsync(ctx->act_counts, 0, sai2b::ACT_COUNTS * sizeof(int), ctx->stream));
-	if (sai2b::launch_action(ctx->d_params, ctx->B, ctx->act, d_action, d_mask, ctx->act_counts, ctx->stream))
+	if (sai2b::launch_action(ctrl_params(ctx), ctx->B, ctx->act, d_action, d_mask, ctx->act_counts, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_apply_action: launch failed");
 	// as the goal setters: the generators of the tasks that took rows compare their goals at the next tick
 	for (int t = 0; t < ctx->T; t++)
@@ -3206,9 +3404,12 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 		if ((rc = copy_rows(ctx, ctx->sim_tau, tau, N, 0))) return rc;
 		t = ctx->sim_tau;
 	}
-	// the kernel saves the pose the tasks cached (q_pose) on its way in, when the state buffer still holds it
+	// the kernel saves the pose the tasks cached (q_pose) on its way in, when the state buffer still holds it; with a joint sensor
+	// the cached pose is the measured q, which the sense stage saves before it overwrites the measurement
 	double* q_keep = ctx->q_is_pose ? ctx->q_pose : nullptr;
 	ctx->q_is_pose = false;
+	double* js_keep = nullptr;
+	if (ctx->js_on) js_keep = q_keep, q_keep = nullptr;
 	// the instantiation for what the context has set: plant payload, contact (whose counter starts each step at zero)
 	const DevParams& hp = ctx->h_params;
 	if (hp.contact) HIP_TRY(ctx, hipMemsetAsync(hp.contact_count, 0, sizeof(int), ctx->stream));
@@ -3235,6 +3436,13 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 		sai2b::SenseParams s;
 		s.rows = ctx->hw_sensor, s.sensed = hp.task[hw_task].sensed, s.filter = ctx->hw_filter, s.clock = ctx->hw_clock, s.rng = hardware_stream(ctx);
 		if (sai2b::launch_sense(ctx->B, s, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "sensor launch failed");
+		ctx->launches++;
+	}
+	// joint sensors: the next reading of the state the plant has just reached, last in the call
+	if (ctx->js_on) {
+		sai2b::JointSenseParams s = joint_sense_params(ctx);
+		s.dt = dt, s.q_pose = js_keep;
+		if (sai2b::launch_joint_sense(ctx->B, s, false, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "joint sensor launch failed");
 		ctx->launches++;
 	}
 	ctx->models_fresh = false;
@@ -3267,7 +3475,7 @@ static int run_status(sai2b_ctx* ctx, int task) {
 	rc = upload_params(ctx);
 	if (rc) return rc;
 	if (!ctx->status_buf && (rc = dev_alloc(ctx, &ctx->status_buf, 68 * (size_t)ctx->B))) return rc;
-	if (sai2b::launch_mft_status(ctx->d_params, ctx->B, task, ctx->status_buf, ctx->stream))
+	if (sai2b::launch_mft_status(ctrl_params(ctx), ctx->B, task, ctx->status_buf, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "status launch failed");
 	return SAI2B_OK;
 }
@@ -3445,10 +3653,10 @@ extern "C" int sai2b_profile_tick(sai2b_ctx* ctx, int steps, double* first_ms, d
 			HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
 			for (int s = 0; s < steps; s++) {
 				if (two || self) ctx->fb.parity ^= 1;
-				if (sai2b::launch_tick_part(ctx->d_params, ctx->B, (two && phase == 0) ? alone : form, ctx->introspection, 0, ctx->fb,
+				if (sai2b::launch_tick_part(ctrl_params(ctx), ctx->B, (two && phase == 0) ? alone : form, ctx->introspection, 0, ctx->fb,
 											sai2b::generic_lanes(ctx->sw, ctx->B, !two), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
-				if (phase == 1 && !self && sai2b::launch_tick_part(ctx->d_params, ctx->B, form, false, 1, ctx->fb, sai2b::generic_lanes(ctx->sw, ctx->B, false), ctx->stream))
+				if (phase == 1 && !self && sai2b::launch_tick_part(ctrl_params(ctx), ctx->B, form, false, 1, ctx->fb, sai2b::generic_lanes(ctx->sw, ctx->B, false), ctx->stream))
 					return set_error(ctx, SAI2B_RUNTIME_ERROR, "tick launch failed");
 			}
 			HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
@@ -3516,7 +3724,8 @@ extern "C" int sai2b_counters(const sai2b_ctx* ctx, long long* launches, long lo
 static_assert(sai2b::SNAP_JOINT_ROWS == sai2b::JOINT_ROWS && sai2b::SNAP_JOINT_STATUS_ROWS == sai2b::JOINT_STATUS_ROWS &&
 				  sai2b::SNAP_WRENCH_MOTION_ROWS + 1 == sai2b::WRENCH_ROWS && 6 + N == sai2b::WRENCH_STATUS_ROWS &&
 				  sai2b::MFT_STATE_ROWS == 12 + 3 * N && sai2b::SNAP_HW_SENSOR_ROWS == sai2b::HW_SENSOR_ROWS &&
-				  sai2b::SNAP_HW_MAX_DEPTH == sai2b::HW_MAX_DELAY && sai2b::HW_FILTER_ROWS == N + 6 && sai2b::HW_ACT_ROWS == 1 + 3 * N,
+				  sai2b::SNAP_HW_MAX_DEPTH == sai2b::HW_MAX_DELAY && sai2b::HW_FILTER_ROWS == N + 6 && sai2b::HW_ACT_ROWS == 1 + 3 * N &&
+				  sai2b::JS_ROWS == 1 + 5 * N,
 			  "sai2b_snapshot_layout.h and the kernels disagree about a buffer's rows");
 
 namespace {
@@ -3569,6 +3778,9 @@ static sai2b::SnapDesc snapshot_describe(const sai2b_ctx* ctx, int what) {
 	d.reset_sampler = epi && ctx->rs_state != nullptr;
 	// the environment sampler's counters and sample rows exist from the first sai2b_set_env_sampler on; the rows are those of the last one
 	d.env_sampler = ctx->es_counter != nullptr ? 1 + ctx->es_lay.total : 0;
+	// the joint sensors' buffers exist from the first sai2b_set_joint_sensor on; the history's depth is that of the last one
+	d.joint_sensor = ctx->js_clock != nullptr;
+	d.joint_sensor_depth = d.joint_sensor && epi ? ctx->js_cfg.max_delay : 0;
 	return d;
 }
 
@@ -3614,6 +3826,13 @@ static void* snapshot_block_base(sai2b_ctx* ctx, const sai2b::SnapRow& r) {
 		case SNAP_RS_EPISODE: return ctx->rs_state;
 		case SNAP_ES_COUNTER: return ctx->es_counter;
 		case SNAP_ES_SAMPLE: return ctx->es_sample;
+		case SNAP_JS_Q: return ctx->js_qm;
+		case SNAP_JS_DQ: return ctx->js_dqm;
+		case SNAP_JS_PREV: return ctx->js_prev;
+		case SNAP_JS_FILTER: return ctx->js_filter;
+		case SNAP_JS_HISTORY: return ctx->js_history;
+		case SNAP_JS_CLOCK: return ctx->js_clock;
+		case SNAP_JS_ROWS: return ctx->js_rows;
 		default: return nullptr;
 	}
 }
@@ -3740,8 +3959,8 @@ static int snapshot_move(sai2b_ctx* ctx, sai2b_snapshot_bank* bank, const int* s
 	const bool episode = bank->desc.what & SAI2B_SNAP_EPISODE;
 	// q_is_pose is one flag for the batch. A save stores the cached pose from wherever it lives. A load puts a loaded robot's pose
 	// into q_pose, so the flag ends for the batch: the robots the call leaves alone get q_pose := q in the same launch.
-	if (save && ctx->q_is_pose) a.pose_src = ctx->q;
-	if (!save && episode && ctx->q_is_pose) a.keep_pose_q = ctx->q, a.keep_pose_dst = ctx->q_pose;
+	if (save && ctx->q_is_pose) a.pose_src = ctrl_q(ctx);
+	if (!save && episode && ctx->q_is_pose) a.keep_pose_q = ctrl_q(ctx), a.keep_pose_dst = ctx->q_pose;
 	if (sai2b::launch_snapshot(a, save, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, fn + ": launch failed");
 	ctx->launches++;
 	HIP_TRY(ctx, hipEventRecord(bank->last, ctx->stream));

@@ -226,6 +226,25 @@ struct SenseParams {
 	const int* clock = nullptr;	   // [2][B] as actuate_kernel left it in this call: the period is clock - 1
 	HwStream rng;
 };
+// joint sensors (sai2b_set_joint_sensor, sai2b_joint_sensor.hip: joint_sense_kernel): the kernel's own parameter block, passed by
+// value like SenseParams; DevParams is not read (the controller-side kernels get a copy of it whose q, dq are the measured pair).
+constexpr int JS_ROWS = 1 + 5 * N;	// delay; offset, position noise, quantum, velocity noise, velocity filter coefficient [N] each
+struct JointSenseParams {
+	const double* rows = nullptr;		  // [JS_ROWS][B]
+	const double *q = nullptr, *dq = nullptr;  // [N][B]: the truth
+	double *q_meas = nullptr, *dq_meas = nullptr;  // [N][B]: the delivered reading
+	double *prev = nullptr, *filter = nullptr;	   // [N][B] each: the previous position reading, the velocity filter's state
+	double* history = nullptr;			  // [depth + 1][2 N][B]
+	int* clock = nullptr;				  // [2][B]: index of the next reading c, episode e
+	double* q_pose = nullptr;			  // step: q_meas is saved here first (NULL: not)
+	const unsigned char* mask = nullptr;  // seed: [B] bytes or NULL = every robot
+	int depth = 0, velocity_mode = 0;
+	int next_episode = 0;  // seed: e += 1
+	double dt = 0;		   // step: the period of the sai2b_sim_step call
+	HwStream rng;
+};
+// seed: reading 0 of the masked robots, clock := 1; else reading c of every robot, clock := c + 1
+int launch_joint_sense(int B, const JointSenseParams& p, bool seed, hipStream_t stream);
 int launch_actuate(int B, const ActuateParams& p, hipStream_t stream);
 int launch_sense(int B, const SenseParams& p, hipStream_t stream);
 // the selected robots' period := 0, episode += 1; mask [B] device bytes

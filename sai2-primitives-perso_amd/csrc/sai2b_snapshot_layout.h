@@ -36,17 +36,30 @@ enum SnapBlock {
 	// ---- appended for the environment sampler (sai2b_set_env_sampler): its per-robot draw counter (int), episode; the drawn
 	// quantities (the sample rows), environment: they travel with the plant rows they describe
 	SNAP_ES_COUNTER = SNAP_BLOCKS, SNAP_ES_SAMPLE,
-	SNAP_BLOCKS_ALL
+	SNAP_BLOCKS_ALL,  // the blocks up to the environment sampler's (a test pins this value too)
+	// ---- appended for the joint sensors (sai2b_set_joint_sensor). Episode: the measured q and dq, the previous position reading,
+	// the velocity filter's state, the history of readings, the clock (next reading, episode; int); environment: the rows
+	SNAP_JS_Q = SNAP_BLOCKS_ALL, SNAP_JS_DQ, SNAP_JS_PREV, SNAP_JS_FILTER, SNAP_JS_HISTORY, SNAP_JS_CLOCK, SNAP_JS_ROWS,
+	SNAP_BLOCKS_EVERY
 };
-static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS_ALL] = {
+static const char* const SNAP_BLOCK_NAME[SNAP_BLOCKS_EVERY] = {
 	"q", "dq", "tau", "q_pose", "goals", "sensed", "state", "istate", "otg_desired", "otg_state", "otg3_traj", "popc_f", "popc_i", "popc_q",
 	"N_prec", "episode_step", "wrench_remaining", "contact_status", "joint_status", "wrench_status",
 	"payload", "plant_payload", "contact", "joint_dynamics", "external_wrench",
 	"hw_history", "hw_filter", "hw_applied", "hw_clock", "hw_actuator", "hw_sensor", "reward_state", "reward_episode",
-	"reset_sampler_episode", "env_sampler_counter", "env_sampler_sample"};
+	"reset_sampler_episode", "env_sampler_counter", "env_sampler_sample",
+	"joint_sensor_q", "joint_sensor_dq", "joint_sensor_previous", "joint_sensor_filter", "joint_sensor_history", "joint_sensor_clock",
+	"joint_sensor_rows"};
 // where a block stands in the sequence snapshot_blocks() draws from: the hardware's, the reward's and the two samplers' episode
-// blocks ahead of the environment group, the environment sampler's sample rows at its end
-static inline int snap_block_order(int block) {
+// blocks ahead of the environment group, the environment sampler's sample rows at its end; the joint sensors' episode blocks
+// behind the episode group's last, their rows behind the environment group's last
+static inline int snap_block_order_base(int block);
+static inline int snap_block_order(int block) {	 // eight places behind every earlier block, for those appended since
+	if (block >= SNAP_JS_Q && block <= SNAP_JS_CLOCK) return 8 * snap_block_order_base(SNAP_ES_COUNTER) + 1 + (block - SNAP_JS_Q);
+	if (block == SNAP_JS_ROWS) return 8 * snap_block_order_base(SNAP_ES_SAMPLE) + 1;
+	return 8 * snap_block_order_base(block);
+}
+static inline int snap_block_order_base(int block) {
 	constexpr int hw_episode = SNAP_HW_CLOCK - SNAP_HW_HISTORY + 1, reward = SNAP_REWARD_EPISODE - SNAP_REWARD_STATE + 1;
 	constexpr int environment = SNAP_WRENCH - SNAP_PAYLOAD + 1, hw_environment = SNAP_HW_SENSOR - SNAP_HW_ACTUATOR + 1, sampler = 2;
 	if (block >= SNAP_PAYLOAD && block <= SNAP_WRENCH) return block + hw_episode + reward + sampler;
@@ -82,8 +95,10 @@ struct SnapDesc {
 	int hardware_depth;	 // D: the torque history holds D + 1 periods
 	int reward;			 // the reward's accumulators exist
 	int reset_sampler;	 // the episode sampler's counter exists
-	int env_sampler;	 // 0: no environment sampler; else 1 + its sample rows. Last: code that zeroes a description and fills the
-						 // fields above stays valid
+	int env_sampler;	 // 0: no environment sampler; else 1 + its sample rows
+	int joint_sensor;	 // the joint sensors' buffers exist (0: none, and joint_sensor_depth is 0)
+	int joint_sensor_depth;	 // D: the history of readings holds D + 1 periods. Appended: code that zeroes a description and fills
+							 // the fields above stays valid
 };
 
 struct SnapRow {
@@ -95,13 +110,14 @@ struct SnapRow {
 };
 constexpr int SNAP_MAX_ROWS_TABLE = 9 + 11 * SAI2B_MAX_TASKS + 5 + 6 + 2;	 // the blocks up to the reward's (a description without the sampler)
 constexpr int SNAP_TABLE_CAPACITY = SNAP_MAX_ROWS_TABLE + 1;			 // and the episode sampler's (a test pins this value too)
-constexpr int SNAP_TABLE_ROOM = SNAP_TABLE_CAPACITY + 2;				 // and the environment sampler's two: what every table below has room for
+constexpr int SNAP_TABLE_ROOM = SNAP_TABLE_CAPACITY + 2;				 // and the environment sampler's two (a test pins this value too)
+constexpr int SNAP_TABLE_FULL = SNAP_TABLE_ROOM + 7;					 // and the joint sensors' seven: what every table below has room for
 
 struct SnapLayout {
 	int n = 0;
 	int words = 0, rows = 0;  // per robot
 	unsigned long long fingerprint = 0;
-	SnapRow row[SNAP_TABLE_ROOM];
+	SnapRow row[SNAP_TABLE_FULL];
 };
 
 static inline int snap_goal_rows(const SnapTaskDesc& t) { return t.kind == SAI2B_MOTION_FORCE_TASK ? MFT_GOAL_ROWS : 3 * t.k0; }
@@ -142,6 +158,9 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_REWARD_EPISODE, -1, d.reward ? 2 : 0, 4);
 		add(SNAP_RS_EPISODE, -1, d.reset_sampler ? 1 : 0, 4);
 		add(SNAP_ES_COUNTER, -1, d.env_sampler ? 1 : 0, 4);
+		for (int blk = SNAP_JS_Q; blk <= SNAP_JS_FILTER; blk++) add(blk, -1, d.joint_sensor ? d.dof : 0, 8);
+		add(SNAP_JS_HISTORY, -1, d.joint_sensor ? (d.joint_sensor_depth + 1) * 2 * d.dof : 0, 8);
+		add(SNAP_JS_CLOCK, -1, d.joint_sensor ? 2 : 0, 4);
 	}
 	if (d.what & SNAP_ENVIRONMENT_BIT) {
 		add(SNAP_PAYLOAD, -1, d.payload ? PAYLOAD_ROWS : 0, 8);
@@ -152,6 +171,7 @@ static inline int snapshot_blocks(const SnapDesc& d, SnapRow* out) {
 		add(SNAP_HW_ACTUATOR, -1, d.hardware ? 1 + 3 * d.dof : 0, 8);
 		add(SNAP_HW_SENSOR, -1, d.hardware ? SNAP_HW_SENSOR_ROWS : 0, 8);
 		add(SNAP_ES_SAMPLE, -1, d.env_sampler ? d.env_sampler - 1 : 0, 8);
+		add(SNAP_JS_ROWS, -1, d.joint_sensor ? 1 + 5 * d.dof : 0, 8);
 	}
 	return n;
 }
@@ -173,6 +193,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 	if (d.reward != 0) mix(d.reward);
 	if (d.reset_sampler != 0) mix(d.reset_sampler);
 	if (d.env_sampler != 0) mix(d.env_sampler);
+	if (d.joint_sensor != 0) mix(d.joint_sensor), mix(d.joint_sensor_depth);
 	return h;
 }
 
@@ -180,7 +201,7 @@ static inline unsigned long long snapshot_fingerprint(const SnapDesc& d) {
 // and stays 8-byte aligned in a [word][capacity] bank of any capacity. Words are contiguous.
 static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 	SnapLayout L;
-	SnapRow all[SNAP_TABLE_ROOM];
+	SnapRow all[SNAP_TABLE_FULL];
 	const int n = snapshot_blocks(d, all);
 	for (int bytes = 8; bytes >= 4; bytes -= 4)
 		for (int i = 0; i < n; i++) {
@@ -198,7 +219,7 @@ static inline SnapLayout snapshot_layout(const SnapDesc& d) {
 static inline bool snapshot_first_difference(const SnapDesc& a, const SnapDesc& b, char* msg, int len) {
 	if (a.dof != b.dof) return std::snprintf(msg, len, "block q: %d joints against %d", a.dof, b.dof), true;
 	if (a.what != b.what) return std::snprintf(msg, len, "block q: groups %d against %d", a.what, b.what), true;
-	SnapRow ra[SNAP_TABLE_ROOM], rb[SNAP_TABLE_ROOM];
+	SnapRow ra[SNAP_TABLE_FULL], rb[SNAP_TABLE_FULL];
 	const int na = snapshot_blocks(a, ra), nb = snapshot_blocks(b, rb);
 	for (int i = 0; i < (na < nb ? na : nb); i++) {
 		const SnapRow &x = ra[i], &y = rb[i];
@@ -212,7 +233,7 @@ static inline bool snapshot_first_difference(const SnapDesc& a, const SnapDesc& 
 		// both lists are drawn from one sequence (globals, then task by task, then the optional features): the earlier entry is missing in the other
 		auto key = [](const SnapRow& r) {
 			const int grp = r.block < SNAP_GOALS ? 0 : r.block <= SNAP_NPREC ? 1 : 2;
-			return (grp * 16 + (r.task < 0 ? 0 : r.task)) * 64 + snap_block_order(r.block);
+			return (grp * 16 + (r.task < 0 ? 0 : r.task)) * 512 + snap_block_order(r.block);
 		};
 		const SnapRow& first = key(x) <= key(y) ? x : y;
 		if (first.task >= 0) return std::snprintf(msg, len, "block %s of task %d", SNAP_BLOCK_NAME[first.block], first.task), true;

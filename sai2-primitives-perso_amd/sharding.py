@@ -77,6 +77,13 @@ def set_hardware(ctrl, world, rank, global_batch, actuator_rows=None, sensor_row
     ctrl.set_hardware(shard_rows(actuator_rows, world, rank), shard_rows(sensor_rows, world, rank), first_robot=lo, **kwargs)
 
 
+def set_joint_sensor(ctrl, world, rank, global_batch, rows=None, **kwargs):
+    """Controller.set_joint_sensor on this rank's shard of the per-robot rows [1 + 5 dof][global_batch] given for the whole
+    batch, with first_robot set to the shard's first global index: every robot draws the noise it draws in the one-context run"""
+    lo, _ = shard_bounds(global_batch, world, rank)
+    ctrl.set_joint_sensor(shard_rows(rows, world, rank), first_robot=lo, **kwargs)
+
+
 def reinitialize_robots(ctrl, world, rank, mask, task=-1):
     """Controller.reinitialize_robots on this rank's shard of a mask given for the whole batch"""
     ctrl.reinitialize_robots(shard_rows(mask, world, rank), task)

@@ -3,7 +3,7 @@
 <unit>_n<N>.s for the device translation units of the Makefile and N = 4, 6, 7, 8, made in csrc/ of either state with
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSAI2B_N=<N> -include sai2b_dof_rename.h --cuda-device-only -S <unit>.hip
-  (sai2b_otg.hip: with -ffp-contract=off, as the Makefile builds it)
+  (sai2b_otg.hip and sai2b_env_sampler.hip: with -ffp-contract=off, as the Makefile builds them)
 
 Compared per kernel: the .amdhsa_* descriptor block and the instruction lines (directives and comments dropped, as
 tests/test_fast_kernel_isa.py filters them). Exit status 0 when every kernel of every unit is the same."""
@@ -11,7 +11,8 @@ import os
 import re
 import sys
 
-UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action", "sai2b_snapshot", "sai2b_hardware"]
+UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action", "sai2b_snapshot", "sai2b_hardware",
+         "sai2b_env_sampler", "sai2b_joint_sensor"]
 
 
 def kernels(path):
