@@ -209,13 +209,16 @@ struct Frames {
 	real R[N][9];
 	real p[N][3];
 };
-template <class MD>
+// LOCAL: positions relative to the origin of joint 0's frame, md.xyz[0] (which carries the base transform), not to the world
+// origin. M, b and every lever arm x - p_i are the same in both; far from the world origin only the local form keeps the
+// composite inertias of mass_matrix (taken about the origin of the coordinates) at the size of the robot
+template <bool LOCAL = false, class MD>
 DI void fk(const MD& md, const real* q, Frames& F) {
 	real Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pp[3] = {0, 0, 0};
 	UNROLL for (int i = 0; i < N; i++) {
 		real RE[9];
 		if (i == 0) {
-			UNROLL for (int k = 0; k < 3; k++) F.p[0][k] = md.xyz[0][k];
+			UNROLL for (int k = 0; k < 3; k++) F.p[0][k] = LOCAL ? 0.0 : md.xyz[0][k];
 			UNROLL for (int k = 0; k < 9; k++) RE[k] = md.E[0][k];
 		} else {
 			UNROLL for (int k = 0; k < 3; k++)

@@ -130,9 +130,10 @@ struct Contact {
 	real p0[3], n[3], k, d, mu;	 // the robot's own plane: rows of the [9][B] buffer
 };
 constexpr int CONTACT_MAX_POINTS = SAI2B_MAX_CONTACT_POINTS;
-DI void contact_load(const real* rows, int B, int b, Contact& ct) {
+// o: the origin of the step's coordinates (fk<true>: joint 0's frame origin); the plane point is taken relative to it
+DI void contact_load(const real* rows, const double* o, int B, int b, Contact& ct) {
 	UNROLL for (int k = 0; k < 3; k++) {
-		ct.p0[k] = ld(rows, k, B, b);
+		ct.p0[k] = ld(rows, k, B, b) - o[k];
 		ct.n[k] = ld(rows, 3 + k, B, b);
 	}
 	ct.k = ld(rows, 6, B, b);
@@ -241,7 +242,7 @@ DI void contact_report(const MD& md, const DevParams& P, const Contact& ct, cons
 	if constexpr (RD::on) {
 		Fr = *given;
 	} else {
-		fk(md, q, Fr);
+		fk<true>(md, q, Fr);
 	}
 	real Rl[9], pl[3], xc[3], Rc[9];
 	link_frame(P.contact_link, Fr, Rl, pl);
@@ -367,7 +368,7 @@ template <class MD, class CT>
 DI void wrench_finish(const MD& md, const DevParams& P, const WrenchParams& W, const Wrench& wr, const CT& ct, const real* q,
 					  const real* dq, int B, int b) {
 	Frames Fr;
-	fk(md, q, Fr);
+	fk<true>(md, q, Fr);
 	WrenchReading rd;
 	wrench_report(md, W, wr, Fr, B, b, rd);
 	rd.add = false;
@@ -388,6 +389,9 @@ DI void wrench_finish(const MD& md, const DevParams& P, const WrenchParams& W, c
 // PL: NoPayload / Payload (the PLANT's payload, sai2b_set_link_payload with SAI2B_PAYLOAD_PLANT), CT: NoContact / Contact;
 // the host launches the instantiation for what the context has set, sim_kernel<NoPayload, NoContact> is the kernel without
 // either feature.
+// Every step body and report of this file works in coordinates whose origin is joint 0's frame (fk<true>): M, b, the lever
+// arms, the moments about x_c and the sensor rows do not depend on the origin, mass_matrix's inertias about it stay the size
+// of the robot however far the base stands from the world origin, and contact_load shifts the plane point to match.
 // q_keep != NULL: the joint positions as they are on entry are saved there first (the pose the tasks cached at
 // their last torque computation: see q_pose in sai2b_host.cpp)
 template <class PL, class CT>
@@ -408,12 +412,12 @@ __global__ __launch_bounds__(64) void sim_kernel(const DevParams* __restrict__ P
 	[[maybe_unused]] PL pl;
 	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
 	[[maybe_unused]] CT ct;
-	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	if constexpr (CT::on) contact_load(P.contact, P.model.xyz[0], B, b, ct);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
 		Frames F;
-		fk(P.model, q, F);
+		fk<true>(P.model, q, F);
 		real M[N * N], L[N * N], dinv[N], bias[N], x[N];
 		bias_forces(P.model, F, dq, with_gravity != 0, bias, pl);
 		if (dbg_bias && s == 0) {
@@ -462,14 +466,14 @@ __global__ __launch_bounds__(64) void sim_wrench_kernel(const DevParams* __restr
 	[[maybe_unused]] PL pl;
 	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
 	[[maybe_unused]] CT ct;
-	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	if constexpr (CT::on) contact_load(P.contact, P.model.xyz[0], B, b, ct);
 	Wrench wr;
 	wrench_load(W, B, b, wr);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
 		Frames F;
-		fk(P.model, q, F);
+		fk<true>(P.model, q, F);
 		real M[N * N], L[N * N], dinv[N], bias[N], x[N];
 		bias_forces(P.model, F, dq, with_gravity != 0, bias, pl);
 		mass_matrix(P.model, F, M, pl);
@@ -563,12 +567,12 @@ __global__ __launch_bounds__(64) void sim_joint_kernel(const DevParams* __restri
 	[[maybe_unused]] PL pl;
 	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
 	[[maybe_unused]] CT ct;
-	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	if constexpr (CT::on) contact_load(P.contact, P.model.xyz[0], B, b, ct);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
 		Frames F;
-		fk(P.model, q, F);
+		fk<true>(P.model, q, F);
 		real M[N * N], L[N * N], dinv[N], x[N];
 		bias_forces(P.model, F, dq, with_gravity != 0, x, pl);
 		if constexpr (CT::on) {
@@ -629,14 +633,14 @@ __global__ __launch_bounds__(64) void sim_joint_wrench_kernel(const DevParams* _
 	[[maybe_unused]] PL pl;
 	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
 	[[maybe_unused]] CT ct;
-	if constexpr (CT::on) contact_load(P.contact, B, b, ct);
+	if constexpr (CT::on) contact_load(P.contact, P.model.xyz[0], B, b, ct);
 	Wrench wr;
 	wrench_load(W, B, b, wr);
 	const real h = dt / substeps;
 #pragma unroll 1
 	for (int s = 0; s < substeps; s++) {
 		Frames F;
-		fk(P.model, q, F);
+		fk<true>(P.model, q, F);
 		real M[N * N], L[N * N], dinv[N], x[N];
 		bias_forces(P.model, F, dq, with_gravity != 0, x, pl);
 		real tx[N], xw[3], Fw[3], Mw[3];

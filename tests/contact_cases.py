@@ -5,7 +5,9 @@ all. Ranges: d in [0, 0.5] s/m, mu in [0, 0.8], v_eps = 1e-3 m/s, joint speeds N
 from [1e3, 2e4] until the one-ulp condition of tests/test_contact_reference.py holds for every robot at B = 200 and 4 099.
 What limits it is not the spring but friction: below v_eps the regularised Coulomb term is a damper of mu f_n / v_eps
 (up to 1.6e4 N s/m at 2e4 N/m and 1 mm depth), which the explicit velocity update amplifies on the light outer links of
-planar_4r and six_r (one-ulp start -> 5e-10 rad/s at k <= 1e4, 4e-12 at k <= 2e3)."""
+planar_4r and six_r (one-ulp start -> 5e-10 rad/s at k <= 1e4, 4e-12 at k <= 2e3).
+Stiff contact (k from 1e4 to 1e6 N/m) is tested against the 40-digit plant instead, under a bound that prices the stiffness:
+tests/hp_plant_fixture.py, tests/test_hp_plant.py on the CPU and tests/test_gpu_hp_plant.py on the GPU."""
 import zlib
 
 import numpy as np

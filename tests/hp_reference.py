@@ -31,6 +31,11 @@ the JointTask's integrator and per-joint saturation. The passivity observer, the
 not restated. The held fixtures of these laws are tests/golden/hp_force.npz (tests/test_hp_force_reference.py).
 A force or moment axis is normalised at the working precision, as the reference normalises what it is given.
 
+The simulated plant beyond the rigid body (contact, joint dynamics, the external wrench, the plant payload, the sensor
+and status rows): plant_step() and plant_report() at the end of this file, written from DESIGN's laws with the point
+Jacobians formed explicitly and the implicit system solved by LU; the fixture is tests/golden/hp_plant.npz
+(tests/test_hp_plant.py), and the planted errors of that test are listed there.
+
 HOOKS plants errors for tests/test_hp_reference.py, tests/test_hp_force_reference.py and tests/test_hp_dynamics.py (each
 must be caught by the checker): alpha_rel, flip_vs_type2, no_clamp, pinv_ls, kv1_for_kv2, stale_q_prior;
 ff_through_lambda, kff_moment_own_flag, sensor_no_lever, integ_after_use, sat_componentwise, vsat_no_pinv,
@@ -748,10 +753,11 @@ def _body_motion(model, q, v):
     return f
 
 
-def bias_terms(model, q, dq, gravity=None):
+def bias_terms(model, q, dq, gravity=None, parts=None):
     """b = sum_k Jv_k^T m_k a_k + Jw_k^T (I_k al_k + w_k x I_k w_k) - m_k Jv_k^T gravity, with a_k, al_k the COM and
     angular accelerations of body k at qdd = 0 (derivatives of the body poses along q + t dq). Returns (b, beta):
-    beta[i] = the sum of the absolute values of the products b[i] is summed from (the forward-error scale)"""
+    beta[i] = the sum of the absolute values of the products b[i] is summed from (the forward-error scale).
+    parts: a list, per body and force at its COM appended (index of the body, the force)"""
     q, dq = M_(q), M_(dq)
     n = model.dof
     dps = mp.dps
@@ -775,6 +781,8 @@ def bias_terms(model, q, dq, gravity=None):
         for vec, Jx in ((m * acc[k], Jv), (Ia, Jw), (gyro, Jw), (-m * gr, Jv)):
             b += Jx.T @ vec
             beta += np.abs(Jx).T @ np.abs(vec)
+            if parts is not None and Jx is Jv:
+                parts.append((k, vec))
     return b, beta
 
 
@@ -823,3 +831,292 @@ def sim_step(model, q, dq, tau, dt, substeps, gravity, info=None):
         dq = dq + h * x
         q = q + h * (dq_old if "explicit_euler" in HOOKS else dq)
     return q, dq
+
+
+# ---- the simulated plant: contact, joint dynamics, external wrench (DESIGN "Contact in the simulated plant", "Joint
+# dynamics in the simulated plant", "External wrench on a link"), written from those laws ----
+# Point Jacobians are formed explicitly (Model.jacobian) and the implicit system is solved by LU. The inputs are dicts:
+#   joint    rows [6][n] (armature, damping, friction, torque limit, lower, upper), k, c, e [n]
+#   contact  link (URDF name), points [K][3] (URDF link frame), rows [9] (p0, n, k, d, mu), v_eps, sensor (a task, or None)
+#   wrench   link, point (URDF link frame), frame ("world" | "link": components in the URDF link frame), rows [7]
+#            (F, M, steps on entry of the call), sensor (a task, or None)
+#   a task   link, point, frot (Model.frame), sensor_rot [9], sensor_pos [3]
+#   payload  the Model of the same robot carrying the payload's body: M and b are its
+# HOOKS plants errors for tests/test_hp_plant.py: diss_explicit, rhs_no_armature, upper_stop_minus, contact_outboard,
+# contact_pris_as_rev, friction_along_v, moment_about_link_origin, couple_on_prismatic, wrench_frame_period_start,
+# wrench_never_expires, shared_sensor_no_wrench_moment.
+
+class Noise:
+    """seeded relative perturbations of size eps (times `scale`), for the scales of tests/golden/hp_plant.npz: what
+    roundings of the working precision of a float64 implementation do to the plant's answer"""
+
+    def __init__(self, seed, scale=1.0):
+        self.rng = np.random.default_rng(seed)
+        self.e = mpf(EPS) * scale
+
+    def u(self, *shape):
+        return M_(self.rng.uniform(-1, 1, shape))
+
+    def rel(self, v):
+        """every component by eps of itself"""
+        v = np.asarray(v, dtype=object)
+        return v * (1 + self.e * self.u(*v.shape))
+
+    def add(self, v, s):
+        """every component by eps s (s: a number or an array of v's shape)"""
+        v = np.asarray(v, dtype=object)
+        return v + self.e * s * self.u(*v.shape)
+
+    def sym(self, A):
+        """a symmetric matrix by eps of its Frobenius norm"""
+        d = self.u(*A.shape)
+        return A + self.e * norm_fro(A) * (d + d.T) / 2
+
+
+def _pmax(a, b):
+    return a if a > b else b
+
+
+def wrench_active(steps):
+    """steps > 0 or steps < 0 on entry (a NaN is inactive)"""
+    s = mpf(steps)
+    return bool(s > 0 or s < 0)
+
+
+def wrench_countdown(steps):
+    """what a call leaves in the row: steps > 0 ? max(steps - 1, 0) : steps (a float)"""
+    s = float(steps)
+    if "wrench_never_expires" in HOOKS:
+        return s
+    return max(s - 1.0, 0.0) if s > 0 else s
+
+
+def _point_jacobian(model, pos, jinfo, link, point, outboard=False):
+    """(Jv 3 x n, Jw 3 x n, x) of a point of a link; outboard: the joints past the link counted as if they moved it"""
+    J, x, _ = model.jacobian(pos, jinfo, link, M_(point))
+    if outboard:
+        for k in range(pos[link][2] + 1, model.dof):
+            aw, o, typ = jinfo[k]
+            J[:3, k] = aw if typ == "prismatic" else _cross(aw, x - o)
+    return J[:3], J[3:], x
+
+
+def _contact_eval(model, pos, jinfo, dq, contact, nz):
+    """per point (x, F, delta, f_n) and tc = sum J_k^T F_k with its sum of absolute products"""
+    rows = M_(contact["rows"])
+    p0, nrm, k, d, mu = rows[0:3], rows[3:6], rows[6], rows[7], rows[8]
+    ve = mpf(contact["v_eps"])
+    n = model.dof
+    pts, tc, mag = [], zeros(n), zeros(n)
+    for c in contact["points"]:
+        Jv, _, x = _point_jacobian(model, pos, jinfo, contact["link"], c, "contact_outboard" in HOOKS)
+        if nz is not None:  # the point and its lever arms carry the rounding of world positions
+            far = norm_inf(x)
+            x = nz.add(x, far)
+            for i in range(n):
+                if jinfo[i][2] != "prismatic" and any(Jv[:, i]):
+                    Jv[:, i] = nz.add(Jv[:, i], far)
+            Jv = nz.rel(Jv)
+        v = Jv @ dq
+        if nz is not None:
+            v = nz.add(v, np.abs(Jv) @ np.abs(dq))
+        delta = nrm @ (p0 - x)
+        vn = nrm @ v
+        fn = _pmax(mpf(0), k * _pmax(mpf(0), delta) * (1 - d * vn))
+        vt = v if "friction_along_v" in HOOKS else v - vn * nrm
+        F = fn * nrm - mu * fn * vt / mp.sqrt(vt @ vt + ve * ve)
+        if nz is not None:
+            F = nz.rel(F)
+        Jt = Jv
+        if "contact_pris_as_rev" in HOOKS:
+            Jt = Jv.copy()
+            for i in range(pos[contact["link"]][2] + 1):
+                if jinfo[i][2] == "prismatic":
+                    Jt[:, i] = _cross(jinfo[i][0], x - jinfo[i][1])
+        tc = tc + Jt.T @ F
+        mag = mag + np.abs(Jt).T @ np.abs(F)
+        pts.append((x, F, delta, fn))
+    if nz is not None:
+        tc = nz.add(tc, mag)
+    return pts, tc
+
+
+def _wrench_eval(model, pos, jinfo, wrench, active, nz, R_first=None):
+    """x, F_w, M_w, tx of an active robot (zeros of an inactive one)"""
+    n = model.dof
+    link = wrench["link"]
+    Jv, Jw, x = _point_jacobian(model, pos, jinfo, link, wrench["point"])
+    if not active:
+        return x, zeros(3), zeros(3), zeros(n)
+    rows = M_(wrench["rows"])
+    F, Mo = rows[0:3], rows[3:6]
+    if wrench["frame"] == "link":
+        Rl = pos[link][0] if R_first is None else R_first
+        if nz is not None:
+            Rl = nz.add(Rl, 1)
+        F, Mo = Rl @ F, Rl @ Mo
+    if nz is not None:
+        far = norm_inf(x)
+        x = nz.add(x, far)
+        for i in range(n):
+            if jinfo[i][2] != "prismatic" and any(Jv[:, i]):
+                Jv[:, i] = nz.add(Jv[:, i], far)
+        F, Mo = nz.rel(F), nz.rel(Mo)
+    tx = Jv.T @ F + Jw.T @ Mo
+    if "couple_on_prismatic" in HOOKS:
+        for i in range(pos[link][2] + 1):
+            if jinfo[i][2] == "prismatic":
+                tx[i] += jinfo[i][0] @ Mo
+    if nz is not None:
+        tx = nz.add(tx, np.abs(Jv).T @ np.abs(F) + np.abs(Jw).T @ np.abs(Mo))
+    return x, F, Mo, tx
+
+
+def _joint_terms(q, dq, tau, joint, nz):
+    """ts, sl, su, g of the law"""
+    a, d, f, t, lo, hi = (M_(r) for r in joint["rows"])
+    k, c, e = M_(joint["k"]), M_(joint["c"]), M_(joint["e"])
+    n = len(q)
+    z = mpf(0)
+    ts = np.array([min(max(tau[i], -t[i]), t[i]) for i in range(n)], dtype=object)
+    sl = np.array([_pmax(z, k[i] * _pmax(z, lo[i] - q[i]) * (1 - c[i] * dq[i])) for i in range(n)], dtype=object)
+    sgn = -1 if "upper_stop_minus" in HOOKS else 1
+    su = np.array([_pmax(z, k[i] * _pmax(z, q[i] - hi[i]) * (1 + sgn * c[i] * dq[i])) for i in range(n)], dtype=object)
+    g = np.array([d[i] + f[i] / mp.sqrt(dq[i] * dq[i] + e[i] * e[i]) for i in range(n)], dtype=object)
+    if nz is not None:
+        sl, su, g = nz.rel(sl), nz.rel(su), nz.rel(g)
+    return a, ts, sl, su, g
+
+
+def _lever_noise(dyn, q, parts, nz):
+    """what the rounding of the bodies' world positions does to M and b: the COM of body k by eps of its own size, and
+    with it every lever arm of a revolute column of its Jacobian, as for the contact points. -> dM, db"""
+    pos, jinfo = dyn.poses(q)
+    n = dyn.dof
+    dM, db = zeros(n, n), zeros(n)
+    k = 0
+    for name, body in dyn.links.items():
+        if body is None or pos[name][2] < 0:
+            continue
+        J, x, _ = dyn.jacobian(pos, jinfo, name, M_(body["com"]))
+        far, m = norm_inf(x), mpf(body["m"])
+        dJ = zeros(3, n)
+        for i in range(pos[name][2] + 1):
+            if jinfo[i][2] != "prismatic":
+                dJ[:, i] = nz.e * far * nz.u(3)
+        dM = dM + m * (dJ.T @ J[:3] + J[:3].T @ dJ)
+        for kk, vec in parts:
+            if kk == k:
+                db = db + dJ.T @ vec
+        k += 1
+    return dM, db
+
+
+def plant_step(model, q, dq, tau, dt, substeps, gravity, joint=None, contact=None, wrench=None, payload=None, info=None):
+    """one control period of the simulated plant: tau held, `substeps` steps of h = dt / substeps, each from the state
+    at its start: without joint dynamics dq+ = dq + h M^-1 (tau + tc + tx - b), with them
+    (M + diag(a) + h diag(g)) dq+ = (M + diag(a)) dq + h (ts + sl - su + tc + tx - b); q+ = q + h dq+.
+    The wrench acts when its steps row is > 0 or < 0 on entry; the countdown is the caller's (wrench_countdown).
+    info: a dict; info["noise"], a Noise, perturbs every quantity a float64 implementation rounds. Returns (q, dq)."""
+    q, dq, tau = M_(q), M_(dq), M_(tau)
+    n = model.dof
+    dyn = model if payload is None else payload
+    nz = None if info is None else info.get("noise")
+    h = mpf(dt) / substeps
+    active = wrench is not None and wrench_active(wrench["rows"][6])
+    R_first = None
+    for _ in range(substeps):
+        if nz is not None:
+            q, dq = nz.rel(q), nz.rel(dq)
+        pos, jinfo = model.poses(q)
+        M = dyn.dynamics(q)[2]
+        parts = None if nz is None else []
+        b, beta = bias_terms(dyn, q, dq, None if gravity else False, parts=parts)
+        if nz is not None:
+            dM, db = _lever_noise(dyn, q, parts, nz)
+            M, b = nz.sym(M) + dM, nz.add(b, beta) + db
+        tc = _contact_eval(model, pos, jinfo, dq, contact, nz)[1] if contact is not None else zeros(n)
+        tx = zeros(n)
+        if wrench is not None:
+            if "wrench_frame_period_start" in HOOKS and R_first is None:
+                R_first = pos[wrench["link"]][0]
+            tx = _wrench_eval(model, pos, jinfo, wrench, active, nz, R_first)[3]
+        if joint is None:
+            r = tau + tc + tx - b
+            if nz is not None:
+                r = nz.add(r, np.abs(tau) + np.abs(tc) + np.abs(tx) + np.abs(b))
+            dq = dq + h * solve(M, r)
+        else:
+            a, ts, sl, su, g = _joint_terms(q, dq, tau, joint, nz)
+            Ma = M + np.diag(a)
+            Mr = M if "rhs_no_armature" in HOOKS else Ma
+            r = ts + sl - su + tc + tx - b
+            mag = np.abs(Mr) @ np.abs(dq) + h * (np.abs(ts) + np.abs(sl) + np.abs(su) + np.abs(tc) + np.abs(tx) + np.abs(b))
+            if "diss_explicit" in HOOKS:
+                A, rhs = Ma, Mr @ dq + h * (r - g * dq)
+            else:
+                A, rhs = Ma + h * np.diag(g), Mr @ dq + h * r
+            if nz is not None:
+                A, rhs = nz.sym(A), nz.add(rhs, mag)
+            dq = solve(A, rhs)
+        q = q + h * dq
+    return q, dq
+
+
+def _sensor_frame(model, pos, jinfo, task, nz):
+    """x_c, o_s, R_s of a task's sensor"""
+    _, xc, Rc = model.frame(pos, jinfo, task)
+    if nz is not None:
+        xc, Rc = nz.add(xc, norm_inf(xc)), nz.add(Rc, 1)
+    return xc, xc + Rc @ M_(task["sensor_pos"]), Rc @ M_(np.asarray(task["sensor_rot"]).reshape(3, 3))
+
+
+def plant_report(model, q, dq, tau, joint=None, contact=None, wrench=None, info=None):
+    """what the kernels store after the last substep of a call, from the state (q, dq) it ended in (tau: the torques held
+    in it, wrench["rows"][6]: the steps row on its entry). A dict of float-able mpf arrays:
+      contact   depth, normal_force [K], wrench_world [6] (sum F_k, sum (x_k - x_c) x F_k; x_c: the control point of the
+                contact's sensor task, the link origin without one), touching
+      joint     applied_torque, stop_torque, dissipative_torque [n], saturated, at_stop
+      wrench    ext_wrench [6] (F_w, M_w), ext_torque [n], steps (counted down), pushed
+      sensed    {id(task) -> [6]}: f_s = R_s^T (-F), m_s = R_s^T (-sum moments about o_s); one task shared by contact and
+                wrench reads the sum"""
+    q, dq, tau = M_(q), M_(dq), M_(tau)
+    nz = None if info is None else info.get("noise")
+    pos, jinfo = model.poses(q)
+    out, sensed = {}, {}
+    if contact is not None:
+        pts, _ = _contact_eval(model, pos, jinfo, dq, contact, nz)
+        task = contact.get("sensor")
+        if task is not None:
+            xc, os_, Rs = _sensor_frame(model, pos, jinfo, task, nz)
+        xo = pos[contact["link"]][1]
+        about = xo if task is None or "moment_about_link_origin" in HOOKS else xc
+        Ft = sum((p[1] for p in pts), zeros(3))
+        out.update(depth=np.array([p[2] for p in pts], dtype=object), normal_force=np.array([p[3] for p in pts], dtype=object),
+                   wrench_world=np.concatenate([Ft, sum((_cross(p[0] - about, p[1]) for p in pts), zeros(3))]),
+                   touching=any(p[3] > 0 for p in pts))
+        if task is not None:
+            sensed[id(task)] = [task, Rs, -Ft, -sum((_cross(p[0] - os_, p[1]) for p in pts), zeros(3))]
+    if joint is not None:
+        a, ts, sl, su, g = _joint_terms(q, dq, tau, joint, nz)
+        t = M_(joint["rows"][3])
+        out.update(applied_torque=ts, stop_torque=sl - su, dissipative_torque=-g * dq,
+                   saturated=any(abs(tau[i]) > t[i] for i in range(len(q))), at_stop=any(x != 0 for x in sl - su))
+    if wrench is not None:
+        steps = wrench["rows"][6]
+        active = wrench_active(steps)
+        x, Fw, Mw, tx = _wrench_eval(model, pos, jinfo, wrench, active, nz)
+        out.update(ext_wrench=np.concatenate([Fw, Mw]), ext_torque=tx, steps=wrench_countdown(steps),
+                   pushed=active and any(float(v) != 0 for v in wrench["rows"][0:6]))
+        task = wrench.get("sensor")
+        if task is not None:
+            _, os_, Rs = _sensor_frame(model, pos, jinfo, task, nz)
+            f, m = -Fw, -(Mw + _cross(x - os_, Fw))
+            if id(task) in sensed:
+                sensed[id(task)][2] = sensed[id(task)][2] + f
+                if "shared_sensor_no_wrench_moment" not in HOOKS:
+                    sensed[id(task)][3] = sensed[id(task)][3] + m
+            else:
+                sensed[id(task)] = [task, Rs, f, m]
+    out["sensed"] = {k: np.concatenate([Rs.T @ f, Rs.T @ m]) for k, (_, Rs, f, m) in sensed.items()}
+    return out
