@@ -1417,6 +1417,135 @@ inline Batch MotionForceTask::getSigmaValues() const {
 	detail::check(ctx(), sai2b_get_mft_singularity(ctx(), index(), out.data(), nullptr, nullptr));
 	return out;
 }
+// Collision proximity (sai2b.h "collision proximity"): what one queryCollision() returns, and the device counts of the last one
+struct CollisionResult {
+	Batch rows;						   // [collisionRows()][B], the selected blocks
+	std::vector<unsigned char> flags;  // [B], SAI2B_COL_FLAG_* bits
+};
+struct CollisionCounts {
+	int plane = 0, obstacle = 0, self = 0, nonfinite = 0, any = 0;
+};
+namespace detail {
+// The geometry as the C ABI takes it, built and judged without a device: spheres by moving-link index (-1: the world), centres
+// row-major n x 3 in the link's frame, radii [n]; the default masks. std::invalid_argument on arrays that do not fit each other
+// and on what sai2b_validate_collision rejects (its message).
+inline sai2b_collision_config collisionGeometry(const int dof, const std::vector<int>& links, const std::vector<double>& centres,
+												const std::vector<double>& radii, const int blocks, const double margin_plane,
+												const double margin_obstacle, const double margin_self, const int view) {
+	if (links.empty() || links.size() > SAI2B_MAX_COLLISION_SPHERES) throw std::invalid_argument("setCollisionGeometry: 1 to 16 spheres");
+	if (centres.size() != 3 * links.size() || radii.size() != links.size())
+		throw std::invalid_argument("setCollisionGeometry: centres must be n x 3 and radii [n] for n links");
+	sai2b_collision_config cfg;
+	check(nullptr, sai2b_default_collision(&cfg, (int)links.size(), links.data(), centres.data(), radii.data()));
+	cfg.blocks = blocks, cfg.view = view;
+	cfg.margin_plane = margin_plane, cfg.margin_obstacle = margin_obstacle, cfg.margin_self = margin_self;
+	char msg[256];
+	if (sai2b_validate_collision(&cfg, dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(std::string("setCollisionGeometry: ") + msg);
+	return cfg;
+}
+// the same with spheres by URDF link NAME, centres in that link's frame (a link behind fixed joints resolves to its moving link;
+// an empty name is the world, its centre a world point)
+inline void resolveCollisionSpheres(const BatchedRobotModel& robot, const std::vector<std::string>& link_names, const std::vector<double>& centres,
+									std::vector<int>* links, std::vector<double>* in_model);
+// rows [6 P + 4 O][B] for the planes and obstacles of a configuration; empty: all absent
+inline void checkCollisionEnvironment(const int n_planes, const int n_obstacles, const size_t B, const Batch& rows) {
+	if (n_planes < 0 || n_planes > SAI2B_MAX_COLLISION_PLANES || n_obstacles < 0 || n_obstacles > SAI2B_MAX_COLLISION_OBSTACLES)
+		throw std::invalid_argument("setCollisionEnvironment: 0 to 2 planes and 0 to 4 obstacles");
+	if (!rows.empty() && rows.size() != (size_t)(6 * n_planes + 4 * n_obstacles) * B)
+		throw std::invalid_argument("setCollisionEnvironment: rows must be [6 planes + 4 obstacles][B]");
+}
+inline void checkEndEpisodes(const size_t B, const std::vector<unsigned char>& done, const std::vector<unsigned char>& extra, const int bit) {
+	if (bit != 64 && bit != 128) throw std::invalid_argument("endEpisodes: bit must be 64 or 128");
+	if (done.size() != B || extra.size() != B) throw std::invalid_argument("endEpisodes: done and extra must be [B]");
+}
+// the members BatchedSimulation has: they act on the context the plant runs in
+class CollisionMembers {
+public:
+	// The arm's spheres. Replaces an earlier geometry and keeps the environment set before (setCollisionEnvironment). blocks:
+	// SAI2B_COL_* flags of what queryCollision stores; view: 0 the plant's q, 1 the measured q while a joint sensor is set.
+	void setCollisionGeometry(const std::vector<int>& links, const std::vector<double>& centres, const std::vector<double>& radii,
+							  const int blocks = SAI2B_COL_DISTANCE, const double margin_plane = 0.0, const double margin_obstacle = 0.0,
+							  const double margin_self = 0.0, const int view = 0) {
+		sai2b_collision_config cfg = collisionGeometry(sai2b_num_joints(_col_ctx), links, centres, radii, blocks, margin_plane, margin_obstacle, margin_self, view);
+		cfg.n_planes = _col_cfg.n_planes, cfg.n_obstacles = _col_cfg.n_obstacles;
+		check(_col_ctx, sai2b_set_collision(_col_ctx, &cfg, _col_env.empty() ? nullptr : _col_env.data(), 0));
+		_col_cfg = cfg, _has_col = true;
+	}
+	inline void setCollisionGeometry(const BatchedRobotModel& robot, const std::vector<std::string>& link_names, const std::vector<double>& centres,
+									 const std::vector<double>& radii, const int blocks = SAI2B_COL_DISTANCE, const double margin_plane = 0.0,
+									 const double margin_obstacle = 0.0, const double margin_self = 0.0, const int view = 0);
+	// The per-robot planes and obstacles: rows [6 planes + 4 obstacles][B] = per plane point 3 and unit normal 3, per obstacle
+	// centre 3 and radius; a NaN makes a plane or an obstacle absent for that robot; empty rows: all absent. Needs a geometry.
+	void setCollisionEnvironment(const int n_planes, const int n_obstacles, const Batch& rows = {}) {
+		if (!_has_col) throw std::invalid_argument("setCollisionEnvironment: set the geometry first (setCollisionGeometry)");
+		checkCollisionEnvironment(n_planes, n_obstacles, (size_t)sai2b_batch(_col_ctx), rows);
+		sai2b_collision_config cfg = _col_cfg;
+		cfg.n_planes = n_planes, cfg.n_obstacles = n_obstacles;
+		check(_col_ctx, sai2b_set_collision(_col_ctx, &cfg, rows.empty() ? nullptr : rows.data(), 0));
+		_col_cfg = cfg, _col_env = rows;
+	}
+	void clearCollision() {
+		check(_col_ctx, sai2b_clear_collision(_col_ctx));
+		_has_col = false, _col_env.clear(), _col_cfg = sai2b_collision_config();
+	}
+	int collisionRows() const { return sai2b_collision_rows(_col_ctx); }
+	// one launch: the selected rows and the flags byte of every robot
+	CollisionResult queryCollision(const bool want_rows = true) {
+		const int rows = sai2b_collision_rows(_col_ctx);
+		if (rows < 0) throw std::invalid_argument("queryCollision: no collision geometry is configured (setCollisionGeometry)");
+		const size_t B = (size_t)sai2b_batch(_col_ctx);
+		CollisionResult r;
+		if (want_rows) r.rows.resize((size_t)rows * B);
+		r.flags.resize(B);
+		check(_col_ctx, sai2b_collision_query(_col_ctx, r.rows.empty() ? nullptr : r.rows.data(), r.flags.data(), 0));
+		return r;
+	}
+	CollisionCounts collisionCounts() const {
+		int c[5];
+		check(_col_ctx, sai2b_get_collision_counts(_col_ctx, c));
+		CollisionCounts out;
+		out.plane = c[0], out.obstacle = c[1], out.self = c[2], out.nonfinite = c[3], out.any = c[4];
+		return out;
+	}
+	// The episodes of the robots with extra[b] != 0 that are not done yet are closed as observeReward closes one; their bytes in
+	// `done` gain `bit` (64 or 128). Returns the robots closed.
+	int endEpisodes(std::vector<unsigned char>& done, const std::vector<unsigned char>& extra, const int bit = SAI2B_DONE_COLLISION) {
+		checkEndEpisodes((size_t)sai2b_batch(_col_ctx), done, extra, bit);
+		check(_col_ctx, sai2b_end_episodes(_col_ctx, done.data(), extra.data(), bit, 0));
+		int n = 0;
+		check(_col_ctx, sai2b_get_end_episode_count(_col_ctx, &n));
+		return n;
+	}
+
+protected:
+	sai2b_ctx* _col_ctx = nullptr;
+	sai2b_collision_config _col_cfg = sai2b_collision_config();
+	Batch _col_env;
+	bool _has_col = false;
+};
+inline void resolveCollisionSpheres(const BatchedRobotModel& robot, const std::vector<std::string>& link_names, const std::vector<double>& centres,
+									std::vector<int>* links, std::vector<double>* in_model) {
+	if (centres.size() != 3 * link_names.size()) throw std::invalid_argument("setCollisionGeometry: centres must be n x 3 for n link names");
+	links->assign(link_names.size(), -1);
+	*in_model = centres;
+	const double zero[3] = {0, 0, 0};
+	for (size_t k = 0; k < link_names.size(); k++) {
+		if (link_names[k].empty()) continue;  // the world
+		double fp[3], R[9];
+		(*links)[k] = robot.resolveLink(link_names[k], zero, nullptr, fp, R);
+		for (int i = 0; i < 3; i++)
+			(*in_model)[3 * k + i] = fp[i] + R[3 * i] * centres[3 * k] + R[3 * i + 1] * centres[3 * k + 1] + R[3 * i + 2] * centres[3 * k + 2];
+	}
+}
+inline void CollisionMembers::setCollisionGeometry(const BatchedRobotModel& robot, const std::vector<std::string>& link_names,
+												   const std::vector<double>& centres, const std::vector<double>& radii, const int blocks,
+												   const double margin_plane, const double margin_obstacle, const double margin_self, const int view) {
+	std::vector<int> links;
+	std::vector<double> in_model;
+	resolveCollisionSpheres(robot, link_names, centres, &links, &in_model);
+	setCollisionGeometry(links, in_model, radii, blocks, margin_plane, margin_obstacle, margin_self, view);
+}
+}  // namespace detail
 // A batch sharded over the GPUs of a node (BASELINE C5: "8-GPU runs simply shard the batch, no RCCL"):
 // one context and ONE HOST THREAD per device, contiguous slices of the batch (the remainder spread over the low
 // shards, as sai2-primitives-perso_amd/sharding.py:shard_bounds), every call scattered to the shards by index, run
@@ -1558,6 +1687,55 @@ public:
 					out.q[(size_t)i * _total + sh.lo + b] = q[(size_t)i * Bs + b], out.dq[(size_t)i * _total + sh.lo + b] = dq[(size_t)i * Bs + b];
 		});
 		return out;
+	}
+	// Collision proximity for the whole sharded batch: the geometry is batch-uniform and goes to every shard as it is, every shard
+	// gets its columns of the environment rows [6 planes + 4 obstacles][B_total] (empty: all absent)
+	void setCollision(const sai2b_collision_config& cfg, const Batch& rows = {}) {
+		char msg[256];
+		if (sai2b_validate_collision(&cfg, _dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(std::string("setCollision: ") + msg);
+		detail::checkCollisionEnvironment(cfg.n_planes, cfg.n_obstacles, (size_t)_total, rows);
+		forAll([&](Shard& sh) {
+			const Batch part = slice(rows, 6 * cfg.n_planes + 4 * cfg.n_obstacles, sh);
+			detail::check(sh.ctx, sai2b_set_collision(sh.ctx, &cfg, ptr(part), 0));
+		});
+	}
+	void clearCollision() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_collision(sh.ctx)); }); }
+	// rows [collision rows][B_total] and flags [B_total] of the whole batch
+	CollisionResult queryCollision() {
+		const int rows = sai2b_collision_rows(_shards.front().ctx);
+		if (rows < 0) throw std::invalid_argument("queryCollision: no collision geometry is configured (setCollision)");
+		CollisionResult out;
+		out.rows.resize((size_t)rows * _total), out.flags.resize((size_t)_total);
+		forAll([&](Shard& sh) {
+			const size_t Bs = (size_t)(sh.hi - sh.lo);
+			Batch part((size_t)rows * Bs);
+			detail::check(sh.ctx, sai2b_collision_query(sh.ctx, part.empty() ? nullptr : part.data(), out.flags.data() + sh.lo, 0));
+			for (int i = 0; i < rows; i++)
+				for (size_t b = 0; b < Bs; b++) out.rows[(size_t)i * _total + sh.lo + b] = part[(size_t)i * Bs + b];
+		});
+		return out;
+	}
+	// summed over the shards
+	CollisionCounts collisionCounts() {
+		CollisionCounts out;
+		for (auto& sh : _shards) {
+			int c[5];
+			detail::check(sh.ctx, sai2b_get_collision_counts(sh.ctx, c));
+			out.plane += c[0], out.obstacle += c[1], out.self += c[2], out.nonfinite += c[3], out.any += c[4];
+		}
+		return out;
+	}
+	// done and extra [B_total]: every shard works on its entries; returns the robots closed, summed over the shards
+	int endEpisodes(std::vector<unsigned char>& done, const std::vector<unsigned char>& extra, const int bit = SAI2B_DONE_COLLISION) {
+		detail::checkEndEpisodes((size_t)_total, done, extra, bit);
+		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_end_episodes(sh.ctx, done.data() + sh.lo, extra.data() + sh.lo, bit, 0)); });
+		int total = 0;
+		for (auto& sh : _shards) {
+			int n = 0;
+			detail::check(sh.ctx, sai2b_get_end_episode_count(sh.ctx, &n));
+			total += n;
+		}
+		return total;
 	}
 	void randomizeRobots(const std::vector<unsigned char>& mask, const unsigned groups = 0) {
 		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "randomizeRobots");
@@ -1788,7 +1966,7 @@ private:
 // integrate, getJointPositions, getJointVelocities): rigid-body dynamics of the whole batch with the
 // state resident on the device (sai2b_sim_step). Without setJointTorques, integrate() consumes the
 // torques of the controller's last computeControlTorques() without a host round trip.
-class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers {
+class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers, public detail::CollisionMembers {
 public:
 	explicit BatchedSimulation(RobotController& controller, const double timestep = 0.001, const int substeps = 1)
 		: BatchedSimulation(controller.ctx(), timestep, substeps) {}
@@ -1799,7 +1977,7 @@ public:
 	BatchedSimulation(sai2b_ctx* ctx, const double timestep, const int substeps) : _c(ctx), _dt(timestep), _substeps(substeps) {
 		if (timestep <= 0 || substeps < 1) throw std::invalid_argument("simulation timestep must be positive");
 		_dof = sai2b_num_joints(ctx);
-		_obs_ctx = _act_ctx = _js_ctx = ctx;
+		_obs_ctx = _act_ctx = _js_ctx = _col_ctx = ctx;
 	}
 	void setTimestep(const double dt) {
 		if (dt <= 0) throw std::invalid_argument("simulation timestep must be positive");

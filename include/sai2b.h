@@ -427,7 +427,12 @@ enum sai2b_buffer {
 	 * between steps, ordered with sai2b_stream(); the next sai2b_sim_step reads them. Such rows are not inspected. */
 	SAI2B_BUF_Q_MEASURED = 21,
 	SAI2B_BUF_DQ_MEASURED = 22,
-	SAI2B_BUF_JOINT_SENSOR = 23
+	SAI2B_BUF_JOINT_SENSOR = 23,
+	/* the per-robot environment rows of the collision proximity (sai2b_set_collision), [6 P + 4 O][B] = per plane point 3 and
+	 * unit normal 3, per obstacle centre 3 and radius. NULL until a collision configuration with a plane or an obstacle has been
+	 * set (and after it is cleared). A device-resident producer may rewrite the rows (move an obstacle every period), ordered
+	 * with sai2b_stream(); the next sai2b_collision_query reads them. Such rows are not inspected. */
+	SAI2B_BUF_COLLISION = 24
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -1059,6 +1064,113 @@ int sai2b_get_reward_counts(sai2b_ctx* ctx, int counts[2]);
 /* the accumulators as they are now, host arrays [B] each, any may be NULL: running return, running discount, return and length
  * of the episode that ended last. Waits for the ctx stream. */
 int sai2b_get_episode_stats(sai2b_ctx* ctx, double* ret, double* discount, double* last_return, int* last_length);
+
+/* ------------------------------------------------------------------ collision proximity
+ * A proximity sensor for the whole arm: clearance to the environment and to the arm itself, the direction of that clearance and
+ * its joint-space gradient, per robot, in ONE launch (sai2b_collision_query). A context that never configures it launches
+ * exactly the kernels it launches without this feature; a configured context launches the kernel only in sai2b_collision_query.
+ * GEOMETRY, batch-uniform (sai2b_collision_config): n_spheres in 1..SAI2B_MAX_COLLISION_SPHERES. Sphere k sits on link_k in
+ * [-1, dof) (-1: the world, i.e. the base after sai2b_model_set_base_transform, which folds the base into joint 0; so a centre on
+ * link -1 is a world point) with centre c_k in that link's frame and radius r_k >= 0. World centre x_k = p_link + R_link c_k in
+ * the chain convention of include/sai2b_detfk.h, plain FP64 (not the bit-reproducible pose of that header).
+ * MASKS: env_mask bit k: sphere k is tested against planes and obstacles. pair_mask[i] bit j, i < j: the pair (i, j) is tested.
+ * sai2b_default_collision sets every bit of env_mask whose sphere is on a moving link (link >= 0) and every pair whose links
+ * differ by at least 2 (with -1 counting as a link).
+ * PER ROBOT, doubles, rows [6 P + 4 O][B] with P = n_planes in 0..2 and O = n_obstacles in 0..4: per plane a point p0 (3) and
+ * the outward unit normal n (3), as sai2b_set_contact takes them; then per obstacle its world centre c_o (3) and radius r_o (1).
+ * A NaN anywhere in a plane's or an obstacle's rows makes it lose every comparison: it is absent for that robot. Every
+ * comparison is written so that a NaN operand gives false, as in the observation.
+ * THREE CATEGORIES, each a minimum with its witness:
+ *     plane     d = n . (x_k - p0) - r_k            p outer, k inner       index 16 p + k
+ *     obstacle  d = |x_k - c_o| - r_k - r_o         o outer, k inner       index 16 o + k
+ *     self      d = |x_i - x_j| - r_i - r_j         i outer, j inner       index 16 i + j
+ *   The first strict minimum (d < best, best starting at +inf) wins. An empty category reports +inf, index -1, the zero normal
+ *   and the zero gradient. The index is an exact integer stored as a double. Witness normal u: n of the winning plane;
+ *   (x_k - c_o) / |x_k - c_o|; (x_i - x_j) / |x_i - x_j|; the zero vector when that norm is 0. Gradient of the minimum with
+ *   respect to q, dof entries: g_m = u . dx/dq_m, for self u . (dx_i/dq_m - dx_j/dq_m), with dx/dq_m = z_m x (x - o_m) about a
+ *   revolute joint and z_m along a prismatic one for m <= link(x), and 0 beyond; z_m is the world z of joint m's frame, o_m
+ *   its world origin.
+ * FLAGS, one byte per robot: bit 0 plane d_min < margin_plane, bit 1 obstacle d_min < margin_obstacle, bit 2 self d_min <
+ * margin_self, bit 3 some q_i is not finite; such a robot gets bit 3 alone (its rows are what the law gives on that q: whatever
+ * a NaN reaches loses its comparisons). COUNTS on the device: robots per bit, then robots with a non-zero byte.
+ * OUTPUT rows [rows][B], the selected blocks in the order of their flags; the first four hold the categories in the order
+ * plane, obstacle, self. `view`: 0 reads SAI2B_BUF_Q, the truth (a collision is a fact of the plant); 1 reads
+ * SAI2B_BUF_Q_MEASURED while a joint sensor is set, and the truth otherwise.
+ * Snapshot banks do not hold the rows or the configuration: the rows stay with the robot index, and a fresh context is
+ * configured again, like the observation's. This law is this library's definition. */
+#define SAI2B_MAX_COLLISION_SPHERES 16
+#define SAI2B_MAX_COLLISION_PLANES 2
+#define SAI2B_MAX_COLLISION_OBSTACLES 4
+enum sai2b_collision_block {
+	SAI2B_COL_DISTANCE = 1, /* 3 rows: d_min of plane, obstacle, self */
+	SAI2B_COL_INDEX = 2,	/* 3 rows: the witness index */
+	SAI2B_COL_NORMAL = 4,	/* 9 rows: the witness normal, 3 per category */
+	SAI2B_COL_GRADIENT = 8, /* 3 dof rows: the gradient, dof per category */
+	SAI2B_COL_CENTRES = 16	/* 3 n_spheres rows: the world centres, sphere k at rows 3 k .. 3 k + 2 */
+};
+enum sai2b_collision_category { SAI2B_COL_PLANE = 0, SAI2B_COL_OBSTACLE = 1, SAI2B_COL_SELF = 2 };
+enum sai2b_collision_flag { SAI2B_COL_FLAG_PLANE = 1, SAI2B_COL_FLAG_OBSTACLE = 2, SAI2B_COL_FLAG_SELF = 4, SAI2B_COL_FLAG_NONFINITE = 8 };
+/* the conventional bit of a done byte for "ended by a collision" (sai2b_end_episodes); not one of enum sai2b_done_reason */
+#define SAI2B_DONE_COLLISION 64
+typedef struct sai2b_collision_config {
+	int n_spheres, n_planes, n_obstacles;
+	int blocks; /* SAI2B_COL_DISTANCE | ... : what sai2b_collision_query stores */
+	int view;	/* 0: the plant's q; 1: the measured q while a joint sensor is set */
+	unsigned env_mask;
+	unsigned pair_mask[SAI2B_MAX_COLLISION_SPHERES];
+	int link[SAI2B_MAX_COLLISION_SPHERES];
+	double centre[SAI2B_MAX_COLLISION_SPHERES][3];
+	double radius[SAI2B_MAX_COLLISION_SPHERES];
+	double margin_plane, margin_obstacle, margin_self;
+	int reserved[8];
+} sai2b_collision_config;
+/* host only: n_spheres spheres (link [n], centre [n][3], radius [n]), the default masks, no plane, no obstacle,
+ * blocks = SAI2B_COL_DISTANCE, margins 0, view 0. SAI2B_INVALID_ARGUMENT for n_spheres outside 1..16 or a NULL array. */
+int sai2b_default_collision(sai2b_collision_config* cfg, int n_spheres, const int* link, const double* centre, const double* radius);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: a count out of range, a link outside [-1, dof), a
+ * centre that is not finite, a radius that is negative or not finite, mask bits beyond n_spheres, a pair bit with j <= i,
+ * unknown block bits, a margin that is not finite, view not 0 or 1 */
+int sai2b_validate_collision(const sai2b_collision_config* cfg, int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_collision_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_collision_config(void);
+/* host only, the layout arithmetic: where `block` (exactly one flag of enum sai2b_collision_block) is stored. category = -1: the
+ * whole block; 0..2: that category's rows of one of the first four blocks. *n_rows = 0 and *first_row = -1 when the
+ * configuration does not select the block; *total_rows: rows of the whole output; *env_rows: 6 P + 4 O. Any output may be NULL.
+ * SAI2B_INVALID_ARGUMENT when block is not exactly one known flag, or category is outside [-1, 2] or names a part of the centres. */
+int sai2b_collision_config_layout(const sai2b_collision_config* cfg, int robot_dof, int block, int category, int* first_row, int* n_rows,
+								  int* total_rows, int* env_rows);
+/* rows [6 P + 4 O][B], host or device (stream contract), NULL: every plane and obstacle absent (NaN) until a producer writes
+ * SAI2B_BUF_COLLISION. Host rows are validated (SAI2B_INVALID_ARGUMENT with the reason): a plane without a NaN needs a
+ * normal within 1e-9 of unit length, an obstacle without a NaN a radius >= 0; a NaN is allowed as "absent". DEVICE rows are
+ * copied as they are. A failing call leaves the context as it was. */
+int sai2b_set_collision(sai2b_ctx* ctx, const sai2b_collision_config* cfg, const double* rows, int on_device);
+/* back to a context without the feature: sai2b_collision_query fails from here on, SAI2B_BUF_COLLISION gives NULL */
+int sai2b_clear_collision(sai2b_ctx* ctx);
+/* the configuration and the rows to the host (either may be NULL); SAI2B_INVALID_ARGUMENT without a configuration */
+int sai2b_get_collision(sai2b_ctx* ctx, sai2b_collision_config* cfg, double* rows);
+/* rows of the configured output; -1 without a configuration */
+int sai2b_collision_rows(sai2b_ctx* ctx);
+/* sai2b_collision_config_layout for the context's configuration; SAI2B_INVALID_ARGUMENT without one */
+int sai2b_collision_layout(sai2b_ctx* ctx, int block, int category, int* first_row, int* n_rows);
+/* One launch: out [rows][B] doubles and flags [B] bytes (either may be NULL), host memory, or device memory when on_device != 0
+ * (stream contract, staging of host outputs as sai2b_observe). A deferred sai2b_update_task_models is not touched: the query
+ * reads q alone. SAI2B_INVALID_ARGUMENT and no launch without a configuration. */
+int sai2b_collision_query(sai2b_ctx* ctx, double* out, unsigned char* flags, int on_device);
+/* of the last sai2b_collision_query, counted on the device: robots per flag bit 0-3 and, last, robots with a non-zero byte. Zeros
+ * before the first; SAI2B_INVALID_ARGUMENT without a configuration. Waits for the ctx stream. */
+int sai2b_get_collision_counts(sai2b_ctx* ctx, int counts[5]);
+/* Ending an episode from outside, for a reason the six built-in criteria do not know (a collision, a criterion computed by the
+ * caller). done_inout and extra: [B] bytes each, host, or device when on_device != 0 (stream contract). bit: 64 or 128, the two
+ * bits above the built-in reasons; anything else is SAI2B_INVALID_ARGUMENT, as is a NULL array. One launch. For every robot
+ * with extra[b] != 0: if done_inout[b] == 0 its episode is closed exactly as step 5 of sai2b_observe_reward closes one (with a
+ * reward configured: last_return = ret, last_length = the observation's episode counter as it stands, ret = 0, disc = 1,
+ * tau_prev invalid; with an observation configured: its episode counter becomes 0) and the robot is counted; then
+ * done_inout[b] |= bit. A robot that was already done keeps its bookkeeping and only gains the bit; a robot with
+ * extra[b] == 0 is neither read nor written. Without a reward and without an observation only the bytes and the count are
+ * written. The flags of sai2b_collision_query, or any byte array of the caller's, serve as `extra`. */
+int sai2b_end_episodes(sai2b_ctx* ctx, unsigned char* done_inout, const unsigned char* extra, int bit, int on_device);
+/* robots whose episode the last sai2b_end_episodes closed, counted on the device; 0 before the first. Waits for the ctx stream. */
+int sai2b_get_end_episode_count(sai2b_ctx* ctx, int* count);
 
 /* ------------------------------------------------------------------ episode starts
  * Where a reset robot starts and what it is asked to do, drawn on the device: sai2b_reset_robots_sampled is sai2b_reset_robots

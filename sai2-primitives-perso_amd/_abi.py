@@ -40,6 +40,13 @@ MAX_ACTUATION_DELAY = 8  # SAI2B_MAX_ACTUATION_DELAY
 BUF_Q_MEASURED, BUF_DQ_MEASURED = 21, 22  # [dof][B] each: the controller's view of the state (sai2b_set_joint_sensor)
 BUF_JOINT_SENSOR = 23  # [1 + 5 dof][B] rows: delay; offset, position noise, quantum, velocity noise, velocity filter coefficient
 JOINT_SENSOR_VELOCITY_MODES = {"tachometer": 0, "finite_difference": 1}
+BUF_COLLISION = 24  # [6 P + 4 O][B]: per plane point 3 and unit normal 3, per obstacle centre 3 and radius (sai2b_set_collision)
+MAX_COLLISION_SPHERES, MAX_COLLISION_PLANES, MAX_COLLISION_OBSTACLES = 16, 2, 4  # SAI2B_MAX_COLLISION_*
+COL_DISTANCE, COL_INDEX, COL_NORMAL, COL_GRADIENT, COL_CENTRES = 1, 2, 4, 8, 16  # enum sai2b_collision_block
+COL_BLOCKS = {"distance": COL_DISTANCE, "index": COL_INDEX, "normal": COL_NORMAL, "gradient": COL_GRADIENT, "centres": COL_CENTRES}
+COL_CATEGORIES = ("plane", "obstacle", "self")  # enum sai2b_collision_category
+COL_FLAGS = {"plane": 1, "obstacle": 2, "self": 4, "nonfinite": 8}  # enum sai2b_collision_flag
+DONE_COLLISION = 64  # SAI2B_DONE_COLLISION: the conventional bit of end_episodes
 HARDWARE_SENSOR_ROWS = 13
 WRENCH_WORLD, WRENCH_LINK = 0, 1  # enum sai2b_wrench_frame
 WRENCH_FRAMES = {"world": WRENCH_WORLD, "link": WRENCH_LINK}
@@ -314,6 +321,27 @@ class JointSensorConfig(C.Structure):
     ]
 
 
+class CollisionConfig(C.Structure):
+    """sai2b_collision_config; load_library() checks the size against sai2b_sizeof_collision_config()"""
+
+    _fields_ = [
+        ("n_spheres", _i),
+        ("n_planes", _i),
+        ("n_obstacles", _i),
+        ("blocks", _i),
+        ("view", _i),
+        ("env_mask", C.c_uint),
+        ("pair_mask", C.c_uint * 16),
+        ("link", _i * 16),
+        ("centre", (C.c_double * 3) * 16),
+        ("radius", C.c_double * 16),
+        ("margin_plane", C.c_double),
+        ("margin_obstacle", C.c_double),
+        ("margin_self", C.c_double),
+        ("reserved", _i * 8),
+    ]
+
+
 MAX_RESET_TRIES = 64  # SAI2B_MAX_RESET_TRIES
 RESET_SAMPLER_COUNTS = ("reset", "rejected", "exhausted")
 RESET_SAMPLER_BLOCKS = {"q_lower": 0, "q_upper": 1, "dq_sigma": 2, "q_nominal": 3, "goal": 4}  # sai2b_reset_sampler_config_layout
@@ -576,6 +604,19 @@ EXPORTS = [
     "sai2b_get_joint_sensor",
     "sai2b_get_joint_sensor_state",
     "sai2b_get_measured_state",
+    "sai2b_default_collision",
+    "sai2b_validate_collision",
+    "sai2b_sizeof_collision_config",
+    "sai2b_collision_config_layout",
+    "sai2b_set_collision",
+    "sai2b_clear_collision",
+    "sai2b_get_collision",
+    "sai2b_collision_rows",
+    "sai2b_collision_layout",
+    "sai2b_collision_query",
+    "sai2b_get_collision_counts",
+    "sai2b_end_episodes",
+    "sai2b_get_end_episode_count",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -790,6 +831,22 @@ def load_library():
     lib.sai2b_get_joint_sensor.argtypes = [vp, P(JointSensorConfig), vp]
     lib.sai2b_get_joint_sensor_state.argtypes = [vp, vp, vp]
     lib.sai2b_get_measured_state.argtypes = [vp, vp, vp]
+    lib.sai2b_default_collision.argtypes = [P(CollisionConfig), _i, vp, vp, vp]
+    lib.sai2b_validate_collision.argtypes = [P(CollisionConfig), _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_collision_config.argtypes = []
+    lib.sai2b_collision_config_layout.argtypes = [P(CollisionConfig), _i, _i, _i, P(_i), P(_i), P(_i), P(_i)]
+    lib.sai2b_set_collision.argtypes = [vp, P(CollisionConfig), vp, _i]
+    lib.sai2b_clear_collision.argtypes = [vp]
+    lib.sai2b_get_collision.argtypes = [vp, P(CollisionConfig), vp]
+    lib.sai2b_collision_rows.argtypes = [vp]
+    lib.sai2b_collision_layout.argtypes = [vp, _i, _i, P(_i), P(_i)]
+    lib.sai2b_collision_query.argtypes = [vp, vp, vp, _i]
+    lib.sai2b_get_collision_counts.argtypes = [vp, P(_i)]
+    lib.sai2b_end_episodes.argtypes = [vp, vp, vp, _i, _i]
+    lib.sai2b_get_end_episode_count.argtypes = [vp, P(_i)]
+    if lib.sai2b_sizeof_collision_config() != C.sizeof(CollisionConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_collision_config is {lib.sai2b_sizeof_collision_config()} bytes in the library, "
+                           f"{C.sizeof(CollisionConfig)} in the ctypes mirror")
     if lib.sai2b_sizeof_joint_sensor_config() != C.sizeof(JointSensorConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_joint_sensor_config is {lib.sai2b_sizeof_joint_sensor_config()} bytes in the library, "
                            f"{C.sizeof(JointSensorConfig)} in the ctypes mirror")

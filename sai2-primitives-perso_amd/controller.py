@@ -126,6 +126,54 @@ def task_configs(tasks):
     return out
 
 
+def collision_config(robot_dof, links, centres, radii, n_planes=0, n_obstacles=0, blocks=("distance",), margin_plane=0.0, margin_obstacle=0.0,
+                     margin_self=0.0, view="truth", env_mask=None, pairs="default"):
+    """sai2b_default_collision() + sai2b_validate_collision() for a robot of robot_dof joints (no device needed) -> CollisionConfig.
+    links [n]: moving-link index of every sphere, -1 = the world; centres [n][3] in the link's
+    frame; radii [n]. blocks: names of _abi.COL_BLOCKS ('distance', 'index', 'normal', 'gradient', 'centres'). view: 'truth' or
+    'measured' (or 0 / 1). env_mask: None = the default (every sphere on a moving link), or an int of bits, or the sphere
+    indices. pairs: 'default' (links at least 2 apart), 'all', 'none', or an iterable of (i, j) with i < j."""
+    links = np.ascontiguousarray(links, dtype=np.int32).reshape(-1)
+    n = links.shape[0]
+    centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 3)
+    radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (n,)))
+    if centres.shape[0] != n:
+        raise ValueError("collision: one centre per sphere is required")
+    lib = _abi.load_library()
+    cfg = _abi.CollisionConfig()
+    if lib.sai2b_default_collision(C.byref(cfg), n, C.c_void_p(links.ctypes.data), C.c_void_p(centres.ctypes.data), C.c_void_p(radii.ctypes.data)):
+        raise ValueError(lib.sai2b_last_error(None).decode())
+    cfg.n_planes, cfg.n_obstacles = int(n_planes), int(n_obstacles)
+    cfg.blocks = Controller._flags(blocks, _abi.COL_BLOCKS, "collision block")
+    cfg.margin_plane, cfg.margin_obstacle, cfg.margin_self = float(margin_plane), float(margin_obstacle), float(margin_self)
+    if isinstance(view, str):
+        if view not in ("truth", "measured"):
+            raise ValueError("view must be 'truth' or 'measured'")
+        view = 0 if view == "truth" else 1
+    cfg.view = int(view)
+    if env_mask is not None:
+        cfg.env_mask = int(env_mask) if isinstance(env_mask, (int, np.integer)) else sum({1 << int(k) for k in env_mask})
+    if not (isinstance(pairs, str) and pairs == "default"):
+        for i in range(16):
+            cfg.pair_mask[i] = 0
+        if isinstance(pairs, str):
+            if pairs not in ("all", "none"):
+                raise ValueError("pairs must be 'default', 'all', 'none' or an iterable of (i, j)")
+            if pairs == "all":
+                for i in range(n):
+                    cfg.pair_mask[i] = ((1 << n) - 1) & ~((2 << i) - 1)
+        else:
+            for i, j in pairs:
+                if not 0 <= int(i) < 16 or not 0 <= int(j) < 32:
+                    raise ValueError(f"collision: pair ({i}, {j}) out of range")
+                cfg.pair_mask[int(i)] |= 1 << int(j)
+    msg = C.create_string_buffer(256)
+    if lib.sai2b_validate_collision(C.byref(cfg), int(robot_dof), msg, 256):
+        raise ValueError(msg.value.decode())
+    return cfg
+
+
+
 class Controller:
     """Array-level binding of one sai2b_ctx (one GPU, one batch)."""
 
@@ -655,6 +703,157 @@ class Controller:
             return torch.as_tensor(_Buf(), device=f"cuda:{self._device}")
 
         return view(pq), view(pd)
+
+    # -- collision proximity and episodes ended from outside (sai2b.h "collision proximity")
+    def collision_config(self, *args, **kwargs):
+        """collision_config() of this module for this controller's robot"""
+        return collision_config(self.dof, *args, **kwargs)
+
+    def collision_env_rows(self, cfg, planes=(), obstacles=()):
+        """-> rows [6 P + 4 O][B] (numpy): planes: per plane (point [3] or [3][B], unit normal [3] or [3][B]); obstacles: per obstacle
+        (centre [3] or [3][B], radius scalar or [B]); one not given is absent (NaN)"""
+        P, O, B = cfg.n_planes, cfg.n_obstacles, self.B
+        rows = np.full((6 * P + 4 * O, B), np.nan)
+        if len(planes) > P or len(obstacles) > O:
+            raise ValueError("collision: more planes or obstacles than the configuration has")
+        col = lambda a: np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(3, -1), (3, B))
+        for k, (p0, nrm) in enumerate(planes):
+            rows[6 * k : 6 * k + 3], rows[6 * k + 3 : 6 * k + 6] = col(p0), col(nrm)
+        for k, (c, r) in enumerate(obstacles):
+            rows[6 * P + 4 * k : 6 * P + 4 * k + 3], rows[6 * P + 4 * k + 3] = col(c), np.broadcast_to(np.asarray(r, dtype=np.float64), (B,))
+        return rows
+
+    def set_collision(self, cfg=None, rows=None, **kwargs):
+        """the arm's proximity sensor: a CollisionConfig (or the arguments of collision_config) and the per-robot environment rows
+        [6 P + 4 O][B], numpy (validated) or torch CUDA (copied as they are); None: every plane and obstacle absent until a
+        producer writes device_buffer(_abi.BUF_COLLISION). Nothing else in the controller changes."""
+        if cfg is None:
+            cfg = self.collision_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_collision: a CollisionConfig or keyword arguments, not both")
+        r = 6 * cfg.n_planes + 4 * cfg.n_obstacles
+        if rows is not None and r == 0:
+            raise ValueError("rows: the configuration has no plane and no obstacle")
+        if rows is not None and not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.shape != (r, self.B):
+                raise ValueError(f"rows: expected an array of shape ({r}, {self.B})")
+        ptr, _keep = self._in(rows, r)
+        self._rc(self.lib.sai2b_set_collision(self.h, C.byref(cfg), ptr, self._dev(rows)))
+
+    def clear_collision(self):
+        self._rc(self.lib.sai2b_clear_collision(self.h))
+
+    def get_collision(self):
+        """-> (CollisionConfig, rows [6 P + 4 O][B])"""
+        cfg = _abi.CollisionConfig()
+        self._rc(self.lib.sai2b_get_collision(self.h, C.byref(cfg), None))
+        rows = np.empty((6 * cfg.n_planes + 4 * cfg.n_obstacles, self.B))
+        if rows.shape[0]:
+            self._rc(self.lib.sai2b_get_collision(self.h, None, C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def collision_env(self):
+        """the per-robot environment rows as a torch view of the device buffer (no copy), [6 P + 4 O][B] float64: a torch op may
+        move an obstacle every period; the next collision_query reads what it wrote. Order writes with stream()."""
+        import torch
+
+        ptr = self.device_buffer(_abi.BUF_COLLISION)
+        if not ptr:
+            raise ValueError("collision_env: no collision geometry with a plane or an obstacle is set (sai2b_set_collision)")
+        cfg = _abi.CollisionConfig()
+        self._rc(self.lib.sai2b_get_collision(self.h, C.byref(cfg), None))
+        shape = (6 * cfg.n_planes + 4 * cfg.n_obstacles, self.B)
+
+        class _Buf:
+            __cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(ptr), False), version=2)
+
+        return torch.as_tensor(_Buf(), device=f"cuda:{self._device}")
+
+    def collision_rows(self):
+        """rows of the configured output; -1 without a configuration"""
+        return self.lib.sai2b_collision_rows(self.h)
+
+    def collision_layout(self):
+        """dict name -> slice of rows of collision_query()'s output: 'distance', 'index', 'normal', 'gradient', 'centres' and, for
+        the first four, 'distance_plane', 'distance_obstacle', 'distance_self', ...; only what the configuration stores"""
+        first, n = C.c_int(), C.c_int()
+        out = {}
+        for name, flag in _abi.COL_BLOCKS.items():
+            self._rc(self.lib.sai2b_collision_layout(self.h, flag, -1, C.byref(first), C.byref(n)))
+            if not n.value:
+                continue
+            out[name] = slice(first.value, first.value + n.value)
+            if flag != _abi.COL_CENTRES:
+                for c, cat in enumerate(_abi.COL_CATEGORIES):
+                    self._rc(self.lib.sai2b_collision_layout(self.h, flag, c, C.byref(first), C.byref(n)))
+                    out[f"{name}_{cat}"] = slice(first.value, first.value + n.value)
+        return out
+
+    def collision_query(self, out=None, flags=None):
+        """one launch -> (rows [collision_rows()][B] float64, flags [B] uint8 with the _abi.COL_FLAGS bits). out / flags: numpy
+        arrays or torch CUDA tensors to fill (both of one kind; a torch pair never leaves the device and nothing synchronises),
+        None: a new numpy array, False: not wanted (None is returned in its place)"""
+        rows = self.collision_rows()
+        if rows < 0:
+            raise ValueError("sai2b_collision_query: no collision geometry is configured (sai2b_set_collision)")
+        given = [o for o in (out, flags) if o is not None and o is not False]
+        dev = self._dev(*given)
+        if dev and (out is None or flags is None):
+            raise ValueError("collision_query: with a device tensor pass the other argument as a tensor too, or False")
+        if out is None:
+            out = np.empty((rows, self.B))
+        if flags is None:
+            flags = np.zeros(self.B, dtype=np.uint8)
+        po = pf = None
+        if out is not False:
+            if hasattr(out, "data_ptr"):
+                po, _ = self._in(out, rows)
+            else:
+                if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (rows, self.B)):
+                    raise ValueError(f"out must be a C-contiguous float64 array of shape ({rows}, {self.B})")
+                po = C.c_void_p(out.ctypes.data)
+        if flags is not False:
+            if hasattr(flags, "data_ptr"):
+                if str(flags.dtype) != "torch.uint8":
+                    raise ValueError("flags must be a uint8 tensor (it receives the flag bits)")
+                pf, _ = self._mask(flags)
+            else:
+                if not (isinstance(flags, np.ndarray) and flags.dtype == np.uint8 and flags.flags.c_contiguous and flags.shape == (self.B,)):
+                    raise ValueError(f"flags must be a C-contiguous uint8 array of shape ({self.B},)")
+                pf = C.c_void_p(flags.ctypes.data)
+        self._rc(self.lib.sai2b_collision_query(self.h, po, pf, dev))
+        return (None if out is False else out), (None if flags is False else flags)
+
+    def collision_counts(self):
+        """of the last collision_query(): dict 'plane', 'obstacle', 'self', 'nonfinite' -> robots with that bit, 'any' -> robots
+        with a non-zero byte"""
+        c = (C.c_int * 5)()
+        self._rc(self.lib.sai2b_get_collision_counts(self.h, c))
+        return dict(zip(list(_abi.COL_FLAGS) + ["any"], list(c)))
+
+    def end_episodes(self, done, extra, bit=_abi.DONE_COLLISION):
+        """one launch: the episodes of the robots with extra != 0 that are not done yet are closed as observe_reward closes one,
+        then their done bytes gain `bit` (64 or 128). done: [B] uint8, updated in place; extra: [B] uint8 or bool; both numpy or
+        both torch CUDA (then nothing synchronises). -> done"""
+        if int(bit) not in (64, 128):
+            raise ValueError("sai2b_end_episodes: bit must be 64 or 128")
+        dev = self._dev(done, extra)
+        if dev:
+            if str(done.dtype) != "torch.uint8":
+                raise ValueError("done must be a uint8 tensor (it receives the bit)")
+        elif not (isinstance(done, np.ndarray) and done.dtype == np.uint8 and done.flags.c_contiguous and done.shape == (self.B,)):
+            raise ValueError(f"done must be a C-contiguous uint8 array of shape ({self.B},)")
+        pd, _kd = self._mask(done)
+        pe, _ke = self._mask(extra)
+        self._rc(self.lib.sai2b_end_episodes(self.h, pd, pe, int(bit), dev))
+        return done
+
+    def end_episode_count(self):
+        """robots whose episode the last end_episodes() closed"""
+        c = C.c_int()
+        self._rc(self.lib.sai2b_get_end_episode_count(self.h, C.byref(c)))
+        return c.value
 
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod

@@ -136,6 +136,18 @@ struct sai2b_ctx {
 	double *js_rows = nullptr, *js_qm = nullptr, *js_dqm = nullptr, *js_prev = nullptr, *js_filter = nullptr, *js_history = nullptr;
 	int* js_clock = nullptr;
 	DevParams* d_params_meas = nullptr;
+	// collision proximity (sai2b_set_collision), created on first use: the environment rows (room for the largest,
+	// [6 * 2 + 4 * 4][B]), the five device counters of the last query and, behind them, the counter of the last sai2b_end_episodes
+	// (col_counts is allocated by either), col_out / col_flags: staging of a query with host arguments (col_out_rows: rows col_out
+	// has room for), end_done / end_extra: staging of sai2b_end_episodes with host arguments. col_on: the configuration is in
+	// force; nothing else in the context reads it
+	bool col_on = false;
+	sai2b_collision_config col_cfg = {};
+	sai2b::ColParams col;
+	int col_rows = 0, col_env_rows = 0, col_out_rows = 0;
+	double *col_env = nullptr, *col_out = nullptr;
+	unsigned char *col_flags = nullptr, *end_done = nullptr, *end_extra = nullptr;
+	int* col_counts = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -1669,6 +1681,7 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_Q_MEASURED: return ctx->js_on ? (void*)ctx->js_qm : nullptr;
 		case SAI2B_BUF_DQ_MEASURED: return ctx->js_on ? (void*)ctx->js_dqm : nullptr;
 		case SAI2B_BUF_JOINT_SENSOR: return ctx->js_on ? (void*)ctx->js_rows : nullptr;
+		case SAI2B_BUF_COLLISION: return ctx->col_on && ctx->col_env_rows > 0 ? (void*)ctx->col_env : nullptr;
 		case SAI2B_BUF_REWARD_STATE: return ctx->rew_on ? (void*)ctx->rew_state : nullptr;
 		case SAI2B_BUF_REWARD_EPISODE: return ctx->rew_on ? (void*)ctx->rew_episode : nullptr;
 		case SAI2B_BUF_ENV_SAMPLE: return ctx->es_on ? (void*)ctx->es_sample : nullptr;
@@ -3186,6 +3199,272 @@ extern "C" int sai2b_get_episode_stats(sai2b_ctx* ctx, double* ret, double* disc
 	for (int k = 0; k < 3; k++)
 		if (dst[k]) HIP_TRY(ctx, hipMemcpyAsync(dst[k], ctx->rew_state + k * B, B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	if (last_length) HIP_TRY(ctx, hipMemcpyAsync(last_length, ctx->rew_episode, B * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// collision proximity (include/sai2b.h "collision proximity"; law: sai2b_collision_law.h; kernels: sai2b_collision.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int sai2b_default_collision(sai2b_collision_config* cfg, int n_spheres, const int* link, const double* centre, const double* radius) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_collision: null config");
+	if (n_spheres < 1 || n_spheres > SAI2B_MAX_COLLISION_SPHERES)
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_collision: n_spheres must be in [1, SAI2B_MAX_COLLISION_SPHERES]");
+	if (!link || !centre || !radius) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_collision: link, centre and radius are required");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->n_spheres = n_spheres;
+	cfg->blocks = SAI2B_COL_DISTANCE;
+	for (int k = 0; k < n_spheres; k++) {
+		cfg->link[k] = link[k];
+		for (int a = 0; a < 3; a++) cfg->centre[k][a] = centre[3 * k + a];
+		cfg->radius[k] = radius[k];
+		if (link[k] >= 0) cfg->env_mask |= 1u << k;
+	}
+	for (int i = 0; i < n_spheres; i++)
+		for (int j = i + 1; j < n_spheres; j++)
+			if (std::abs(link[i] - link[j]) >= 2) cfg->pair_mask[i] |= 1u << j;
+	return SAI2B_OK;
+}
+static std::string collision_config_error(const sai2b_collision_config* c) {
+	if (!c) return "collision: null config";
+	if (c->n_spheres < 1 || c->n_spheres > SAI2B_MAX_COLLISION_SPHERES) return "collision: n_spheres must be in [1, SAI2B_MAX_COLLISION_SPHERES]";
+	if (c->n_planes < 0 || c->n_planes > SAI2B_MAX_COLLISION_PLANES) return "collision: n_planes must be in [0, SAI2B_MAX_COLLISION_PLANES]";
+	if (c->n_obstacles < 0 || c->n_obstacles > SAI2B_MAX_COLLISION_OBSTACLES) return "collision: n_obstacles must be in [0, SAI2B_MAX_COLLISION_OBSTACLES]";
+	const unsigned beyond = c->n_spheres == 32 ? 0u : ~((1u << c->n_spheres) - 1u);
+	for (int k = 0; k < c->n_spheres; k++) {
+		if (c->link[k] < -1 || c->link[k] >= N) return "collision: a sphere's link must be in [-1, dof)";
+		for (int a = 0; a < 3; a++)
+			if (!std::isfinite(c->centre[k][a])) return "collision: a sphere's centre must be finite";
+		if (!std::isfinite(c->radius[k]) || c->radius[k] < 0) return "collision: a sphere's radius must be finite and not negative";
+	}
+	if (c->env_mask & beyond) return "collision: env_mask has bits beyond n_spheres";
+	for (int i = 0; i < SAI2B_MAX_COLLISION_SPHERES; i++) {
+		if (i >= c->n_spheres && c->pair_mask[i]) return "collision: pair_mask has entries beyond n_spheres";
+		if (c->pair_mask[i] & beyond) return "collision: pair_mask has bits beyond n_spheres";
+		if (c->pair_mask[i] & ((2u << i) - 1u)) return "collision: a pair (i, j) needs i < j";
+	}
+	if (c->blocks & ~sai2b::COL_ALL_BLOCKS) return "collision: unknown bits in blocks";
+	if (!std::isfinite(c->margin_plane) || !std::isfinite(c->margin_obstacle) || !std::isfinite(c->margin_self)) return "collision: the margins must be finite";
+	if (c->view != 0 && c->view != 1) return "collision: view must be 0 (the plant's q) or 1 (the measured q)";
+	return "";
+}
+// host rows: a plane or an obstacle with a NaN is absent; the others are held to what the law assumes
+static std::string collision_rows_error(const sai2b_collision_config* c, const double* rows, size_t B) {
+	if (!rows) return "";
+	for (int p = 0; p < c->n_planes; p++) {
+		const double* r = rows + (size_t)sai2b::COL_PLANE_ROWS * p * B;
+		for (size_t b = 0; b < B; b++) {
+			bool absent = false, inf = false;
+			for (int a = 0; a < 6; a++) absent = absent || std::isnan(r[a * B + b]), inf = inf || std::isinf(r[a * B + b]);
+			if (absent) continue;
+			if (inf) return "collision: a plane's rows must be finite (or hold a NaN: absent)";
+			const double n2 = r[3 * B + b] * r[3 * B + b] + r[4 * B + b] * r[4 * B + b] + r[5 * B + b] * r[5 * B + b];
+			if (!(std::fabs(std::sqrt(n2) - 1.0) <= 1e-9)) return "collision: a plane's normal must have unit length (within 1e-9)";
+		}
+	}
+	for (int o = 0; o < c->n_obstacles; o++) {
+		const double* r = rows + ((size_t)sai2b::COL_PLANE_ROWS * c->n_planes + (size_t)sai2b::COL_OBSTACLE_ROWS * o) * B;
+		for (size_t b = 0; b < B; b++) {
+			bool absent = false, inf = false;
+			for (int a = 0; a < 4; a++) absent = absent || std::isnan(r[a * B + b]), inf = inf || std::isinf(r[a * B + b]);
+			if (absent) continue;
+			if (inf) return "collision: an obstacle's rows must be finite (or hold a NaN: absent)";
+			if (r[3 * B + b] < 0) return "collision: an obstacle's radius must not be negative";
+		}
+	}
+	return "";
+}
+extern "C" int sai2b_validate_collision(const sai2b_collision_config* cfg, int robot_dof, char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? collision_config_error(cfg) : "collision: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (err.empty()) return SAI2B_OK;
+	return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_validate_collision: " + err);
+}
+extern "C" int sai2b_sizeof_collision_config(void) { return (int)sizeof(sai2b_collision_config); }
+extern "C" int sai2b_collision_config_layout(const sai2b_collision_config* cfg, int robot_dof, int block, int category, int* first_row,
+											 int* n_rows, int* total_rows, int* env_rows) {
+	if (robot_dof != N) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_config_layout: this build serves another robot size");
+	const std::string err = collision_config_error(cfg);
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_config_layout: " + err);
+	int k = -1;
+	for (int i = 0; i < sai2b::COL_BLOCKS; i++)
+		if (block == (1 << i)) k = i;
+	if (k < 0) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_config_layout: block must be exactly one SAI2B_COL_* flag");
+	if (category < -1 || category >= sai2b::COL_CATEGORIES || (category >= 0 && block == SAI2B_COL_CENTRES))
+		return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_config_layout: category must be -1, or 0..2 for a per-category block");
+	int row[sai2b::COL_BLOCKS];
+	const int rows = sai2b::col_layout(cfg->blocks, N, cfg->n_spheres, row);
+	int first = row[k], n = first < 0 ? 0 : sai2b::col_block_rows(block, N, cfg->n_spheres);
+	if (first >= 0 && category >= 0) n /= sai2b::COL_CATEGORIES, first += n * category;
+	if (first_row) *first_row = first;
+	if (n_rows) *n_rows = n;
+	if (total_rows) *total_rows = rows;
+	if (env_rows) *env_rows = sai2b::col_env_rows(cfg->n_planes, cfg->n_obstacles);
+	return SAI2B_OK;
+}
+static int collision_counts_alloc(sai2b_ctx* ctx) {
+	if (ctx->col_counts) return SAI2B_OK;
+	if (int rc = dev_alloc(ctx, &ctx->col_counts, (size_t)sai2b::COL_COUNTS + 1)) return rc;
+	HIP_TRY(ctx, hipMemsetAsync(ctx->col_counts, 0, (sai2b::COL_COUNTS + 1) * sizeof(int), ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_set_collision(sai2b_ctx* ctx, const sai2b_collision_config* cfg, const double* rows, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_collision: null ctx");
+	std::string err = collision_config_error(cfg);
+	const size_t B = ctx->B;
+	if (err.empty() && !on_device) err = collision_rows_error(cfg, rows, B);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	if (!ctx->col_env && (rc = dev_alloc(ctx, &ctx->col_env, (size_t)sai2b::COL_ENV_ROWS_MAX * B))) return rc;
+	if ((rc = collision_counts_alloc(ctx))) return rc;
+	const int env_rows = sai2b::col_env_rows(cfg->n_planes, cfg->n_obstacles);
+	// the rows go into the buffer only now that nothing can be refused any more; a copy that fails leaves no configuration
+	ctx->col_on = false;
+	if (env_rows > 0) {
+		if (rows) {
+			if ((rc = copy_rows(ctx, ctx->col_env, rows, env_rows, on_device))) return rc;
+		} else {
+			const std::vector<double> absent((size_t)env_rows * B, std::nan(""));
+			if ((rc = copy_rows(ctx, ctx->col_env, absent.data(), env_rows, 0))) return rc;
+		}
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->col_counts, 0, sai2b::COL_COUNTS * sizeof(int), ctx->stream));
+	sai2b::ColParams p;
+	sai2b::ColLaw<N>& L = p.law;
+	const sai2b::DevModel& m = ctx->h_params.model;
+	for (int i = 0; i < N; i++) {
+		for (int a = 0; a < 9; a++) L.E[i][a] = m.E[i][a];
+		for (int a = 0; a < 3; a++) L.xyz[i][a] = m.xyz[i][a];
+		L.jtype[i] = m.jtype[i];
+	}
+	L.n_spheres = cfg->n_spheres, L.n_planes = cfg->n_planes, L.n_obstacles = cfg->n_obstacles, L.blocks = cfg->blocks;
+	L.env_mask = cfg->env_mask;
+	for (int k = 0; k < SAI2B_MAX_COLLISION_SPHERES; k++) {
+		const bool on = k < cfg->n_spheres;
+		L.pair_mask[k] = on ? cfg->pair_mask[k] : 0u;
+		L.link[k] = on ? cfg->link[k] : -1;
+		for (int a = 0; a < 3; a++) L.centre[k][a] = on ? cfg->centre[k][a] : 0.0;
+		L.radius[k] = on ? cfg->radius[k] : 0.0;
+	}
+	L.margin[0] = cfg->margin_plane, L.margin[1] = cfg->margin_obstacle, L.margin[2] = cfg->margin_self;
+	ctx->col_rows = sai2b::col_layout(cfg->blocks, N, cfg->n_spheres, L.row);
+	ctx->col_env_rows = env_rows;
+	ctx->col = p;
+	ctx->col_cfg = *cfg;
+	std::memset(ctx->col_cfg.reserved, 0, sizeof(ctx->col_cfg.reserved));
+	ctx->col_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_collision(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_collision: null ctx");
+	ctx->col_on = false;
+	ctx->col_rows = ctx->col_env_rows = 0;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_collision(sai2b_ctx* ctx, sai2b_collision_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_collision: null ctx");
+	if (!ctx->col_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_collision: no collision geometry is configured (sai2b_set_collision)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) *cfg = ctx->col_cfg;
+	if (ctx->col_env_rows == 0) return SAI2B_OK;
+	return fetch_rows(ctx, ctx->col_env, 0, ctx->col_env_rows, rows);
+}
+extern "C" int sai2b_collision_rows(sai2b_ctx* ctx) { return ctx && ctx->col_on ? ctx->col_rows : -1; }
+extern "C" int sai2b_collision_layout(sai2b_ctx* ctx, int block, int category, int* first_row, int* n_rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_layout: null ctx");
+	if (!ctx->col_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_collision_layout: no collision geometry is configured (sai2b_set_collision)");
+	const int rc = sai2b_collision_config_layout(&ctx->col_cfg, N, block, category, first_row, n_rows, nullptr, nullptr);
+	return rc ? set_error(ctx, rc, g_error) : SAI2B_OK;
+}
+extern "C" int sai2b_collision_query(sai2b_ctx* ctx, double* out, unsigned char* flags, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_collision_query: null ctx");
+	if (!ctx->col_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_collision_query: no collision geometry is configured (sai2b_set_collision)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	const size_t B = ctx->B;
+	const bool want_out = out && ctx->col_rows > 0;
+	double* d_out = want_out ? out : nullptr;
+	unsigned char* d_flags = flags;
+	if (on_device) {
+		// device results are written on the ctx stream: what the caller's stream still does with those buffers comes first
+		if ((want_out || flags) && (rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (want_out) {
+			if (ctx->col_out_rows < ctx->col_rows) {  // a configuration with more rows: the smaller staging buffer goes
+				if (ctx->col_out) {
+					HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+					ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void*)ctx->col_out), ctx->allocs.end());
+					HIP_TRY(ctx, hipFree(ctx->col_out));
+					ctx->col_out = nullptr, ctx->col_out_rows = 0;
+				}
+				if ((rc = dev_alloc(ctx, &ctx->col_out, (size_t)ctx->col_rows * B))) return rc;
+				ctx->col_out_rows = ctx->col_rows;
+			}
+			d_out = ctx->col_out;
+		}
+		if (flags) {
+			if (!ctx->col_flags && (rc = dev_alloc(ctx, &ctx->col_flags, B))) return rc;
+			d_flags = ctx->col_flags;
+		}
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->col_counts, 0, sai2b::COL_COUNTS * sizeof(int), ctx->stream));
+	sai2b::ColParams p = ctx->col;
+	p.q = ctx->col_cfg.view == 1 ? ctrl_q(ctx) : ctx->q;
+	p.rows = ctx->col_env_rows > 0 ? ctx->col_env : nullptr;
+	p.out = d_out, p.flags = d_flags, p.counts = ctx->col_counts;
+	if (sai2b::launch_collision(ctx->B, p, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_collision_query: launch failed");
+	ctx->launches++;
+	if (on_device) return (want_out || flags) ? caller_after_read(ctx) : SAI2B_OK;
+	if (want_out) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)ctx->col_rows * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	if (flags) HIP_TRY(ctx, hipMemcpyAsync(flags, d_flags, B, hipMemcpyDeviceToHost, ctx->stream));
+	if (want_out || flags) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_collision_counts(sai2b_ctx* ctx, int counts[5]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_collision_counts: bad arguments");
+	if (!ctx->col_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_collision_counts: no collision geometry is configured (sai2b_set_collision)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->col_counts, sai2b::COL_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_end_episodes(sai2b_ctx* ctx, unsigned char* done_inout, const unsigned char* extra, int bit, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_end_episodes: null ctx");
+	if (bit != 64 && bit != 128) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_end_episodes: bit must be 64 or 128");
+	if (!done_inout || !extra) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_end_episodes: done_inout and extra are required");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	const size_t B = ctx->B;
+	if ((rc = collision_counts_alloc(ctx))) return rc;
+	sai2b::EndParams p;
+	p.done = done_inout, p.extra = extra, p.bit = bit;
+	if (on_device) {
+		if ((rc = caller_before_read(ctx))) return rc;
+	} else {
+		if (!ctx->end_done && (rc = dev_alloc(ctx, &ctx->end_done, B))) return rc;
+		if (!ctx->end_extra && (rc = dev_alloc(ctx, &ctx->end_extra, B))) return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->end_done, done_inout, B, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->end_extra, extra, B, hipMemcpyHostToDevice, ctx->stream));
+		p.done = ctx->end_done, p.extra = ctx->end_extra;
+	}
+	if (ctx->rew_on) p.state = ctx->rew_state, p.episode = ctx->rew_episode;
+	if (ctx->obs_on) p.steps = ctx->obs_steps;
+	p.count = ctx->col_counts + sai2b::COL_COUNTS;
+	HIP_TRY(ctx, hipMemsetAsync(p.count, 0, sizeof(int), ctx->stream));
+	if (sai2b::launch_end_episodes(ctx->B, p, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_end_episodes: launch failed");
+	ctx->launches++;
+	if (on_device) return caller_after_read(ctx);
+	HIP_TRY(ctx, hipMemcpyAsync(done_inout, ctx->end_done, B, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_end_episode_count(sai2b_ctx* ctx, int* count) {
+	if (!ctx || !count) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_end_episode_count: bad arguments");
+	*count = 0;
+	if (!ctx->col_counts) return SAI2B_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(count, ctx->col_counts + sai2b::COL_COUNTS, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }

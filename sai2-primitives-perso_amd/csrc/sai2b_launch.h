@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sai2b_collision_law.h"  // ColLaw
 #include "sai2b_env_draw.h"  // EnvDraw
 #include "sai2b_params.h"
 #include "sai2b_tick_policy.h"  // TickForm, TickCall
@@ -291,5 +292,30 @@ struct EnvParams {
 };
 // mask [B] device bytes
 int launch_env_randomize(int B, const EnvParams& p, const unsigned char* mask, hipStream_t stream);
+
+// sai2b_collision_query (sai2b_collision.hip: collision_kernel): its own parameter block, passed by value as a kernel argument;
+// DevParams is not read (the chain's constants are part of the law's block, sai2b_collision_law.h).
+struct ColParams {
+	ColLaw<N> law;
+	const double* q = nullptr;	   // [N][B]: the truth, or the measured q (view)
+	const double* rows = nullptr;  // [6 P + 4 O][B] or NULL without planes and obstacles
+	double* out = nullptr;		   // [rows][B] or NULL
+	unsigned char* flags = nullptr;	 // [B] or NULL
+	int* counts = nullptr;		   // [COL_COUNTS], zeroed by the caller on the stream ahead of the launch
+};
+int launch_collision(int B, const ColParams& p, hipStream_t stream);
+// sai2b_end_episodes (sai2b_collision.hip: end_episodes_kernel): the robots of `extra` that are not done yet are closed as step 5
+// of observe_reward_kernel closes them, then done |= bit. state / episode: the reward's accumulators or NULL; steps: the
+// observation's episode counters or NULL; count: one int, zeroed by the caller on the stream ahead of the launch
+struct EndParams {
+	unsigned char* done = nullptr;		   // [B]
+	const unsigned char* extra = nullptr;  // [B]
+	double* state = nullptr;			   // [REW_STATE_ROWS][B]
+	int* episode = nullptr;				   // [REW_EPISODE_ROWS][B]
+	int* steps = nullptr;				   // [B]
+	int* count = nullptr;
+	int bit = 0;
+};
+int launch_end_episodes(int B, const EndParams& p, hipStream_t stream);
 
 }  // namespace sai2b

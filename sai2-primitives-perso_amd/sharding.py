@@ -84,6 +84,19 @@ def set_joint_sensor(ctrl, world, rank, global_batch, rows=None, **kwargs):
     ctrl.set_joint_sensor(shard_rows(rows, world, rank), first_robot=lo, **kwargs)
 
 
+def set_collision(ctrl, world, rank, global_batch, cfg, rows=None):
+    """Controller.set_collision on this rank's shard of the per-robot environment rows [6 P + 4 O][global_batch] given for the
+    whole batch; the configuration is batch-uniform and goes to every shard as it is"""
+    ctrl.set_collision(cfg, shard_rows(rows, world, rank))
+
+
+def end_episodes(ctrl, world, rank, done, extra, bit=64):
+    """Controller.end_episodes on this rank's shard of done and extra given for the whole batch (numpy): the shard's slice of
+    done is updated in place"""
+    lo, hi = shard_bounds(done.shape[0], world, rank)
+    ctrl.end_episodes(done[lo:hi], shard_rows(extra, world, rank), bit)
+
+
 def reinitialize_robots(ctrl, world, rank, mask, task=-1):
     """Controller.reinitialize_robots on this rank's shard of a mask given for the whole batch"""
     ctrl.reinitialize_robots(shard_rows(mask, world, rank), task)
