@@ -1422,6 +1422,32 @@ struct CollisionResult {
 	Batch rows;						   // [collisionRows()][B], the selected blocks
 	std::vector<unsigned char> flags;  // [B], SAI2B_COL_FLAG_* bits
 };
+// Whole-arm contact (sai2b.h "whole-arm contact"): what the last integrate() left
+struct BodyContactState {
+	Batch status;  // [9 + dof][B]: per category the deepest penetration 3, its witness index 3 (-1: none), the sum of f_n 3, then tb
+	int plane = 0, obstacle = 0, self = 0, any = 0;	 // robots with some f_n > 0
+};
+namespace detail {
+// What setBodyContact checks before the device is touched: the shapes (all the C ABI cannot see) and what
+// sai2b_validate_body_contact rejects (its message). rows [3][B]: stiffness, damping, friction.
+inline sai2b_body_contact_config bodyContactConfig(const int dof, const size_t B, const Batch& rows, const int categories, const double v_eps) {
+	if (rows.size() != 3 * B) throw std::invalid_argument("setBodyContact: rows must be [3][B] (stiffness, damping, friction)");
+	sai2b_body_contact_config cfg;
+	check(nullptr, sai2b_default_body_contact(&cfg));
+	cfg.categories = categories, cfg.v_eps = v_eps;
+	char msg[256];
+	if (sai2b_validate_body_contact(&cfg, dof, msg, sizeof(msg)) != SAI2B_OK) throw std::invalid_argument(std::string("setBodyContact: ") + msg);
+	return cfg;
+}
+inline Batch bodyContactRows(const size_t B, const Batch& stiffness, const Batch& damping, const Batch& friction) {
+	if (stiffness.size() != B || (!damping.empty() && damping.size() != B) || (!friction.empty() && friction.size() != B))
+		throw std::invalid_argument("setBodyContact: stiffness, damping and friction must be [B] (damping and friction may be empty: 0)");
+	Batch rows(3 * B, 0.0);
+	for (size_t b = 0; b < B; b++) rows[b] = stiffness[b], rows[B + b] = damping.empty() ? 0.0 : damping[b], rows[2 * B + b] = friction.empty() ? 0.0 : friction[b];
+	return rows;
+}
+constexpr int BODY_CONTACT_ALL = (1 << SAI2B_COL_PLANE) | (1 << SAI2B_COL_OBSTACLE) | (1 << SAI2B_COL_SELF);
+}  // namespace detail
 struct CollisionCounts {
 	int plane = 0, obstacle = 0, self = 0, nonfinite = 0, any = 0;
 };
@@ -1487,6 +1513,39 @@ public:
 	void clearCollision() {
 		check(_col_ctx, sai2b_clear_collision(_col_ctx));
 		_has_col = false, _col_env.clear(), _col_cfg = sai2b_collision_config();
+	}
+	// The collision geometry as a physical body of the plant: from the next integrate() on, its spheres are pushed out of the
+	// robot's planes, obstacles and each other (categories: bits 1 << SAI2B_COL_PLANE ...). stiffness (N/m), damping (s/m) and
+	// friction per robot, [B] each (damping, friction: empty = 0). Needs a geometry; the environment rows are read at every
+	// step. std::invalid_argument on other shapes and on what the C ABI rejects (its message).
+	void setBodyContact(const Batch& stiffness, const Batch& damping = {}, const Batch& friction = {}, const int categories = BODY_CONTACT_ALL,
+						const double v_eps = 1e-3) {
+		const size_t B = (size_t)sai2b_batch(_col_ctx);
+		const Batch rows = bodyContactRows(B, stiffness, damping, friction);
+		const sai2b_body_contact_config cfg = bodyContactConfig(sai2b_num_joints(_col_ctx), B, rows, categories, v_eps);
+		check(_col_ctx, sai2b_set_body_contact(_col_ctx, &cfg, rows.data(), 0));
+	}
+	void clearBodyContact() { check(_col_ctx, sai2b_clear_body_contact(_col_ctx)); }
+	// the rows in force, [3][B]; zeros without one. categories (may be NULL): the categories in force, 0 without one
+	Batch getBodyContact(int* categories = nullptr) const {
+		sai2b_body_contact_config cfg;
+		Batch rows(3 * (size_t)sai2b_batch(_col_ctx));
+		check(_col_ctx, sai2b_get_body_contact(_col_ctx, &cfg, rows.data()));
+		if (categories) *categories = cfg.categories;
+		return rows;
+	}
+	BodyContactState getBodyContactState() const {
+		BodyContactState s;
+		s.status.resize((size_t)(9 + sai2b_num_joints(_col_ctx)) * (size_t)sai2b_batch(_col_ctx));
+		int c[4];
+		check(_col_ctx, sai2b_get_body_contact_state(_col_ctx, s.status.data(), c));
+		s.plane = c[0], s.obstacle = c[1], s.self = c[2], s.any = c[3];
+		return s;
+	}
+	int robotsTouching() const {
+		int c[4];
+		check(_col_ctx, sai2b_get_body_contact_state(_col_ctx, nullptr, c));
+		return c[3];
 	}
 	int collisionRows() const { return sai2b_collision_rows(_col_ctx); }
 	// one launch: the selected rows and the flags byte of every robot
@@ -1722,6 +1781,34 @@ public:
 			int c[5];
 			detail::check(sh.ctx, sai2b_get_collision_counts(sh.ctx, c));
 			out.plane += c[0], out.obstacle += c[1], out.self += c[2], out.nonfinite += c[3], out.any += c[4];
+		}
+		return out;
+	}
+	// Whole-arm contact for the whole sharded batch: rows [3][B_total] (stiffness, damping, friction), every shard gets its columns
+	void setBodyContact(const Batch& rows, const int categories = detail::BODY_CONTACT_ALL, const double v_eps = 1e-3) {
+		const sai2b_body_contact_config cfg = detail::bodyContactConfig(_dof, (size_t)_total, rows, categories, v_eps);
+		forAll([&](Shard& sh) {
+			const Batch part = slice(rows, 3, sh);
+			detail::check(sh.ctx, sai2b_set_body_contact(sh.ctx, &cfg, ptr(part), 0));
+		});
+	}
+	void clearBodyContact() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_body_contact(sh.ctx)); }); }
+	// the status [9 + dof][B_total] of the whole batch, the counts summed over the shards
+	BodyContactState getBodyContactState() {
+		const int rows = 9 + _dof;
+		BodyContactState out;
+		out.status.resize((size_t)rows * _total);
+		forAll([&](Shard& sh) {
+			const size_t Bs = (size_t)(sh.hi - sh.lo);
+			Batch part((size_t)rows * Bs);
+			detail::check(sh.ctx, sai2b_get_body_contact_state(sh.ctx, part.data(), nullptr));
+			for (int i = 0; i < rows; i++)
+				for (size_t b = 0; b < Bs; b++) out.status[(size_t)i * _total + sh.lo + b] = part[(size_t)i * Bs + b];
+		});
+		for (auto& sh : _shards) {
+			int c[4];
+			detail::check(sh.ctx, sai2b_get_body_contact_state(sh.ctx, nullptr, c));
+			out.plane += c[0], out.obstacle += c[1], out.self += c[2], out.any += c[3];
 		}
 		return out;
 	}

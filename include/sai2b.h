@@ -432,7 +432,13 @@ enum sai2b_buffer {
 	 * unit normal 3, per obstacle centre 3 and radius. NULL until a collision configuration with a plane or an obstacle has been
 	 * set (and after it is cleared). A device-resident producer may rewrite the rows (move an obstacle every period), ordered
 	 * with sai2b_stream(); the next sai2b_collision_query reads them. Such rows are not inspected. */
-	SAI2B_BUF_COLLISION = 24
+	SAI2B_BUF_COLLISION = 24,
+	/* the rows of the whole-arm contact (sai2b_set_body_contact), [3][B] = stiffness, damping, friction, and what the last
+	 * sai2b_sim_step left, [9 + dof][B] = per category the deepest penetration 3, its witness index 3, the sum of the normal
+	 * forces 3, then the joint torques tb. NULL until a whole-arm contact has been set (and after it is cleared). A
+	 * device-resident producer may rewrite the rows between steps, ordered with sai2b_stream(); such rows are not inspected. */
+	SAI2B_BUF_BODY_CONTACT = 25,
+	SAI2B_BUF_BODY_CONTACT_STATUS = 26
 };
 /* (A producer that writes q through SAI2B_BUF_Q bypasses the bookkeeping of the tasks' cached pose: an OTG
  * enabled / a space re-parametrised after such a write and before the next tick starts from the state as
@@ -1171,6 +1177,64 @@ int sai2b_get_collision_counts(sai2b_ctx* ctx, int counts[5]);
 int sai2b_end_episodes(sai2b_ctx* ctx, unsigned char* done_inout, const unsigned char* extra, int bit, int on_device);
 /* robots whose episode the last sai2b_end_episodes closed, counted on the device; 0 before the first. Waits for the ctx stream. */
 int sai2b_get_end_episode_count(sai2b_ctx* ctx, int* count);
+
+/* ------------------------------------------------------------------ whole-arm contact
+ * The collision configuration's geometry as a physical body of the simulated plant: inside every substep of sai2b_sim_step the
+ * link spheres are pushed out of the robot's planes, its obstacle spheres and each other, so that an arm can brush an obstacle,
+ * lean an elbow on a table or be stopped by a wall. A context that never sets it launches exactly the kernels it launches
+ * without this feature; one that has it set launches sim_body_kernel instead of the other simulation kernels.
+ * GEOMETRY: the collision configuration's own (sai2b_set_collision, which must be in force: SAI2B_INVALID_ARGUMENT without
+ * one): spheres (link, centre, radius), env_mask, pair_mask, and the per-robot environment rows [6 P + 4 O][B] of
+ * SAI2B_BUF_COLLISION, READ LIVE at every step: a producer that moves an obstacle on the device between two steps moves the
+ * force. A later sai2b_set_collision changes the body with it; sai2b_clear_collision clears the whole-arm contact too.
+ * Batch-uniform (sai2b_body_contact_config): `categories`, bit c = 1 << (enum sai2b_collision_category) c: which of plane,
+ * obstacle and self push; v_eps > 0, the friction regularisation (m/s). PER ROBOT, doubles, rows [3][B]: stiffness k (N/m),
+ * damping d (s/m), friction mu; finite and >= 0 when given from the host (device rows are copied as they are). A robot whose
+ * three rows are not all >= 0 (a NaN compares false) feels nothing, as does one with k = 0. SAI2B_BUF_BODY_CONTACT.
+ * THE LAW. x: a sphere's centre; v(c): the velocity of the link's material point at c, 0 on link -1. EVERY tested candidate
+ * that penetrates contributes, not the deepest alone:
+ *     plane p, sphere k      u = n                          delta = r_k - n . (x_k - p0)        c = x_k - r_k u      v_rel = v(c)
+ *     obstacle o, sphere k   u = (x_k - c_o) / |x_k - c_o|  delta = r_k + r_o - |x_k - c_o|     c = x_k - r_k u      v_rel = v(c)
+ *     self pair (i, j)       u = (x_i - x_j) / |x_i - x_j|  delta = r_i + r_j - |x_i - x_j|     c_i = x_i - r_i u, c_j = x_j + r_j u
+ *                            v_rel = v(c_i) - v(c_j); F acts on link(i) at c_i and -F on link(j) at c_j
+ *   A zero norm gives no force. The force is the contact's (sai2b_set_contact), term for term:
+ *     vn = u . v_rel,  f_n = max(0, k max(0, delta) (1 - d vn)),  v_t = v_rel - vn u,
+ *     F = f_n u - mu f_n v_t / sqrt(|v_t|^2 + v_eps^2)
+ *   Every comparison is written so that a NaN operand gives false: an absent (NaN) plane or obstacle gives no force.
+ *   Joint torques tb_m = sum z_m . ((c - o_m) x F) about a revolute joint m <= link, z_m . F along a prismatic one, 0 beyond.
+ *   tb enters the step exactly where the plane contact's tc does: explicit in the plain step, on the right-hand side of the
+ *   linear-implicit step when joint dynamics are set, never clipped by the torque limit.
+ * STATUS, at the final state after the last substep, [9 + dof][B] (SAI2B_BUF_BODY_CONTACT_STATUS): rows 0-2 per category the
+ * deepest max(0, delta), 0 without a penetration (geometry alone: also for a robot with k = 0); rows 3-5 its witness index in the
+ * collision's encoding (16 p + k, 16 o + k, 16 i + j; of equally deep ones the smallest), -1 without one, an exact integer stored
+ * as a double; rows 6-8 the sum of f_n; rows 9.. tb. COUNTS on the device, int[4]: robots with some f_n > 0 per category, and
+ * in any.
+ * Snapshot banks hold neither rows nor status (they stay with the robot index, like the collision's); no sensor reads the body
+ * forces. This law is this library's definition. */
+typedef struct sai2b_body_contact_config {
+	int categories; /* bits 1 << SAI2B_COL_PLANE, 1 << SAI2B_COL_OBSTACLE, 1 << SAI2B_COL_SELF */
+	int reserved0;
+	double v_eps;
+	int reserved[8];
+} sai2b_body_contact_config;
+/* host only: every category, v_eps = 1e-3 */
+int sai2b_default_body_contact(sai2b_body_contact_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: no category or unknown bits, v_eps not finite or not > 0 */
+int sai2b_validate_body_contact(const sai2b_body_contact_config* cfg, int robot_dof, char* msg, int msg_len);
+/* sizeof(sai2b_body_contact_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_body_contact_config(void);
+/* rows [3][B] (k, d, mu), host (validated: finite and >= 0) or device when on_device != 0 (stream contract, copied as they are).
+ * SAI2B_INVALID_ARGUMENT without a collision configuration, with NULL rows, or for what the validator rejects. A call that fails
+ * on its arguments leaves the context as it was; one that fails while copying the rows leaves the plant without whole-arm
+ * contact (never with rows that are half the old ones and half the new). */
+int sai2b_set_body_contact(sai2b_ctx* ctx, const sai2b_body_contact_config* cfg, const double* rows, int on_device);
+/* back to the plant without it (the rows are kept for a later set; both buffers give NULL, the status reads as zeros) */
+int sai2b_clear_body_contact(sai2b_ctx* ctx);
+/* the configuration and the rows to the host (either may be NULL); without one: categories 0 and zero rows */
+int sai2b_get_body_contact(sai2b_ctx* ctx, sai2b_body_contact_config* cfg, double* rows);
+/* what the last sai2b_sim_step left: status [9 + dof][B] and counts int[4] (either may be NULL); zeros before the first step
+ * with the feature and after a clear. Waits for the ctx stream. */
+int sai2b_get_body_contact_state(sai2b_ctx* ctx, double* status, int counts[4]);
 
 /* ------------------------------------------------------------------ episode starts
  * Where a reset robot starts and what it is asked to do, drawn on the device: sai2b_reset_robots_sampled is sai2b_reset_robots

@@ -28,6 +28,7 @@ from .controller import (  # noqa: F401,E402
     MotionForceTask,
     RobotController,
     SnapshotBank,
+    body_contact_config,
     collision_config,
     joint_task_config,
     model_from_urdf,

@@ -42,6 +42,8 @@ BUF_JOINT_SENSOR = 23  # [1 + 5 dof][B] rows: delay; offset, position noise, qua
 JOINT_SENSOR_VELOCITY_MODES = {"tachometer": 0, "finite_difference": 1}
 BUF_COLLISION = 24  # [6 P + 4 O][B]: per plane point 3 and unit normal 3, per obstacle centre 3 and radius (sai2b_set_collision)
 MAX_COLLISION_SPHERES, MAX_COLLISION_PLANES, MAX_COLLISION_OBSTACLES = 16, 2, 4  # SAI2B_MAX_COLLISION_*
+BUF_BODY_CONTACT = 25  # [3][B]: stiffness, damping, friction (sai2b_set_body_contact)
+BUF_BODY_CONTACT_STATUS = 26  # [9 + dof][B]: deepest penetration 3, witness index 3, sum of f_n 3, tb dof
 COL_DISTANCE, COL_INDEX, COL_NORMAL, COL_GRADIENT, COL_CENTRES = 1, 2, 4, 8, 16  # enum sai2b_collision_block
 COL_BLOCKS = {"distance": COL_DISTANCE, "index": COL_INDEX, "normal": COL_NORMAL, "gradient": COL_GRADIENT, "centres": COL_CENTRES}
 COL_CATEGORIES = ("plane", "obstacle", "self")  # enum sai2b_collision_category
@@ -342,6 +344,13 @@ class CollisionConfig(C.Structure):
     ]
 
 
+class BodyContactConfig(C.Structure):
+    """sai2b_body_contact_config; load_library() checks the size against sai2b_sizeof_body_contact_config()"""
+
+    _fields_ = [("categories", _i), ("reserved0", _i), ("v_eps", C.c_double), ("reserved", _i * 8)]
+
+
+BODY_CONTACT_COUNTS = COL_CATEGORIES + ("any",)
 MAX_RESET_TRIES = 64  # SAI2B_MAX_RESET_TRIES
 RESET_SAMPLER_COUNTS = ("reset", "rejected", "exhausted")
 RESET_SAMPLER_BLOCKS = {"q_lower": 0, "q_upper": 1, "dq_sigma": 2, "q_nominal": 3, "goal": 4}  # sai2b_reset_sampler_config_layout
@@ -617,6 +626,13 @@ EXPORTS = [
     "sai2b_get_collision_counts",
     "sai2b_end_episodes",
     "sai2b_get_end_episode_count",
+    "sai2b_default_body_contact",
+    "sai2b_validate_body_contact",
+    "sai2b_sizeof_body_contact_config",
+    "sai2b_set_body_contact",
+    "sai2b_clear_body_contact",
+    "sai2b_get_body_contact",
+    "sai2b_get_body_contact_state",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -844,6 +860,16 @@ def load_library():
     lib.sai2b_get_collision_counts.argtypes = [vp, P(_i)]
     lib.sai2b_end_episodes.argtypes = [vp, vp, vp, _i, _i]
     lib.sai2b_get_end_episode_count.argtypes = [vp, P(_i)]
+    lib.sai2b_default_body_contact.argtypes = [P(BodyContactConfig)]
+    lib.sai2b_validate_body_contact.argtypes = [P(BodyContactConfig), _i, C.c_char_p, _i]
+    lib.sai2b_sizeof_body_contact_config.argtypes = []
+    lib.sai2b_set_body_contact.argtypes = [vp, P(BodyContactConfig), vp, _i]
+    lib.sai2b_clear_body_contact.argtypes = [vp]
+    lib.sai2b_get_body_contact.argtypes = [vp, P(BodyContactConfig), vp]
+    lib.sai2b_get_body_contact_state.argtypes = [vp, vp, P(_i)]
+    if lib.sai2b_sizeof_body_contact_config() != C.sizeof(BodyContactConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_body_contact_config is {lib.sai2b_sizeof_body_contact_config()} bytes in the library, "
+                           f"{C.sizeof(BodyContactConfig)} in the ctypes mirror")
     if lib.sai2b_sizeof_collision_config() != C.sizeof(CollisionConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_collision_config is {lib.sai2b_sizeof_collision_config()} bytes in the library, "
                            f"{C.sizeof(CollisionConfig)} in the ctypes mirror")

@@ -126,6 +126,30 @@ def task_configs(tasks):
     return out
 
 
+def body_contact_config(robot_dof, categories=("plane", "obstacle", "self"), v_eps=1e-3):
+    """sai2b_default_body_contact() + sai2b_validate_body_contact() for a robot of robot_dof joints (no device needed) ->
+    BodyContactConfig. categories: names of _abi.COL_CATEGORIES (or an int of bits 1 << category); v_eps: the friction
+    regularisation (m/s)."""
+    lib = _abi.load_library()
+    cfg = _abi.BodyContactConfig()
+    if lib.sai2b_default_body_contact(C.byref(cfg)):
+        raise ValueError(lib.sai2b_last_error(None).decode())
+    if isinstance(categories, (int, np.integer)):
+        cfg.categories = int(categories)
+    else:
+        bits = 0
+        for name in ([categories] if isinstance(categories, str) else categories):
+            if name not in _abi.COL_CATEGORIES:
+                raise ValueError(f"unknown body contact category {name!r} (one of {_abi.COL_CATEGORIES})")
+            bits |= 1 << _abi.COL_CATEGORIES.index(name)
+        cfg.categories = bits
+    cfg.v_eps = float(v_eps)
+    msg = C.create_string_buffer(256)
+    if lib.sai2b_validate_body_contact(C.byref(cfg), int(robot_dof), msg, 256):
+        raise ValueError(msg.value.decode())
+    return cfg
+
+
 def collision_config(robot_dof, links, centres, radii, n_planes=0, n_obstacles=0, blocks=("distance",), margin_plane=0.0, margin_obstacle=0.0,
                      margin_self=0.0, view="truth", env_mask=None, pairs="default"):
     """sai2b_default_collision() + sai2b_validate_collision() for a robot of robot_dof joints (no device needed) -> CollisionConfig.
@@ -854,6 +878,58 @@ class Controller:
         c = C.c_int()
         self._rc(self.lib.sai2b_get_end_episode_count(self.h, C.byref(c)))
         return c.value
+
+    # -- whole-arm contact of the simulated plant (sai2b.h "whole-arm contact")
+    def body_contact_config(self, *args, **kwargs):
+        """body_contact_config() of this module for this controller's robot"""
+        return body_contact_config(self.dof, *args, **kwargs)
+
+    def set_body_contact(self, stiffness, damping=0.0, friction=0.0, cfg=None, **kwargs):
+        """the collision configuration's spheres as a physical body for sim_step: stiffness k (N/m), damping d (s/m) and friction
+        mu per robot, scalars or [B] numpy arrays (validated: finite and >= 0), or `stiffness` alone as the whole [3][B] rows,
+        numpy or a torch CUDA tensor (copied as it is). cfg: a BodyContactConfig, or the keyword arguments of
+        body_contact_config. Needs set_collision first; the environment rows are read live at every step."""
+        if cfg is None:
+            cfg = self.body_contact_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_body_contact: a BodyContactConfig or keyword arguments, not both")
+        if hasattr(stiffness, "data_ptr"):
+            rows = stiffness
+        else:
+            k = np.asarray(stiffness, dtype=np.float64)
+            if k.shape == (3, self.B):
+                rows = np.ascontiguousarray(k)
+            else:
+                try:
+                    rows = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(a, dtype=np.float64), (self.B,)) for a in (k, damping, friction)]))
+                except ValueError:
+                    raise ValueError(f"stiffness, damping, friction: expected scalars or {self.B} values each") from None
+        ptr, _keep = self._in(rows, 3)
+        self._rc(self.lib.sai2b_set_body_contact(self.h, C.byref(cfg), ptr, self._dev(rows)))
+
+    def clear_body_contact(self):
+        self._rc(self.lib.sai2b_clear_body_contact(self.h))
+
+    def get_body_contact(self):
+        """-> (BodyContactConfig, rows [3][B]: stiffness, damping, friction); categories 0 and zeros without one"""
+        cfg, rows = _abi.BodyContactConfig(), np.empty((3, self.B))
+        self._rc(self.lib.sai2b_get_body_contact(self.h, C.byref(cfg), C.c_void_p(rows.ctypes.data)))
+        return cfg, rows
+
+    def get_body_contact_state(self):
+        """what the last sim_step left: dict depth [3][B] (deepest penetration of plane, obstacle, self), index [3][B] (its
+        witness, -1: none), normal_force [3][B] (sum of f_n), torque [dof][B] (tb), status (all rows, [9 + dof][B]), counts
+        (dict 'plane', 'obstacle', 'self', 'any' -> robots with some f_n > 0)"""
+        st, c = np.empty((9 + self.dof, self.B)), (C.c_int * 4)()
+        self._rc(self.lib.sai2b_get_body_contact_state(self.h, C.c_void_p(st.ctypes.data), c))
+        return dict(depth=st[0:3], index=st[3:6].astype(np.int64), normal_force=st[6:9], torque=st[9:], status=st,
+                    counts=dict(zip(_abi.BODY_CONTACT_COUNTS, list(c))))
+
+    def robots_touching(self):
+        """robots with some f_n > 0 after the last sim_step"""
+        c = (C.c_int * 4)()
+        self._rc(self.lib.sai2b_get_body_contact_state(self.h, None, c))
+        return c[3]
 
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod

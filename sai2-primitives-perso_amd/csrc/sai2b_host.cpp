@@ -148,6 +148,13 @@ struct sai2b_ctx {
 	double *col_env = nullptr, *col_out = nullptr;
 	unsigned char *col_flags = nullptr, *end_done = nullptr, *end_extra = nullptr;
 	int* col_counts = nullptr;
+	// whole-arm contact of the plant (sai2b_set_body_contact), created on first use: the [3][B] rows, the [9 + dof][B] status rows
+	// and the four device counters. body_on: sai2b_sim_step launches sim_body_kernel; its geometry is taken from `col` at every
+	// step, so it follows the collision configuration (which must be in force: sai2b_clear_collision clears this too)
+	bool body_on = false;
+	sai2b_body_contact_config body_cfg = {};
+	double *body_rows = nullptr, *body_status = nullptr;
+	int* body_counts = nullptr;
 	double* sim_tau = nullptr;	// staging for host torques / bias read-back of the simulation harness
 	// observations and episode-end flags (sai2b_set_observation): the configuration in force and what observe_kernel takes
 	// from it, the per-robot episode counters and the device counters of the last observe, created on first use; obs_out /
@@ -1682,6 +1689,8 @@ extern "C" void* sai2b_device_buffer(sai2b_ctx* ctx, int which, int task) {
 		case SAI2B_BUF_DQ_MEASURED: return ctx->js_on ? (void*)ctx->js_dqm : nullptr;
 		case SAI2B_BUF_JOINT_SENSOR: return ctx->js_on ? (void*)ctx->js_rows : nullptr;
 		case SAI2B_BUF_COLLISION: return ctx->col_on && ctx->col_env_rows > 0 ? (void*)ctx->col_env : nullptr;
+		case SAI2B_BUF_BODY_CONTACT: return ctx->body_on ? (void*)ctx->body_rows : nullptr;
+		case SAI2B_BUF_BODY_CONTACT_STATUS: return ctx->body_on ? (void*)ctx->body_status : nullptr;
 		case SAI2B_BUF_REWARD_STATE: return ctx->rew_on ? (void*)ctx->rew_state : nullptr;
 		case SAI2B_BUF_REWARD_EPISODE: return ctx->rew_on ? (void*)ctx->rew_episode : nullptr;
 		case SAI2B_BUF_ENV_SAMPLE: return ctx->es_on ? (void*)ctx->es_sample : nullptr;
@@ -3358,6 +3367,8 @@ extern "C" int sai2b_set_collision(sai2b_ctx* ctx, const sai2b_collision_config*
 }
 extern "C" int sai2b_clear_collision(sai2b_ctx* ctx) {
 	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_collision: null ctx");
+	if (ctx->body_on)  // the body is the collision's geometry: it goes with it
+		if (int rc = sai2b_clear_body_contact(ctx)) return rc;
 	ctx->col_on = false;
 	ctx->col_rows = ctx->col_env_rows = 0;
 	return SAI2B_OK;
@@ -3429,6 +3440,133 @@ extern "C" int sai2b_get_collision_counts(sai2b_ctx* ctx, int counts[5]) {
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }
+
+// ---- whole-arm contact of the simulated plant (include/sai2b.h "whole-arm contact"; law: sai2b_body_contact_law.h; kernel:
+// sai2b_sim.hip: sim_body_kernel) ----
+static_assert(sai2b::COL_MAX_SPHERES == SAI2B_MAX_COLLISION_SPHERES, "sai2b_collision_law.h and sai2b.h disagree about the spheres");
+extern "C" int sai2b_default_body_contact(sai2b_body_contact_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_body_contact: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->categories = (1 << SAI2B_COL_PLANE) | (1 << SAI2B_COL_OBSTACLE) | (1 << SAI2B_COL_SELF);
+	cfg->v_eps = 1e-3;
+	return SAI2B_OK;
+}
+static std::string body_contact_config_error(const sai2b_body_contact_config* c) {
+	if (!c) return "body contact: null config";
+	const int all = (1 << SAI2B_COL_PLANE) | (1 << SAI2B_COL_OBSTACLE) | (1 << SAI2B_COL_SELF);
+	if (c->categories & ~all) return "body contact: unknown bits in categories";
+	if (!(c->categories & all)) return "body contact: categories selects nothing";
+	if (!std::isfinite(c->v_eps) || !(c->v_eps > 0)) return "body contact: v_eps must be finite and > 0";
+	return "";
+}
+extern "C" int sai2b_validate_body_contact(const sai2b_body_contact_config* cfg, int robot_dof, char* msg, int msg_len) {
+	const std::string err = robot_dof == N ? body_contact_config_error(cfg) : "body contact: this build serves another robot size";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (err.empty()) return SAI2B_OK;
+	return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_validate_body_contact: " + err);
+}
+extern "C" int sai2b_sizeof_body_contact_config(void) { return (int)sizeof(sai2b_body_contact_config); }
+extern "C" int sai2b_set_body_contact(sai2b_ctx* ctx, const sai2b_body_contact_config* cfg, const double* rows, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_body_contact: null ctx");
+	std::string err = body_contact_config_error(cfg);
+	const size_t B = ctx->B;
+	if (err.empty() && !ctx->col_on) err = "body contact: needs a collision configuration (sai2b_set_collision)";
+	if (err.empty() && !rows) err = "body contact: rows are required";
+	if (err.empty() && !on_device)
+		for (size_t i = 0; i < (size_t)sai2b::BC_ROWS * B; i++)
+			if (!std::isfinite(rows[i]) || rows[i] < 0) {
+				err = "body contact: stiffness, damping and friction must be finite and >= 0";
+				break;
+			}
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	int rc;
+	if ((rc = flush_update(ctx))) return rc;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t status_rows = (size_t)sai2b::bc_status_rows(N);
+	// three buffers, each created once: a failed allocation leaves the others for the next call, and the context as it was
+	if (!ctx->body_rows && (rc = dev_alloc(ctx, &ctx->body_rows, (size_t)sai2b::BC_ROWS * B))) return rc;
+	if (!ctx->body_status) {
+		if ((rc = dev_alloc(ctx, &ctx->body_status, status_rows * B))) return rc;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->body_status, 0, status_rows * B * sizeof(double), ctx->stream));
+	}
+	if (!ctx->body_counts) {
+		if ((rc = dev_alloc(ctx, &ctx->body_counts, (size_t)sai2b::BC_COUNTS))) return rc;
+		HIP_TRY(ctx, hipMemsetAsync(ctx->body_counts, 0, sai2b::BC_COUNTS * sizeof(int), ctx->stream));
+	}
+	// rows already in force are rewritten in place: taken out of force first, so that a copy that fails leaves the plant without
+	// the feature, never with rows that are half the old ones and half the new
+	ctx->body_on = false;
+	if ((rc = copy_rows(ctx, ctx->body_rows, rows, sai2b::BC_ROWS, on_device))) return rc;
+	ctx->body_cfg = *cfg;
+	ctx->body_cfg.reserved0 = 0;
+	std::memset(ctx->body_cfg.reserved, 0, sizeof(ctx->body_cfg.reserved));
+	ctx->body_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_body_contact(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_body_contact: null ctx");
+	if (int rc = flush_update(ctx)) return rc;
+	// the status of the last step with the feature does not outlive it: sai2b_get_body_contact_state gives zeros from here on
+	if (ctx->body_status && ctx->body_counts) {
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->body_status, 0, (size_t)sai2b::bc_status_rows(N) * ctx->B * sizeof(double), ctx->stream));
+		HIP_TRY(ctx, hipMemsetAsync(ctx->body_counts, 0, sai2b::BC_COUNTS * sizeof(int), ctx->stream));
+	}
+	ctx->body_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_body_contact(sai2b_ctx* ctx, sai2b_body_contact_config* cfg, double* rows) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_body_contact: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (cfg) {
+		if (ctx->body_on)
+			*cfg = ctx->body_cfg;
+		else
+			std::memset(cfg, 0, sizeof(*cfg));
+	}
+	if (!ctx->body_on) {
+		if (rows) std::fill(rows, rows + (size_t)sai2b::BC_ROWS * ctx->B, 0.0);
+		return SAI2B_OK;
+	}
+	return fetch_rows(ctx, ctx->body_rows, 0, sai2b::BC_ROWS, rows);
+}
+extern "C" int sai2b_get_body_contact_state(sai2b_ctx* ctx, double* status, int counts[4]) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_get_body_contact_state: null ctx");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t status_rows = (size_t)sai2b::bc_status_rows(N);
+	if (!ctx->body_status || !ctx->body_counts) {  // never had it
+		if (status) std::fill(status, status + status_rows * ctx->B, 0.0);
+		if (counts) std::fill(counts, counts + sai2b::BC_COUNTS, 0);
+		return SAI2B_OK;
+	}
+	if (int rc = fetch_rows(ctx, ctx->body_status, 0, status_rows, status)) return rc;
+	if (counts) {
+		HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->body_counts, sai2b::BC_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	return SAI2B_OK;
+}
+// what sim_body_kernel takes: the collision configuration's geometry as it is now, the live environment rows
+static sai2b::BodyParams body_params(const sai2b_ctx* ctx) {
+	sai2b::BodyParams p;
+	sai2b::BcGeom& G = p.geom;
+	const sai2b::ColLaw<N>& L = ctx->col.law;
+	G.n_spheres = L.n_spheres, G.n_planes = L.n_planes, G.n_obstacles = L.n_obstacles;
+	G.categories = ctx->body_cfg.categories;
+	G.env_mask = L.env_mask;
+	for (int a = 0; a < sai2b::COL_MAX_SPHERES; a++) {
+		G.partner[a] = L.pair_mask[a];
+		for (int b = 0; b < a; b++) G.partner[a] |= ((L.pair_mask[b] >> a) & 1u) << b;
+		G.link[a] = L.link[a];
+		for (int k = 0; k < 3; k++) G.centre[a][k] = L.centre[a][k];
+		G.radius[a] = L.radius[a];
+	}
+	G.v_eps = ctx->body_cfg.v_eps;
+	p.env = ctx->col_env_rows > 0 ? ctx->col_env : nullptr;
+	p.rows = ctx->body_rows, p.status = ctx->body_status, p.counts = ctx->body_counts;
+	return p;
+}
+
 extern "C" int sai2b_end_episodes(sai2b_ctx* ctx, unsigned char* done_inout, const unsigned char* extra, int bit, int on_device) {
 	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_end_episodes: null ctx");
 	if (bit != 64 && bit != 128) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_end_episodes: bit must be 64 or 128");
@@ -3696,6 +3834,13 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 	if (ctx->joint_on) HIP_TRY(ctx, hipMemsetAsync(ctx->joint_counts, 0, sai2b::JOINT_COUNTS * sizeof(int), ctx->stream));
 	// external wrench: the wrench forms of either kernel, the counter of robots pushed zeroed alike
 	if (ctx->wrench_on) HIP_TRY(ctx, hipMemsetAsync(ctx->wrench_count, 0, sizeof(int), ctx->stream));
+	// whole-arm contact: sim_body_kernel for every form, its four counters zeroed alike
+	const bool body_on = ctx->body_on && ctx->col_on;
+	sai2b::BodyParams body;
+	if (body_on) {
+		body = body_params(ctx);
+		HIP_TRY(ctx, hipMemsetAsync(ctx->body_counts, 0, sai2b::BC_COUNTS * sizeof(int), ctx->stream));
+	}
 	// hardware: actuate_kernel turns the command into the applied torques, which the simulation kernel receives as its tau
 	if (ctx->hw_on) {
 		sai2b::ActuateParams a;
@@ -3706,7 +3851,8 @@ extern "C" int sai2b_sim_step(sai2b_ctx* ctx, const double* tau, int on_device, 
 		t = ctx->hw_applied;
 	}
 	if (sai2b::launch_sim(ctx->d_params, ctx->B, t, dt, substeps, with_gravity, hp.plant_payload != nullptr, hp.contact != nullptr,
-						  ctx->joint_on ? &ctx->joint : nullptr, ctx->wrench_on ? &ctx->wrench : nullptr, nullptr, q_keep, ctx->stream))
+						  ctx->joint_on ? &ctx->joint : nullptr, ctx->wrench_on ? &ctx->wrench : nullptr, body_on ? &body : nullptr, nullptr, q_keep,
+						  ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	ctx->launches++;
 	// hardware: sense_kernel, only when the simulation kernel has just written the ideal reading into the sensor's task
@@ -3743,7 +3889,7 @@ extern "C" int sai2b_get_bias(sai2b_ctx* ctx, int with_gravity, double* bias) {
 	if (rc) return rc;
 	if (!ctx->sim_tau && (rc = dev_alloc(ctx, &ctx->sim_tau, (size_t)N * ctx->B))) return rc;
 	// a zero-length step leaves the state as it is and writes the bias vector of the current state
-	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, nullptr, nullptr, ctx->sim_tau, nullptr, ctx->stream))
+	if (sai2b::launch_sim(ctx->d_params, ctx->B, nullptr, 0.0, 1, with_gravity, ctx->h_params.plant_payload != nullptr, false, nullptr, nullptr, nullptr, ctx->sim_tau, nullptr, ctx->stream))
 		return set_error(ctx, SAI2B_RUNTIME_ERROR, "simulation launch failed");
 	return fetch_rows(ctx, ctx->sim_tau, 0, N, bias);
 }

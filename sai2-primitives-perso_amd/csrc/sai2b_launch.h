@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "sai2b_body_contact_law.h"  // BcGeom
 #include "sai2b_collision_law.h"  // ColLaw
 #include "sai2b_env_draw.h"  // EnvDraw
 #include "sai2b_params.h"
@@ -99,12 +100,23 @@ struct WrenchParams {
 	int link = 0, frame = 0, sensor_task = -1;
 	double point[3] = {};
 };
+// whole-arm contact of the plant (sai2b_set_body_contact, sai2b_sim.hip: sim_body_kernel): the kernel's own parameter block, passed
+// by value as a kernel argument like WrenchParams; DevParams is not touched by the feature. The geometry is the collision
+// configuration's, the environment rows are the collision's own buffer, read live.
+struct BodyParams {
+	BcGeom geom = {};
+	const double* env = nullptr;   // [6 P + 4 O][B], or NULL without planes and obstacles
+	const double* rows = nullptr;  // [BC_ROWS][B]: stiffness, damping, friction
+	double* status = nullptr;	   // [9 + N][B]
+	int* counts = nullptr;		   // [BC_COUNTS]; zeroed by the caller ahead of the launch
+};
 // simulation harness (sai2b_sim.hip): one control period of rigid-body dynamics, state updated in place.
 // payload / contact select the instantiation: the plant's payload rows, the contact rows, status and counter of DevParams;
 // joint != NULL: sim_joint_kernel (the same two selectors) instead of sim_kernel, dbg_bias must be NULL then;
-// wrench != NULL: the forms of either with an external wrench, dbg_bias must be NULL then
+// wrench != NULL: the forms of either with an external wrench, dbg_bias must be NULL then;
+// body != NULL: sim_body_kernel instead of all of them (joint and wrench become its switches), dbg_bias must be NULL then
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   const JointParams* joint, const WrenchParams* wrench, double* dbg_bias, double* q_keep, hipStream_t stream);
+			   const JointParams* joint, const WrenchParams* wrench, const BodyParams* body, double* dbg_bias, double* q_keep, hipStream_t stream);
 // observers of a MotionForceTask between ticks: out [68][B] (rows in sai2b_sim.hip: mft_status_kernel)
 int launch_mft_status(const DevParams* d_params, int B, int task, double* out, hipStream_t stream);
 

@@ -10,6 +10,7 @@
 // One lane per robot, as everywhere in this library; FK and the mass matrix are the tick kernel's own.
 #include <hip/hip_runtime.h>
 
+#include "sai2b_body_contact_law.h"
 #include "sai2b_device.hpp"
 #include "sai2b_fast.hpp"
 #include "sai2b_launch.h"
@@ -675,6 +676,194 @@ __global__ __launch_bounds__(64) void sim_joint_wrench_kernel(const DevParams* _
 	joint_report(J, jr, ts, saturated, q, dq, B, b);
 }
 
+// ---- whole-arm contact of the plant (sai2b_set_body_contact): the collision configuration's link spheres pushed out of the
+// robot's planes, its obstacle spheres and each other. The law is sai2b_body_contact_law.h (DESIGN "Whole-arm contact"); this file
+// gives it the robot's sphere centres and link twists in per-lane LDS slots (slot s of lane t at [s * 64 + t]: a wavefront's
+// lanes touch 512 contiguous bytes, and a lane reads what it wrote itself, so nothing is synchronised) and the joint axes
+// from the frames.
+// Centres: the frames live in registers under compile-time indices, so the link loop is unrolled and, inside it, a real loop
+// over the spheres stores those that sit on the link (a scalar test on the by-value block). Twists about the origin of the
+// coordinates: w_i and the velocity vo_i of frame i's origin run down the chain, v0_i = vo_i - w_i x p_i, and the material
+// point of link i at c moves with v0_i + w_i x c, which is sum_{m <= i} dq_m z_m x (c - p_m) (dq_m z_m along a prismatic joint).
+DI void body_fill(const DevModel& md, const BcGeom& G, const Frames& F, const real* dq, real* lds, real (&z)[N][3], real (&o)[N][3]) {
+	real* xs = lds;
+	real* tw = lds + (size_t)(3 * G.n_spheres) * 64;
+#pragma unroll 1
+	for (int k = 0; k < G.n_spheres; k++) {
+		if (G.link[k] < 0) {  // a world point, in the step's coordinates
+			UNROLL for (int a = 0; a < 3; a++) xs[(size_t)(3 * k + a) * 64] = G.centre[k][a] - md.xyz[0][a];
+		}
+	}
+	real w[3] = {0, 0, 0}, vo[3] = {0, 0, 0};
+	UNROLL for (int i = 0; i < N; i++) {
+		const real* R = F.R[i];
+		const real* p = F.p[i];
+		UNROLL for (int a = 0; a < 3; a++) z[i][a] = R[3 * a + 2], o[i][a] = p[a];
+		if (i > 0) {  // frame i's origin rides on link i - 1 (the world does not move)
+			const real d[3] = {p[0] - F.p[i - 1][0], p[1] - F.p[i - 1][1], p[2] - F.p[i - 1][2]};
+			real t[3];
+			cross3(w, d, t);
+			UNROLL for (int a = 0; a < 3; a++) vo[a] += t[a];
+		}
+		const bool pris = md.jtype[i] != 0;
+		UNROLL for (int a = 0; a < 3; a++) {
+			const real zq = z[i][a] * dq[i];
+			vo[a] += pris ? zq : 0.0;
+			w[a] += pris ? 0.0 : zq;
+		}
+		real t[3];
+		cross3(w, p, t);
+		UNROLL for (int a = 0; a < 3; a++) {
+			tw[(size_t)(6 * i + a) * 64] = vo[a] - t[a];
+			tw[(size_t)(6 * i + 3 + a) * 64] = w[a];
+		}
+#pragma unroll 1
+		for (int k = 0; k < G.n_spheres; k++) {
+			if (G.link[k] == i) {
+				const double* c = G.centre[k];
+				UNROLL for (int a = 0; a < 3; a++)
+					xs[(size_t)(3 * k + a) * 64] = fma(R[3 * a], c[0], fma(R[3 * a + 1], c[1], fma(R[3 * a + 2], c[2], p[a])));
+			}
+		}
+	}
+}
+// tb of the state the frames belong to; lds: the lane's first slot
+DI void body_torques(const DevParams& P, const BodyParams& Bp, const Frames& F, const real* dq, real* lds, int B, int b, real k, real d,
+					 real mu, real (&tb)[N]) {
+	real z[N][3], o[N][3];
+	body_fill(P.model, Bp.geom, F, dq, lds, z, o);
+	body_contact_law<N, false>(Bp.geom, lds, lds + (size_t)(3 * Bp.geom.n_spheres) * 64, 64, z, o, P.model.jtype, P.model.xyz[0], Bp.env + b,
+							   (size_t)B, k, d, mu, tb, nullptr);
+}
+// After the last substep, from the frames of the final state: the status rows [9 + N][B] (per category the deepest penetration,
+// its witness, the sum of f_n; tb) and the four counters, one ballot and one atomic each
+DI void body_report(const DevParams& P, const BodyParams& Bp, const real* q, const real* dq, real* lds, int B, int b, real k, real d, real mu) {
+	Frames Fr;
+	fk<true>(P.model, q, Fr);
+	real z[N][3], o[N][3], tb[N];
+	body_fill(P.model, Bp.geom, Fr, dq, lds, z, o);
+	BcStatus s;
+	body_contact_law<N, true>(Bp.geom, lds, lds + (size_t)(3 * Bp.geom.n_spheres) * 64, 64, z, o, P.model.jtype, P.model.xyz[0], Bp.env + b,
+							  (size_t)B, k, d, mu, tb, &s);
+	bool any = false;
+	UNROLL for (int c = 0; c < COL_CATEGORIES; c++) {
+		st(Bp.status, BC_DEPTH + c, B, b, s.depth[c]);
+		st(Bp.status, BC_INDEX + c, B, b, (real)s.index[c]);
+		st(Bp.status, BC_FSUM + c, B, b, s.fsum[c]);
+		const bool touching = s.fsum[c] > 0.0;
+		any = any || touching;
+		const unsigned long long hit = __ballot(touching);
+		if (threadIdx.x == 0 && hit) atomicAdd(Bp.counts + c, __popcll(hit));  // lane 0 always has a robot
+	}
+	UNROLL for (int i = 0; i < N; i++) st(Bp.status, BC_TORQUE + i, B, b, tb[i]);
+	const unsigned long long hit = __ballot(any);
+	if (threadIdx.x == 0 && hit) atomicAdd(Bp.counts + COL_CATEGORIES, __popcll(hit));
+}
+
+// The step of a context with whole-arm contact: PL / CT as everywhere, joint dynamics and the external wrench as run-time,
+// batch-uniform switches (joint_on, wrench_on: scalar branches around the statements of sim_joint_kernel and sim_wrench_kernel),
+// so that the feature adds four kernels per robot size, not sixteen. The four kernels above are not instantiations of this
+// body, for the reason given at sim_wrench_kernel. tb joins the right-hand side beside tc and tx: explicit in the plain step,
+// inside h (...) of the linear-implicit one, behind the torque limit. Dynamic LDS: 64 * bc_lds_slots(n_spheres, N) doubles.
+template <class PL, class CT>
+__global__ __launch_bounds__(64) void sim_body_kernel(const DevParams* __restrict__ Pp, const real* __restrict__ tau, real dt, int substeps,
+													  int with_gravity, real* __restrict__ q_keep, const BodyParams Bp, const JointParams J,
+													  const WrenchParams W, int joint_on, int wrench_on) {
+	extern __shared__ real body_lds[];
+	const DevParams& P = *Pp;
+	const int B = P.B;
+	const int b = blockIdx.x * 64 + threadIdx.x;
+	if (b >= B) return;
+	real* lds = body_lds + threadIdx.x;
+	real q[N], dq[N], ts[N];
+	JointRows jr;
+	bool saturated = false;
+	UNROLL for (int i = 0; i < N; i++) {
+		q[i] = ld(P.q, i, B, b);
+		dq[i] = ld(P.dq, i, B, b);
+		const real tq = tau ? ld(tau, i, B, b) : 0.0;
+		if (q_keep) st(q_keep, i, B, b, q[i]);
+		ts[i] = tq;
+		jr.a[i] = jr.d[i] = jr.f[i] = 0.0;
+		jr.lo[i] = -HUGE_VAL, jr.hi[i] = HUGE_VAL;
+		if (joint_on) {
+			jr.a[i] = ld(J.rows, JOINT_ARMATURE * N + i, B, b);
+			jr.d[i] = ld(J.rows, JOINT_DAMPING * N + i, B, b);
+			jr.f[i] = ld(J.rows, JOINT_FRICTION * N + i, B, b);
+			jr.lo[i] = ld(J.rows, JOINT_LOWER * N + i, B, b);
+			jr.hi[i] = ld(J.rows, JOINT_UPPER * N + i, B, b);
+			const real lim = ld(J.rows, JOINT_TORQUE_LIMIT * N + i, B, b);
+			saturated = saturated || fabs(tq) > lim;
+			ts[i] = fmin(fmax(tq, -lim), lim);
+		}
+	}
+	[[maybe_unused]] PL pl;
+	if constexpr (PL::on) payload_load(P.plant_payload, P.plant_payload_link, B, b, pl);
+	[[maybe_unused]] CT ct;
+	if constexpr (CT::on) contact_load(P.contact, P.model.xyz[0], B, b, ct);
+	Wrench wr;
+	UNROLL for (int k = 0; k < 3; k++) wr.F[k] = wr.M[k] = 0.0;
+	wr.steps = 0.0, wr.active = false;
+	if (wrench_on) wrench_load(W, B, b, wr);
+	const real bk = ld(Bp.rows, 0, B, b), bd = ld(Bp.rows, 1, B, b), bmu = ld(Bp.rows, 2, B, b);
+	const real h = dt / substeps;
+#pragma unroll 1
+	for (int s = 0; s < substeps; s++) {
+		Frames F;
+		fk<true>(P.model, q, F);
+		real M[N * N], L[N * N], dinv[N], x[N];
+		bias_forces(P.model, F, dq, with_gravity != 0, x, pl);
+		real tb[N];
+		body_torques(P, Bp, F, dq, lds, B, b, bk, bd, bmu, tb);
+		real tx[N];
+		UNROLL for (int i = 0; i < N; i++) tx[i] = 0.0;
+		if (wrench_on) {
+			real xw[3], Fw[3], Mw[3];
+			wrench_torques(P.model, W, wr, F, xw, Fw, Mw, tx);
+		}
+		if constexpr (CT::on) {
+			real tc[N];
+			contact_torques(P.model, P, ct, F, dq, tc);
+			UNROLL for (int i = 0; i < N; i++) {
+				const real stop = joint_on ? joint_stop_torque(J, jr, i, q[i], dq[i]) : 0.0;
+				x[i] = ((((ts[i] + stop) + tc[i]) + tx[i]) + tb[i]) - x[i];
+			}
+		} else {
+			UNROLL for (int i = 0; i < N; i++) {
+				const real stop = joint_on ? joint_stop_torque(J, jr, i, q[i], dq[i]) : 0.0;
+				x[i] = (((ts[i] + stop) + tx[i]) + tb[i]) - x[i];
+			}
+		}
+		mass_matrix(P.model, F, M, pl);
+		if (joint_on) {
+			UNROLL for (int i = 0; i < N; i++) {
+				real m = jr.a[i] * dq[i];
+				UNROLL for (int j = 0; j < N; j++) m = fma(M[i * N + j], dq[j], m);
+				x[i] = fma(h, x[i], m);
+			}
+			UNROLL for (int i = 0; i < N; i++) M[i * N + i] += fma(h, joint_dissipation(J, jr, i, dq[i]), jr.a[i]);
+		}
+		chol<N>(M, L, dinv);
+		solve_lower<N>(L, dinv, x);
+		solve_lower_t<N>(L, dinv, x);
+		UNROLL for (int i = 0; i < N; i++) {
+			dq[i] = joint_on ? x[i] : fma(h, x[i], dq[i]);
+			q[i] = fma(h, dq[i], q[i]);
+		}
+	}
+	UNROLL for (int i = 0; i < N; i++) {
+		st((real*)P.q, i, B, b, q[i]);
+		st((real*)P.dq, i, B, b, dq[i]);
+	}
+	if (wrench_on) {
+		wrench_finish(P.model, P, W, wr, ct, q, dq, B, b);
+	} else {
+		if constexpr (CT::on) contact_report(P.model, P, ct, q, dq, B, b, NoReading{}, nullptr);
+	}
+	if (joint_on) joint_report(J, jr, ts, saturated, q, dq, B, b);
+	body_report(P, Bp, q, dq, lds, B, b, bk, bd, bmu);
+}
+
 // What the tasks' observers read between ticks (MotionForceTask.h:121-165: getCurrentPosition /
 // Orientation, getSensedForce/MomentControlWorldFrame; MotionForceTask.cpp:540-579: getPositionError,
 // getOrientationError, goalPositionReached, goalOrientationReached), computed from the state and goal
@@ -744,8 +933,18 @@ int launch_mft_status(const DevParams* d_params, int B, int task, double* out, h
 }
 
 int launch_sim(const DevParams* d_params, int B, const double* tau, double dt, int substeps, int with_gravity, bool payload, bool contact,
-			   const JointParams* joint, const WrenchParams* wrench, double* dbg_bias, double* q_keep, hipStream_t stream) {
+			   const JointParams* joint, const WrenchParams* wrench, const BodyParams* body, double* dbg_bias, double* q_keep, hipStream_t stream) {
 	const dim3 grid((B + 63) / 64), block(64);
+	if (body) {	 // whole-arm contact: one kernel for every form, joint dynamics and the wrench as its run-time switches
+		if (dbg_bias) return 1;
+		static constexpr decltype(&sim_body_kernel<NoPayload, NoContact>) body_kernel[2][2] = {
+			{sim_body_kernel<NoPayload, NoContact>, sim_body_kernel<Payload, NoContact>},
+			{sim_body_kernel<NoPayload, Contact>, sim_body_kernel<Payload, Contact>}};
+		const size_t lds = (size_t)64 * bc_lds_slots(body->geom.n_spheres, N) * sizeof(double);
+		hipLaunchKernelGGL(body_kernel[contact][payload], grid, block, lds, stream, d_params, tau, dt, substeps, with_gravity, q_keep, *body,
+						   joint ? *joint : JointParams{}, wrench ? *wrench : WrenchParams{}, joint ? 1 : 0, wrench ? 1 : 0);
+		return launch_result();
+	}
 	if (wrench) {  // the forms with an external wrench (dbg_bias: sai2b_get_bias never sees one)
 		if (dbg_bias) return 1;
 		if (joint) {
