@@ -72,22 +72,64 @@ DI bool certify_nonsingular(const real* J, real s_abs_tol, real s_max) {
 struct JtEarly {
 	real f[N], ddq[N], integ[N];
 };
+// A batch-uniform value of the FastBlock, pinned in scalar registers from here on. The reads of a group are written first and
+// the ties behind them: every tie needs its value, so the group's scalar loads are all issued ahead of the first tie and one
+// wait serves the lot; nothing of the group is fetched again later, one field and one wait at a time.
+template <class T>
+DI void sgpr_tie(T& v) {
+	asm volatile("" : "+s"(v));
+}
+// Gains of the JointTask law in registers, fetched as one burst. VSAT: with the velocity-saturation limits.
+struct JtGains {
+	real dt, kp[N], kv[N], ki[N], vsat[N];
+};
+template <bool VSAT>
+DI void jt_gains_burst(const FastJt& s, JtGains& g) {
+	g.dt = s.dt;
+	UNROLL for (int i = 0; i < N; i++) {
+		g.kp[i] = s.kp[i], g.kv[i] = s.kv[i], g.ki[i] = s.ki[i];
+		if constexpr (VSAT) g.vsat[i] = s.vsat[i];
+	}
+	sgpr_tie(g.dt);
+	UNROLL for (int i = 0; i < N; i++) {
+		sgpr_tie(g.kp[i]), sgpr_tie(g.kv[i]), sgpr_tie(g.ki[i]);
+		if constexpr (VSAT) sgpr_tie(g.vsat[i]);
+	}
+}
+// JointTask.cpp:299-345, S = I. use_vsat is batch-uniform: one branch around two loops, each fetching its gains in one burst.
 template <class Rows>
-DI void fast_jt_early(const DevTask& t1, const RobotCtx& rc, const Rows& r, JtEarly& e) {
-	UNROLL for (int i = 0; i < N; i++) {  // JointTask.cpp:299-345, S = I
-		const real qd = r.law_goal(i), dqd = r.law_goal(N + i);
-		e.ddq[i] = r.law_goal(2 * N + i);
-		const real integ = fma(rc.q[i] - qd, t1.dt, r.state(i));
-		e.integ[i] = integ;
-		if (t1.use_vsat) {
-			const real kvi = gain_pinv(t1.kv[i]);
-			real dv = -t1.kp[i] * kvi * (rc.q[i] - qd) - t1.ki[i] * kvi * integ;
-			dv = fmin(fmax(dv, -t1.vsat[i]), t1.vsat[i]);
-			e.f[i] = -t1.kv[i] * (rc.dq[i] - dv);
-		} else {
-			e.f[i] = -t1.kp[i] * (rc.q[i] - qd) - t1.kv[i] * (rc.dq[i] - dqd) - t1.ki[i] * integ;
+DI void fast_jt_law(const JtGains& g, bool use_vsat, const RobotCtx& rc, const Rows& r, JtEarly& e) {
+	if (use_vsat) {
+		UNROLL for (int i = 0; i < N; i++) {
+			const real qd = r.law_goal(i);
+			e.ddq[i] = r.law_goal(2 * N + i);
+			const real integ = fma(rc.q[i] - qd, g.dt, r.state(i));
+			e.integ[i] = integ;
+			const real kvi = gain_pinv(g.kv[i]);
+			real dv = -g.kp[i] * kvi * (rc.q[i] - qd) - g.ki[i] * kvi * integ;
+			dv = fmin(fmax(dv, -g.vsat[i]), g.vsat[i]);
+			e.f[i] = -g.kv[i] * (rc.dq[i] - dv);
+		}
+	} else {
+		UNROLL for (int i = 0; i < N; i++) {
+			const real qd = r.law_goal(i), dqd = r.law_goal(N + i);
+			e.ddq[i] = r.law_goal(2 * N + i);
+			const real integ = fma(rc.q[i] - qd, g.dt, r.state(i));
+			e.integ[i] = integ;
+			e.f[i] = -g.kp[i] * (rc.q[i] - qd) - g.kv[i] * (rc.dq[i] - dqd) - g.ki[i] * integ;
 		}
 	}
+}
+
+// the same with the gains fetched here (the forms that evaluate the law ahead of the chain)
+template <class Rows>
+DI void fast_jt_early(const FastJt& t1, bool use_vsat, const RobotCtx& rc, const Rows& r, JtEarly& e) {
+	JtGains g;
+	if (use_vsat)
+		jt_gains_burst<true>(t1, g);
+	else
+		jt_gains_burst<false>(t1, g);
+	fast_jt_law(g, use_vsat, rc, r, e);
 }
 
 // Scheduling fence between phases (and a marker in the ISA for per-phase inspection): the kernel is
@@ -130,19 +172,20 @@ struct StageLayout {
 };
 
 // first element of image row k in the batched arrays (the pad row repeats the last one)
+// (P: the kernel's copy of the FastBlock's entry group, already in registers: no DMA instruction waits for a row base)
 template <int FAST, bool PAY = false>
-DI const real* stage_row(const DevParams& P, int k) {
+DI const real* stage_row(const FastEntry& P, int k) {
 	using S = StageLayout<FAST, PAY>;
 	const int B = P.B;
 	if (k >= S::ROWS) k = S::ROWS - 1;
 	if (k < S::JG) return P.dq + (size_t)(k - S::DQ) * B;
-	if (k < S::JS) return P.task[1].law_goals + (size_t)(k - S::JG) * B;
-	if (k < S::MG) return P.task[1].state + (size_t)(k - S::JS) * B;
-	if (k < S::MS) return P.task[0].law_goals + (size_t)(k - S::MG) * B;
+	if (k < S::JS) return P.law_goals1 + (size_t)(k - S::JG) * B;
+	if (k < S::MG) return P.state1 + (size_t)(k - S::JS) * B;
+	if (k < S::MS) return P.law_goals0 + (size_t)(k - S::MG) * B;
 	if constexpr (PAY) {
 		if (k >= S::PLD) return P.payload + (size_t)(k - S::PLD) * B;
 	}
-	return P.task[0].state + (size_t)(k - S::MS) * B;
+	return P.state0 + (size_t)(k - S::MS) * B;
 }
 
 DI void glds(const void* src, real* lds, int bytes) {
@@ -157,7 +200,7 @@ DI void glds(const void* src, real* lds, int bytes) {
 // Issue the DMA of the whole image for the 64 robots from b0 on; all 64 lanes take part, also those past B (the
 // source columns of lanes past B are clamped into the batch, and the columns they fill are never read).
 template <int FAST, bool PAY = false>
-DI void stage_issue(const DevParams& P, real* img, int b0) {
+DI void stage_issue(const FastEntry& P, real* img, int b0) {
 	using S = StageLayout<FAST, PAY>;
 	const int B = P.B, lane = threadIdx.x;
 	if ((B & 1) == 0) {	 // every row starts 16-byte aligned: lane l moves robots col, col + 1 of row 2i + l / 32
@@ -172,7 +215,7 @@ DI void stage_issue(const DevParams& P, real* img, int b0) {
 				glds((const int*)(stage_row<FAST, PAY>(P, k) + col) + (lane & 1), img + k * 64 + 32 * h, 4);
 		}
 	}
-	glds(P.task[0].istate + (size_t)IS_NTYPES * B + min(b0 + lane, B - 1), img + S::IROW * 64, 4);
+	glds(P.istate0 + (size_t)IS_NTYPES * B + min(b0 + lane, B - 1), img + S::IROW * 64, 4);
 }
 
 // The rows of one task as the fast kernel reads them after the barrier: staged rows from the image (this lane's
@@ -188,6 +231,91 @@ struct StagedRows {
 	DI real sensed(int k) const { return ld(t.sensed, k, B, b); }
 	DI real state(int k) const { return k < st_rows ? st[k * 64] : ld(t.state, k, B, b); }
 };
+
+// ---- The functions of sai2b_device.hpp that read a DevTask, restated on the FastBlock's copies (sai2b_params.h) for the
+// headline body: the same expressions in the same order. The originals stay as they are, so that every other kernel compiles
+// to the code it had.
+// frame_pose()
+DI void frame_pose(const FastPose& t, const Frames& F, real* x, real* R) {
+	real Rl[9], pl[3];
+	UNROLL for (int k = 0; k < 9; k++) Rl[k] = F.R[N - 1][k];
+	UNROLL for (int k = 0; k < 3; k++) pl[k] = F.p[N - 1][k];
+	UNROLL for (int i = 0; i < N - 1; i++)
+		if (t.link == i) {
+			UNROLL for (int k = 0; k < 9; k++) Rl[k] = F.R[i][k];
+			UNROLL for (int k = 0; k < 3; k++) pl[k] = F.p[i][k];
+		}
+	UNROLL for (int k = 0; k < 3; k++)
+		x[k] = fma(Rl[3 * k], t.frame_pos[0], fma(Rl[3 * k + 1], t.frame_pos[1], fma(Rl[3 * k + 2], t.frame_pos[2], pl[k])));
+	mm<3, 3, 3>(Rl, t.frame_rot, R);
+}
+// jacobian()
+template <class MD>
+DI void jacobian(const MD& md, const FastPose& t, const Frames& F, const real* x, real* J) {
+	UNROLL for (int i = 0; i < N; i++) {
+		real z[3] = {F.R[i][2], F.R[i][5], F.R[i][8]};
+		real d[3] = {x[0] - F.p[i][0], x[1] - F.p[i][1], x[2] - F.p[i][2]}, v[3];
+		cross3(z, d, v);
+		const bool on = i <= t.link, pris = md.jtype[i] != 0;
+		UNROLL for (int k = 0; k < 3; k++) {
+			J[k * N + i] = on ? (pris ? z[k] : v[k]) : 0.0;
+			J[(3 + k) * N + i] = (on && !pris) ? z[k] : 0.0;
+		}
+	}
+}
+// mft_load(), its batch-uniform branches from the flags word (FastEntry::flags)
+template <class Rows>
+DI void fast_mft_load(int flags, const Rows& r, MftIn& in) {
+	UNROLL for (int k = 0; k < 3; k++) {
+		in.g_pos[k] = r.law_goal(k);
+		in.g_v[k] = r.law_goal(12 + k);
+		in.g_w[k] = r.law_goal(15 + k);
+		in.g_a[k] = r.law_goal(18 + k);
+		in.g_al[k] = r.law_goal(21 + k);
+		in.g_f[k] = in.g_m[k] = in.s_f[k] = in.s_m[k] = 0;
+	}
+	UNROLL for (int k = 0; k < 9; k++) in.g_rot[k] = r.law_goal(3 + k);
+	UNROLL for (int k = 0; k < 6; k++) in.integ[k] = r.state(k);
+	UNROLL for (int k = 6; k < 12; k++) in.integ[k] = 0;
+	if (flags & FB_USES_FORCE) {
+		UNROLL for (int k = 0; k < 3; k++) {
+			in.g_f[k] = r.goal(24 + k);
+			in.g_m[k] = r.goal(27 + k);
+		}
+		if (flags & (FB_CL_FORCE | FB_CL_MOMENT)) {
+			UNROLL for (int k = 0; k < 3; k++) {
+				in.s_f[k] = r.sensed(k);
+				in.s_m[k] = r.sensed(3 + k);
+			}
+		}
+	}
+	if (flags & (FB_CL_FORCE | FB_CL_MOMENT)) {
+		UNROLL for (int k = 6; k < 12; k++) in.integ[k] = r.state(k);
+	}
+}
+// mft_store_integrators()
+DI void fast_mft_store_integrators(int flags, real* state, int B, int b, const MftIn& in) {
+	UNROLL for (int k = 0; k < 6; k++) st(state, k, B, b, in.integ[k]);
+	if (flags & FB_CL_FORCE) {
+		UNROLL for (int k = 6; k < 9; k++) st(state, k, B, b, in.integ[k]);
+	}
+	if (flags & FB_CL_MOMENT) {
+		UNROLL for (int k = 9; k < 12; k++) st(state, k, B, b, in.integ[k]);
+	}
+}
+// the plain_motion branch of mft_law_vw()
+DI void fast_mft_law_plain(const FastLaw& t, const real* v, const real* w, const real* x, const real* R, MftIn& in, real* Fu, real* Ff) {
+	real oe[3];
+	orientation_error(in.g_rot, R, oe);
+	UNROLL for (int k = 0; k < 3; k++) {
+		const real ex = x[k] - in.g_pos[k];
+		in.integ[k] = fma(ex, t.dt, in.integ[k]);
+		in.integ[3 + k] = fma(oe[k], t.dt, in.integ[3 + k]);
+		Fu[k] = in.g_a[k] - t.kp_pos[k] * ex - t.kv_pos[k] * (v[k] - in.g_v[k]) - t.ki_pos[k] * in.integ[k];
+		Fu[3 + k] = in.g_al[k] - t.kp_ori[k] * oe[k] - t.kv_ori[k] * (w[k] - in.g_w[k]) - t.ki_ori[k] * in.integ[3 + k];
+		Ff[k] = Ff[3 + k] = 0;
+	}
+}
 
 // A symmetric N x N matrix parked in the LDS image (StageLayout::PARKED): row i (i + 1) / 2 + j of this lane's column
 // holds element (i, j), j <= i. Indexed like the array it stands in for, lower triangle only.
@@ -216,23 +344,40 @@ struct JtGiven {
 // that q is not live across it; project() evaluates the same fast_jt_early from them (dq from the image), stores the
 // advanced integrators (the caller is past worklist_append: this lane is committed to the fast path) and forms the two
 // dot products.
+// EARLY: where the law's gains are fetched, as one burst either way. true: with q, behind the QR, so that their round trip is
+// over long before the nullspace vector exists (some 44 scalar registers held until then). false: at the top of project().
+// Chosen per kernel from its ISA: the BAKED forms have the registers to hold them, in the others holding them costs lane spills
+// (tests/test_fast_scalar_waits_isa.py counts both).
+template <bool EARLY>
 struct JtLate {
-	const DevTask& t1;
+	const FastJt& t1;  // the law's gains, where they lie in the parameter block
+	bool use_vsat;
+	const real* law_goals;	// the JointTask's rows
+	real* state;
 	int B, b;
 	const real* dq;	 // image row of dq[0], at this lane's column
 	const real* qrows;
 	real lg[3 * N], s[N], q[N];
+	JtGains g;
 	struct Rows {
 		const real *lg, *s;
 		DI real law_goal(int k) const { return lg[k]; }
 		DI real state(int k) const { return s[k]; }
 	};
 	DI void prefetch() {
-		UNROLL for (int k = 0; k < 3 * N; k++) lg[k] = ld(t1.law_goals, k, B, b);
-		UNROLL for (int i = 0; i < N; i++) s[i] = ld(t1.state, i, B, b);
+		UNROLL for (int k = 0; k < 3 * N; k++) lg[k] = ld(law_goals, k, B, b);
+		UNROLL for (int i = 0; i < N; i++) s[i] = ld(state, i, B, b);
 	}
 	DI void prefetch_q() {
 		UNROLL for (int i = 0; i < N; i++) q[i] = ld(qrows, i, B, b);
+		// the gains with them: their one round trip is over long before the nullspace vector exists
+		if constexpr (EARLY) gains();
+	}
+	DI void gains() {
+		if (use_vsat)
+			jt_gains_burst<true>(t1, g);
+		else
+			jt_gains_burst<false>(t1, g);
 	}
 	DI void project(const real* a, real& af, real& aacc) {
 		// Nothing in the law depends on a, and arithmetic without a dependency is free to move up to the loads, taking
@@ -244,8 +389,11 @@ struct JtLate {
 			rc.dq[i] = dq[i * 64];
 		}
 		JtEarly e;
-		fast_jt_early(t1, rc, Rows{lg, s}, e);
-		UNROLL for (int i = 0; i < N; i++) st(t1.state, i, B, b, e.integ[i]);
+		asm volatile("; SAI2B_MARK jt_law_begin");
+		if constexpr (!EARLY) gains();
+		fast_jt_law(g, use_vsat, rc, Rows{lg, s}, e);
+		asm volatile("; SAI2B_MARK jt_law_end");
+		UNROLL for (int i = 0; i < N; i++) st(state, i, B, b, e.integ[i]);
 		JtGiven{e}.project(a, af, aacc);
 	}
 };
@@ -332,18 +480,21 @@ DI void fast_tick_mft(const DevParams& P, const real* J, const Mat& M, const rea
 // the factor R of J Mx^-1 J^T for the MotionForceTask solves and the nullspace direction w = Q e_6 in one pass; the
 // projector is N = a bb^T with a, bb from nv = Lx^-T w and M nv. jt is the JointTask law (JtGiven or JtLate): its loads
 // are issued ahead of the whole chain, which is what hides them.
+// flags: FastEntry::flags, the tasks' decouplings among them; one bounded inertia estimate for the tasks that ask for it (the
+// host checks that the thresholds agree, and FastChain holds the one that counts)
+template <class Mat, class JT>
+DI void fast_tick2(int flags, const FastChain& c, const real* J, const Mat& M, const real* Fu, const real* Ff, bool with_comp, JT& jt,
+				   real* tau) {
+	chain::tick2<N>(J, M, Fu, Ff, (flags & FB_MFT_BIE) != 0, (flags & FB_MFT_FULL) != 0, (flags & FB_JT_FULL) != 0,
+					(flags & FB_JT_IMP) != 0, c.bie_threshold, with_comp, jt, tau);
+}
 template <bool HAS_JT, class Mat, class JT>
 DI void fast_tick(const DevParams& P, const real* J, const Mat& M, const real* Fu, const real* Ff, int B, int b,
 				  bool with_comp, JT& jt, real* tau) {
 	if constexpr (!HAS_JT) {
 		fast_tick_mft(P, J, M, Fu, Ff, tau);
 	} else {
-		const DevTask &t0 = P.task[0], &t1 = P.task[1];
-		// one bounded inertia estimate for the tasks that ask for it (host checks thresholds agree)
-		const bool jt_bie = t1.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES;
-		chain::tick2<N>(J, M, Fu, Ff, t0.decoupling == SAI2B_BOUNDED_INERTIA_ESTIMATES,
-						t0.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING, t1.decoupling == SAI2B_FULL_DYNAMIC_DECOUPLING,
-						t1.decoupling == SAI2B_IMPEDANCE, jt_bie ? t1.bie_threshold : t0.bie_threshold, with_comp, jt, tau);
+		fast_tick2(P.fast.entry.flags, P.fast.chain, J, M, Fu, Ff, with_comp, jt, tau);
 	}
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sai2b_launch.h"
+#include "sai2b_fast_block.h"
 #include "sai2b_snapshot_layout.h"
 #include "sai2b_reset_sampler_layout.h"
 #include "sai2b_env_sampler_layout.h"
@@ -777,12 +778,15 @@ static int upload_params(sai2b_ctx* ctx) {
 			ctx->h_params.any_bie = 1;
 			ctx->h_params.bie_thr = ctx->h_params.task[t].bie_threshold;
 		}
+	// the headline body's block of copies: written here and nowhere else, from what is about to be sent
+	sai2b::fast_block_fill(ctx->h_params);
 	// stream-ordered so that kernels already enqueued keep the parameters they were launched with
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_params, &ctx->h_params, sizeof(DevParams), hipMemcpyHostToDevice, ctx->stream));
 	DevParams meas;
 	if (ctx->js_on) {  // the same parameters with the measured pair as their state
 		meas = ctx->h_params;
 		meas.q = ctx->js_qm, meas.dq = ctx->js_dqm;
+		sai2b::fast_block_fill(meas);
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_params_meas, &meas, sizeof(DevParams), hipMemcpyHostToDevice, ctx->stream));
 	}
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // h_params may be edited again right after

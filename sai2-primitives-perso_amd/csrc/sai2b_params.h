@@ -2,6 +2,8 @@
 // One block per ctx lives in device memory; every field is batch-uniform, so the kernels read it
 // with scalar loads.
 #pragma once
+#include <cstddef>
+
 #include "../../include/sai2b.h"
 
 namespace sai2b {
@@ -158,6 +160,72 @@ enum TaskCertBits {
 	TASK_CERT_NO_INLANE = 4	  // as TICK_CERT_NO_INLANE
 };
 
+// ---- FastBlock: what the SVD-free headline body (sai2b_fast_body.hpp, FAST = 2) reads of the batch-uniform parameters, copied
+// into one compact block and grouped by the phase that consumes it. Every group is contiguous and starts on a 64-byte line, so
+// that a phase fetches its group as a few wide scalar loads behind ONE wait, instead of one field, one wait at a time out of
+// DevTask (2.5 KB, the fields of one phase spread over many lines). The block holds copies only; fast_block_fill()
+// (sai2b_fast_block.h) writes all of it from the fields above it, and upload_params() is its one caller. The generic kernels
+// keep reading DevTask.
+enum FastFlags {
+	FB_GRAVITY_COMP = 1 << 0,
+	FB_PLAIN_MOTION = 1 << 1,  // task[0].plain_motion
+	FB_USES_FORCE = 1 << 2,	   // task[0]: (fdim | mdim) != 0
+	FB_CL_FORCE = 1 << 3,
+	FB_CL_MOMENT = 1 << 4,
+	FB_MFT_VSAT = 1 << 5,  // use_vsat of task[0] and of task[1]
+	FB_JT_VSAT = 1 << 6,
+	FB_MFT_BIE = 1 << 7,  // the decoupling modes, one bit per comparison fast_tick makes
+	FB_MFT_FULL = 1 << 8,
+	FB_JT_BIE = 1 << 9,
+	FB_JT_FULL = 1 << 10,
+	FB_JT_IMP = 1 << 11
+};
+struct alignas(64) FastEntry {
+	// first line, kernel entry: all of it is in registers before q is asked for and before the first DMA instruction
+	int B;
+	int flags;	// FastFlags
+	const double* q;
+	const double* dq;
+	const double* law_goals0;  // task[0]: law_goals, state, istate
+	double* state0;
+	const int* istate0;
+	const double* payload;
+	int payload_link, reserved;
+	// second line, the rows of the chain: fetched behind the MotionForceTask law (the payload forms stage the JointTask rows
+	// and fetch it at entry), so that nothing of it is held across the window and the law
+	double* tau;
+	const double* law_goals1;  // task[1]: the JointTask rows
+	double* state1;
+	const double* q_again;	// = q, for the loads behind the QR
+	double* state0_again;	// = state0, for the integrator store
+};
+static_assert(offsetof(FastEntry, tau) == 64, "the entry group is two lines");
+struct alignas(64) FastPose {  // frame pose, Jacobian and certificate (member names as DevTask has them)
+	double frame_pos[3], frame_rot[9];
+	double s_abs_tol, s_max;
+	int link, reserved;
+};
+struct alignas(64) FastLaw {  // the plain-motion MotionForceTask law
+	double dt;
+	double kp_pos[3], kv_pos[3], ki_pos[3], kp_ori[3], kv_ori[3], ki_ori[3];
+};
+struct alignas(64) FastChain {	// chain::tick2: the decouplings are in FastEntry::flags
+	double bie_threshold;  // the JointTask's when it is bounded-inertia, else the MotionForceTask's (as fast_tick chose it)
+};
+struct alignas(64) FastJt {	 // the JointTask law (fast_jt_early)
+	double dt;
+	double kp[N], kv[N], ki[N];
+	double vsat[N];
+	int use_vsat, reserved;
+};
+struct alignas(64) FastBlock {
+	FastEntry entry;
+	FastPose pose;
+	FastLaw law;
+	FastChain chain;
+	FastJt jt;
+};
+
 struct DevParams {
 	int B;
 	int n_tasks;
@@ -185,6 +253,11 @@ struct DevParams {
 	int contact_link, contact_n_points, contact_sensor_task, contact_reserved;
 	double contact_points[SAI2B_MAX_CONTACT_POINTS][3];
 	double contact_v_eps;
+	// the headline body's copy of what it reads of all the above (FastBlock), behind everything else once more
+	FastBlock fast;
 };
+static_assert(offsetof(DevParams, fast) % 64 == 0 && offsetof(FastBlock, pose) % 64 == 0 && offsetof(FastBlock, law) % 64 == 0 &&
+				  offsetof(FastBlock, chain) % 64 == 0 && offsetof(FastBlock, jt) % 64 == 0,
+			  "every group of the FastBlock starts on a 64-byte line");
 
 }  // namespace sai2b
