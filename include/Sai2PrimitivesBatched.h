@@ -1235,8 +1235,78 @@ protected:
 	Batch _g[10];  // pos rot v w a alpha f m sensed_f sensed_m
 };
 
+// Inverse kinematics (sai2b.h "inverse kinematics"): what one solveInverseKinematics() returns, and the device counts of the last one
+struct IkResult {
+	Batch q;						   // [dof][B]; a robot that is not selected or not finite keeps a NaN column
+	Batch status;					   // [5][B]: |e_pos|, |e_rot| at q, iterations, index of the winning start, final mu
+	std::vector<unsigned char> flags;  // [B], SAI2B_IK_* bits; 0 for a robot that is not selected
+};
+struct IkCounts {
+	int selected = 0, converged = 0, exhausted = 0, nonfinite = 0;
+};
+namespace detail {
+// judged without a device: std::invalid_argument with the validator's message
+inline void checkIkConfig(const sai2b_ik_config& cfg, const int dof, const sai2b_robot_model* model, const char* who) {
+	char msg[256] = "";
+	if (sai2b_validate_ik(&cfg, dof, model ? model->q_lower : nullptr, model ? model->q_upper : nullptr, msg, sizeof(msg)) != SAI2B_OK)
+		throw std::invalid_argument(std::string(who) + ": " + (msg[0] ? msg : sai2b_last_error(nullptr)));
+}
+// the rows one solve reads under a configuration, checked against what the caller passed
+inline void checkIkRows(const sai2b_ik_config& cfg, const int dof, const size_t B, const Batch& goal_rows, const Batch& seed_rows,
+						const std::vector<unsigned char>& mask) {
+	int g = 0, s = 0;
+	check(nullptr, sai2b_ik_input_rows(&cfg, dof, &g, &s));
+	if (goal_rows.size() != (size_t)g * B) throw std::invalid_argument("solveInverseKinematics: goal_rows must be [" + std::to_string(g) + "][B]");
+	if (seed_rows.size() != (size_t)s * B) throw std::invalid_argument("solveInverseKinematics: seed_rows must be [" + std::to_string(s) + "][B]");
+	if (!mask.empty() && mask.size() != B) throw std::invalid_argument("solveInverseKinematics: mask must be [B] or empty (every robot)");
+}
+inline IkResult emptyIkResult(const int dof, const size_t B) {
+	IkResult r;
+	r.q.assign((size_t)dof * B, std::nan("")), r.status.assign((size_t)SAI2B_IK_STATUS_ROWS * B, std::nan("")), r.flags.assign(B, 0);
+	return r;
+}
+// the members RobotController and BatchedSimulation have: they act on the controller's context
+class IkMembers {
+public:
+	// Validates against the context's model and task (std::invalid_argument with the validator's message) and keeps the
+	// configuration; nothing else in the controller changes
+	void setInverseKinematics(const sai2b_ik_config& cfg) {
+		checkIkConfig(cfg, sai2b_num_joints(_ik_ctx), nullptr, "setInverseKinematics");
+		if (sai2b_set_ik(_ik_ctx, &cfg) != SAI2B_OK) throw std::invalid_argument(std::string("setInverseKinematics: ") + sai2b_last_error(_ik_ctx));
+	}
+	void clearInverseKinematics() { check(_ik_ctx, sai2b_clear_ik(_ik_ctx)); }
+	sai2b_ik_config getInverseKinematics() const {
+		sai2b_ik_config cfg;
+		if (sai2b_get_ik(_ik_ctx, &cfg) != SAI2B_OK) throw std::invalid_argument(sai2b_last_error(_ik_ctx));
+		return cfg;
+	}
+	// One launch. goal_rows [12 (+ dof)][B]: position 3, rotation 9 row-major, then the rest posture when rest_weight > 0 (empty when
+	// the configuration reads none); seed_rows [dof][B] (empty when the seed is the state); mask [B] or empty: every robot.
+	IkResult solveInverseKinematics(const Batch& goal_rows, const Batch& seed_rows = {}, const std::vector<unsigned char>& mask = {}) {
+		const sai2b_ik_config cfg = getInverseKinematics();
+		const int dof = sai2b_num_joints(_ik_ctx);
+		const size_t B = (size_t)sai2b_batch(_ik_ctx);
+		checkIkRows(cfg, dof, B, goal_rows, seed_rows, mask);
+		IkResult r = emptyIkResult(dof, B);
+		check(_ik_ctx, sai2b_solve_ik(_ik_ctx, goal_rows.empty() ? nullptr : goal_rows.data(), seed_rows.empty() ? nullptr : seed_rows.data(),
+									   mask.empty() ? nullptr : mask.data(), r.q.data(), r.status.data(), r.flags.data(), 0));
+		return r;
+	}
+	IkCounts getInverseKinematicsCounts() const {
+		int c[4];
+		check(_ik_ctx, sai2b_get_ik_counts(_ik_ctx, c));
+		IkCounts out;
+		out.selected = c[0], out.converged = c[1], out.exhausted = c[2], out.nonfinite = c[3];
+		return out;
+	}
+
+protected:
+	sai2b_ctx* _ik_ctx = nullptr;
+};
+}  // namespace detail
+
 // reference src/RobotController.{h,cpp}
-class RobotController : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers {
+class RobotController : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers, public detail::IkMembers {
 public:
 	RobotController(std::shared_ptr<BatchedRobotModel>& robot, std::vector<std::shared_ptr<TemplateTask>>& tasks) : _robot(robot) {
 		if (tasks.size() == 0) throw std::invalid_argument("RobotController must have at least one task");
@@ -1252,7 +1322,7 @@ public:
 			if (msg.find("HIP") != std::string::npos || msg.find("hip") != std::string::npos) throw std::runtime_error(msg);
 			throw std::invalid_argument(msg);
 		}
-		_obs_ctx = _act_ctx = _js_ctx = _ctx;
+		_obs_ctx = _act_ctx = _js_ctx = _ik_ctx = _ctx;
 		_tasks = tasks;
 		robot->_controller = this;
 		robot->applyPayloads(_ctx, SAI2B_PAYLOAD_BOTH);
@@ -1824,6 +1894,46 @@ public:
 		}
 		return total;
 	}
+	// Inverse kinematics for the whole sharded batch: the configuration goes to every shard with first_robot moved to the shard's first
+	// global index, so that every robot draws the restart seeds it draws in one context; rows and mask are scattered by column
+	void setInverseKinematics(const sai2b_ik_config& cfg) {
+		detail::checkIkConfig(cfg, _dof, nullptr, "setInverseKinematics");
+		forAll([&](Shard& sh) {
+			sai2b_ik_config part = cfg;
+			part.first_robot = cfg.first_robot + (unsigned)sh.lo;
+			if (sai2b_set_ik(sh.ctx, &part) != SAI2B_OK) throw std::invalid_argument(std::string("setInverseKinematics: ") + sai2b_last_error(sh.ctx));
+		});
+	}
+	void clearInverseKinematics() { forAll([](Shard& sh) { detail::check(sh.ctx, sai2b_clear_ik(sh.ctx)); }); }
+	IkResult solveInverseKinematics(const Batch& goal_rows, const Batch& seed_rows = {}, const std::vector<unsigned char>& mask = {}) {
+		sai2b_ik_config cfg;
+		if (sai2b_get_ik(_shards.front().ctx, &cfg) != SAI2B_OK) throw std::invalid_argument(sai2b_last_error(_shards.front().ctx));
+		detail::checkIkRows(cfg, _dof, (size_t)_total, goal_rows, seed_rows, mask);
+		int g = 0, s = 0;
+		detail::check(nullptr, sai2b_ik_input_rows(&cfg, _dof, &g, &s));
+		IkResult out = detail::emptyIkResult(_dof, (size_t)_total);
+		forAll([&](Shard& sh) {
+			const size_t Bs = (size_t)(sh.hi - sh.lo);
+			const Batch goal = slice(goal_rows, g, sh), seed = slice(seed_rows, s, sh);
+			IkResult part = detail::emptyIkResult(_dof, Bs);
+			detail::check(sh.ctx, sai2b_solve_ik(sh.ctx, ptr(goal), ptr(seed), mask.empty() ? nullptr : mask.data() + sh.lo, part.q.data(), part.status.data(),
+												 out.flags.data() + sh.lo, 0));
+			for (int i = 0; i < _dof; i++) std::copy(part.q.begin() + (size_t)i * Bs, part.q.begin() + (size_t)(i + 1) * Bs, out.q.begin() + (size_t)i * _total + sh.lo);
+			for (int i = 0; i < SAI2B_IK_STATUS_ROWS; i++)
+				std::copy(part.status.begin() + (size_t)i * Bs, part.status.begin() + (size_t)(i + 1) * Bs, out.status.begin() + (size_t)i * _total + sh.lo);
+		});
+		return out;
+	}
+	// summed over the shards
+	IkCounts getInverseKinematicsCounts() {
+		IkCounts out;
+		for (auto& sh : _shards) {
+			int c[4];
+			detail::check(sh.ctx, sai2b_get_ik_counts(sh.ctx, c));
+			out.selected += c[0], out.converged += c[1], out.exhausted += c[2], out.nonfinite += c[3];
+		}
+		return out;
+	}
 	void randomizeRobots(const std::vector<unsigned char>& mask, const unsigned groups = 0) {
 		detail::checkResetArguments(_dof, (size_t)_total, mask, {}, {}, "randomizeRobots");
 		forAll([&](Shard& sh) { detail::check(sh.ctx, sai2b_randomize_robots(sh.ctx, mask.data() + sh.lo, groups, 0)); });
@@ -2053,7 +2163,8 @@ private:
 // integrate, getJointPositions, getJointVelocities): rigid-body dynamics of the whole batch with the
 // state resident on the device (sai2b_sim_step). Without setJointTorques, integrate() consumes the
 // torques of the controller's last computeControlTorques() without a host round trip.
-class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers, public detail::CollisionMembers {
+class BatchedSimulation : public detail::ObservationMembers, public detail::ActionMembers, public detail::JointSensorMembers, public detail::CollisionMembers,
+						  public detail::IkMembers {
 public:
 	explicit BatchedSimulation(RobotController& controller, const double timestep = 0.001, const int substeps = 1)
 		: BatchedSimulation(controller.ctx(), timestep, substeps) {}
@@ -2064,7 +2175,7 @@ public:
 	BatchedSimulation(sai2b_ctx* ctx, const double timestep, const int substeps) : _c(ctx), _dt(timestep), _substeps(substeps) {
 		if (timestep <= 0 || substeps < 1) throw std::invalid_argument("simulation timestep must be positive");
 		_dof = sai2b_num_joints(ctx);
-		_obs_ctx = _act_ctx = _js_ctx = _col_ctx = ctx;
+		_obs_ctx = _act_ctx = _js_ctx = _col_ctx = _ik_ctx = ctx;
 	}
 	void setTimestep(const double dt) {
 		if (dt <= 0) throw std::invalid_argument("simulation timestep must be positive");

@@ -1236,6 +1236,111 @@ int sai2b_get_body_contact(sai2b_ctx* ctx, sai2b_body_contact_config* cfg, doubl
  * with the feature and after a clear. Waits for the ctx stream. */
 int sai2b_get_body_contact_state(sai2b_ctx* ctx, double* status, int counts[4]);
 
+/* ------------------------------------------------------------------ inverse kinematics
+ * Poses to joints, for every robot, in ONE launch (sai2b_solve_ik): a damped least-squares (Levenberg-Marquardt) solve for the
+ * control frame of a MotionForceTask, per robot from a seed q to a goal pose, with optional restarts from seeds drawn on the
+ * device. The call keeps no per-robot state and changes none of the controller's: it reads the model, the task's link and control
+ * frame and (when asked) the state and the task's goal rows, and writes only its outputs. A context that never configures it
+ * launches exactly what it launches without this feature; a configured one launches ik_kernel only in sai2b_solve_ik.
+ * FRAME. x(q), R(q): origin and rotation of the task's control frame in the world (the base after
+ * sai2b_model_set_base_transform), chain convention of include/sai2b_detfk.h, plain FP64. J(q), 6 x dof, world frame: column m
+ * is (z_m x (x - o_m) ; z_m) about a revolute joint and (z_m ; 0) along a prismatic one for m <= the task's link, 0 beyond; z_m
+ * the world z of joint m's frame, o_m its world origin.
+ * ERROR. e = (x_goal - x ; r), r the rotation vector of D = R_goal R^T in the world frame, the full logarithm: with
+ * c = (tr D - 1) / 2 clamped to [-1, 1], v = vee(D - D^T) / 2, s = |v|, theta = atan2(s, c):
+ *     c >= 0:  r = (theta / s) v, and r = v when s < 1e-12
+ *     c <  0:  M = (D + D^T) / 2 - c I; k the first largest diagonal entry of M; a = M[:, k] / sqrt((1 - c) M[k][k]), negated when
+ *              a . v < 0; r = theta a   (accurate up to theta = pi, where v vanishes)
+ * WEIGHTS. axes: bit i selects component i of e (x, y, z, wx, wy, wz; world frame). W = diag(axes . (1, 1, 1, L, L, L)) with
+ * L = rot_length > 0 in metres per radian. E(q) = |W e|^2. pos(q), rot(q): the 2-norms of the selected components of e's first
+ * and last three entries, unweighted. CONVERGED means pos <= tol_pos and rot <= tol_rot.
+ * LIMITS. lo = q_lower + limit_margin, hi = q_upper - limit_margin with use_limits, -inf and +inf without. clamp(q) =
+ * min(max(q, lo), hi) per joint.
+ * A START n = 0 .. restarts: q = clamp(seed) for n = 0; for n >= 1, q_i = lo_i + (hi_i - lo_i) u_i (one product, one sum: the
+ * reset sampler's rs_lerp) with u_i = (word (i mod 4) + 0.5) 2^-32 of Philox4x32-10 under key (seed & 0xffffffff, seed >> 32)
+ * and counter (n, draw_id, 256 * 11 + i / 4, first_robot + b): STREAM 11 (streams 0-1 are the hardware's, 2-4 the episode
+ * sampler's, 5-9 the environment sampler's, 10 the joint sensor's). mu = mu0, and then, while the robot has not converged and
+ * fewer than max_iterations iterations of this start have run, ONE ITERATION:
+ *     solve (J^T W^2 J + (mu + nu) I) d = J^T W^2 e + nu (q_rest - q)       (Cholesky; nu = rest_weight, 0 drops q_rest)
+ *     m = max_i |d_i|;  if m > step_max: d = (step_max / m) d
+ *     q' = clamp(q + d);   e' = e(q')                                        (the pose alone)
+ *     if E(q') < E(q) (strictly; false for a NaN): q = q', mu = max(mu mu_down, mu_min), and J is rebuilt at q
+ *     else: q stays, mu = min(mu mu_up, mu_max)
+ * A robot that converges stops: its q is q_out. A start that ends without convergence leaves its q (its smallest E: E never grows
+ * within a start) as a candidate; the robot keeps the candidate of start 0, replaced by a later start's only when that one's E is
+ * strictly smaller, and starts again while n < restarts. A robot not converged after the last start is EXHAUSTED and gets that
+ * best candidate.
+ * OUTPUT per selected robot: q_out [dof][B]; status [5][B] = pos(q_out), rot(q_out), iterations spent over all starts, the index
+ * of the start that produced q_out, mu as the solve ended (counts and indices are exact integers stored as doubles); a flags byte:
+ * 1 converged, 2 exhausted, 4 some q_out_i <= lo_i or >= hi_i (use_limits only), 8 the goal pose, the seed or the rest posture is
+ * not finite. A robot with bit 8 gets that bit alone, is counted, and its q_out and status are NOT written. An unselected
+ * robot's q_out, status and flags are not touched. COUNTS on the device: selected, converged, exhausted, non-finite.
+ * INPUT ROWS. goal_rows [12 (+ dof)][B]: position 3, rotation 9 row-major (goal_source = SAI2B_IK_ROWS; with
+ * SAI2B_IK_TASK_GOAL the task's current goal rows are read instead and these 12 rows are absent), then the rest posture q_rest,
+ * dof rows, when rest_weight > 0. seed_rows [dof][B] (seed_source = SAI2B_IK_ROWS), or the robot's q in the configured view
+ * (SAI2B_IK_STATE; view as sai2b_collision_config's: 0 the truth, 1 the measured q while a joint sensor is set).
+ * COMPOSITION: q_out in device memory is what sai2b_reset_robots(mask, q, dq, on_device = 1), sai2b_set_jt_goals and
+ * sai2b_set_mft_type1_posture take; flags & 1 is a mask. Snapshot banks hold nothing of this. This law is this library's
+ * definition. */
+enum sai2b_ik_source { SAI2B_IK_ROWS = 0, SAI2B_IK_TASK_GOAL = 1, SAI2B_IK_STATE = 1 };
+enum sai2b_ik_flag { SAI2B_IK_CONVERGED = 1, SAI2B_IK_EXHAUSTED = 2, SAI2B_IK_AT_LIMIT = 4, SAI2B_IK_NONFINITE = 8 };
+#define SAI2B_IK_MAX_ITERATIONS 200
+#define SAI2B_IK_MAX_RESTARTS 16
+#define SAI2B_IK_STATUS_ROWS 5
+typedef struct sai2b_ik_config {
+	int task;			/* a MotionForceTask: its link and control frame are solved for */
+	int axes;			/* bits 0-5: x, y, z, wx, wy, wz of the world-frame error; at least one */
+	int max_iterations; /* per start, 1..SAI2B_IK_MAX_ITERATIONS */
+	int restarts;		/* 0..SAI2B_IK_MAX_RESTARTS further starts from drawn seeds */
+	int use_limits;		/* clamp every iterate to q_lower + limit_margin .. q_upper - limit_margin */
+	int view;			/* seed_source = SAI2B_IK_STATE: 0 the plant's q, 1 the measured q while a joint sensor is set */
+	int goal_source;	/* SAI2B_IK_ROWS or SAI2B_IK_TASK_GOAL */
+	int seed_source;	/* SAI2B_IK_ROWS or SAI2B_IK_STATE */
+	double rot_length;	/* L > 0, metres per radian */
+	double tol_pos, tol_rot;
+	double mu0, mu_min, mu_max, mu_down, mu_up; /* 0 < mu_min <= mu0 <= mu_max, 0 < mu_down < 1 < mu_up */
+	double step_max;							/* > 0: the largest |d_i| of one step */
+	double limit_margin;						/* >= 0 */
+	double rest_weight;							/* nu >= 0 */
+	unsigned long long seed;					/* the generator's key */
+	unsigned first_robot;						/* global index of this context's robot 0 (shards) */
+	unsigned draw_id;							/* second counter word: a caller that wants fresh restarts per call bumps it */
+	int reserved[8];
+} sai2b_ik_config;
+/* host only: task 0, every axis, L = 0.25, 40 iterations, no restart, tolerances 1e-6, mu0 1e-2 in [1e-9, 1e3], mu_down 0.25,
+ * mu_up 8, step_max 0.5, limits on with margin 0, no rest posture, view 0, goal and seed from the call's rows, seed 0 */
+int sai2b_default_ik(sai2b_ik_config* cfg);
+/* host only: SAI2B_OK, or SAI2B_INVALID_ARGUMENT with the reason in msg: a task index outside [0, SAI2B_MAX_TASKS), axes without
+ * a bit or with unknown bits, rot_length / tolerances / schedule / step_max / limit_margin / rest_weight outside what the law
+ * states above or not finite, counts out of range, view / sources unknown. q_lower, q_upper [robot_dof]: the model's limits, or
+ * both NULL when they are not known yet (sai2b_set_ik checks with the context's model): with use_limits a clamped interval
+ * must not be empty or NaN; with restarts > 0 limits must be in use and every clamped limit finite. */
+int sai2b_validate_ik(const sai2b_ik_config* cfg, int robot_dof, const double* q_lower, const double* q_upper, char* msg, int msg_len);
+/* sizeof(sai2b_ik_config) as the library was compiled, for bindings that mirror the struct */
+int sai2b_sizeof_ik_config(void);
+/* host only: rows of goal_rows (12 with goal_source = SAI2B_IK_ROWS, plus robot_dof with rest_weight > 0; the pose rows come
+ * first) and of seed_rows (robot_dof or 0) that sai2b_solve_ik reads under this configuration. Either output may be NULL. */
+int sai2b_ik_input_rows(const sai2b_ik_config* cfg, int robot_dof, int* goal_rows, int* seed_rows);
+/* validates (with the context's model; the task must be a MotionForceTask) and keeps the configuration. No launch, no device
+ * memory but the four counters. A failing call leaves the context as it was. */
+int sai2b_set_ik(sai2b_ctx* ctx, const sai2b_ik_config* cfg);
+/* back to a context without the feature: sai2b_solve_ik fails from here on */
+int sai2b_clear_ik(sai2b_ctx* ctx);
+/* the configuration in force; SAI2B_INVALID_ARGUMENT without one */
+int sai2b_get_ik(sai2b_ctx* ctx, sai2b_ik_config* cfg);
+/* One launch. goal_rows, seed_rows: as sai2b_ik_input_rows counts them; one that has no rows may be NULL. mask: [B] bytes, a robot
+ * with a non-zero byte is solved for; NULL: every robot. q_out [dof][B], status [5][B], flags [B] bytes: all three required.
+ * Everything in host memory, or everything in device memory when on_device != 0 (stream contract of sai2b_set_caller_stream). A host
+ * call stages the three outputs on the device as the caller passed them, so that what the kernel leaves untouched comes back
+ * unchanged. The task's control frame is read at this call (a later sai2b_update_task_config is seen); a deferred
+ * sai2b_update_task_models is not touched. SAI2B_INVALID_ARGUMENT and no launch without a configuration,
+ * with a missing array, or when the task is not a MotionForceTask. */
+int sai2b_solve_ik(sai2b_ctx* ctx, const double* goal_rows, const double* seed_rows, const unsigned char* mask, double* q_out, double* status,
+				   unsigned char* flags, int on_device);
+/* of the last sai2b_solve_ik, counted on the device: robots selected, converged, exhausted, not finite. Zeros before the first;
+ * SAI2B_INVALID_ARGUMENT without a configuration. Waits for the ctx stream. */
+int sai2b_get_ik_counts(sai2b_ctx* ctx, int counts[4]);
+
 /* ------------------------------------------------------------------ episode starts
  * Where a reset robot starts and what it is asked to do, drawn on the device: sai2b_reset_robots_sampled is sai2b_reset_robots
  * with q, dq and the goals of the new episode drawn per robot, in ONE launch (plus the follow-up launches sai2b_reset_robots makes

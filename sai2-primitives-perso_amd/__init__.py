@@ -30,6 +30,7 @@ from .controller import (  # noqa: F401,E402
     SnapshotBank,
     body_contact_config,
     collision_config,
+    ik_config,
     joint_task_config,
     model_from_urdf,
     resolve_link_frame,

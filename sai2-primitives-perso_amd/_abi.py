@@ -351,6 +351,43 @@ class BodyContactConfig(C.Structure):
 
 
 BODY_CONTACT_COUNTS = COL_CATEGORIES + ("any",)
+IK_ROWS, IK_TASK_GOAL, IK_STATE = 0, 1, 1  # enum sai2b_ik_source
+IK_FLAGS = {"converged": 1, "exhausted": 2, "at_limit": 4, "nonfinite": 8}  # enum sai2b_ik_flag
+IK_COUNTS = ("selected", "converged", "exhausted", "nonfinite")
+IK_STATUS_ROWS, IK_POSE_ROWS = 5, 12  # |e_pos|, |e_rot|, iterations, start index, mu; position 3 and rotation 9 row-major
+IK_STREAM = 11  # the Philox stream of the restart seeds
+
+
+class IkConfig(C.Structure):
+    """sai2b_ik_config; load_library() checks the size against sai2b_sizeof_ik_config()"""
+
+    _fields_ = [
+        ("task", _i),
+        ("axes", _i),
+        ("max_iterations", _i),
+        ("restarts", _i),
+        ("use_limits", _i),
+        ("view", _i),
+        ("goal_source", _i),
+        ("seed_source", _i),
+        ("rot_length", C.c_double),
+        ("tol_pos", C.c_double),
+        ("tol_rot", C.c_double),
+        ("mu0", C.c_double),
+        ("mu_min", C.c_double),
+        ("mu_max", C.c_double),
+        ("mu_down", C.c_double),
+        ("mu_up", C.c_double),
+        ("step_max", C.c_double),
+        ("limit_margin", C.c_double),
+        ("rest_weight", C.c_double),
+        ("seed", C.c_ulonglong),
+        ("first_robot", C.c_uint),
+        ("draw_id", C.c_uint),
+        ("reserved", _i * 8),
+    ]
+
+
 MAX_RESET_TRIES = 64  # SAI2B_MAX_RESET_TRIES
 RESET_SAMPLER_COUNTS = ("reset", "rejected", "exhausted")
 RESET_SAMPLER_BLOCKS = {"q_lower": 0, "q_upper": 1, "dq_sigma": 2, "q_nominal": 3, "goal": 4}  # sai2b_reset_sampler_config_layout
@@ -633,6 +670,15 @@ EXPORTS = [
     "sai2b_clear_body_contact",
     "sai2b_get_body_contact",
     "sai2b_get_body_contact_state",
+    "sai2b_default_ik",
+    "sai2b_validate_ik",
+    "sai2b_sizeof_ik_config",
+    "sai2b_ik_input_rows",
+    "sai2b_set_ik",
+    "sai2b_clear_ik",
+    "sai2b_get_ik",
+    "sai2b_solve_ik",
+    "sai2b_get_ik_counts",
     "sai2b_snapshot_words",
     "sai2b_snapshot_layout",
     "sai2b_snapshot_bank_create",
@@ -867,6 +913,18 @@ def load_library():
     lib.sai2b_clear_body_contact.argtypes = [vp]
     lib.sai2b_get_body_contact.argtypes = [vp, P(BodyContactConfig), vp]
     lib.sai2b_get_body_contact_state.argtypes = [vp, vp, P(_i)]
+    lib.sai2b_default_ik.argtypes = [P(IkConfig)]
+    lib.sai2b_validate_ik.argtypes = [P(IkConfig), _i, vp, vp, C.c_char_p, _i]
+    lib.sai2b_sizeof_ik_config.argtypes = []
+    lib.sai2b_ik_input_rows.argtypes = [P(IkConfig), _i, P(_i), P(_i)]
+    lib.sai2b_set_ik.argtypes = [vp, P(IkConfig)]
+    lib.sai2b_clear_ik.argtypes = [vp]
+    lib.sai2b_get_ik.argtypes = [vp, P(IkConfig)]
+    lib.sai2b_solve_ik.argtypes = [vp, vp, vp, vp, vp, vp, vp, _i]
+    lib.sai2b_get_ik_counts.argtypes = [vp, P(_i)]
+    if lib.sai2b_sizeof_ik_config() != C.sizeof(IkConfig):
+        raise RuntimeError(f"{LIB_PATH}: sai2b_ik_config is {lib.sai2b_sizeof_ik_config()} bytes in the library, "
+                           f"{C.sizeof(IkConfig)} in the ctypes mirror")
     if lib.sai2b_sizeof_body_contact_config() != C.sizeof(BodyContactConfig):
         raise RuntimeError(f"{LIB_PATH}: sai2b_body_contact_config is {lib.sai2b_sizeof_body_contact_config()} bytes in the library, "
                            f"{C.sizeof(BodyContactConfig)} in the ctypes mirror")

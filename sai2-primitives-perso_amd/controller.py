@@ -198,6 +198,37 @@ def collision_config(robot_dof, links, centres, radii, n_planes=0, n_obstacles=0
 
 
 
+def ik_config(model, task=0, axes=0b111111, rot_length=0.25, max_iterations=40, restarts=0, tol_pos=1e-6, tol_rot=1e-6, mu0=1e-2, mu_min=1e-9,
+              mu_max=1e3, mu_down=0.25, mu_up=8.0, step_max=0.5, use_limits=True, limit_margin=0.0, rest_weight=0.0, view="truth",
+              goal_source="rows", seed_source="rows", seed=0, first_robot=0, draw_id=0):
+    """sai2b_default_ik() + sai2b_validate_ik() against a RobotModel's size and limits (no device needed) -> IkConfig. axes: an int of bits or an iterable of 'x', 'y', 'z', 'wx', 'wy',
+    'wz'; view: 'truth' or 'measured'; goal_source: 'rows' or 'task'; seed_source: 'rows' or 'state'"""
+    lib, dof = _abi.load_library(), int(model.dof)
+    cfg = _abi.IkConfig()
+    if lib.sai2b_default_ik(C.byref(cfg)):
+        raise ValueError(lib.sai2b_last_error(None).decode())
+    names = ("x", "y", "z", "wx", "wy", "wz")
+    try:
+        cfg.axes = int(axes) if isinstance(axes, (int, np.integer)) else sum({1 << names.index(a) for a in axes})
+        cfg.view = {"truth": 0, "measured": 1}[view] if isinstance(view, str) else int(view)
+        cfg.goal_source = {"rows": _abi.IK_ROWS, "task": _abi.IK_TASK_GOAL}[goal_source] if isinstance(goal_source, str) else int(goal_source)
+        cfg.seed_source = {"rows": _abi.IK_ROWS, "state": _abi.IK_STATE}[seed_source] if isinstance(seed_source, str) else int(seed_source)
+    except (KeyError, ValueError):
+        raise ValueError("ik: axes are 'x', 'y', 'z', 'wx', 'wy', 'wz'; view 'truth' or 'measured'; goal_source 'rows' or 'task'; "
+                         "seed_source 'rows' or 'state'") from None
+    cfg.task, cfg.max_iterations, cfg.restarts, cfg.use_limits = int(task), int(max_iterations), int(restarts), int(bool(use_limits))
+    cfg.rot_length, cfg.tol_pos, cfg.tol_rot = float(rot_length), float(tol_pos), float(tol_rot)
+    cfg.mu0, cfg.mu_min, cfg.mu_max, cfg.mu_down, cfg.mu_up = float(mu0), float(mu_min), float(mu_max), float(mu_down), float(mu_up)
+    cfg.step_max, cfg.limit_margin, cfg.rest_weight = float(step_max), float(limit_margin), float(rest_weight)
+    cfg.seed, cfg.first_robot, cfg.draw_id = int(seed), int(first_robot), int(draw_id)
+    lo = np.array(model.q_lower[: dof], dtype=np.float64)
+    hi = np.array(model.q_upper[: dof], dtype=np.float64)
+    msg = C.create_string_buffer(256)
+    if lib.sai2b_validate_ik(C.byref(cfg), dof, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), msg, 256):
+        raise ValueError(msg.value.decode())
+    return cfg
+
+
 class Controller:
     """Array-level binding of one sai2b_ctx (one GPU, one batch)."""
 
@@ -930,6 +961,76 @@ class Controller:
         c = (C.c_int * 4)()
         self._rc(self.lib.sai2b_get_body_contact_state(self.h, None, c))
         return c[3]
+
+    # -- inverse kinematics (sai2b.h "inverse kinematics")
+    def ik_config(self, **kwargs):
+        """ik_config() of this module for this controller's model"""
+        return ik_config(self.model, **kwargs)
+
+    def set_ik(self, cfg=None, **kwargs):
+        """the inverse kinematics of solve_ik(): an IkConfig (or the arguments of ik_config). Nothing else in the controller changes."""
+        if cfg is None:
+            cfg = self.ik_config(**kwargs)
+        elif kwargs:
+            raise ValueError("set_ik: an IkConfig or keyword arguments, not both")
+        self._rc(self.lib.sai2b_set_ik(self.h, C.byref(cfg)))
+
+    def clear_ik(self):
+        self._rc(self.lib.sai2b_clear_ik(self.h))
+
+    def get_ik(self):
+        cfg = _abi.IkConfig()
+        self._rc(self.lib.sai2b_get_ik(self.h, C.byref(cfg)))
+        return cfg
+
+    def ik_input_rows(self):
+        """-> (rows of goal_rows, rows of seed_rows) that solve_ik() reads under the configuration in force"""
+        cfg = self.get_ik()
+        g, s = C.c_int(), C.c_int()
+        self._rc(self.lib.sai2b_ik_input_rows(C.byref(cfg), self.dof, C.byref(g), C.byref(s)))
+        return g.value, s.value
+
+    def solve_ik(self, goal_rows=None, seed_rows=None, mask=None, q_out=None, status=None, flags=None):
+        """one launch -> (q_out [dof][B], status [5][B] float64, flags [B] uint8 with the _abi.IK_FLAGS bits). goal_rows [12 (+ dof)][B]:
+        position 3, rotation 9 row-major, then the rest posture when rest_weight > 0 (without the pose rows when the goal is the
+        task's); seed_rows [dof][B] (None when the seed is the state); mask [B] bool / uint8, None: every robot. Everything numpy, or
+        everything torch CUDA (then the three outputs are required, nothing leaves the device and nothing synchronises). Outputs not
+        given are new numpy arrays of zeros; those given keep what the call does not write (unselected and non-finite robots)."""
+        g_rows, s_rows = self.ik_input_rows()
+        dev = self._dev(goal_rows, seed_rows, mask, q_out, status, flags)
+        if dev and (q_out is None or status is None or flags is None):
+            raise ValueError("solve_ik: with device tensors pass q_out, status and flags as tensors too")
+        if (goal_rows is None) != (g_rows == 0) or (seed_rows is None) != (s_rows == 0):
+            raise ValueError(f"solve_ik: the configuration reads {g_rows} goal rows and {s_rows} seed rows")
+        pg, _kg = self._in(goal_rows, g_rows)
+        ps, _ks = self._in(seed_rows, s_rows)
+        pm, _km = self._mask(mask) if mask is not None else (None, None)
+        if q_out is None:
+            q_out = np.zeros((self.dof, self.B))
+        if status is None:
+            status = np.zeros((_abi.IK_STATUS_ROWS, self.B))
+        if flags is None:
+            flags = np.zeros(self.B, dtype=np.uint8)
+        if dev:
+            if str(flags.dtype) != "torch.uint8":
+                raise ValueError("flags must be a uint8 tensor (it receives the flag bits)")
+            pq, _ = self._in(q_out, self.dof)
+            pst, _ = self._in(status, _abi.IK_STATUS_ROWS)
+            pf, _ = self._mask(flags)
+        else:
+            for a, shape, dt, name in ((q_out, (self.dof, self.B), np.float64, "q_out"), (status, (_abi.IK_STATUS_ROWS, self.B), np.float64, "status"),
+                                       (flags, (self.B,), np.uint8, "flags")):
+                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.shape == shape):
+                    raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            pq, pst, pf = (C.c_void_p(a.ctypes.data) for a in (q_out, status, flags))
+        self._rc(self.lib.sai2b_solve_ik(self.h, pg, ps, pm, pq, pst, pf, dev))
+        return q_out, status, flags
+
+    def get_ik_counts(self):
+        """of the last solve_ik(): dict 'selected', 'converged', 'exhausted', 'nonfinite' -> robots"""
+        c = (C.c_int * 4)()
+        self._rc(self.lib.sai2b_get_ik_counts(self.h, c))
+        return dict(zip(_abi.IK_COUNTS, list(c)))
 
     # -- observations and episode-end flags (sai2b.h "observations and episode-end flags")
     @staticmethod

@@ -149,6 +149,14 @@ struct sai2b_ctx {
 	double *col_env = nullptr, *col_out = nullptr;
 	unsigned char *col_flags = nullptr, *end_done = nullptr, *end_extra = nullptr;
 	int* col_counts = nullptr;
+	// inverse kinematics (sai2b_set_ik): the configuration in force, the four device counters of the last solve, and the staging
+	// of a solve with host arguments (ik_rows: goal 12 + N, seed N, q_out N, status 5 rows; ik_bytes: mask and flags), created
+	// on first use. Nothing else in the context reads any of it
+	bool ik_on = false;
+	sai2b_ik_config ik_cfg = {};
+	int* ik_counts = nullptr;
+	double* ik_rows = nullptr;
+	unsigned char* ik_bytes = nullptr;
 	// whole-arm contact of the plant (sai2b_set_body_contact), created on first use: the [3][B] rows, the [9 + dof][B] status rows
 	// and the four device counters. body_on: sai2b_sim_step launches sim_body_kernel; its geometry is taken from `col` at every
 	// step, so it follows the collision configuration (which must be in force: sai2b_clear_collision clears this too)
@@ -3607,6 +3615,192 @@ extern "C" int sai2b_get_end_episode_count(sai2b_ctx* ctx, int* count) {
 	if (!ctx->col_counts) return SAI2B_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipMemcpyAsync(count, ctx->col_counts + sai2b::COL_COUNTS, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// inverse kinematics (include/sai2b.h "inverse kinematics"; law: sai2b_ik_law.h; kernel: sai2b_ik.hip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int sai2b_default_ik(sai2b_ik_config* cfg) {
+	if (!cfg) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_default_ik: null config");
+	std::memset(cfg, 0, sizeof(*cfg));
+	cfg->axes = 63, cfg->max_iterations = 40, cfg->use_limits = 1;
+	cfg->rot_length = 0.25, cfg->tol_pos = cfg->tol_rot = 1e-6;
+	cfg->mu0 = 1e-2, cfg->mu_min = 1e-9, cfg->mu_max = 1e3, cfg->mu_down = 0.25, cfg->mu_up = 8.0;
+	cfg->step_max = 0.5;
+	return SAI2B_OK;
+}
+// lower / upper: the model's limits or both NULL (not known yet: what hangs on them is not checked)
+static std::string ik_config_error(const sai2b_ik_config* c, const double* lower, const double* upper) {
+	if (!c) return "ik: null config";
+	if (c->task < 0 || c->task >= SAI2B_MAX_TASKS) return "ik: task must be a task index";
+	if (c->axes & ~63) return "ik: unknown bits in axes";
+	if (!(c->axes & 63)) return "ik: axes selects no component";
+	if (!std::isfinite(c->rot_length) || !(c->rot_length > 0)) return "ik: rot_length must be finite and > 0";
+	if (c->max_iterations < 1 || c->max_iterations > SAI2B_IK_MAX_ITERATIONS) return "ik: max_iterations must be in [1, SAI2B_IK_MAX_ITERATIONS]";
+	if (c->restarts < 0 || c->restarts > SAI2B_IK_MAX_RESTARTS) return "ik: restarts must be in [0, SAI2B_IK_MAX_RESTARTS]";
+	if (!std::isfinite(c->tol_pos) || !std::isfinite(c->tol_rot) || c->tol_pos < 0 || c->tol_rot < 0) return "ik: tol_pos and tol_rot must be finite and >= 0";
+	if (!std::isfinite(c->mu_min) || !std::isfinite(c->mu0) || !std::isfinite(c->mu_max) || !(c->mu_min > 0) || !(c->mu_min <= c->mu0) || !(c->mu0 <= c->mu_max))
+		return "ik: damping needs 0 < mu_min <= mu0 <= mu_max, all finite";
+	if (!(c->mu_down > 0) || !(c->mu_down < 1)) return "ik: mu_down must be in (0, 1)";
+	if (!std::isfinite(c->mu_up) || !(c->mu_up > 1)) return "ik: mu_up must be finite and > 1";
+	if (!std::isfinite(c->step_max) || !(c->step_max > 0)) return "ik: step_max must be finite and > 0";
+	if (c->use_limits != 0 && c->use_limits != 1) return "ik: use_limits must be 0 or 1";
+	if (!std::isfinite(c->limit_margin) || c->limit_margin < 0) return "ik: limit_margin must be finite and >= 0";
+	if (!std::isfinite(c->rest_weight) || c->rest_weight < 0) return "ik: rest_weight must be finite and >= 0";
+	if (c->view != 0 && c->view != 1) return "ik: view must be 0 (the plant's q) or 1 (the measured q)";
+	if (c->goal_source != SAI2B_IK_ROWS && c->goal_source != SAI2B_IK_TASK_GOAL) return "ik: goal_source must be SAI2B_IK_ROWS or SAI2B_IK_TASK_GOAL";
+	if (c->seed_source != SAI2B_IK_ROWS && c->seed_source != SAI2B_IK_STATE) return "ik: seed_source must be SAI2B_IK_ROWS or SAI2B_IK_STATE";
+	if (c->restarts > 0 && !c->use_limits) return "ik: restarts need use_limits (the seeds are drawn inside the limits)";
+	if (lower && upper && c->use_limits) {
+		for (int i = 0; i < N; i++) {
+			const double lo = lower[i] + c->limit_margin, hi = upper[i] - c->limit_margin;
+			if (!(lo <= hi)) return "ik: limit_margin leaves a joint no interval (or a limit is NaN)";
+			if (c->restarts > 0 && (!std::isfinite(lo) || !std::isfinite(hi))) return "ik: restarts need finite limits on every joint";
+		}
+	}
+	return "";
+}
+extern "C" int sai2b_validate_ik(const sai2b_ik_config* cfg, int robot_dof, const double* q_lower, const double* q_upper, char* msg, int msg_len) {
+	std::string err = robot_dof == N ? ik_config_error(cfg, q_lower, q_upper) : "ik: this build serves another robot size";
+	if (err.empty() && (q_lower == nullptr) != (q_upper == nullptr)) err = "ik: q_lower and q_upper are given together or not at all";
+	if (msg && msg_len > 0) std::snprintf(msg, msg_len, "%s", err.c_str());
+	if (err.empty()) return SAI2B_OK;
+	return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_validate_ik: " + err);
+}
+extern "C" int sai2b_sizeof_ik_config(void) { return (int)sizeof(sai2b_ik_config); }
+extern "C" int sai2b_ik_input_rows(const sai2b_ik_config* cfg, int robot_dof, int* goal_rows, int* seed_rows) {
+	if (robot_dof != N) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_ik_input_rows: this build serves another robot size");
+	const std::string err = ik_config_error(cfg, nullptr, nullptr);
+	if (!err.empty()) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_ik_input_rows: " + err);
+	if (goal_rows) *goal_rows = (cfg->goal_source == SAI2B_IK_ROWS ? sai2b::IK_POSE_ROWS : 0) + (cfg->rest_weight > 0 ? N : 0);
+	if (seed_rows) *seed_rows = cfg->seed_source == SAI2B_IK_ROWS ? N : 0;
+	return SAI2B_OK;
+}
+static std::string ik_context_error(const sai2b_ctx* ctx, const sai2b_ik_config* cfg) {
+	std::string err = ik_config_error(cfg, ctx->h_params.model.q_lower, ctx->h_params.model.q_upper);
+	if (err.empty() && cfg->task >= ctx->T) err = "ik: task must be a task index";
+	if (err.empty() && ctx->h_params.task[cfg->task].type != SAI2B_MOTION_FORCE_TASK) err = "ik: task must be a MotionForceTask";
+	return err;
+}
+extern "C" int sai2b_set_ik(sai2b_ctx* ctx, const sai2b_ik_config* cfg) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_set_ik: null ctx");
+	const std::string err = cfg ? ik_context_error(ctx, cfg) : "ik: null config";
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_set_" + err);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (!ctx->ik_counts) {
+		if (int rc = dev_alloc(ctx, &ctx->ik_counts, (size_t)sai2b::IK_COUNTS)) return rc;
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->ik_counts, 0, sai2b::IK_COUNTS * sizeof(int), ctx->stream));
+	ctx->ik_cfg = *cfg;
+	std::memset(ctx->ik_cfg.reserved, 0, sizeof(ctx->ik_cfg.reserved));
+	ctx->ik_on = true;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_clear_ik(sai2b_ctx* ctx) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_clear_ik: null ctx");
+	ctx->ik_on = false;
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_ik(sai2b_ctx* ctx, sai2b_ik_config* cfg) {
+	if (!ctx || !cfg) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_ik: bad arguments");
+	if (!ctx->ik_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_ik: no inverse kinematics is configured (sai2b_set_ik)");
+	*cfg = ctx->ik_cfg;
+	return SAI2B_OK;
+}
+// the law's block from the configuration and the context's model and task as they stand
+static void ik_fill_law(const sai2b_ctx* ctx, sai2b::IkLaw<N>& L) {
+	const sai2b_ik_config& c = ctx->ik_cfg;
+	const sai2b::DevModel& m = ctx->h_params.model;
+	const DevTask& t = ctx->h_params.task[c.task];
+	for (int i = 0; i < N; i++) {
+		for (int a = 0; a < 9; a++) L.E[i][a] = m.E[i][a];
+		for (int a = 0; a < 3; a++) L.xyz[i][a] = m.xyz[i][a];
+		L.jtype[i] = m.jtype[i];
+		L.lo[i] = c.use_limits ? m.q_lower[i] + c.limit_margin : -HUGE_VAL;
+		L.hi[i] = c.use_limits ? m.q_upper[i] - c.limit_margin : HUGE_VAL;
+	}
+	L.link = t.link;
+	for (int a = 0; a < 3; a++) L.frame_pos[a] = t.frame_pos[a];
+	for (int a = 0; a < 9; a++) L.frame_rot[a] = t.frame_rot[a];
+	for (int a = 0; a < 6; a++) {
+		const bool on = (c.axes >> a) & 1;
+		L.sel[a] = on ? 1.0 : 0.0;
+		L.w2[a] = on ? (a < 3 ? 1.0 : c.rot_length * c.rot_length) : 0.0;
+	}
+	L.max_iterations = c.max_iterations, L.restarts = c.restarts, L.use_limits = c.use_limits;
+	L.tol_pos = c.tol_pos, L.tol_rot = c.tol_rot;
+	L.mu0 = c.mu0, L.mu_min = c.mu_min, L.mu_max = c.mu_max, L.mu_down = c.mu_down, L.mu_up = c.mu_up;
+	L.step_max = c.step_max, L.rest_weight = c.rest_weight;
+	L.key0 = (unsigned)(c.seed & 0xffffffffull), L.key1 = (unsigned)(c.seed >> 32);
+	L.first_robot = c.first_robot, L.draw_id = c.draw_id;
+}
+extern "C" int sai2b_solve_ik(sai2b_ctx* ctx, const double* goal_rows, const double* seed_rows, const unsigned char* mask, double* q_out, double* status,
+							  unsigned char* flags, int on_device) {
+	if (!ctx) return set_error(nullptr, SAI2B_INVALID_ARGUMENT, "sai2b_solve_ik: null ctx");
+	if (!ctx->ik_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_solve_ik: no inverse kinematics is configured (sai2b_set_ik)");
+	const sai2b_ik_config& c = ctx->ik_cfg;
+	// the model's limits or the task may have changed since sai2b_set_ik
+	const std::string err = ik_context_error(ctx, &c);
+	if (!err.empty()) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_solve_" + err);
+	const int pose_rows = c.goal_source == SAI2B_IK_ROWS ? sai2b::IK_POSE_ROWS : 0, rest_rows = c.rest_weight > 0 ? N : 0;
+	const int g_rows = pose_rows + rest_rows, s_rows = c.seed_source == SAI2B_IK_ROWS ? N : 0;
+	if (g_rows > 0 && !goal_rows) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_solve_ik: goal_rows is NULL");
+	if (s_rows > 0 && !seed_rows) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_solve_ik: seed_rows is NULL");
+	if (!q_out || !status || !flags) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_solve_ik: q_out, status and flags are required");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc;
+	const size_t B = ctx->B;
+	const double *d_goal = goal_rows, *d_seed = seed_rows;
+	const unsigned char* d_mask = mask;
+	double *d_q = q_out, *d_status = status;
+	unsigned char* d_flags = flags;
+	if (on_device) {
+		if ((rc = caller_before_read(ctx))) return rc;
+	} else {
+		// staging, created on the first host call: goal 12 + N, seed N, q_out N, status 5 rows; mask and flags B bytes each
+		constexpr size_t ROWS = sai2b::IK_POSE_ROWS + 3 * N + sai2b::IK_STATUS_ROWS;
+		if (!ctx->ik_rows && (rc = dev_alloc(ctx, &ctx->ik_rows, ROWS * B))) return rc;
+		if (!ctx->ik_bytes && (rc = dev_alloc(ctx, &ctx->ik_bytes, 2 * B))) return rc;
+		double* r = ctx->ik_rows;
+		if (g_rows > 0) HIP_TRY(ctx, hipMemcpyAsync(r, goal_rows, (size_t)g_rows * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		d_goal = r, r += (size_t)(sai2b::IK_POSE_ROWS + N) * B;
+		if (s_rows > 0) HIP_TRY(ctx, hipMemcpyAsync(r, seed_rows, (size_t)N * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		d_seed = r, r += (size_t)N * B;
+		HIP_TRY(ctx, hipMemcpyAsync(r, q_out, (size_t)N * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		d_q = r, r += (size_t)N * B;
+		HIP_TRY(ctx, hipMemcpyAsync(r, status, (size_t)sai2b::IK_STATUS_ROWS * B * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+		d_status = r;
+		if (mask) {
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->ik_bytes, mask, B, hipMemcpyHostToDevice, ctx->stream));
+			d_mask = ctx->ik_bytes;
+		}
+		d_flags = ctx->ik_bytes + B;
+		HIP_TRY(ctx, hipMemcpyAsync(d_flags, flags, B, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // pageable host memory may be reused by the caller
+	}
+	HIP_TRY(ctx, hipMemsetAsync(ctx->ik_counts, 0, sai2b::IK_COUNTS * sizeof(int), ctx->stream));
+	sai2b::IkParams p;
+	ik_fill_law(ctx, p.law);
+	p.goal = pose_rows ? d_goal : ctx->h_params.task[c.task].goals;
+	p.rest = rest_rows ? d_goal + (size_t)pose_rows * B : nullptr;
+	p.seed = s_rows ? d_seed : (c.view == 1 ? ctrl_q(ctx) : ctx->q);
+	p.mask = d_mask, p.q_out = d_q, p.status = d_status, p.flags = d_flags, p.counts = ctx->ik_counts;
+	if (sai2b::launch_ik(ctx->B, p, ctx->stream)) return set_error(ctx, SAI2B_RUNTIME_ERROR, "sai2b_solve_ik: launch failed");
+	ctx->launches++;
+	if (on_device) return caller_after_read(ctx);
+	HIP_TRY(ctx, hipMemcpyAsync(q_out, d_q, (size_t)N * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(status, d_status, (size_t)sai2b::IK_STATUS_ROWS * B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(flags, d_flags, B, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return SAI2B_OK;
+}
+extern "C" int sai2b_get_ik_counts(sai2b_ctx* ctx, int counts[4]) {
+	if (!ctx || !counts) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_ik_counts: bad arguments");
+	if (!ctx->ik_on) return set_error(ctx, SAI2B_INVALID_ARGUMENT, "sai2b_get_ik_counts: no inverse kinematics is configured (sai2b_set_ik)");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->ik_counts, sai2b::IK_COUNTS * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return SAI2B_OK;
 }

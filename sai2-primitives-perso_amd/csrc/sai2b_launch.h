@@ -6,6 +6,7 @@
 #include "sai2b_body_contact_law.h"  // BcGeom
 #include "sai2b_collision_law.h"  // ColLaw
 #include "sai2b_env_draw.h"  // EnvDraw
+#include "sai2b_ik_law.h"  // IkLaw
 #include "sai2b_params.h"
 #include "sai2b_tick_policy.h"  // TickForm, TickCall
 
@@ -329,5 +330,20 @@ struct EndParams {
 	int bit = 0;
 };
 int launch_end_episodes(int B, const EndParams& p, hipStream_t stream);
+
+// sai2b_solve_ik (sai2b_ik.hip: ik_kernel): its own parameter block, passed by value as a kernel argument; DevParams is not read
+// (the chain, the task's frame and the clamped limits are part of the law's block, sai2b_ik_law.h).
+struct IkParams {
+	IkLaw<N> law;
+	const double* goal = nullptr;		  // [12][B]: position 3, rotation 9 row-major (the call's rows or the task's goal rows)
+	const double* rest = nullptr;		  // [N][B] or NULL (rest_weight == 0)
+	const double* seed = nullptr;		  // [N][B]: the call's rows, or the state in the configured view
+	const unsigned char* mask = nullptr;  // [B] or NULL: every robot
+	double* q_out = nullptr;			  // [N][B]
+	double* status = nullptr;			  // [IK_STATUS_ROWS][B]
+	unsigned char* flags = nullptr;		  // [B]
+	int* counts = nullptr;				  // [IK_COUNTS], zeroed by the caller on the stream ahead of the launch
+};
+int launch_ik(int B, const IkParams& p, hipStream_t stream);
 
 }  // namespace sai2b

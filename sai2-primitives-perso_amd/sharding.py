@@ -90,6 +90,13 @@ def set_collision(ctrl, world, rank, global_batch, cfg, rows=None):
     ctrl.set_collision(cfg, shard_rows(rows, world, rank))
 
 
+def set_ik(ctrl, world, rank, global_batch, **kwargs):
+    """Controller.set_ik with first_robot set to the shard's first global index: every robot draws the restart seeds it draws
+    in the one-context run. The rows of solve_ik are sharded with shard_rows."""
+    lo, _ = shard_bounds(global_batch, world, rank)
+    ctrl.set_ik(first_robot=lo, **kwargs)
+
+
 def end_episodes(ctrl, world, rank, done, extra, bit=64):
     """Controller.end_episodes on this rank's shard of done and extra given for the whole batch (numpy): the shard's slice of
     done is updated in place"""

@@ -12,7 +12,7 @@ import re
 import sys
 
 UNITS = ["sai2b_kernels", "sai2b_self", "sai2b_cert", "sai2b_group", "sai2b_otg", "sai2b_sim", "sai2b_observe", "sai2b_action", "sai2b_snapshot", "sai2b_hardware",
-         "sai2b_env_sampler", "sai2b_joint_sensor", "sai2b_collision"]
+         "sai2b_env_sampler", "sai2b_joint_sensor", "sai2b_collision", "sai2b_ik"]
 
 
 def kernels(path):
